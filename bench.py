@@ -15,9 +15,16 @@ A step = one pass of the hot path over one batch of synthetic input that is alre
       u64 per band over RCCL), the bodies gathered over xGMI, spliced on rank 0 (strong scaling).
   c2_444, c2_unaligned (4094 wide: rows not dword aligned), c3 (64 x 1080p, one launch), c1, c5 (PNG filters).
 
-Timing: W warmup steps, then R blocks (--blocks) of EXACTLY K steps, each bracketed by a barrier and
-torch.cuda.synchronize() on both sides, MAX over ranks per block; `ms_per_step` is the MEDIAN block (min and max
-beside it).  Rank 0 prints ONE JSON line with the contract's keys plus `roofline`, `cpu_baseline`, `other_configs`.
+Timing: W warmup steps, then R blocks (--blocks; 1 by default, so that exactly K steps are timed) of EXACTLY K steps,
+each bracketed by a barrier and torch.cuda.synchronize() on both sides, MAX over ranks per block; `ms_per_step` is the
+MEDIAN block (min and max beside it).  Rank 0 prints ONE JSON line with the contract's keys.
+
+A plain run does only what that line needs: set up, warm up, time, print.  --full adds everything else: R = 15 blocks by
+default, the oracle check of the outputs, `roofline` (engine clock, same-run copy, counter profiles), `whole_file`,
+`small_files`, `other_configs`, the multi-GPU legs with `rccl`, `cpu_baseline` and `cpu_reference`.
+
+--dump-outputs DIR: after the timed steps, what the last step computed goes to DIR/<name>.npy (float32 or float64, at most
+64 MB in all; larger outputs as the same seeded sample of their rows in every run).  c2: y.npy, cb.npy, cr.npy.
 """
 import os
 import sys

@@ -32,12 +32,23 @@ WORKLOADS = {
 }
 
 
+FULL_BLOCKS = 15  # --full: the metric's K-step block is timed this many times unless --blocks says otherwise
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--blocks", type=int, default=15, help="R: the K-step block is timed R times; median/min/max are reported")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="R: the K-step block is timed R times; median/min/max are reported (default: 1, so that exactly K steps "
+                         "are timed; %d with --full)" % FULL_BLOCKS)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the oracle check, rooflines (engine clock, same-run copy, counter "
+                         "profiles), whole-file and other-configuration legs, the multi-GPU legs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: larger outputs as a fixed, seeded sample of their rows)")
     ap.add_argument("--settle-ms", type=float, default=100.0,
                     help="untimed launches before the warmup steps until this much wall time has passed: after an idle "
                          "period the GPU needs ~20 ms of work to reach its steady clocks (tools/warmup_probe.py); 0 = none")
@@ -51,7 +62,12 @@ def parse(argv=None):
                          "band over its own GPU's PCIe link) instead of one rank per GPU over RCCL; pixels start in HOST memory")
     ap.add_argument("--stub", action="store_true",
                     help="plumbing test without a GPU: gloo process group, the step is a short sleep (data: 'stub')")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.blocks is None:
+        args.blocks = FULL_BLOCKS if args.full else 1
+    if args.steps < 1 or args.blocks < 1 or args.warmup < 0:
+        ap.error("--steps and --blocks must be at least 1, --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -173,6 +189,7 @@ class Job:
             if events and not self.stub:
                 evs.append(e0.elapsed_time(e1))
         self.barrier()
+        self.last_step = n - 1  # the index the last timed step was called with (--dump-outputs)
         return walls, evs
 
     def finish(self, line=None):
@@ -188,6 +205,44 @@ class Job:
             except Exception:
                 pass
             emit(line)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: data bytes of all arrays together (under the 64 MB cap with room for the headers)
+
+
+DUMP_SEED = 20240601  # the rows a sampled output keeps: the same from run to run and from build to build
+
+
+def dump_rows(n_rows, keep, seed=DUMP_SEED):
+    """The sorted row indices a sampled output keeps: all of them when `keep` >= `n_rows`, else a seeded draw (a function of
+    (n_rows, keep, seed) alone, so two builds of the project keep the same rows)."""
+    import numpy as np
+    if keep >= n_rows:
+        return np.arange(n_rows)
+    return np.unique(np.random.default_rng(seed).integers(0, n_rows, size=keep, dtype=np.int64))
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes every (name, array) of `arrays` as dirname/<name>.npy: integers of up to 16 bits as float32, wider ones and floats
+    as float64 (both exact).  When the arrays together exceed `budget` bytes, every one keeps the same fraction of its rows
+    (first axis), drawn by dump_rows.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    conv = []
+    for name, a in arrays:
+        a = np.asarray(a)
+        a = a.reshape(1) if a.ndim == 0 else a
+        dt = np.float32 if a.dtype.kind in "iub" and a.dtype.itemsize <= 2 else np.float64
+        conv.append((name, a, dt))
+    total = sum(a.size * np.dtype(dt).itemsize for _, a, dt in conv)
+    frac = min(1.0, budget / total) if total else 1.0
+    shapes = {}
+    for name, a, dt in conv:
+        rows = dump_rows(a.shape[0], max(1, int(a.shape[0] * frac))) if frac < 1.0 else slice(None)
+        out = a[rows].astype(dt)
+        np.save(os.path.join(dirname, name + ".npy"), out)
+        shapes[name] = list(out.shape)
+    return shapes
 
 
 def block_stats(walls, steps):

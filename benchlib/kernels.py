@@ -50,6 +50,13 @@ class CoeffWorkload:
         y, cb, cr = self.outs[k]
         self.jpeg.coefficients_device(self.ins[k], self.w, self.h, 2, self.ss, self.q, y, cb, cr, batch=self.batch, stream=self.stream)
 
+    def outputs(self, i):
+        """what step(i) handed its caller: the quantised Y, Cb and Cr blocks (int16, 64 per row, images of a batch one after
+        the other)"""
+        self.job.sync()
+        y, cb, cr = self.outs[i % self.nbuf]
+        return [("y", y.cpu().numpy()), ("cb", cb.cpu().numpy()), ("cr", cr.cpu().numpy())]
+
     def check(self):
         """correctness inside the bench: buffer 0 against the oracle on a 64-row strip (Y, Cb and Cr)"""
         import oracle_lib as O
@@ -132,6 +139,17 @@ class PngWorkload:
         k = i % self.nbuf
         self.png.apply_filters_async(self.ins[k], self.w, self.h, self.bpp, self.outs[k], self.sums[k], self.scratch,
                                      self.png.FilterStrategy.ADAPTIVE, 0, self.stream)
+
+    def outputs(self, i):
+        """what step(i) handed its caller: the filtered stream (a filter byte + the filtered row, row by row), the per-row
+        Adler-32 sums and the Adler-32 they make"""
+        import numpy as np
+        self.job.sync()
+        k = i % self.nbuf
+        sums = self.sums[k].cpu().numpy()
+        adler = self.png.adler32_from_row_sums(sums.view(np.uint64), self.w, self.h, self.bpp)
+        filtered = self.outs[k].cpu().numpy().reshape(self.h, -1)
+        return [("filtered", filtered), ("row_sums", sums.reshape(self.h, 2)), ("adler32", np.array([adler], dtype=np.int64))]
 
     def check(self):
         """buffer 0 against the reference-made vector of SURVEY §8c (rank 0's input is that very image)"""

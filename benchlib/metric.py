@@ -12,14 +12,23 @@ from .multi import *  # noqa: F401,F403
 from . import multi as _multi  # noqa: F401
 
 
+def write_outputs(job, args, wl):
+    """--dump-outputs: what the last timed step computed (rank 0; nothing for --stub, whose step computes nothing)"""
+    if args.dump_outputs and job.rank == 0 and not job.stub:
+        shapes = dump_outputs(args.dump_outputs, wl.outputs(job.last_step))
+        sys.stderr.write("bench: outputs of step %d written to %s: %s\n" % (job.last_step, args.dump_outputs, shapes))
+
+
 def run_coeffs(job, args):
     wl = CoeffWorkload(job, args.workload, args.quality)
     settled = job.settle(wl.step, 0 if job.stub else args.settle_ms)
     walls, evs = job.time_blocks(wl.step, args.steps, args.warmup, args.blocks)
-    if job.rank == 0 and job.world == 1:
+    write_outputs(job, args, wl)
+    full = args.full and not os.environ.get("PIXO_BENCH_ABLATION")
+    if args.full and job.rank == 0 and job.world == 1:
         measure_engine_clock(job)
     copy_ms = None
-    if job.rank == 0 and not job.stub and job.world == 1 and wl.batch == 1:
+    if args.full and job.rank == 0 and not job.stub and job.world == 1 and wl.batch == 1:
         # right behind the metric's blocks, same clocks, same protocol: the plain copy of the kernel's bytes; then the
         # kernel once more, so that the pair (kernel, copy) is also available in the order copy -> kernel
         try:
@@ -33,9 +42,9 @@ def run_coeffs(job, args):
         except BaseException as ex:  # the metric must not depend on the comparison
             copy_ms = None
             sys.stderr.write("bench: same-run copy failed: %r\n" % (ex,))
-    if job.rank == 0 and not job.stub and not os.environ.get("PIXO_BENCH_ABLATION"):
+    if full and job.rank == 0 and not job.stub:
         wl.check()
-    multi = (not args.no_extras) and args.workload == "c2" and not os.environ.get("PIXO_BENCH_ABLATION")
+    multi = full and (not args.no_extras) and args.workload == "c2"
     if job.rank != 0:
         if multi:
             del wl
@@ -64,14 +73,17 @@ def run_coeffs(job, args):
                    "settle_launches_before_warmup": settled,
                    "timing": "median of %d blocks of %d steps, each block barrier+synchronize bracketed, max over ranks" % (st["blocks"], args.steps),
                    "parallelism": "one process per GPU, images sharded across ranks, no collective"},
-        "roofline": wl.roofline(kernel_ms, copy_ms),
     }
+    if not args.full:  # a plain run: the headline figure and nothing else
+        job.finish(line)
+        return
+    line["roofline"] = wl.roofline(kernel_ms, copy_ms)
     if copy_ms:
         line["roofline"]["kernel_us_after_copy"] = round(kernel_after_copy_ms * 1e3, 3)
     if evs:
         per = sorted(e / args.steps * 1e3 for e in evs)
         line["roofline"]["kernel_us_block_min"], line["roofline"]["kernel_us_block_max"] = round(per[0], 3), round(per[-1], 3)
-    extras = (not args.no_extras) and job.world == 1 and not job.stub and not os.environ.get("PIXO_BENCH_ABLATION")
+    extras = full and (not args.no_extras) and job.world == 1 and not job.stub
     if extras and wl.batch == 1 and args.workload in ("c2", "c2_444"):
         line["whole_file"] = whole_file(job, wl)
         line["small_files"] = small_files(wl)
@@ -135,18 +147,15 @@ def run_png(job, args):
     wl = PngWorkload(job)
     settled = job.settle(wl.step, args.settle_ms)
     walls, evs = job.time_blocks(wl.step, args.steps, args.warmup, args.blocks)
-    if job.rank == 0 and job.world == 1:
+    write_outputs(job, args, wl)
+    if args.full and job.rank == 0 and job.world == 1:
         measure_engine_clock(job)
-    if job.rank == 0 and not os.environ.get("PIXO_BENCH_ABLATION"):
+    if args.full and job.rank == 0 and not os.environ.get("PIXO_BENCH_ABLATION"):
         wl.check()
     if job.rank != 0:
         job.finish()
         return
     st = block_stats(walls, args.steps)
-    kernel_ms = statistics.median(evs) / args.steps
-    alg = wl.in_bytes + wl.out_bytes
-    achieved = alg / (kernel_ms * 1e-3) / 1e9
-    traffic, src = traffic_of("c5")
     line = {"metric": "Mpixels/s PNG row filters + Adler-32 partials (Adaptive), 4096x4096 RGBA8",
             "value": round(wl.w * wl.h * job.world / (st["ms_per_step"] * 1e-3) / 1e6, 1),
             "unit": "Mpixels/s", "n_gpus": job.world, "steps": args.steps, "warmup": args.warmup,
@@ -155,11 +164,18 @@ def run_png(job, args):
             "dtype": "u8", "data": "synthetic",
             "config": {"workload": "configs[4]: 4096x4096 RGBA8, FilterStrategy::Adaptive, rows independent", "width": wl.w, "height": wl.h,
                        "buffers_rotated": wl.nbuf, "settle_launches_before_warmup": settled,
-                       "parallelism": "one process per GPU, images sharded across ranks, no collective"},
-            "roofline": {"bound": bound_of(achieved / HBM_PEAK_GBPS, issue_of("c5", kernel_ms * 1e3)), "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": src,
-                         **issue_of("c5", kernel_ms * 1e3),
-                         "kernel": "png_filter_kernel<4, true>", "algorithmic_bytes_per_launch": alg, "kernel_us_avg": round(kernel_ms * 1e3, 3)}}
+                       "parallelism": "one process per GPU, images sharded across ranks, no collective"}}
+    if not args.full:  # a plain run: the headline figure and nothing else
+        job.finish(line)
+        return
+    kernel_ms = statistics.median(evs) / args.steps
+    alg = wl.in_bytes + wl.out_bytes
+    achieved = alg / (kernel_ms * 1e-3) / 1e9
+    traffic, src = traffic_of("c5")
+    line["roofline"] = {"bound": bound_of(achieved / HBM_PEAK_GBPS, issue_of("c5", kernel_ms * 1e3)), "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
+                        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": src,
+                        **issue_of("c5", kernel_ms * 1e3),
+                        "kernel": "png_filter_kernel<4, true>", "algorithmic_bytes_per_launch": alg, "kernel_us_avg": round(kernel_ms * 1e3, 3)}
     if job.world == 1 and not args.no_extras:
         with_copy(job, line["roofline"], wl.in_bytes, wl.out_bytes, kernel_ms * 1e3, line["roofline"], steps=args.steps)
     if not args.no_cpu_baseline and job.world == 1:

@@ -71,12 +71,14 @@ def gather_phases(job, ph):
     return got
 
 
-def measure_c4(job, q, steps, warmup, blocks, settle_ms, shared_arena=False):
+def measure_c4(job, q, steps, warmup, blocks, settle_ms, shared_arena=False, full=True):
     """configs[3]: MCU-row bands of ONE 16384x16384 image resident on the N GPUs; a step = the finished file on rank 0.
     Strong scaling: the image is fixed, every rank holds 1/N of it.  Every rank calls; rank 0 gets the result dict.
     shared_arena: the file is assembled in ONE node-shared, registered segment — every rank copies its band's body over its OWN
     PCIe link (1/N of the 178 MB each) instead of all bodies travelling to rank 0 over xGMI and then over rank 0's single link.
-    --stub: a 256x192 image through the host twins over gloo (plumbing), the oracle's file as the reference."""
+    --stub: a 256x192 image through the host twins over gloo (plumbing), the oracle's file as the reference.
+    full=False (a plain bench run): no kernel-only timing, no instrumented call, no comparison with the reference's file; rank 0's
+    result carries the last step's file as "_file" (uint8) instead."""
     import synth
     from pixo_amd import jpeg, sharded
     torch = job.torch
@@ -124,17 +126,17 @@ def measure_c4(job, q, steps, warmup, blocks, settle_ms, shared_arena=False):
             jpeg.coefficients_device(d_band, w, rows, 2, 1, q, ty, tcb, tcr, stream=stream)
 
         job.settle(kstep, settle_ms)
-        _, kev = job.time_blocks(kstep, 20, 5, 5)
+        _, kev = job.time_blocks(kstep, 20, 5, 5) if full else (None, None)
         del ty, tcb, tcr
     try:
         walls, _ = job.time_blocks(step, steps, warmup, blocks, events=False)
         # one more, instrumented call: where a step's time goes on every rank (diagnosis of the first node run)
         ph = {}
-        if job.stub:
+        if full and job.stub:
             sharded.encode_banded(mine, opts, coeff_fn=lambda sub, o: O.coeffs(sub, o.width, o.height, 2, 1, o.quality), shared=shared, phases=ph)
-        else:
+        elif full:
             sharded.encode_banded(d_band, opts, device=job.gpu_index, out=out, shared=shared, phases=ph)
-        state["phases"] = gather_phases(job, ph)
+        state["phases"] = gather_phases(job, ph) if full else None
         if job.rank == 0 and shared is not None and not job.stub:
             out = torch.from_numpy(shared.array()[: state["len"]].copy())
     finally:
@@ -143,7 +145,11 @@ def measure_c4(job, q, steps, warmup, blocks, settle_ms, shared_arena=False):
             shared.close(unlink=job.rank == 0)
     if job.rank != 0:
         return None
-    if job.stub:
+    if not full:
+        import numpy as np
+        last = np.frombuffer(state["file"], dtype=np.uint8) if job.stub else out[: state["len"]].numpy().copy()
+        n, digest = last.size, None
+    elif job.stub:
         blob = state["file"]
         n, digest = len(blob), hashlib.sha256(blob).hexdigest()
         want = hashlib.sha256(O.encode(synth.noise(w, h, 42), O.make_options(w, h, 2, q, 1))).hexdigest()
@@ -166,6 +172,8 @@ def measure_c4(job, q, steps, warmup, blocks, settle_ms, shared_arena=False):
                       "parallelism": "one process per GPU, one band per rank"},
            "phases_ms_by_rank": state.get("phases"),
            "roofline": None}
+    if not full:
+        res["_file"] = last
     if kev:
         kernel_ms = statistics.median(kev) / 20
         alg = 6 * w * rows
@@ -180,12 +188,15 @@ def run_c4(job, args):
     steps = max(1, min(args.steps, 20))
     warmup = max(1, min(args.warmup, 3))
     try:
-        res = measure_c4(job, args.quality, steps, warmup, max(3, min(args.blocks, 7)), args.settle_ms)
+        res = measure_c4(job, args.quality, steps, warmup, max(3, min(args.blocks, 7)), args.settle_ms, full=args.full)
     except RuntimeError as ex:
         raise SystemExit("bench: %s — refusing to report a number" % ex)
     if job.rank != 0:
         job.finish()
         return
+    last = res.pop("_file", None)
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, [("file", last)])
     line = {"metric": "Mpixels/s JPEG encode, whole file, one 16384x16384 RGB8 image q=80 4:2:0 across the GPUs (configs[3])",
             "value": res["value"], "unit": "Mpixels/s", "n_gpus": job.world, "steps": steps, "warmup": warmup,
             "ms_per_step": res["ms_per_step"], "ms_per_step_min": res["ms_per_step_min"], "ms_per_step_max": res["ms_per_step_max"],
@@ -430,8 +441,11 @@ def run_c4_single_process(job, args):
     steps = max(1, min(args.steps, 5))
     walls, _ = job.time_blocks(step, steps, 1, max(3, min(args.blocks, 5)), events=False)
     blob = state["file"]
+    if args.dump_outputs:
+        import numpy as np
+        dump_outputs(args.dump_outputs, [("file", np.frombuffer(blob, dtype=np.uint8))])
     digest = hashlib.sha256(blob).hexdigest()
-    if (len(blob) != 178548465 or digest != C4_SHA256) and not os.environ.get("PIXO_BENCH_ABLATION"):
+    if args.full and (len(blob) != 178548465 or digest != C4_SHA256) and not os.environ.get("PIXO_BENCH_ABLATION"):
         raise SystemExit("bench: the 16384x16384 file differs from the reference's — refusing to report a number")
     st = block_stats(walls, steps)
     line = {"metric": "Mpixels/s JPEG encode, whole file from host pixels, one 16384x16384 RGB8 image q=80 4:2:0 across the GPUs of one process (configs[3])",

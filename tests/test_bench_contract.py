@@ -4,6 +4,8 @@ the metric BASELINE.json names and a self-consistent roofline object; `--gpus N`
 import json
 import os
 
+import pytest
+
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 
 
@@ -41,7 +43,7 @@ def test_committed_bench_line_follows_the_contract():
 def _stub_line(gpus, extra=()):
     import subprocess, sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--gpus", str(gpus), "--steps", "4", "--warmup", "1",
-                        "--blocks", "3", "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=300)
+                        "--blocks", "3", "--no-cpu-baseline", "--full", *extra], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout  # stdout carries ONE line: the JSON (libraries' banners go to stderr)
@@ -85,7 +87,7 @@ def test_bench_refuses_a_launcher_world_that_differs_from_gpus():
 def test_bench_parses_its_flags_without_a_gpu():
     import subprocess, sys
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, check=True).stdout.decode()
-    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--blocks", "c4", "c2_unaligned"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--blocks", "c4", "c2_unaligned", "--full", "--dump-outputs"):
         assert flag in out
 
 
@@ -96,7 +98,7 @@ def test_a_stuck_multi_gpu_leg_cannot_take_the_metric_line_with_it():
     import subprocess, sys
     code = r'''
 import sys, time
-sys.argv = ["bench.py", "--stub", "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "3", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--stub", "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "3", "--no-cpu-baseline", "--full"]
 import bench
 import benchlib.multi
 benchlib.multi.MULTI_LEGS_DEADLINE_S = 2.0
@@ -109,3 +111,79 @@ bench.main()
     assert len(lines) == 1
     line = json.loads(lines[0])
     assert line["value"] > 0 and line["n_gpus"] == 1 and "abandoned" in line["other_configs"]["multi_gpu_legs"]["error"]
+
+
+def test_a_plain_run_times_exactly_its_steps_and_prints_only_the_headline():
+    """Without --full the line carries the headline figure alone: one block of exactly --steps steps, no roofline, no other
+    configurations, no multi-GPU legs, no CPU baselines (--stub: plumbing only, the step is a sleep)."""
+    import subprocess, sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--gpus", "1", "--steps", "7", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert key in line, key
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["blocks"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "Mpixels/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["ms_per_step"] > 0
+    for key in ("roofline", "other_configs", "rccl", "cpu_baseline", "cpu_reference", "whole_file", "small_files"):
+        assert key not in line, key
+
+
+def test_dumped_outputs_are_exact_floats_under_the_cap_and_the_same_sample_every_time(tmp_path):
+    import numpy as np
+    from benchlib.common import DUMP_BUDGET_BYTES, dump_outputs
+    rng = np.random.default_rng(1)
+    y = rng.integers(-2048, 2048, size=(262144, 64), dtype=np.int16)  # 64 MiB as float32: over the cap alone
+    cb = rng.integers(-2048, 2048, size=(65536, 64), dtype=np.int16)
+    sums = rng.integers(0, 1 << 40, size=(4096, 2), dtype=np.int64)  # wider than float32's mantissa
+    one = np.array([0x90CC12E3], dtype=np.int64)
+    arrays = [("y", y), ("cb", cb), ("sums", sums), ("one", one)]
+    shapes = dump_outputs(str(tmp_path / "a"), arrays)
+    dump_outputs(str(tmp_path / "b"), arrays)
+    total = 0
+    for name, a in arrays:
+        got = np.load(tmp_path / "a" / (name + ".npy"))
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+        assert got.dtype == (np.float32 if a.dtype.itemsize <= 2 else np.float64), name
+        assert list(got.shape) == shapes[name] and got.shape[1:] == a.shape[1:] and 0 < got.shape[0] <= a.shape[0], name
+        assert np.array_equal(got, np.load(tmp_path / "b" / (name + ".npy"))), name  # the same rows in every run
+        # every row written is a row of the array, exactly
+        full = a.astype(got.dtype)
+        keys = {r.tobytes() for r in full.reshape(full.shape[0], -1)}
+        assert all(r.tobytes() in keys for r in got.reshape(got.shape[0], -1)), name
+    assert total <= 64 * 10**6 and DUMP_BUDGET_BYTES <= 64 * 10**6
+    assert np.array_equal(np.load(tmp_path / "a" / "one.npy"), one.astype(np.float64))
+    small = dump_outputs(str(tmp_path / "c"), [("cb", cb)])  # under the cap: everything, in order
+    assert small["cb"] == [65536, 64] and np.array_equal(np.load(tmp_path / "c" / "cb.npy"), cb.astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_of_a_plain_run_are_the_oracle_coefficients_of_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (the metric's workload, c2): DIR holds the Y, Cb and Cr blocks of the
+    last timed step — buffer (W + K - 1) mod buffers_rotated, whose pixels are noise(4096, 4096, 42) XOR that index — and they are
+    the oracle's coefficients of those pixels, sampled by the same rule."""
+    import subprocess, sys
+    import numpy as np
+    import oracle_lib as O
+    import synth
+    from benchlib.common import dump_outputs
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[:2000]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["blocks"] == 1 and line["value"] > 0 and "roofline" not in line
+    k = (2 + 3 - 1) % line["config"]["buffers_rotated"]
+    px = synth.noise(4096, 4096, 42)
+    if k:
+        px = px ^ np.uint8(k)
+    oy, ocb, ocr = O.coeffs(px, 4096, 4096, 2, 1, 80)
+    dump_outputs(str(tmp_path / "want"), [("y", oy), ("cb", ocb), ("cr", ocr)])
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 10**6
+    for name in ("y", "cb", "cr"):
+        got, want = np.load(out / (name + ".npy")), np.load(tmp_path / "want" / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == want.shape and np.array_equal(got, want), name

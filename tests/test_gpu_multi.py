@@ -274,7 +274,7 @@ def test_world_of_one_rccl_batch_and_bench_legs_of_a_multi_gpu_run():
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "BATCH_OK" in r.stdout, r.stderr[-3000:]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--blocks", "3",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     import json
     assert [l[:1] for l in r.stdout.splitlines() if l.strip()] == ["{"], r.stdout[:2000]  # ONE line on stdout, RCCL's banner included in stderr
@@ -399,7 +399,7 @@ def test_bench_run_of_two_ranks_sharing_the_gpu_measures_every_multi_gpu_leg():
     import json
     env = dict(os.environ, PIXO_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--blocks", "3",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=env)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[:2000]
