@@ -359,6 +359,10 @@ int pixo_hip_debug_configure(const char *switches_or_null);
 /* How often a single-pass entropy kernel gave up waiting (its waits on other workgroups are bounded) and the scan was
  * coded again by the multi-pass kernels, in this process.  0 in normal operation. */
 uint64_t pixo_hip_debug_lookback_fallbacks(void);
+/* Tests only: the set of internal routes (which kernel forms, stores and retries) that served calls in this process since the
+ * record was last cleared, one bit per route (pixo_amd/csrc/capi_internal.hpp, namespace route; mirrored in pixo_amd/jpeg.py).
+ * clear != 0: the record starts empty again.  Process-wide: calls of other threads show up too. */
+uint64_t pixo_hip_debug_routes(int clear);
 /* The dispatch gate of the single-pass kernels (pixo_amd/csrc/dispatch_gate.hpp: calls of several threads are kept from
  * starting such kernels on an empty device at the same moment — two launches that split the device's workgroup slots wait for
  * each other until the bounded waits give up): how often a launch found the launch before it, another thread's, not yet fully

@@ -292,6 +292,7 @@ int pixo_hip_jpeg_splice_layout(const pixo_jpeg_options *options, const uint64_t
 int pixo_hip_jpeg_splice_finish(const pixo_jpeg_options *options, const uint64_t *total_counts, const uint8_t *piece_headers,
                                 uint32_t parts, uint8_t *file, size_t file_len)
 {
+    CallerStorageScope storage(file && file_len);
     PIXO_REQUIRE(options);
     PIXO_REQUIRE(piece_headers);
     PIXO_REQUIRE(file);
@@ -487,6 +488,7 @@ int pixo_hip_jpeg_encode_multi(const uint8_t *data, size_t data_len, const pixo_
         return rc;
     }
     const uint32_t parts = n_devices;
+    note_route(route::BANDS_MULTI);
     const size_t bpp = whole.gray ? 1 : 3;
     struct Band {
         pixo_hip_band_encoder *enc = nullptr;
@@ -620,6 +622,7 @@ void drop_batch_worker_buffers()
 int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options *options, uint32_t batch, const int *devices, uint32_t n_devices,
                                      uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens)
 {
+    CallerStorageScope storage(arena && capacity);
     PIXO_REQUIRE(options);
     PIXO_REQUIRE(devices);
     PIXO_REQUIRE(offsets);

@@ -10,8 +10,11 @@ namespace pixo_capi {
 
 thread_local std::string t_error = "";
 
+thread_local bool t_caller_storage = false;
+
 int fail(int code, const std::string &msg)
 {
+    if (code == PIXO_ERR_BUFFER_TOO_SMALL && t_caller_storage) note_route(route::CALLER_RETRY);
     t_error = msg;
     return code;
 }

@@ -23,6 +23,7 @@ int encode_to_view(const uint8_t *data, size_t data_len, const pixo_jpeg_options
     const pixo_host::Geometry g = pixo_host::geometry(o.width, o.height, o.color_type, o.subsampling);
     Context &c = thread_context();
     if (!o.progressive && debug().host_entropy) { // (experiments: the host twin of the entropy stage)
+        note_route(route::HOST_ENTROPY);
         const int16_t *y, *cb, *cr;
         if ((rc = coeffs_to_pinned(c, data, o, g, &y, &cb, &cr))) return rc;
         pixo_host::encode_file(y, cb, cr, o, spill);
@@ -100,6 +101,7 @@ int pixo_hip_jpeg_encode(const uint8_t *data, size_t data_len, const pixo_jpeg_o
 int pixo_hip_jpeg_encode_into(uint8_t *output, size_t capacity, const uint8_t *data, size_t data_len,
                               const pixo_jpeg_options *options, size_t *out_len)
 {
+    CallerStorageScope storage(output && capacity);
     PIXO_REQUIRE(options);
     PIXO_REQUIRE(out_len);
     if (capacity && !output) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'output'");
@@ -330,6 +332,7 @@ int pixo_hip_jpeg_encode_device(const void *d_pixels, const pixo_jpeg_options *o
 int pixo_hip_jpeg_encode_device_into(const void *d_pixels, const pixo_jpeg_options *options, uint8_t *output, size_t capacity,
                                      size_t *out_len)
 {
+    CallerStorageScope storage(output && capacity);
     PIXO_REQUIRE(options);
     PIXO_REQUIRE(out_len);
     std::string msg;
@@ -493,6 +496,7 @@ int pixo_hip_jpeg_encode_batch_device(const void *d_pixels, const pixo_jpeg_opti
 int pixo_hip_jpeg_encode_batch_device_into(const void *d_pixels, const pixo_jpeg_options *options, uint32_t batch,
                                            uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens)
 {
+    CallerStorageScope storage(arena && capacity);
     PIXO_REQUIRE(options);
     PIXO_REQUIRE(offsets);
     PIXO_REQUIRE(lens);
@@ -566,9 +570,13 @@ int pixo_hip_jpeg_encode_batch_device_into(const void *d_pixels, const pixo_jpeg
         return 1;
     };
     uint32_t parts = parts_for(c->batch_per_block);
-    if (debug().batch_parts) parts = std::min<uint32_t>(debug().batch_parts, batch);
+    if (debug().batch_parts) parts = debug().batch_parts;
+    // (every sub-batch holds two images or more: a sub-batch of one would take the single-image path, whose files are not
+    // left in the context's buffer at their batch spacing — no image starts to place them by)
+    parts = std::max<uint32_t>(std::min<uint32_t>(parts, batch / 2), 1);
     Context *second = nullptr;
     if (parts > 1) {
+        note_route(route::SUB_BATCHES);
         second = pool().take(c->device);
         if (second && (second->ensure() || order_after_producer(*second))) { pool().give(second); second = nullptr; }
     }
@@ -583,6 +591,10 @@ int pixo_hip_jpeg_encode_batch_device_into(const void *d_pixels, const pixo_jpeg
         std::vector<uint64_t> starts;
         bool gaps = false;
         if ((rc = batch_on_device(cx, static_cast<const uint8_t *>(d_pixels) + static_cast<size_t>(first) * px_bytes, o, g, nb, head, starts, &gaps))) break;
+        if (starts.size() < static_cast<size_t>(nb) + 1) { // (the layout below needs where every image's bytes begin)
+            rc = fail(PIXO_ERR_COMPRESSION, "Compression error: sub-batch of " + std::to_string(nb) + " image(s) without image starts");
+            break;
+        }
         const size_t hdr = head.size(), gap = gaps ? hdr + 2 : 0;
         const size_t at0 = at;
         for (uint32_t i = 0; i < nb; ++i) {
@@ -657,6 +669,7 @@ int pixo_hip_jpeg_encode_batch_device_into(const void *d_pixels, const pixo_jpeg
 }
 
 uint64_t pixo_hip_debug_lookback_fallbacks(void) { return lookback_fallbacks(); }
+uint64_t pixo_hip_debug_routes(int clear) { return take_routes(clear != 0); }
 int pixo_hip_debug_dispatch_gate(uint64_t *waits, uint64_t *timeouts)
 {
     unsigned long long w = 0, t = 0;

@@ -10,6 +10,7 @@
 #include <atomic>
 
 
+#include "capi_internal.hpp" // (route record)
 #include "jpeg_kernels.hpp"
 #include "jpeg_tile.h"
 
@@ -230,7 +231,9 @@ void set_coef_form(int form) { g_coef_form.store(form, std::memory_order_relaxed
 bool packed_launch(uint64_t workgroups)
 {
     const int form = g_coef_form.load(std::memory_order_relaxed);
-    return form == 1 ? false : (form == 2 ? true : workgroups > 2048);
+    const bool packed = form == 1 ? false : (form == 2 ? true : workgroups > 2048);
+    pixo_capi::note_route(packed ? pixo_capi::route::COEF_PACKED : pixo_capi::route::COEF_SCALAR);
+    return packed;
 }
 
 // The late start of dispatch numbers 1024..2047 assumes that 2048 workgroups are ONE resident generation: the whole MI355X
@@ -273,6 +276,8 @@ template <int MODE, int LOAD> static hipError_t launch_mode(KArgs &a, hipStream_
 
 template <int MODE> static hipError_t launch_load(int load, KArgs &a, hipStream_t s)
 {
+    namespace r = pixo_capi::route;
+    pixo_capi::note_route(load == L_ALIGNED ? r::LOAD_ALIGNED : (load == L_FUNNEL ? r::LOAD_FUNNEL : r::LOAD_BYTES));
     if (load == L_ALIGNED) return launch_mode<MODE, L_ALIGNED>(a, s);
     if (load == L_FUNNEL) return launch_mode<MODE, L_FUNNEL>(a, s);
     return launch_mode<MODE, L_BYTES>(a, s);

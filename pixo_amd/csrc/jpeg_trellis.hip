@@ -17,6 +17,7 @@
 
 #include "jpeg_trellis.h"
 #include "jpeg_trellis.hpp"
+#include "capi_internal.hpp" // (route record)
 
 #pragma clang fp contract(off)
 
@@ -200,6 +201,7 @@ hipError_t launch_trellis(const float *d_raw, const float *d_q_luma, const float
     // eight lanes per block while the one-lane form's wavefronts (64 blocks each) would leave SIMDs idle anyway
     const int form = g_trellis_form.load(std::memory_order_relaxed);
     const bool lanes = form == 2 || (form == 0 && nblocks <= kTrellisLanesBlocks);
+    pixo_capi::note_route(lanes ? pixo_capi::route::TRELLIS_GROUP : pixo_capi::route::TRELLIS_LANE);
     if (lanes)
         hipLaunchKernelGGL(trellis_lanes_kernel, dim3((unsigned)((nblocks + kGroupsPerWave - 1) / kGroupsPerWave)), dim3(64), 0, s, d_raw, d_q_luma,
                            d_q_chroma, d_out, nblocks, nluma);

@@ -109,6 +109,7 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
                           const PixelSource *src)
 { // dst: where the stuffed scan goes on the host (dst_cap bytes available); tables are uploaded, j.a is set up
     namespace pd = pixo_dev;
+    note_route(route::PIECES | route::TWO_KERNEL | route::SINGLE_PASS_TUPLE | (src && src->host_px ? route::HOST_BANDS : 0));
     const uint64_t kGroupBlocks = 192, groups = (j.n + kGroupBlocks - 1) / kGroupBlocks;
     // where the pieces begin (in groups).  A large scan: equal pieces of at least piece_min_groups().  A medium one (a
     // 4096x4096 image): a few pieces that GROW — the first small, so that its bytes leave early, each next one coded
@@ -381,6 +382,8 @@ static int device_entropy_to_pinned_once(Context &c, const int16_t *dy, const in
     // as it does for the pieces.  profiles/r06_long_groups_chain.txt)
     const bool dense_stream = batch == 1 && c.last_scan_blocks && c.last_scan_bytes > 30 * c.last_scan_blocks && !debug().fused_batch;
     const bool from_pixels = src && !dense_stream && pixels_code_usable(j, o, g, batch);
+    if (src && dense_stream && pixels_code_usable(j, o, g, batch)) note_route(route::DENSE_STREAM_RULE);
+    if (batch > 1) note_route(from_pixels ? route::BATCH_FUSED : route::BATCH_TWO_KERNEL);
     if (from_pixels && batch > 1 && gaps_left) *gaps_left = j.seg_gap == seg_gap && seg_gap != 0; // (the fused kernel leaves any gap between its segments)
     // Second session of round 6: a LARGE scan from device pixels takes the fused kernel too when its stores can go straight to where the file
     // is wanted (the library's pinned buffer, or storage of the caller's the GPU can write) — one kernel whose groups finish one after
@@ -440,6 +443,7 @@ static int device_entropy_to_pinned_once(Context &c, const int16_t *dy, const in
             return PIXO_OK;
         }
         c.code_state_zero_words = 0; // (rc == 1: start over in one piece, below)
+        note_route(route::PIECES_REDO);
     }
     if ((rc = upload_all())) return rc;
     const bool fuse_now = from_pixels && src; // (src is null once a pieces attempt above has computed the tuple)
@@ -473,6 +477,7 @@ static int device_entropy_to_pinned_once(Context &c, const int16_t *dy, const in
         // early ones cross PCIe while the late ones are still coding — 4096x4096 photo-like content 0.129 -> 0.112 ms, noise
         // (11 MB, PCIe-bound either way) 0.291 -> 0.283 ms against kernel + copy engine (profiles/r05_whole_file.txt).
         if (batch == 1 && !j.segmented && (direct_host_stores() || small_file || (fuse_now && !debug().no_direct_small))) {
+            head.clear(); // (a pieces attempt above that started over has written them once already)
             pixo_host::file_headers(head, o, j.h); // (the tables are known since scan_lengths)
             if (!dest) {
                 target.grow = true;
@@ -490,6 +495,7 @@ static int device_entropy_to_pinned_once(Context &c, const int16_t *dy, const in
                 }
             }
         }
+        if (direct && !fuse_now) note_route(route::DIRECT_STORES);
         if (fuse_now) rc = scan_from_pixels(c, j, o, g, stream, src->d_px, direct ? &target : nullptr, /*wait=*/true, batch);
         else rc = scan_stuff_fused(c, j, stream, 0, nullptr, nullptr, nullptr, /*chained=*/true, direct ? &target : nullptr);
         if (rc) return rc;
@@ -783,6 +789,7 @@ int hand_over(const std::vector<uint8_t> &v, uint8_t **out, size_t *out_len)
 int device_tuple_to_malloc(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
                            const pixo_host::Geometry &g, Context &c, uint8_t **out, size_t *out_len)
 {
+    if (debug().host_entropy) note_route(route::HOST_ENTROPY);
     if (!debug().host_entropy) {
         if (!o.progressive) return device_entropy_to_malloc(c, dy, dcb, dcr, o, g, c.stream, out, out_len);
         pixo_host::HuffSet h;

@@ -132,6 +132,7 @@ extern "C" {
 int pixo_hip_png_filter(const uint8_t *data, size_t data_len, uint32_t width, uint32_t height, uint32_t bytes_per_pixel,
                         uint8_t strategy, uint32_t flags, uint8_t *out, size_t out_capacity, uint32_t *adler32)
 {
+    CallerStorageScope storage(out && out_capacity);
     int run = 0;
     bool seq = false;
     int rc = png_plan(width, height, bytes_per_pixel, strategy, flags, &run, &seq);

@@ -14,6 +14,7 @@
 // written once: no intermediate in HBM.  Byte work bounded by HBM and VALU issue; no MFMA.
 #include <hip/hip_runtime.h>
 
+#include "capi_internal.hpp" // (route record)
 #include "jpeg_kernels.hpp"
 #include "png_filter.hpp"
 #include "png_filter_math.h"
@@ -534,23 +535,33 @@ __global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const Args a
 template <int BPP> hipError_t launch_bpp(const Args &a, uint32_t rows, bool fast, hipStream_t s)
 {
     const uint64_t ndw = (a.row_bytes + 3) / 4;
+    namespace r = pixo_capi::route;
     if (a.strategy == PNG_S_BIGRAMS && a.stage_bytes != 0 && ndw <= (uint64_t)kRegIters * kThreads * 4) {
+        pixo_capi::note_route(r::PNG_BIGRAMS_REGS);
         const uint32_t lds = a.stage_bytes + 2 * 8192u + 4u * (kRegIters * kThreads + 1); // stage | two bitmaps | exchange array
         if (fast) hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, true>), dim3(rows), dim3(kThreads), lds, s, a);
         else hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, false>), dim3(rows), dim3(kThreads), lds, s, a);
     } else if (a.strategy == PNG_S_BIGRAMS) {
+        pixo_capi::note_route(r::PNG_BIGRAMS);
         const uint32_t lds = a.stage_bytes + 8192u;
         if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_BIGRAMS>), dim3(rows), dim3(kThreads), lds, s, a);
         else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_BIGRAMS>), dim3(rows), dim3(kThreads), lds, s, a);
     } else if (a.strategy > PNG_S_PAETH && !a.forced && ndw <= (uint64_t)kRegIters * 2 * kThreads * 4 && a.stage_bytes != 0) {
         // rows of up to 16 KiB: 256 threads hold them; up to 32 KiB: 512 threads
         if (ndw <= (uint64_t)kRegIters * kThreads * 4) {
+            pixo_capi::note_route(r::PNG_REGS);
             if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
             else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
-        } else if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS512>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
-        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS512>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
-    } else if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_GENERAL>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
-    else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_GENERAL>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+        } else {
+            pixo_capi::note_route(r::PNG_REGS512);
+            if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS512>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
+            else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS512>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
+        }
+    } else {
+        pixo_capi::note_route(r::PNG_GENERAL);
+        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_GENERAL>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_GENERAL>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+    }
     return hipGetLastError();
 }
 

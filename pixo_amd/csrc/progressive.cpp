@@ -212,6 +212,7 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
             if (rc_f) return rc_f;
             direct_host = direct_dev = c.h_file; direct_cap = c.hfile_cap;
         }
+        note_route(route::PROG_DIRECT_SMALL);
     }
     for (int attempt = 0;; ++attempt) {
         uint8_t *out = nullptr;
@@ -303,8 +304,9 @@ int device_progressive_scans(const int16_t *dy, const int16_t *dcb, const int16_
 {
     if (!debug().multipass_entropy) {
         const int rc = device_progressive_scans_fused(dy, dcb, dcr, g, h, c, head, file, file_len, pinned_dest, dest_cap);
-        if (rc != kRetryMultipass) return rc;
+        if (rc != kRetryMultipass) { if (rc == PIXO_OK) note_route(route::PROG_SINGLE_PASS); return rc; }
     }
+    note_route(route::PROG_MULTI_PASS | route::MULTI_PASS);
     return device_progressive_scans_multipass(dy, dcb, dcr, g, h, c, head, file, file_len, pinned_dest, dest_cap);
 }
 
@@ -368,6 +370,7 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
     const bool side_stats = late_tables && !debug().no_side_stats && g.y_blocks + 2 * g.c_blocks <= kSideStatsBlocks;
     hipStream_t stats_stream = c.stream;
     if (side_stats) {
+        note_route(route::SIDE_STATS);
         if (!c.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
         if (!c.side_ready) HIP_TRY(hipEventCreateWithFlags(&c.side_ready, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c.side_ready, c.stream)); // (the context's stream is ordered behind the pixels' producer)
@@ -416,6 +419,7 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
         split_counts(c.h_segs, dc, ac);
         h = pixo_host::HuffSet::optimized(dc, ac, !g.gray);
     }
+    if (debug().host_entropy) note_route(route::HOST_ENTROPY);
     if (!debug().host_entropy) {
         std::vector<uint8_t> head;
         pixo_host::file_headers(head, o, h);

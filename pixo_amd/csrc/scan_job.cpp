@@ -116,9 +116,14 @@ int scan_retry_multipass(Context &c)
 {
     c.code_state_zero_words = 0; // (the descriptors and the flag are dirty: the next single-pass launch starts with a memset)
     g_lookback_fallbacks.fetch_add(1, std::memory_order_relaxed);
+    note_route(route::FALLBACK);
     return kRetryMultipass;
 }
 uint64_t lookback_fallbacks() { return g_lookback_fallbacks.load(std::memory_order_relaxed); }
+
+static std::atomic<uint64_t> g_routes{0};
+void note_route(uint64_t bits) { g_routes.fetch_or(bits, std::memory_order_relaxed); }
+uint64_t take_routes(bool clear) { return clear ? g_routes.exchange(0, std::memory_order_relaxed) : g_routes.load(std::memory_order_relaxed); }
 
 constexpr uint64_t kMinSegBlocks = 96; // a segment's groups are aligned with it: at least half a group of 192 blocks
 
@@ -293,6 +298,7 @@ int scan_lengths(Context &c, ScanJob &j, const pixo_jpeg_options &o, const pixo_
         const int rc = scan_tables(c, j, o, g, stream, counts);
         if (rc) return rc;
     }
+    note_route(route::TWO_KERNEL | (j.segmented ? route::SEGMENTED_TUPLE : 0) | (j.fused ? route::SINGLE_PASS_TUPLE : route::MULTI_PASS));
     if (j.segmented) { // every segment packed into its own stream from bit 0; always chained with the stuffing kernel
         const size_t state_words = pd::fused_code_state_words_seg(j.seg.nsegs, j.seg.blocks);
         const bool zero = c.code_state_zero_words >= state_words;
@@ -377,6 +383,7 @@ int scan_from_pixels(Context &c, ScanJob &j, const pixo_jpeg_options &o, const p
     const bool segs = plan.segments > 1;
     const uint32_t gap = !segs ? 0u : (restart ? 2u : j.seg_gap); // RSTn, or what a batch wants between its files' scans
     const bool rst = segs && restart != 0;
+    note_route((segs ? route::FUSED_SEGMENTED : route::FUSED) | (host ? route::FUSED_DIRECT : 0));
     if (segs) { // (where every segment ends: the kernel's pinned mailbox, like the single-pass tuple kernels')
         if ((rc = c.reserve_hsegs(plan.segments))) return rc;
         j.pc_seg = true;
@@ -426,6 +433,7 @@ int scan_from_pixels(Context &c, ScanJob &j, const pixo_jpeg_options &o, const p
         if (j.scan_bytes > out_cap) { // (nothing was stored beyond the capacity: more room, the same kernel again)
             if (host && !host->grow) return PIXO_OK; // (the caller's storage is what it is: the caller reports the size needed)
             if (attempt > 1) return fail(PIXO_ERR_COMPRESSION, "Compression error: scan larger than announced");
+            note_route(route::RESTUFF_GROW);
             want_cap = static_cast<size_t>(j.scan_bytes);
             continue;
         }
@@ -470,6 +478,7 @@ int scan_stuff_segmented(Context &c, ScanJob &j, hipStream_t stream)
         j.scan_bytes = c.h_totals[1];
         if (j.scan_bytes > c.e_out.cap) { // (unusually many 0xFF bytes: grow and repeat the stuffing pass only)
             if (attempt > 2) return fail(PIXO_ERR_COMPRESSION, "Compression error: stuffed stream larger than announced");
+            note_route(route::RESTUFF_GROW);
             want_cap = static_cast<size_t>(j.scan_bytes);
             first_tile = 0;
             tiles = all_tiles;
@@ -541,6 +550,7 @@ int scan_stuff_fused(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_b
         if (j.scan_bytes > out_cap) { // (first call with unusually many 0xFF bytes: grow and repeat the stuffing pass only)
             if (host && !host->grow) return PIXO_OK; // (the caller's storage is what it is: the caller reports the size needed)
             if (attempt > 2) return fail(PIXO_ERR_COMPRESSION, "Compression error: stuffed stream larger than announced");
+            note_route(route::RESTUFF_GROW);
             want_cap = static_cast<size_t>(j.scan_bytes);
             first_tile = 0;
             tiles = pd::stuff_tiles(packed);

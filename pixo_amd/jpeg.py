@@ -509,6 +509,33 @@ def lookback_fallbacks() -> int:
     return int(_lib.load().pixo_hip_debug_lookback_fallbacks())
 
 
+# The route record (include/pixo_hip.h pixo_hip_debug_routes): one bit per internal route, as pixo_amd/csrc/capi_internal.hpp
+# (namespace route) defines them.
+ROUTES = {
+    "FUSED": 0, "FUSED_SEGMENTED": 1, "FUSED_DIRECT": 2, "TWO_KERNEL": 3, "DENSE_STREAM_RULE": 4,
+    "SINGLE_PASS_TUPLE": 5, "MULTI_PASS": 6, "FALLBACK": 7, "HOST_ENTROPY": 8,
+    "PIECES": 9, "HOST_BANDS": 10, "DIRECT_STORES": 11, "RESTUFF_GROW": 12, "CALLER_RETRY": 13,
+    "COEF_PACKED": 14, "COEF_SCALAR": 15, "LOAD_ALIGNED": 16, "LOAD_FUNNEL": 17, "LOAD_BYTES": 18,
+    "PROG_SINGLE_PASS": 19, "PROG_DIRECT_SMALL": 20, "SIDE_STATS": 21, "TRELLIS_LANE": 22, "TRELLIS_GROUP": 23,
+    "BATCH_FUSED": 24, "BATCH_TWO_KERNEL": 25, "SUB_BATCHES": 26, "BANDS_MULTI": 27,
+    "PNG_REGS": 28, "PNG_GENERAL": 29, "PNG_BIGRAMS_REGS": 30, "PNG_BIGRAMS": 31,
+    "SEGMENTED_TUPLE": 32, "PROG_MULTI_PASS": 33, "PIECES_REDO": 34, "PNG_REGS512": 35,
+}
+for _name, _bit in ROUTES.items():
+    globals()["ROUTE_" + _name] = 1 << _bit
+del _name, _bit
+
+
+def debug_routes(clear: bool = True) -> int:
+    """The route bits (ROUTE_*) that served calls in this process since the record was last cleared; clear=True empties it."""
+    return int(_lib.load().pixo_hip_debug_routes(1 if clear else 0))
+
+
+def route_names(bits: int):
+    """The names of the ROUTES set in `bits`."""
+    return [n for n, b in ROUTES.items() if bits >> b & 1]
+
+
 def dispatch_gate_stats():
     """(waits, timeouts) of the single-pass kernels' dispatch gate (include/pixo_hip.h pixo_hip_debug_dispatch_gate; tests, tools)."""
     w, t = C.c_uint64(0), C.c_uint64(0)
