@@ -202,10 +202,8 @@ int pixo_hip_band_encoder_copy_body(pixo_hip_band_encoder *e, uint8_t *dst)
     const size_t body = static_cast<size_t>(e->job.scan_bytes);
     if (!body) return PIXO_OK;
     PIXO_REQUIRE(dst);
-    hipPointerAttribute_t attr;
-    const bool known = hipPointerGetAttributes(&attr, dst) == hipSuccess;
-    if (!known) (void)hipGetLastError(); // (plain malloc memory is "invalid value" to the runtime)
-    if (known && (attr.type == hipMemoryTypeHost || attr.type == hipMemoryTypeDevice)) {
+    const hipMemoryType dst_type = pointer_info(dst).type;
+    if (dst_type == hipMemoryTypeHost || dst_type == hipMemoryTypeDevice) {
         // registered / hipHostMalloc'd storage: the device-to-host copy is the only pass over the bytes;
         // device storage (e.g. the send buffer of a collective): device to device
         HIP_TRY(hipMemcpyAsync(dst, c.e_out.p, body, hipMemcpyDefault, c.stream));
@@ -641,9 +639,8 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
     // or in host memory (every GPU fetches its own images over its own PCIe link)
     int src_device = -1;
     {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, pixels) == hipSuccess && at.type == hipMemoryTypeDevice) src_device = at.device;
-        else (void)hipGetLastError(); // (plain host memory is "invalid value" to the runtime: not an error)
+        const PointerInfo at = pointer_info(pixels);
+        if (at.type == hipMemoryTypeDevice) src_device = at.device;
     }
     // Device pixels may still be being written on the caller's producer stream (pixo_hip_set_producer_stream; default: the NULL
     // stream).  The work below runs on worker threads with streams of their own: the caller's stream is drained first.

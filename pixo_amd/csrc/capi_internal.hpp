@@ -3,7 +3,9 @@
 //   context.cpp      error state, per-device table cache, the thread's Context (stream + grow-only buffers), the pool that
 //                    outlives threads, device selection, the debug-switch parser
 //   scan_job.cpp     coefficient launches on a context; one pass of the device entropy stage in the steps a band needs
-//   pieces.cpp       a scan coded in pieces while the file travels; device tuple / pixels -> whole baseline file
+//   baseline_file.cpp  device tuple / pixels -> whole baseline file: runs the route baseline_plan.hpp chooses, finishes the file
+//   pieces.cpp       a scan coded in pieces while the file travels (and the context's copy helper thread)
+//   host_memory.cpp  blocks for files the caller will own (kept large blocks, the pinned pool), copies into fresh memory
 //   progressive.cpp  preset 2: trellis tuple, the seven progressive scans
 //   jpeg_api.cpp     the extern "C" JPEG entry points
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
@@ -27,6 +29,8 @@
 #include "jpeg_kernels.hpp"
 #include "jpeg_pixels_code.hpp"
 #include "jpeg_scan_block.h" // (the table form of the flat walk: built on the host, see upload_scan_tables)
+#include "baseline_plan.hpp"
+#include "routes.hpp"
 
 namespace pixo_capi {
 
@@ -84,48 +88,7 @@ struct DebugSwitches {
 const DebugSwitches &debug();
 
 // ---- route record (tests: pixo_hip_debug_routes) ----------------------------------------------------------------------
-// Which of the library's forms served the calls since the record was last cleared: every decision point below ORs its bit
-// into one process-wide word (one relaxed fetch_or per decision, nothing on the device).  pixo_amd/jpeg.py mirrors the names.
-namespace route {
-enum : uint64_t {
-    FUSED = 1ull << 0,             // the fused pixel -> scan kernel (jpeg_pixels_code.hip), one uninterrupted scan
-    FUSED_SEGMENTED = 1ull << 1,   // ... its segments: the images of a batch or restart intervals of whole MCU rows
-    FUSED_DIRECT = 1ull << 2,      // ... storing straight into host memory the GPU can write
-    TWO_KERNEL = 1ull << 3,        // coefficient kernel + scan_code (a tuple in HBM coded by the entropy stage)
-    DENSE_STREAM_RULE = 1ull << 4, // the context's last file was dense: the fused kernel would have served, the two-kernel form did
-    SINGLE_PASS_TUPLE = 1ull << 5, // the single-pass tuple coders of jpeg_scan_fused.hip
-    MULTI_PASS = 1ull << 6,        // the multi-pass entropy kernels of jpeg_entropy.hip (baseline or progressive)
-    FALLBACK = 1ull << 7,          // a single-pass launch gave up waiting: the job ran again with the multi-pass kernels
-    HOST_ENTROPY = 1ull << 8,      // the host twin of the scan coders (debug switch host_entropy)
-    PIECES = 1ull << 9,            // a scan coded in pieces while the file travels (device_entropy_pieces)
-    HOST_BANDS = 1ull << 10,       // ... with host pixels uploaded in bands
-    DIRECT_STORES = 1ull << 11,    // the stuffing kernel stores straight into pinned host memory (baseline)
-    RESTUFF_GROW = 1ull << 12,     // the output buffer was short: grown, the stuffing pass repeated
-    CALLER_RETRY = 1ull << 13,     // the caller's storage was too small (PIXO_ERR_BUFFER_TOO_SMALL)
-    COEF_PACKED = 1ull << 14,      // packed DCT / quantiser forms (jpeg_kernels.hip packed_launch)
-    COEF_SCALAR = 1ull << 15,      // scalar forms
-    LOAD_ALIGNED = 1ull << 16,     // coefficient kernel: 12-byte loads of aligned rows
-    LOAD_FUNNEL = 1ull << 17,      // ... aligned dwords and shifts
-    LOAD_BYTES = 1ull << 18,       // ... byte gathers (images narrower than 4 pixels)
-    PROG_SINGLE_PASS = 1ull << 19, // progressive scans by the single-pass kernels
-    PROG_DIRECT_SMALL = 1ull << 20, // ... stored straight into host memory (small progressive files after a small one)
-    SIDE_STATS = 1ull << 21,       // preset 2, small images: the statistics on a second stream beside the search
-    TRELLIS_LANE = 1ull << 22,     // trellis search: one lane per block
-    TRELLIS_GROUP = 1ull << 23,    // ... eight lanes per block
-    BATCH_FUSED = 1ull << 24,      // a batch through the fused kernel, every image a segment
-    BATCH_TWO_KERNEL = 1ull << 25, // a batch through coefficient kernel + entropy stage
-    SUB_BATCHES = 1ull << 26,      // a batch in several sub-batches over two contexts
-    BANDS_MULTI = 1ull << 27,      // one image in bands over several devices (pixo_hip_jpeg_encode_multi)
-    PNG_REGS = 1ull << 28,         // PNG filter kernel: adaptive strategies with the row in the registers of 256 threads
-    PNG_GENERAL = 1ull << 29,      // ... the general form (fixed filters, or rows too long for registers)
-    PNG_BIGRAMS_REGS = 1ull << 30, // ... bigrams with the row in registers
-    PNG_BIGRAMS = 1ull << 31,      // ... bigrams, general form
-    SEGMENTED_TUPLE = 1ull << 32,  // the single-pass tuple coders over byte-aligned segments (batches, restart intervals)
-    PROG_MULTI_PASS = 1ull << 33,  // progressive scans by the multi-pass kernels
-    PIECES_REDO = 1ull << 34,      // a scan in pieces outgrew its guesses (0xFF bytes, dense content) and was coded again in one piece
-    PNG_REGS512 = 1ull << 35,      // PNG filter kernel: adaptive strategies, rows of 16-32 KiB in the registers of 512 threads
-};
-}
+// (the bits: routes.hpp)
 void note_route(uint64_t bits);
 uint64_t take_routes(bool clear);
 // route::CALLER_RETRY is noted by fail(PIXO_ERR_BUFFER_TOO_SMALL) only inside an entry point that was given storage of its
@@ -200,9 +163,10 @@ struct Context {
     std::vector<hipEvent_t> piece_done, band_up;
     uint32_t *h_tables = nullptr; // pinned staging of tables_held for the upload
     uint32_t tables_held[pixo_scan::kScanTableUpload]; bool tables_valid = false; hipStream_t tables_stream = nullptr; // what e_tables holds (no upload when unchanged)
-    uint32_t packed_per_block = 0; // bytes per block of the last whole scan this context coded (0: none yet), see device_entropy_to_pinned
     uint64_t last_prog_bytes = 0; // the last progressive file's entropy-coded bytes (small: the next one is stored directly)
-    uint64_t last_scan_bytes = 0, last_scan_blocks = 0; // ... exactly (a smooth image is below one byte per block): predicts the next file's size
+    // the last whole baseline scan this context coded (0 blocks: none yet; baseline_file.cpp remember_scan): predicts the next
+    // file's size and density (baseline_plan.hpp).  Exact: a smooth image is below one byte per block
+    uint64_t last_scan_bytes = 0, last_scan_blocks = 0;
     uint32_t batch_per_block = 0;  // ... of the last batch (1 + bytes per block; 0: none yet): whether sub-batches pay, jpeg_api.cpp
     size_t code_state_zero_words = 0; // this many words of e_code_state are known to be zero (the stuffing kernel cleans up behind itself)
     Buf p_in, p_out, p_sums, p_scratch; // PNG filter stage
@@ -268,7 +232,25 @@ struct Stopwatch { // debug switch `trace`: per-phase wall times of the device e
 
 void destroy_copy_helper(struct CopyHelper *h); // pieces.cpp (the type is complete only there)
 
-// ---- host memory helpers (pieces.cpp) -------------------------------------------------------------------------------
+// What the runtime knows of a host or device address.  Plain malloc'd memory is "invalid value" to it: not an error — the
+// lookup's error is cleared and the type stays hipMemoryTypeUnregistered.  Each caller decides which types it accepts.
+struct PointerInfo {
+    hipMemoryType type = hipMemoryTypeUnregistered;
+    int device = -1;
+    void *device_ptr = nullptr; // (pinned / registered host memory: the address the GPU stores to)
+};
+inline PointerInfo pointer_info(const void *p)
+{
+    PointerInfo r;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return r; }
+    r.type = at.type;
+    r.device = at.device;
+    r.device_ptr = at.devicePointer;
+    return r;
+}
+
+// ---- host memory helpers (host_memory.cpp) --------------------------------------------------------------------------
 template <class F> void run_on_threads(unsigned t, F &&body) // body(index) for index in [0, t)
 {
     if (t <= 1) { body(0u); return; }
@@ -364,7 +346,7 @@ int scan_stuff_fused(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_b
 int scan_pack(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_bit_offset = 0, uint32_t *head = nullptr,
               int *tail_bits = nullptr, uint32_t *tail = nullptr);
 
-// ---- whole baseline files (pieces.cpp) ----------------------------------------------------------------------------
+// ---- whole baseline files (baseline_file.cpp; the route: baseline_plan.hpp) ------------------------------------------
 // Pixels whose coefficients have not been computed yet (the tuple's place is reserved): the entropy stage launches the
 // coefficient kernel itself — for a scan coded in pieces, band by band in front of each piece.  host_px != null: the
 // pixels are still in HOST memory and are uploaded band by band as well (upload_stream), each band's kernels waiting
@@ -376,17 +358,42 @@ struct PixelSource {
     int16_t *dy, *dcb, *dcr;
     const uint8_t *host_px = nullptr;
 };
-int device_entropy_to_pinned(Context &c, const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
-                             const pixo_host::Geometry &g, hipStream_t stream, const uint8_t **file, size_t *file_len,
-                             uint32_t batch = 1, std::vector<uint64_t> *image_starts = nullptr, size_t *header_len = nullptr,
-                             uint8_t *dest = nullptr, size_t dest_cap = 0, bool *own_malloc = nullptr, const PixelSource *src = nullptr,
-                             std::vector<uint8_t> *head_out = nullptr, uint32_t seg_gap = 0, bool *gaps_left = nullptr);
-// (head_out != null: no copy to the host — *head_out receives the file headers, *file_len the bytes of the stuffed scan(s)
-// left in c.e_out, image_starts where each image's bytes begin; the caller delivers them.  seg_gap: bytes to leave free in
-// c.e_out between consecutive images' scans, *gaps_left says whether that was done — only segmented single-pass jobs can —:
-// image_starts then counts the gaps, image i's bytes are [starts[i], starts[i + 1] - gap).)
-int device_entropy_to_malloc(Context &c, const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
-                             const pixo_host::Geometry &g, hipStream_t stream, uint8_t **out_buf, size_t *out_len);
+// Where encode_baseline_file puts the file.  Pinned by default on purpose: a device-to-host copy into fresh pageable memory
+// makes the runtime pin those pages first, which costs 10-25 ms for an 11 MB file every time the address changes.
+struct FileDest {
+    DestKind kind = DestKind::Pinned;
+    uint8_t *p = nullptr; size_t cap = 0; // Caller: the file goes straight into this storage (no pinned intermediate); when it
+                                          // does not fit, nothing is copied there and the result's len says how much is needed
+    uint32_t batch = 1, seg_gap = 0;      // InHbm: `batch` (2 or more) equal images back to back, every one a byte-aligned
+                                          // segment of ONE scan; seg_gap: bytes to leave free in c.e_out between their scans
+    static FileDest caller(uint8_t *p, size_t cap) { FileDest d; d.kind = DestKind::Caller; d.p = p; d.cap = cap; return d; }
+    // OwnBlock: once the size is known the block is allocated and the device-to-host copy goes straight into it; the copy into
+    // pageable memory runs at the link's rate, and what it saves is the second pass over the file from the pinned buffer
+    // (tools/ubench/upload.cpp: 0.21 ms + a warm 11 MB memcpy, or 1.30 against 1.38 ms for new pages).  Pieces and direct
+    // stores fill the pinned buffer instead (the result's own_block stays false): the caller copies with deliver.
+    static FileDest own_block() { FileDest d; d.kind = DestKind::OwnBlock; return d; }
+    static FileDest in_hbm(uint32_t batch, uint32_t seg_gap) { FileDest d; d.kind = DestKind::InHbm; d.batch = batch; d.seg_gap = seg_gap; return d; }
+};
+struct FileResult {
+    const uint8_t *file = nullptr; // the whole file (InHbm: null)
+    size_t len = 0;                // its bytes; InHbm: the bytes of the stuffed scans in c.e_out; PIXO_ERR_BUFFER_TOO_SMALL: the size needed
+    size_t header_len = 0;
+    bool own_block = false;        // `file` is a block the caller owns (OwnBlock, copied-out route)
+    std::vector<uint8_t> head;     // InHbm: the file headers, the same for every image (no EOI is written)
+    // InHbm: where each image's bytes begin in c.e_out (batch + 1 entries).  gaps_left: seg_gap was left between the images'
+    // scans — only segmented single-pass jobs can —; image_starts then counts the gaps, image i's bytes are
+    // [starts[i], starts[i + 1] - gap).
+    std::vector<uint64_t> image_starts;
+    bool gaps_left = false;
+    bool tuple_done = false;       // the tuple has been computed (a multi-pass retry does not compute it again)
+};
+// The tuple dy / dcb / dcr has been computed (src null), or its place is reserved for src's pixels.
+int encode_baseline_file(Context &c, const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const PixelSource *src,
+                         const pixo_jpeg_options &o, const pixo_host::Geometry &g, const FileDest &dest, FileResult &res);
+// A scan coded in pieces while the file travels (pieces.cpp): 0 = its *scan_bytes are at dst; 1 = it outgrew its guesses and
+// nothing of it is kept (code it again in one piece); kRetryMultipass; or an error.
+int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *dst, size_t dst_cap, uint64_t *scan_bytes,
+                          const PixelSource *src);
 int device_tuple_to_malloc(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
                            const pixo_host::Geometry &g, Context &c, uint8_t **out, size_t *out_len);
 

@@ -8,14 +8,13 @@
 using namespace pixo_capi;
 
 namespace {
-// Encodes host pixels; on return `*file` points at the finished file, either in the context's
+// Encodes host pixels; on return `r.file` points at the finished file, either in the context's
 // pinned buffer or in `spill` (host coder: scans with restart markers).
-// dest / dest_cap / own_malloc: as for device_entropy_to_pinned (honoured by the baseline device path; the others
-// return a view and the caller copies).
-int encode_to_view(const uint8_t *data, size_t data_len, const pixo_jpeg_options &o, std::vector<uint8_t> &spill,
-                   const uint8_t **file, size_t *file_len, uint8_t *dest = nullptr, size_t dest_cap = 0, bool *own_malloc = nullptr)
+// dest: as for encode_baseline_file (honoured by the baseline device path; the others return a view and the caller copies;
+// caller storage the GPU can write takes the progressive scans straight from the device).
+int encode_to_view(const uint8_t *data, size_t data_len, const pixo_jpeg_options &o, std::vector<uint8_t> &spill, const FileDest &dest,
+                   FileResult &r)
 {
-    if (own_malloc) *own_malloc = false;
     std::string msg;
     int rc = pixo_host::validate(o, true, data_len, msg);
     if (rc) return fail(rc, msg);
@@ -27,8 +26,8 @@ int encode_to_view(const uint8_t *data, size_t data_len, const pixo_jpeg_options
         const int16_t *y, *cb, *cr;
         if ((rc = coeffs_to_pinned(c, data, o, g, &y, &cb, &cr))) return rc;
         pixo_host::encode_file(y, cb, cr, o, spill);
-        *file = spill.data();
-        *file_len = spill.size();
+        r.file = spill.data();
+        r.len = spill.size();
         return PIXO_OK;
     }
     if ((rc = c.ensure())) return rc;
@@ -38,20 +37,16 @@ int encode_to_view(const uint8_t *data, size_t data_len, const pixo_jpeg_options
     if (o.progressive) {
         HIP_TRY(hipMemcpyAsync(c.d_px, data, px_bytes, hipMemcpyHostToDevice, c.stream));
         uint8_t *direct = nullptr; // pinned / registered caller storage: the scans are copied from the device straight into it
-        if (dest && dest_cap > 1) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, dest) == hipSuccess && at.type == hipMemoryTypeHost) direct = dest;
-            else (void)hipGetLastError(); // (plain malloc'd memory is "invalid value" to the runtime: not an error)
-        }
-        return progressive_to_view(c.d_px, o, g, c, spill, file, file_len, direct, dest_cap);
+        if (dest.kind == DestKind::Caller && dest.cap > 1 && pointer_info(dest.p).type == hipMemoryTypeHost) direct = dest.p;
+        return progressive_to_view(c.d_px, o, g, c, spill, &r.file, &r.len, direct, dest.cap);
     }
     // baseline: the entropy stage launches the uploads and the coefficient kernel itself — band by band for images of
     // 2048x2048 pixels and more, so that bands are transformed and coded while the next ones cross PCIe and the file's
     // first pieces travel back meanwhile (pieces.cpp)
     int16_t *dy, *dcb, *dcr;
     if ((rc = coeffs_reserve(c, g, &dy, &dcb, &dcr))) return rc;
-    PixelSource src{c.d_px, &o, &g, dy, dcb, dcr, data};
-    return device_entropy_to_pinned(c, dy, dcb, dcr, o, g, c.stream, file, file_len, 1, nullptr, nullptr, dest, dest_cap, own_malloc, &src);
+    const PixelSource src{c.d_px, &o, &g, dy, dcb, dcr, data};
+    return encode_baseline_file(c, dy, dcb, dcr, &src, o, g, dest, r);
 }
 
 int fail_tuple_trellis()
@@ -82,18 +77,16 @@ int pixo_hip_jpeg_encode(const uint8_t *data, size_t data_len, const pixo_jpeg_o
     PIXO_REQUIRE(out);
     PIXO_REQUIRE(out_len);
     std::vector<uint8_t> spill;
-    const uint8_t *file = nullptr;
-    size_t n = 0;
-    bool own = false;
-    int rc = encode_to_view(data, data_len, *options, spill, &file, &n, nullptr, 0, &own);
+    FileResult r;
+    int rc = encode_to_view(data, data_len, *options, spill, FileDest::own_block(), r);
     if (rc) return rc;
-    if (own) { // (the device-to-host copy went straight into the block the caller gets)
-        *out = const_cast<uint8_t *>(file);
-        *out_len = n;
+    if (r.own_block) { // (the device-to-host copy went straight into the block the caller gets)
+        *out = const_cast<uint8_t *>(r.file);
+        *out_len = r.len;
         return PIXO_OK;
     }
     Stopwatch sw;
-    rc = deliver(file, n, out, out_len);
+    rc = deliver(r.file, r.len, out, out_len);
     sw.lap("file into fresh host memory");
     return rc;
 }
@@ -106,16 +99,15 @@ int pixo_hip_jpeg_encode_into(uint8_t *output, size_t capacity, const uint8_t *d
     PIXO_REQUIRE(out_len);
     if (capacity && !output) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'output'");
     std::vector<uint8_t> spill;
-    const uint8_t *file = nullptr;
-    size_t n = 0;
+    FileResult r;
     static uint8_t nowhere; // (a null output with capacity 0 is a size query)
-    int rc = encode_to_view(data, data_len, *options, spill, &file, &n, output ? output : &nowhere, output ? capacity : 0);
-    if (rc == PIXO_OK || rc == PIXO_ERR_BUFFER_TOO_SMALL) *out_len = n; // (the size needed when the file does not fit)
+    int rc = encode_to_view(data, data_len, *options, spill, FileDest::caller(output ? output : &nowhere, output ? capacity : 0), r);
+    if (rc == PIXO_OK || rc == PIXO_ERR_BUFFER_TOO_SMALL) *out_len = r.len; // (the size needed when the file does not fit)
     if (rc) return rc;
-    if (file == output) return PIXO_OK; // (copied from the device straight into the caller's storage)
-    if (n > capacity)
-        return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(n) + " bytes");
-    std::memcpy(output, file, n);
+    if (r.file == output) return PIXO_OK; // (copied from the device straight into the caller's storage)
+    if (r.len > capacity)
+        return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(r.len) + " bytes");
+    std::memcpy(output, r.file, r.len);
     return PIXO_OK;
 }
 
@@ -347,11 +339,7 @@ int pixo_hip_jpeg_encode_device_into(const void *d_pixels, const pixo_jpeg_optio
         const uint8_t *file = nullptr;
         size_t n = 0;
         uint8_t *direct = nullptr; // pinned / registered storage: the scans are copied from the device straight into it
-        if (output && capacity) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, output) == hipSuccess && at.type == hipMemoryTypeHost) direct = output;
-            else (void)hipGetLastError(); // (plain malloc'd memory is "invalid value" to the runtime: not an error)
-        }
+        if (output && capacity && pointer_info(output).type == hipMemoryTypeHost) direct = output;
         if ((rc = progressive_to_view(d_pixels, *options, g, *c, spill, &file, &n, direct, capacity))) return rc;
         *out_len = n;
         if (n > capacity) return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(n) + " bytes");
@@ -375,11 +363,11 @@ int pixo_hip_jpeg_encode_device_into(const void *d_pixels, const pixo_jpeg_optio
     int16_t *dy, *dcb, *dcr;
     if ((rc = coeffs_reserve(*c, g, &dy, &dcb, &dcr))) return rc;
     const PixelSource src{d_pixels, options, &g, dy, dcb, dcr}; // (the entropy stage launches the coefficient kernel: whole, or band by band)
-    const uint8_t *file = nullptr;
-    // (a null output with capacity 0 is a size query)
-    static uint8_t nowhere;
-    return device_entropy_to_pinned(*c, dy, dcb, dcr, *options, g, c->stream, &file, out_len, 1, nullptr, nullptr,
-                                    output ? output : &nowhere, output ? capacity : 0, nullptr, &src);
+    static uint8_t nowhere; // (a null output with capacity 0 is a size query)
+    FileResult r;
+    rc = encode_baseline_file(*c, dy, dcb, dcr, &src, *options, g, FileDest::caller(output ? output : &nowhere, output ? capacity : 0), r);
+    if (rc == PIXO_OK || rc == PIXO_ERR_BUFFER_TOO_SMALL) *out_len = r.len; // (the size needed when the file does not fit)
+    return rc;
 }
 
 } // extern "C"
@@ -402,10 +390,12 @@ int batch_on_device(Context &c, const void *d_pixels, const pixo_jpeg_options &o
     // (round 6: the entropy stage gets the PIXELS — an RGB batch goes through the fused pixel -> scan kernel, every image a segment,
     // and never writes the tuple; otherwise the stage launches the coefficient kernel over the batch itself)
     const PixelSource src{d_pixels, &o, &g, dy, dcb, dcr};
-    const uint8_t *unused = nullptr;
-    size_t scan_bytes = 0;
-    return device_entropy_to_pinned(c, dy, dcb, dcr, o, g, c.stream, &unused, &scan_bytes, batch, &starts, nullptr, nullptr, 0, nullptr, &src, &head,
-                                    gap, gaps);
+    FileResult r;
+    if ((rc = encode_baseline_file(c, dy, dcb, dcr, &src, o, g, FileDest::in_hbm(batch, gap), r))) return rc;
+    head = std::move(r.head);
+    starts = std::move(r.image_starts);
+    *gaps = r.gaps_left;
+    return PIXO_OK;
 }
 bool batch_in_one_pass(const pixo_jpeg_options &o, const pixo_host::Geometry &g, uint32_t batch, size_t px_bytes)
 {
@@ -444,7 +434,7 @@ int pixo_hip_jpeg_encode_batch_device(const void *d_pixels, const pixo_jpeg_opti
     if ((rc = batch_on_device(*c, d_pixels, o, g, batch, head, starts, &gaps))) return rc;
     const size_t hdr = head.size(), scan_bytes = static_cast<size_t>(starts[batch]), gap = gaps ? hdr + 2 : 0;
     for (uint32_t i = 0; i < batch; ++i) lens[i] = hdr + static_cast<size_t>(starts[i + 1] - starts[i]) - (i + 1 < batch ? gap : 0) + 2;
-    // Round 6: every file's block comes from the library's pool of PINNED host memory (pieces.cpp pool_take: resident pages that
+    // Round 6: every file's block comes from the library's pool of PINNED host memory (host_memory.cpp pool_take: resident pages that
     // pixo_hip_free gives back) and its entropy-coded bytes are copied from the device straight into it — 64 x 1080p noise: 26.8 ->
     // ~2.5 ms a batch, where fresh malloc'd blocks cost 22,000 page faults.  The pool exhausted (or debug switch plain_host): the
     // old way below.
@@ -512,14 +502,8 @@ int pixo_hip_jpeg_encode_batch_device_into(const void *d_pixels, const pixo_jpeg
     const pixo_host::Geometry g = pixo_host::geometry(o.width, o.height, o.color_type, o.subsampling);
     const size_t px_bytes = static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3);
     for (uint32_t i = 0; i < batch; ++i) { offsets[i] = 0; lens[i] = 0; }
-    bool arena_pinned = false, arena_device = false;
-    if (arena) {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, arena) == hipSuccess) {
-            arena_pinned = pa.type == hipMemoryTypeHost;
-            arena_device = pa.type == hipMemoryTypeDevice;
-        } else (void)hipGetLastError(); // (plain malloc'd memory is "invalid value" to the runtime: not an error)
-    }
+    const hipMemoryType arena_type = arena ? pointer_info(arena).type : hipMemoryTypeUnregistered;
+    const bool arena_pinned = arena_type == hipMemoryTypeHost, arena_device = arena_type == hipMemoryTypeDevice;
     if (!batch_in_one_pass(o, g, batch, px_bytes) && arena_device) { // per-image tables / segments inside the images, files to stay in HBM:
         size_t at = 0;                                                // each image through a host file, then host-to-device behind the one before
         hipError_t e = hipSuccess;

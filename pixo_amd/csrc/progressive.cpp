@@ -191,7 +191,7 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     uint64_t first_tile = 0, tiles = pd::stuff_tiles(blocks_all * 40 + 4096) + a.nscans;
     size_t want_cap = std::max<size_t>(stream_bytes / 4, 4096);
     uint64_t scan_bytes = 0;
-    // Small files (round 5; like the baseline path, pieces.cpp): the stuffing kernel stores the scans straight into host memory the
+    // Small files (round 5; like the baseline path, baseline_plan.hpp): the stuffing kernel stores the scans straight into host memory the
     // GPU can write — the caller's pinned storage or the context's pinned file buffer — at their places in the FILE; no copy and no
     // second wait.  "Small": the last progressive file of this context was (768 KB); all seven scans present (the gaps between
     // them are then exactly the SOS headers' places).  Too small a destination: the stuffing pass runs again into device memory.
@@ -202,10 +202,10 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     if (a.nscans == 7 && !debug().no_direct_small && c.last_prog_bytes && c.last_prog_bytes <= kDirectBytes) {
         const size_t guess = body_at + 2 * static_cast<size_t>(c.last_prog_bytes) + 4096;
         if (pinned_dest && dest_cap >= guess) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, pinned_dest) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) {
-                direct_host = pinned_dest; direct_dev = static_cast<uint8_t *>(at.devicePointer); direct_cap = dest_cap;
-            } else (void)hipGetLastError();
+            const PointerInfo at = pointer_info(pinned_dest);
+            if (at.type == hipMemoryTypeHost && at.device_ptr) {
+                direct_host = pinned_dest; direct_dev = static_cast<uint8_t *>(at.device_ptr); direct_cap = dest_cap;
+            }
         }
         if (!direct_host) {
             const int rc_f = c.reserve_hfile(guess);

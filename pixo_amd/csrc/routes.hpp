@@ -1,0 +1,51 @@
+// routes.hpp — the route record's bits (tests: pixo_hip_debug_routes).  No HIP headers: the baseline planner
+// (baseline_plan.hpp) names them, and its CPU test compiles without the library.
+#pragma once
+#include <cstdint>
+
+namespace pixo_capi {
+
+// Which of the library's forms served the calls since the record was last cleared: every decision point ORs its bit
+// into one process-wide word (one relaxed fetch_or per decision, nothing on the device).  pixo_amd/jpeg.py mirrors the names.
+namespace route {
+enum : uint64_t {
+    FUSED = 1ull << 0,             // the fused pixel -> scan kernel (jpeg_pixels_code.hip), one uninterrupted scan
+    FUSED_SEGMENTED = 1ull << 1,   // ... its segments: the images of a batch or restart intervals of whole MCU rows
+    FUSED_DIRECT = 1ull << 2,      // ... storing straight into host memory the GPU can write
+    TWO_KERNEL = 1ull << 3,        // coefficient kernel + scan_code (a tuple in HBM coded by the entropy stage)
+    DENSE_STREAM_RULE = 1ull << 4, // the context's last file was dense: the fused kernel would have served, the two-kernel form did
+    SINGLE_PASS_TUPLE = 1ull << 5, // the single-pass tuple coders of jpeg_scan_fused.hip
+    MULTI_PASS = 1ull << 6,        // the multi-pass entropy kernels of jpeg_entropy.hip (baseline or progressive)
+    FALLBACK = 1ull << 7,          // a single-pass launch gave up waiting: the job ran again with the multi-pass kernels
+    HOST_ENTROPY = 1ull << 8,      // the host twin of the scan coders (debug switch host_entropy)
+    PIECES = 1ull << 9,            // a scan coded in pieces while the file travels (device_entropy_pieces)
+    HOST_BANDS = 1ull << 10,       // ... with host pixels uploaded in bands
+    DIRECT_STORES = 1ull << 11,    // the stuffing kernel stores straight into pinned host memory (baseline)
+    RESTUFF_GROW = 1ull << 12,     // the output buffer was short: grown, the stuffing pass repeated
+    CALLER_RETRY = 1ull << 13,     // the caller's storage was too small (PIXO_ERR_BUFFER_TOO_SMALL)
+    COEF_PACKED = 1ull << 14,      // packed DCT / quantiser forms (jpeg_kernels.hip packed_launch)
+    COEF_SCALAR = 1ull << 15,      // scalar forms
+    LOAD_ALIGNED = 1ull << 16,     // coefficient kernel: 12-byte loads of aligned rows
+    LOAD_FUNNEL = 1ull << 17,      // ... aligned dwords and shifts
+    LOAD_BYTES = 1ull << 18,       // ... byte gathers (images narrower than 4 pixels)
+    PROG_SINGLE_PASS = 1ull << 19, // progressive scans by the single-pass kernels
+    PROG_DIRECT_SMALL = 1ull << 20, // ... stored straight into host memory (small progressive files after a small one)
+    SIDE_STATS = 1ull << 21,       // preset 2, small images: the statistics on a second stream beside the search
+    TRELLIS_LANE = 1ull << 22,     // trellis search: one lane per block
+    TRELLIS_GROUP = 1ull << 23,    // ... eight lanes per block
+    BATCH_FUSED = 1ull << 24,      // a batch through the fused kernel, every image a segment
+    BATCH_TWO_KERNEL = 1ull << 25, // a batch through coefficient kernel + entropy stage
+    SUB_BATCHES = 1ull << 26,      // a batch in several sub-batches over two contexts
+    BANDS_MULTI = 1ull << 27,      // one image in bands over several devices (pixo_hip_jpeg_encode_multi)
+    PNG_REGS = 1ull << 28,         // PNG filter kernel: adaptive strategies with the row in the registers of 256 threads
+    PNG_GENERAL = 1ull << 29,      // ... the general form (fixed filters, or rows too long for registers)
+    PNG_BIGRAMS_REGS = 1ull << 30, // ... bigrams with the row in registers
+    PNG_BIGRAMS = 1ull << 31,      // ... bigrams, general form
+    SEGMENTED_TUPLE = 1ull << 32,  // the single-pass tuple coders over byte-aligned segments (batches, restart intervals)
+    PROG_MULTI_PASS = 1ull << 33,  // progressive scans by the multi-pass kernels
+    PIECES_REDO = 1ull << 34,      // a scan in pieces outgrew its guesses (0xFF bytes, dense content) and was coded again in one piece
+    PNG_REGS512 = 1ull << 35,      // PNG filter kernel: adaptive strategies, rows of 16-32 KiB in the registers of 512 threads
+};
+}
+
+} // namespace pixo_capi

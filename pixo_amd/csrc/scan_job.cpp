@@ -368,6 +368,27 @@ bool pixels_code_usable(const ScanJob &j, const pixo_jpeg_options &o, const pixo
     return pixo_dev::pixels_code_supported(o.width, o.height, g.gray, g.s420, batch, restart);
 }
 
+// Where a kernel stores the stuffed bytes: at `host` (memory of the host the GPU can write; the context's pinned file buffer is
+// grown to want_cap first), or in the context's device buffer c.e_out, grown to want_cap.
+static int output_window(Context &c, HostTarget *host, size_t want_cap, uint8_t **out, size_t *out_cap)
+{
+    if (!host) {
+        HIP_TRY(c.e_out.reserve(want_cap));
+        *out = c.e_out.as<uint8_t>();
+        *out_cap = c.e_out.cap;
+        return PIXO_OK;
+    }
+    if (host->grow) {
+        const int rc = c.reserve_hfile(host->before + want_cap + host->after);
+        if (rc) return rc;
+        host->p = c.h_file + host->before;
+        host->cap = c.hfile_cap - host->before - host->after;
+    }
+    *out = host->p;
+    *out_cap = host->cap;
+    return PIXO_OK;
+}
+
 int scan_from_pixels(Context &c, ScanJob &j, const pixo_jpeg_options &o, const pixo_host::Geometry &g, hipStream_t stream, const void *d_pixels,
                      HostTarget *host, bool wait, uint32_t batch)
 {
@@ -403,20 +424,7 @@ int scan_from_pixels(Context &c, ScanJob &j, const pixo_jpeg_options &o, const p
     for (int attempt = 0;; ++attempt) {
         uint8_t *out = nullptr;
         size_t out_cap = 0;
-        if (host) {
-            if (host->grow) {
-                const int rc_h = c.reserve_hfile(host->before + want_cap + host->after);
-                if (rc_h) return rc_h;
-                host->p = c.h_file + host->before;
-                host->cap = c.hfile_cap - host->before - host->after;
-            }
-            out = host->p;
-            out_cap = host->cap;
-        } else {
-            HIP_TRY(c.e_out.reserve(want_cap));
-            out = c.e_out.as<uint8_t>();
-            out_cap = c.e_out.cap;
-        }
+        if ((rc = output_window(c, host, want_cap, &out, &out_cap))) return rc;
         unsigned long long *mine = c.e_pc_state.as<unsigned long long>() + static_cast<size_t>(c.pc_flip) * words;
         unsigned long long *other = c.e_pc_state.as<unsigned long long>() + static_cast<size_t>(c.pc_flip ^ 1) * words;
         c.pc_flip ^= 1;
@@ -508,20 +516,7 @@ int scan_stuff_fused(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_b
     for (int attempt = 0;; ++attempt) {
         uint8_t *out = nullptr;
         size_t out_cap = 0;
-        if (host) {
-            if (host->grow) {
-                const int rc = c.reserve_hfile(host->before + want_cap + host->after);
-                if (rc) return rc;
-                host->p = c.h_file + host->before;
-                host->cap = c.hfile_cap - host->before - host->after;
-            }
-            out = host->p;
-            out_cap = host->cap;
-        } else {
-            HIP_TRY(c.e_out.reserve(want_cap));
-            out = c.e_out.as<uint8_t>();
-            out_cap = c.e_out.cap;
-        }
+        if (const int rc = output_window(c, host, want_cap, &out, &out_cap)) return rc;
         HIP_TRY(pd::launch_stuff_fused(c.e_stream.as<uint32_t>(), c.e_code_state.as<unsigned long long>(), j.code_state_words,
                                        shift, j.band, j.stream_cap, first_tile, tiles, c.e_stuff_state.as<unsigned long long>(),
                                        /*state_is_zero=*/chained && attempt == 0, out, out_cap,

@@ -9,7 +9,7 @@ cd "$(dirname "$0")/../pixo_amd/csrc"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize"
 OBJ=/tmp/pixo_ab_obj; mkdir -p $OBJ ../../tools/ab
 SRC=${AB_SRC:-jpeg_kernels.hip}; BASE=${SRC%.*}
-for f in jpeg_kernels.hip jpeg_pixels_code.hip jpeg_integer.hip jpeg_entropy.hip jpeg_scan_fused.hip jpeg_trellis.hip png_filter.hip stream_copy.hip context.cpp dispatch_gate.cpp scan_job.cpp pieces.cpp progressive.cpp jpeg_api.cpp png_api.cpp bands.cpp jpeg_host.cpp; do
+for f in jpeg_kernels.hip jpeg_pixels_code.hip jpeg_integer.hip jpeg_entropy.hip jpeg_scan_fused.hip jpeg_trellis.hip png_filter.hip stream_copy.hip context.cpp dispatch_gate.cpp scan_job.cpp baseline_file.cpp pieces.cpp host_memory.cpp progressive.cpp jpeg_api.cpp png_api.cpp bands.cpp jpeg_host.cpp; do
   o=$OBJ/${f%.*}.o
   K=""; { [ $f = jpeg_kernels.hip ] || [ $f = jpeg_pixels_code.hip ]; } && K="-mllvm -amdgpu-kernarg-preload-count=14"
   if [ ! -f $o ] || [ $f -nt $o ] || [ -n "$(find . ../../include -name '*.h*' -newer $o | head -1)" ]; then /opt/rocm/bin/hipcc $FLAGS $K -c $f -o $o & fi

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Files of more than 30 bytes per block (photographs at q = 100, noise at q >= 90): the context's last file sends the next one through the
-two-kernel form (pieces.cpp dense_stream).  Wall us per 4096x4096 file, device pixels -> pinned buffer, median of 15 — default against the fused
+two-kernel form (baseline_plan.hpp dense_stream).  Wall us per 4096x4096 file, device pixels -> pinned buffer, median of 15 — default against the fused
 kernel forced (debug switch fused_batch)."""
 import os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
