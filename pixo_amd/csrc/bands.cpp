@@ -101,16 +101,15 @@ int pixo_hip_band_encoder_coeffs(pixo_hip_band_encoder *e, const void *band_pixe
     const void *d_px = band_pixels;
     if (!on_device) { // the band's rows come over this GPU's own PCIe link
         const size_t px_bytes = static_cast<size_t>(e->band.width) * e->rows * (e->g.gray ? 1 : 3);
-        if ((rc = c.reserve_px((px_bytes + 15) & ~size_t{15}))) return rc;
-        HIP_TRY(hipMemcpyAsync(c.d_px, band_pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
-        d_px = c.d_px;
+        if ((rc = c.d_px.reserve((px_bytes + 15) & ~size_t{15}))) return rc;
+        HIP_TRY(hipMemcpyAsync(c.d_px.p, band_pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
+        d_px = c.d_px.p;
     } else if ((rc = order_after_producer(c))) {
         return rc;
     }
     if ((rc = coeffs_on_device(c, d_px, e->band, e->g, c.stream, &e->dy, &e->dcb, &e->dcr))) return rc;
     // the DCs the next band predicts from: first coefficient of the last block of every plane
-    { const int rc_t = c.ensure_totals(); if (rc_t) return rc_t; }
-    int16_t *h = reinterpret_cast<int16_t *>(c.h_totals + Context::kTotalsWords - 1); // (the mailbox's last word: no kernel of the entropy stage writes it)
+    int16_t *h = c.mail->last_dc;
     HIP_TRY(pixo_dev::launch_last_dcs(e->dy, e->g.y_blocks, e->dcb, e->dcr, e->g.c_blocks, h, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     e->last_dc[0] = h[0];
@@ -211,12 +210,12 @@ int pixo_hip_band_encoder_copy_body(pixo_hip_band_encoder *e, uint8_t *dst)
         return PIXO_OK;
     }
     // pageable destination: through the context's pinned buffer (a direct copy makes the runtime pin the pages first)
-    int rc = c.reserve_hfile(body);
+    int rc = c.h_file.reserve(body);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c.h_file, c.e_out.p, body, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.h_file.p, c.e_out.p, body, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    if (e->parts <= 2) big_copy(dst, c.h_file, body); // (few bands: nobody else is copying — the library's copy threads)
-    else std::memcpy(dst, c.h_file, body);
+    if (e->parts <= 2) big_copy(dst, c.h_file.as<uint8_t>(), body); // (few bands: nobody else is copying — the library's copy threads)
+    else std::memcpy(dst, c.h_file.p, body);
     return PIXO_OK;
 }
 
@@ -584,25 +583,13 @@ namespace {
 // received from another GPU, and its files before they travel.
 struct BatchWorkerBuffers {
     int device = -1;
-    void *px = nullptr, *arena = nullptr;
-    size_t px_cap = 0, arena_cap = 0;
+    Buf px{Buf::Mem::Device, Buf::Grow::Exact}, arena{Buf::Mem::Device, Buf::Grow::Exact};
     void drop()
     {
-        if (device >= 0) {
-            DeviceScope on(device);
-            if (px) (void)hipFree(px);
-            if (arena) (void)hipFree(arena);
-        }
-        px = arena = nullptr; px_cap = arena_cap = 0;
-    }
-    hipError_t reserve(void **p, size_t *cap, size_t want)
-    {
-        if (*cap >= want) return hipSuccess;
-        if (*p) (void)hipFree(*p);
-        *p = nullptr; *cap = 0;
-        const hipError_t e = hipMalloc(p, want);
-        if (e == hipSuccess) *cap = want;
-        return e;
+        if (device < 0) return; // (nothing reserved yet)
+        DeviceScope on(device);
+        px.drop();
+        arena.drop();
     }
 };
 thread_local BatchWorkerBuffers t_batch_buffers;
@@ -681,11 +668,11 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
             const void *local = src;
             const size_t px_bytes = static_cast<size_t>(sh.count) * image_bytes;
             if (!sh.rc && src_device != dev) {
-                hip_step(buf.reserve(&buf.px, &buf.px_cap, px_bytes), "hipMalloc (images of a batch share)");
+                step(buf.px.reserve(px_bytes));
                 if (!sh.rc) {
-                    if (src_device >= 0) hip_step(hipMemcpyPeer(buf.px, dev, src, src_device, px_bytes), "hipMemcpyPeer (images of a batch share)");
-                    else hip_step(hipMemcpy(buf.px, src, px_bytes, hipMemcpyHostToDevice), "upload of a batch share");
-                    local = buf.px;
+                    if (src_device >= 0) hip_step(hipMemcpyPeer(buf.px.p, dev, src, src_device, px_bytes), "hipMemcpyPeer (images of a batch share)");
+                    else hip_step(hipMemcpy(buf.px.p, src, px_bytes, hipMemcpyHostToDevice), "upload of a batch share");
+                    local = buf.px.p;
                 }
             }
             sh.offs.assign(sh.count, 0); sh.lens.assign(sh.count, 0);
@@ -701,9 +688,9 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
             // was short: pixo_hip_jpeg_encode_batch_device_into fills in the lengths either way)
             size_t want = std::max<size_t>(px_bytes / 3, size_t{1} << 16);
             for (int attempt = 0; !sh.rc && attempt < 3; ++attempt) {
-                hip_step(buf.reserve(&buf.arena, &buf.arena_cap, want), "hipMalloc (files of a batch share)");
+                step(buf.arena.reserve(want));
                 if (sh.rc) break;
-                const int r = pixo_hip_jpeg_encode_batch_device_into(local, options, sh.count, static_cast<uint8_t *>(buf.arena), buf.arena_cap,
+                const int r = pixo_hip_jpeg_encode_batch_device_into(local, options, sh.count, buf.arena.as<uint8_t>(), buf.arena.cap,
                                                                      sh.offs.data(), sh.lens.data());
                 if (r == PIXO_ERR_BUFFER_TOO_SMALL && attempt < 2) { want = sh.offs[sh.count - 1] + sh.lens[sh.count - 1] + 4096; continue; }
                 if (r == PIXO_ERR_BUFFER_TOO_SMALL) // (the sizes changed between three identical calls: not the CALLER's arena that is too small)
@@ -728,7 +715,7 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
         barrier.arrive();
         // ---- every share's run of files to its final place, over its own GPU's PCIe link, on its own thread
         if (!failed.load() && !too_small.load() && sh.count && sh.bytes)
-            hip_step(hipMemcpy(arena + offsets[sh.first], buf.arena, sh.bytes, hipMemcpyDeviceToHost), "device-to-host copy of a batch share's files");
+            hip_step(hipMemcpy(arena + offsets[sh.first], buf.arena.p, sh.bytes, hipMemcpyDeviceToHost), "device-to-host copy of a batch share's files");
     };
     if (!band_workers_instance().run(parts, body)) return fail(PIXO_ERR_COMPRESSION, "Compression error: could not start the worker threads");
     for (Share &sh : shares)

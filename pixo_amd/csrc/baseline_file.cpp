@@ -68,11 +68,12 @@ int batch_image_starts(Context &c, const ScanJob &j, uint32_t batch, uint64_t sc
     starts.assign(batch + 1, 0);
     if (j.segmented || j.pc_seg) { // the stuffing kernel / the fused kernel left every image's end in the pinned mailbox
         // (h_segs[i]: where image i's bytes end; the next image begins behind the gap)
-        for (uint32_t i = 0; i < batch; ++i) starts[i + 1] = c.h_segs[i] + (i + 1 < batch ? j.seg.marker_bytes : 0);
+        const uint64_t *ends = c.h_segs.as<uint64_t>();
+        for (uint32_t i = 0; i < batch; ++i) starts[i + 1] = ends[i] + (i + 1 < batch ? j.seg.marker_bytes : 0);
         return PIXO_OK;
     }
     // where every image's segment begins in the stuffed stream (reuses the seg_bytes buffer: 8 B/entry)
-    HIP_TRY(c.e_seg_bytes.reserve(j.nseg * 8));
+    if (const int rc = c.e_seg_bytes.reserve(j.nseg * 8)) return rc;
     HIP_TRY(pixo_dev::launch_segment_out_offsets(j.plan, j.nbytes, c.e_stream.as<uint32_t>(), c.e_tile_base.as<uint64_t>(),
                                                  c.e_seg_bytes.as<uint64_t>(), c.stream));
     HIP_TRY(hipMemcpyAsync(starts.data(), c.e_seg_bytes.p, j.nseg * 8, hipMemcpyDeviceToHost, c.stream));
@@ -108,8 +109,8 @@ int finish_file(Context &c, const FileDest &d, const ScanJob &j, const std::vect
             if (!(buf = alloc_file(total))) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
             mine = true;
         } else {
-            if (const int rc = c.reserve_hfile(total)) return rc;
-            buf = c.h_file;
+            if (const int rc = c.h_file.reserve(total)) return rc;
+            buf = c.h_file.as<uint8_t>();
         }
         hipError_t ce = hipMemcpyAsync(buf + hdr, c.e_out.p, scan_bytes, hipMemcpyDeviceToHost, c.stream);
         if (ce == hipSuccess) ce = hipStreamSynchronize(c.stream);
@@ -171,9 +172,9 @@ int run_pieces(Context &c, ScanJob &j, const PixelSource *src, const pixo_jpeg_o
     if (d.kind == DestKind::Caller) {
         advise_huge(buf, std::min(cap, bound));
     } else {
-        if ((rc = c.reserve_hfile(bound))) return rc;
-        buf = c.h_file;
-        cap = c.hfile_cap;
+        if ((rc = c.h_file.reserve(bound))) return rc;
+        buf = c.h_file.as<uint8_t>();
+        cap = c.h_file.cap;
     }
     uint64_t scan_bytes = 0;
     rc = device_entropy_pieces(c, j, c.stream, buf + hdr, cap - hdr - 2, &scan_bytes, src);
@@ -222,7 +223,7 @@ int run_one_piece(Context &c, ScanJob &j, const PixelSource *src, const pixo_jpe
     else rc = scan_stuff_fused(c, j, c.stream, 0, nullptr, nullptr, nullptr, /*chained=*/true, direct ? &target : nullptr);
     if (rc) return rc;
     sw.lap("code+stuff (fused)");
-    uint8_t *placed = !direct ? nullptr : d.kind == DestKind::Caller ? d.p : c.h_file; // (h_file only now: the kernel may have grown it)
+    uint8_t *placed = !direct ? nullptr : d.kind == DestKind::Caller ? d.p : c.h_file.as<uint8_t>(); // (h_file only now: the kernel may have grown it)
     return finish_file(c, d, j, head, j.scan_bytes, placed, r);
 }
 
@@ -242,7 +243,7 @@ int encode_once(Context &c, const int16_t *dy, const int16_t *dcb, const int16_t
     if (p.form == Form::Pieces) {
         const int rc = run_pieces(c, j, src, o, g, p, d, r);
         if (rc != 1) return rc;
-        c.code_state_zero_words = 0;
+        c.e_code_state.known = 0; // (the pieces' kernels left it dirty)
         note_route(route::PIECES_REDO);
         p = plan_baseline_file(tuple_computed_no_pieces(facts));
         note_route(p.notes);
@@ -298,9 +299,9 @@ int device_tuple_to_malloc(const int16_t *dy, const int16_t *dcb, const int16_t 
     }
     // for experiments, the host twin of the scan coders: host code on a copy of the tuple
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128;
-    int rc = c.reserve_hcoef(coef_bytes);
+    int rc = c.h_coef.reserve(coef_bytes);
     if (rc) return rc;
-    int16_t *hy = static_cast<int16_t *>(c.h_coef), *hcb = hy + g.y_blocks * 64, *hcr = hcb + g.c_blocks * 64;
+    int16_t *hy = c.h_coef.as<int16_t>(), *hcb = hy + g.y_blocks * 64, *hcr = hcb + g.c_blocks * 64;
     HIP_TRY(hipMemcpyAsync(hy, dy, g.y_blocks * 128, hipMemcpyDeviceToHost, c.stream));
     if (g.c_blocks) {
         HIP_TRY(hipMemcpyAsync(hcb, dcb, g.c_blocks * 128, hipMemcpyDeviceToHost, c.stream));

@@ -121,7 +121,41 @@ struct DeviceScope {
     DeviceScope &operator=(const DeviceScope &) = delete;
 };
 
+// ---- grow-only buffers ---------------------------------------------------------------------------------------------------
+// The library's only grow-only buffer: device memory or pinned host memory, with a growth rule fixed per buffer.  Two rules
+// keep the buffers sound:
+//   * one purpose per buffer: a buffer holds one kind of thing, so that no use of it can move it under another;
+//   * a job reserves everything it needs before it hands any address to a kernel: reserve frees the old memory before it
+//     allocates the new, so an address taken before a growing reserve is dangling.
+// `known` is what the owner knows about the contents (its meaning is the owner's; 0: nothing).  It is forgotten whenever the
+// memory is freed or moves.
+struct Buf {
+    enum class Mem : uint8_t { Device, Pinned };
+    enum class Grow : uint8_t {
+        Exact,    // n
+        Headroom, // n + n/4: sizes are data dependent
+        SegEnds,  // u64 words w = n / 8 -> w + w/4 + 16 words
+    };
+    void *p = nullptr;
+    size_t cap = 0; // bytes
+    size_t known = 0;
+    Mem mem = Mem::Device;
+    Grow grow = Grow::Headroom;
+
+    Buf() = default;
+    Buf(Mem m, Grow g) : mem(m), grow(g) {}
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    int reserve(size_t n) { return n <= cap ? PIXO_OK : regrow(n); } // a library status (hip_fail)
+    void drop();                                                      // back to the driver (on the current device)
+    template <class T> T *as() const { return static_cast<T *>(p); }
+
+private:
+    int regrow(size_t n);
+};
+
 // ---- thread-local execution context --------------------------------------------------
+// (every Buf member is listed once, in context.cpp each_buf: held_bytes, shrink_to and release walk that list)
 struct Context {
     int device = 0;
     bool ready = false;
@@ -129,67 +163,58 @@ struct Context {
     hipEvent_t producer_done = nullptr; // orders the context's stream after the caller's (device-pointer entries)
     hipEvent_t stats_done = nullptr;    // preset 2: the symbol counts of the statistics pass have reached the host (progressive.cpp)
     hipEvent_t side_ready = nullptr;    // preset 2, small images: the second stream may start (the pixels are there)
-    void *d_px = nullptr;   size_t px_cap = 0;
-    void *d_coef = nullptr; size_t coef_cap = 0;
-    void *h_coef = nullptr; size_t hcoef_cap = 0; // pinned
-    // device entropy stage (grow-only)
-    struct Buf {
-        void *p = nullptr; size_t cap = 0;
-        hipError_t reserve(size_t n)
-        {
-            if (n <= cap) return hipSuccess;
-            if (p) (void)hipFree(p);
-            p = nullptr; cap = 0;
-            const size_t want = n + n / 4; // head-room: sizes are data dependent
-            hipError_t e = hipMalloc(&p, want);
-            if (e == hipSuccess) cap = want;
-            return e;
-        }
-        template <class T> T *as() const { return static_cast<T *>(p); }
-    };
-    Buf e_tables, e_hist, e_count, e_len, e_off, e_tmp, e_totals, e_stream, e_tile_ff, e_tile_base, e_out, e_seg_bytes, e_seg_off;
-    Buf e_code_state, e_stuff_state; // single-pass kernels (jpeg_scan_fused.hip): look-back descriptors, totals
+    Buf d_px{Buf::Mem::Device, Buf::Grow::Exact};   // pixels uploaded from the host (callers round up to 16 bytes)
+    Buf d_coef{Buf::Mem::Device, Buf::Grow::Exact}; // the coefficient tuple
+    Buf h_coef{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... copied to the host
+    // device entropy stage
+    Buf e_tables;                    // known: 1 = it holds tables_held, uploaded on tables_stream (no upload when unchanged)
+    Buf e_hist, e_count, e_len, e_off, e_tmp, e_totals, e_stream, e_tile_ff, e_tile_base, e_out, e_seg_bytes, e_seg_off;
+    Buf e_code_state, e_stuff_state; // single-pass kernels (jpeg_scan_fused.hip): look-back descriptors, totals.  e_code_state.known: this
+                                     //   many of its words are zero (the stuffing kernel cleans up behind itself)
     Buf e_pc_state;                  // the fused pixel -> scan kernel (jpeg_pixels_code.hip): TWO state blocks that alternate — a launch zeroes the
-    size_t pc_half_words = 0;        //   block of the launch before it (words per block; 0: nothing is known to be zero)
+                                     //   block of the launch before it.  known: words per block (both are zero or being zeroed; 0: nothing known)
     int pc_flip = 0;                 //   which block the next launch uses
     Buf e_pc_spill;                  //   where a group of several 6 KiB rounds parks its quantised blocks between the rounds' walks (a buffer of its
                                      //   own: growing d_coef here would free the tuple a caller's retry path still points into)
     Buf e_chain;                     // a scan coded in pieces: bits / bytes of the scan before every piece (device_entropy_pieces)
     Buf e_seams;                     // batch files that stay in HBM: their offsets + the header bytes for batch_seams_kernel
     Buf e_segs;                      // segmented scans (batches, restart intervals): per-segment results of the single-pass kernels
+    Buf h_segs{Buf::Mem::Pinned, Buf::Grow::SegEnds}; // u64 words: where every segment of a segmented scan ends (reserved by scan_begin)
     hipStream_t copy_stream = nullptr; // ... whose bytes travel to the host on this stream while the next piece is coded
     hipStream_t upload_stream = nullptr; // host pixels arrive band by band on this stream while earlier bands are transformed
     struct CopyHelper *helper = nullptr; // ... and a second host thread sends the coded pieces back meanwhile (pieces.cpp; stopped and joined by release())
     std::vector<hipEvent_t> piece_done, band_up;
-    uint32_t *h_tables = nullptr; // pinned staging of tables_held for the upload
-    uint32_t tables_held[pixo_scan::kScanTableUpload]; bool tables_valid = false; hipStream_t tables_stream = nullptr; // what e_tables holds (no upload when unchanged)
+    uint32_t tables_held[pixo_scan::kScanTableUpload]; hipStream_t tables_stream = nullptr; // what e_tables holds
     uint64_t last_prog_bytes = 0; // the last progressive file's entropy-coded bytes (small: the next one is stored directly)
     // the last whole baseline scan this context coded (0 blocks: none yet; baseline_file.cpp remember_scan): predicts the next
     // file's size and density (baseline_plan.hpp).  Exact: a smooth image is below one byte per block
     uint64_t last_scan_bytes = 0, last_scan_blocks = 0;
     uint32_t batch_per_block = 0;  // ... of the last batch (1 + bytes per block; 0: none yet): whether sub-batches pay, jpeg_api.cpp
-    size_t code_state_zero_words = 0; // this many words of e_code_state are known to be zero (the stuffing kernel cleans up behind itself)
     Buf p_in, p_out, p_sums, p_scratch; // PNG filter stage
+    Buf h_sums{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... p_sums copied to the host
     Buf t_raw, t_trail;                 // progressive + trellis: unquantised DCT blocks (f32), Viterbi back-pointers
     Buf t_plain;                        // preset 2, small images: the plain quantiser's tuple of the statistics pass on the second stream
     Buf g_flags, g_rank, g_by_rank;     // progressive scans: band flags, rank among non-empty blocks and its inverse
-    unsigned long long *h_sums = nullptr; size_t hsums_cap = 0; // pinned
-    uint64_t *h_totals = nullptr; // pinned, kTotalsWords words: the kernels' mailbox (4 words per piece of a scan)
-    static constexpr size_t kTotalsWords = 4 * 32;
-    uint64_t *h_segs = nullptr; size_t hsegs_cap = 0; // pinned: per-segment byte offsets of a segmented scan
-    uint8_t *h_file = nullptr; size_t hfile_cap = 0; // pinned: the finished file lands here
+    Buf h_file{Buf::Mem::Pinned, Buf::Grow::Headroom}; // the finished file lands here
+
+    // Small results for the host, one field per purpose: pinned, allocated once with the stream (ensure).
+    struct Mailbox {
+        static constexpr size_t kTotalsWords = 4 * 32;
+        uint64_t totals[kTotalsWords];                 // the kernels' totals, 4 words per piece of a scan: [0] bits, [1] stuffed bytes,
+                                                       //   [2] packed bytes or tiles, [3] a look-back gave up
+        uint64_t counts[pixo_host::kScanTableWords];   // symbol counts of an optimised-tables pass
+        int16_t last_dc[4];                            // the band encoder: last DC of every plane
+        uint32_t tables[pixo_scan::kScanTableUpload];  // staging of upload_scan_tables
+    };
+    Mailbox *mail = nullptr;
 
     int ensure();
-    int reserve_px(size_t n);
-    int reserve_coef(size_t n);
-    int reserve_hcoef(size_t n);
-    int reserve_hfile(size_t n);
-    int reserve_hsegs(size_t words);
-    int ensure_totals();
     size_t held_bytes() const; // device + pinned bytes this context keeps
     void shrink_to(size_t max_buffer_bytes); // releases every buffer larger than this (a parked context keeps the small ones)
     void release(); // everything back to the driver; the context starts over at its next use
 };
+// The totals as the kernels take them
+inline unsigned long long *mailbox(Context &c) { return reinterpret_cast<unsigned long long *>(c.mail->totals); }
 
 // Contexts outlive the threads that use them (context.cpp): a thread that ends parks its context in the pool — no HIP
 // call in a thread-local destructor — and the next thread that needs one adopts it.
@@ -338,7 +363,7 @@ struct HostTarget {
 bool pixels_code_usable(const ScanJob &j, const pixo_jpeg_options &o, const pixo_host::Geometry &g, uint32_t batch);
 // ... tables + that kernel: afterwards the finished (stuffed, padded) scan lies in c.e_out — or at `host`, memory of the host
 // that the GPU can write — and j.scan_bytes / j.total_bits / j.nbytes say how long it is.  No tuple, no packed stream is written.
-// wait = false: only enqueued (measurements); the totals are then in c.h_totals[0..2] once the stream has been synchronised.
+// wait = false: only enqueued (measurements); the totals are then in c.mail->totals[0..2] once the stream has been synchronised.
 int scan_from_pixels(Context &c, ScanJob &j, const pixo_jpeg_options &o, const pixo_host::Geometry &g, hipStream_t stream, const void *d_pixels,
                      HostTarget *host, bool wait = true, uint32_t batch = 1);
 int scan_stuff_fused(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_bit_offset, uint32_t *head, int *tail_bits,

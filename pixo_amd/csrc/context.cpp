@@ -112,6 +112,24 @@ DebugSwitches &switches()
 } // namespace
 const DebugSwitches &debug() { return switches(); }
 
+// ---- grow-only buffers --------------------------------------------------------------------------------------------------
+int Buf::regrow(size_t n)
+{
+    drop(); // (first: the old block's memory is free for the new one)
+    size_t want = n;
+    if (grow == Grow::Headroom) want = n + n / 4;
+    else if (grow == Grow::SegEnds) want = (n / 8 + n / 32 + 16) * 8;
+    const hipError_t e = mem == Mem::Device ? hipMalloc(&p, want) : hipHostMalloc(&p, want, hipHostMallocDefault);
+    if (e != hipSuccess) { p = nullptr; return hip_fail(e, mem == Mem::Device ? "hipMalloc" : "hipHostMalloc"); }
+    cap = want;
+    return PIXO_OK;
+}
+void Buf::drop()
+{
+    if (p) (void)(mem == Mem::Device ? hipFree(p) : hipHostFree(p));
+    p = nullptr; cap = 0; known = 0;
+}
+
 // ---- Context ---------------------------------------------------------------------------------------------------------
 int Context::ensure()
 {
@@ -124,84 +142,26 @@ int Context::ensure()
     if (device < 0 || device >= n) return fail(PIXO_ERR_COMPRESSION, "Compression error: no HIP device " + std::to_string(device));
     DeviceScope on(device);
     if (on.err != hipSuccess) return hip_fail(on.err, "hipSetDevice");
+    if (!mail) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&mail), sizeof(Mailbox), hipHostMallocDefault));
     HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     ready = true;
-    return PIXO_OK;
-}
-int Context::reserve_px(size_t n)
-{
-    if (n <= px_cap) return PIXO_OK;
-    if (d_px) (void)hipFree(d_px);
-    d_px = nullptr; px_cap = 0;
-    HIP_TRY(hipMalloc(&d_px, n));
-    px_cap = n;
-    return PIXO_OK;
-}
-int Context::reserve_coef(size_t n)
-{
-    if (n > coef_cap) {
-        if (d_coef) (void)hipFree(d_coef);
-        d_coef = nullptr; coef_cap = 0;
-        HIP_TRY(hipMalloc(&d_coef, n));
-        coef_cap = n;
-    }
-    return PIXO_OK;
-}
-int Context::reserve_hcoef(size_t n)
-{
-    if (n > hcoef_cap) {
-        if (h_coef) (void)hipHostFree(h_coef);
-        h_coef = nullptr; hcoef_cap = 0;
-        HIP_TRY(hipHostMalloc(&h_coef, n, hipHostMallocDefault));
-        hcoef_cap = n;
-    }
-    return PIXO_OK;
-}
-int Context::reserve_hfile(size_t n)
-{
-    if (n > hfile_cap) {
-        if (h_file) (void)hipHostFree(h_file);
-        h_file = nullptr; hfile_cap = 0;
-        const size_t want = n + n / 4;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_file), want, hipHostMallocDefault));
-        hfile_cap = want;
-    }
-    return PIXO_OK;
-}
-int Context::reserve_hsegs(size_t words)
-{
-    if (words > hsegs_cap) {
-        if (h_segs) (void)hipHostFree(h_segs);
-        h_segs = nullptr; hsegs_cap = 0;
-        // (never below 1024 words: the block also receives the 536 symbol counters of an optimised-tables pass, and a job that has handed
-        // the block's address to a kernel — SegArgs::host_out_end — must not see it move when the counters ask for their room: a
-        // standard-tables call followed by an optimised-tables call with restart intervals had the stuffing kernel write the segments'
-        // ends into the freed block — a GPU memory fault, found by tools/stress_parity.py seed 955)
-        const size_t want = (words < 1024 ? 1024 : words) + words / 4 + 16;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_segs), want * 8, hipHostMallocDefault));
-        hsegs_cap = want;
-    }
-    return PIXO_OK;
-}
-int Context::ensure_totals()
-{
-    if (!h_totals) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_totals), kTotalsWords * 8, hipHostMallocDefault));
     return PIXO_OK;
 }
 
 namespace {
 template <class F> void each_buf(Context &c, F &&f)
 {
-    Context::Buf *bufs[] = {&c.e_tables, &c.e_hist, &c.e_count, &c.e_len, &c.e_off, &c.e_tmp, &c.e_totals, &c.e_stream, &c.e_tile_ff, &c.e_tile_base,
-                            &c.e_out, &c.e_seg_bytes, &c.e_seg_off, &c.e_code_state, &c.e_stuff_state, &c.e_pc_state, &c.e_pc_spill, &c.e_chain, &c.e_segs, &c.e_seams, &c.p_in, &c.p_out,
-                            &c.p_sums, &c.p_scratch, &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank};
-    for (Context::Buf *b : bufs) f(*b);
+    Buf *bufs[] = {&c.d_px, &c.d_coef, &c.h_coef, &c.e_tables, &c.e_hist, &c.e_count, &c.e_len, &c.e_off, &c.e_tmp, &c.e_totals, &c.e_stream,
+                   &c.e_tile_ff, &c.e_tile_base, &c.e_out, &c.e_seg_bytes, &c.e_seg_off, &c.e_code_state, &c.e_stuff_state, &c.e_pc_state,
+                   &c.e_pc_spill, &c.e_chain, &c.e_seams, &c.e_segs, &c.h_segs, &c.p_in, &c.p_out, &c.p_sums, &c.p_scratch, &c.h_sums,
+                   &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank, &c.h_file};
+    for (Buf *b : bufs) f(*b);
 }
 } // namespace
 
 size_t Context::held_bytes() const
 {
-    size_t n = px_cap + coef_cap + hcoef_cap + hfile_cap + hsums_cap + hsegs_cap * 8;
+    size_t n = 0;
     each_buf(const_cast<Context &>(*this), [&](Buf &b) { n += b.cap; });
     return n;
 }
@@ -212,16 +172,7 @@ void Context::shrink_to(size_t max_buffer_bytes)
     DeviceScope on(device);
     if (on.err != hipSuccess) return;
     if (stream) (void)hipStreamSynchronize(stream);
-    each_buf(*this, [&](Buf &b) {
-        if (b.cap > max_buffer_bytes) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    });
-    if (e_tables.p == nullptr) tables_valid = false;
-    if (e_code_state.p == nullptr) code_state_zero_words = 0;
-    if (e_pc_state.p == nullptr) pc_half_words = 0;
-    if (px_cap > max_buffer_bytes) { (void)hipFree(d_px); d_px = nullptr; px_cap = 0; }
-    if (coef_cap > max_buffer_bytes) { (void)hipFree(d_coef); d_coef = nullptr; coef_cap = 0; }
-    if (hcoef_cap > max_buffer_bytes) { (void)hipHostFree(h_coef); h_coef = nullptr; hcoef_cap = 0; }
-    if (hfile_cap > max_buffer_bytes) { (void)hipHostFree(h_file); h_file = nullptr; hfile_cap = 0; }
+    each_buf(*this, [&](Buf &b) { if (b.cap > max_buffer_bytes) b.drop(); });
 }
 
 void Context::release()
@@ -231,19 +182,9 @@ void Context::release()
     DeviceScope on(device);
     if (on.err != hipSuccess) return;
     if (stream) (void)hipStreamSynchronize(stream);
-    each_buf(*this, [](Buf &b) {
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr; b.cap = 0;
-    });
-    if (d_px) (void)hipFree(d_px);
-    if (d_coef) (void)hipFree(d_coef);
-    if (h_coef) (void)hipHostFree(h_coef);
-    if (h_sums) (void)hipHostFree(h_sums);
-    if (h_totals) (void)hipHostFree(h_totals);
-    if (h_segs) (void)hipHostFree(h_segs);
-    if (h_tables) (void)hipHostFree(h_tables);
-    h_tables = nullptr; tables_valid = false;
-    if (h_file) (void)hipHostFree(h_file);
+    each_buf(*this, [](Buf &b) { b.drop(); });
+    if (mail) (void)hipHostFree(mail);
+    mail = nullptr;
     if (stream) (void)hipStreamDestroy(stream);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (upload_stream) (void)hipStreamDestroy(upload_stream);
@@ -257,10 +198,6 @@ void Context::release()
     if (stats_done) (void)hipEventDestroy(stats_done);
     if (side_ready) (void)hipEventDestroy(side_ready);
     stats_done = side_ready = nullptr;
-    code_state_zero_words = 0;
-    tables_valid = false;
-    d_px = d_coef = h_coef = nullptr; px_cap = coef_cap = hcoef_cap = 0;
-    h_sums = nullptr; hsums_cap = 0; h_totals = nullptr; h_segs = nullptr; hsegs_cap = 0; h_file = nullptr; hfile_cap = 0;
     stream = nullptr; ready = false;
 }
 

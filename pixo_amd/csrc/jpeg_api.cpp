@@ -33,19 +33,19 @@ int encode_to_view(const uint8_t *data, size_t data_len, const pixo_jpeg_options
     if ((rc = c.ensure())) return rc;
     PIXO_ON_DEVICE_OF(c);
     const size_t px_bytes = static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3);
-    if ((rc = c.reserve_px((px_bytes + 15) & ~size_t{15}))) return rc;
+    if ((rc = c.d_px.reserve((px_bytes + 15) & ~size_t{15}))) return rc;
     if (o.progressive) {
-        HIP_TRY(hipMemcpyAsync(c.d_px, data, px_bytes, hipMemcpyHostToDevice, c.stream));
+        HIP_TRY(hipMemcpyAsync(c.d_px.p, data, px_bytes, hipMemcpyHostToDevice, c.stream));
         uint8_t *direct = nullptr; // pinned / registered caller storage: the scans are copied from the device straight into it
         if (dest.kind == DestKind::Caller && dest.cap > 1 && pointer_info(dest.p).type == hipMemoryTypeHost) direct = dest.p;
-        return progressive_to_view(c.d_px, o, g, c, spill, &r.file, &r.len, direct, dest.cap);
+        return progressive_to_view(c.d_px.p, o, g, c, spill, &r.file, &r.len, direct, dest.cap);
     }
     // baseline: the entropy stage launches the uploads and the coefficient kernel itself — band by band for images of
     // 2048x2048 pixels and more, so that bands are transformed and coded while the next ones cross PCIe and the file's
     // first pieces travel back meanwhile (pieces.cpp)
     int16_t *dy, *dcb, *dcr;
     if ((rc = coeffs_reserve(c, g, &dy, &dcb, &dcr))) return rc;
-    const PixelSource src{c.d_px, &o, &g, dy, dcb, dcr, data};
+    const PixelSource src{c.d_px.p, &o, &g, dy, dcb, dcr, data};
     return encode_baseline_file(c, dy, dcb, dcr, &src, o, g, dest, r);
 }
 
@@ -246,15 +246,15 @@ int pixo_hip_jpeg_coeffs_integer(const uint8_t *pixels, uint32_t width, uint32_t
     if ((rc = c.ensure())) return rc;
     PIXO_ON_DEVICE_OF(c);
     const size_t px_bytes = static_cast<size_t>(width) * height * (g.gray ? 1 : 3), coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128;
-    if ((rc = c.reserve_px((px_bytes + 15) & ~size_t{15}))) return rc;
-    if ((rc = c.reserve_coef(coef_bytes))) return rc;
-    if ((rc = c.reserve_hcoef(coef_bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.d_px, pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
-    int16_t *dy = static_cast<int16_t *>(c.d_coef), *dcb = dy + g.y_blocks * 64, *dcr = dcb + g.c_blocks * 64;
-    if ((rc = pixo_hip_jpeg_coeffs_integer_device(c.d_px, width, height, color_type, PIXO_S444, quality, dy, dcb, dcr, c.stream))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.h_coef, c.d_coef, coef_bytes, hipMemcpyDeviceToHost, c.stream));
+    if ((rc = c.d_px.reserve((px_bytes + 15) & ~size_t{15}))) return rc;
+    if ((rc = c.d_coef.reserve(coef_bytes))) return rc;
+    if ((rc = c.h_coef.reserve(coef_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c.d_px.p, pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
+    int16_t *dy = c.d_coef.as<int16_t>(), *dcb = dy + g.y_blocks * 64, *dcr = dcb + g.c_blocks * 64;
+    if ((rc = pixo_hip_jpeg_coeffs_integer_device(c.d_px.p, width, height, color_type, PIXO_S444, quality, dy, dcb, dcr, c.stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(c.h_coef.p, c.d_coef.p, coef_bytes, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    const int16_t *hy = static_cast<const int16_t *>(c.h_coef);
+    const int16_t *hy = c.h_coef.as<const int16_t>();
     std::memcpy(y, hy, g.y_blocks * 128);
     if (g.c_blocks) {
         std::memcpy(cb, hy + g.y_blocks * 64, g.c_blocks * 128);
@@ -385,8 +385,8 @@ int batch_on_device(Context &c, const void *d_pixels, const pixo_jpeg_options &o
     int rc = device_tables(c.device, &qt_all);
     if (rc) return rc;
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128 * batch;
-    if ((rc = c.reserve_coef(coef_bytes))) return rc;
-    int16_t *dy = static_cast<int16_t *>(c.d_coef), *dcb = dy + g.y_blocks * 64 * batch, *dcr = dcb + g.c_blocks * 64 * batch;
+    if ((rc = c.d_coef.reserve(coef_bytes))) return rc;
+    int16_t *dy = c.d_coef.as<int16_t>(), *dcb = dy + g.y_blocks * 64 * batch, *dcr = dcb + g.c_blocks * 64 * batch;
     // (round 6: the entropy stage gets the PIXELS — an RGB batch goes through the fused pixel -> scan kernel, every image a segment,
     // and never writes the tuple; otherwise the stage launches the coefficient kernel over the batch itself)
     const PixelSource src{d_pixels, &o, &g, dy, dcb, dcr};
@@ -462,8 +462,8 @@ int pixo_hip_jpeg_encode_batch_device(const void *d_pixels, const pixo_jpeg_opti
     // the stuffed bytes cross PCIe once, into the context's pinned buffer (a device-to-host copy into fresh pageable blocks
     // would make the runtime pin new pages every call); from there into the files the caller will own — fresh memory,
     // page-fault bound: several threads (see big_copy)
-    if ((rc = c->reserve_hfile(scan_bytes ? scan_bytes : 1))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_file, c->e_out.p, scan_bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = c->h_file.reserve(scan_bytes ? scan_bytes : 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_file.p, c->e_out.p, scan_bytes, hipMemcpyDeviceToHost, c->stream));
     for (uint32_t i = 0; i < batch; ++i) {
         files[i] = static_cast<uint8_t *>(std::malloc(lens[i]));
         if (!files[i]) { (void)hipStreamSynchronize(c->stream); return release(fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory")); }
@@ -476,7 +476,7 @@ int pixo_hip_jpeg_encode_batch_device(const void *d_pixels, const pixo_jpeg_opti
             const size_t seg = lens[i] - hdr - 2;
             uint8_t *p = files[i];
             std::memcpy(p, head.data(), hdr);
-            std::memcpy(p + hdr, c->h_file + starts[i], seg);
+            std::memcpy(p + hdr, c->h_file.as<uint8_t>() + starts[i], seg);
             p[hdr + seg] = 0xFF; p[hdr + seg + 1] = 0xD9;
         }
     });
@@ -595,10 +595,10 @@ int pixo_hip_jpeg_encode_batch_device_into(const void *d_pixels, const pixo_jpeg
                                          // into pageable pages makes the runtime fault them in and pin them as it goes)
                 const size_t run = static_cast<size_t>(starts[nb]);
                 if (run) {
-                    if ((rc = cx.reserve_hfile(run))) break;
-                    e = hipMemcpyAsync(cx.h_file, cx.e_out.p, run, hipMemcpyDeviceToHost, cx.stream);
+                    if ((rc = cx.h_file.reserve(run))) break;
+                    e = hipMemcpyAsync(cx.h_file.p, cx.e_out.p, run, hipMemcpyDeviceToHost, cx.stream);
                     if (e == hipSuccess) e = hipStreamSynchronize(cx.stream);
-                    if (e == hipSuccess) big_copy(arena + at0 + hdr, cx.h_file, run);
+                    if (e == hipSuccess) big_copy(arena + at0 + hdr, cx.h_file.as<uint8_t>(), run);
                 }
             } else if (gaps) { // the scans lie in the device buffer at their files' final spacing: ONE copy, the host fills the gaps in afterwards
                 const size_t run = static_cast<size_t>(starts[nb]);
@@ -637,8 +637,8 @@ int pixo_hip_jpeg_encode_batch_device_into(const void *d_pixels, const pixo_jpeg
         for (uint32_t i = 0; i < batch; ++i) meta[i] = offsets[i];
         meta[batch] = at;
         std::memcpy(meta.data() + batch + 1, head.data(), hdr);
-        hipError_t e = c->e_seams.reserve(meta.size() * 8);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->e_seams.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->stream);
+        if ((rc = c->e_seams.reserve(meta.size() * 8))) return rc;
+        hipError_t e = hipMemcpyAsync(c->e_seams.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = pixo_dev::launch_batch_seams(arena, c->e_seams.as<unsigned long long>(), batch, static_cast<uint32_t>(hdr), c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return hip_fail(e, "headers of the batch files");

@@ -163,10 +163,10 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c.piece_done.push_back(e);
     }
-    HIP_TRY(c.e_chain.reserve(2 * (kMaxPieces + 1) * 8));
+    if (const int rc = c.e_chain.reserve(2 * (kMaxPieces + 1) * 8)) return rc;
     unsigned long long *bits_chain = c.e_chain.as<unsigned long long>(), *out_chain = bits_chain + kMaxPieces + 1;
     const size_t out_cap = std::max<size_t>(j.stream_cap / 4, 4096);
-    HIP_TRY(c.e_out.reserve(out_cap));
+    if (const int rc = c.e_out.reserve(out_cap)) return rc;
     // every piece has its own part of the stream buffer (a block has at most 209 bytes; 64 bytes of slack per piece)
     struct Piece { uint64_t first_block, blocks, tiles; uint32_t *stream; };
     Piece pc[kMaxPieces];
@@ -175,7 +175,7 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
         pc[k].blocks = std::min<uint64_t>(j.n, begin[k + 1] * kGroupBlocks) - pc[k].first_block;
         pc[k].tiles = pd::stuff_tiles(pc[k].blocks * 64 + 4096);
     }
-    HIP_TRY(c.e_stream.reserve(j.stream_cap + 80 * kMaxPieces));
+    if (const int rc = c.e_stream.reserve(j.stream_cap + 80 * kMaxPieces)) return rc;
     for (uint32_t k = 0; k < pieces; ++k) pc[k].stream = c.e_stream.as<uint32_t>() + (pc[k].first_block * 209 + 64 * k + 15) / 16 * 4;
     const size_t state_words = pd::fused_code_state_words(j.n);
     Stopwatch sw;
@@ -186,7 +186,7 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
     Stopwatch sw_send; // (send_piece may run on the helper thread: a stopwatch of its own)
     auto send_piece = [&](uint32_t k) -> int {
         if (redo) return PIXO_OK; // (everything that was enqueued is still waited for)
-        const uint64_t *mail = c.h_totals + 4 * k;
+        const uint64_t *mail = c.mail->totals + 4 * k;
         if (mail[3]) { redo = gave_up = true; return PIXO_OK; } // (a kernel of this piece gave up waiting: the later pieces follow suit)
         const uint64_t stream_bits = mail[0], packed = k + 1 != pieces ? stream_bits / 8 : (stream_bits + 7) / 8;
         if (pd::stuff_tiles(packed) > pc[k].tiles) { redo = true; return PIXO_OK; } // (the stuffing grid was a guess: this piece is not complete)
@@ -203,9 +203,9 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
         a.nblocks = pc[k].blocks;
         a.pad_last = k + 1 == pieces ? 1u : 0u;
         const pd::ScanPiece piece{pc[k].first_block, k, bits_chain, k ? pc[k - 1].stream : nullptr};
-        unsigned long long *mail = reinterpret_cast<unsigned long long *>(c.h_totals) + 4 * k;
-        const bool zero = c.code_state_zero_words >= state_words;
-        c.code_state_zero_words = 0;
+        unsigned long long *mail = mailbox(c) + 4 * k;
+        const bool zero = c.e_code_state.known >= state_words;
+        c.e_code_state.known = 0;
         if (groups_per_row) {
             const uint32_t row0 = static_cast<uint32_t>(begin[k] / groups_per_row);
             const uint32_t rows = k + 1 == pieces ? 0u : static_cast<uint32_t>(begin[k + 1] / groups_per_row) - row0;
@@ -218,7 +218,7 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
         HIP_TRY(pd::launch_stuff_fused(pc[k].stream, c.e_code_state.as<unsigned long long>(), state_words, 0, /*band=*/k + 1 != pieces,
                                        j.stream_cap, 0, pc[k].tiles, c.e_stuff_state.as<unsigned long long>(), /*state_is_zero=*/true,
                                        c.e_out.as<uint8_t>(), c.e_out.cap, mail, stream, out_chain, k, nullptr, debug().spin_budget));
-        c.code_state_zero_words = state_words;
+        c.e_code_state.known = state_words;
         HIP_TRY(hipEventRecord(c.piece_done[k], stream));
         return PIXO_OK;
     };

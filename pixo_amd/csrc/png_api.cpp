@@ -40,22 +40,23 @@ uint32_t combine_adler(const unsigned long long *sums, uint32_t height, uint64_t
     return static_cast<uint32_t>((s2 << 16) | s1);
 }
 
+// The per-row sums on the device, their copy on the host, the kernels' scratch word
+int reserve_sums(Context &c, uint32_t height)
+{
+    int rc;
+    if ((rc = c.p_sums.reserve(static_cast<size_t>(height) * 16)) || (rc = c.h_sums.reserve(static_cast<size_t>(height) * 16))) return rc;
+    return c.p_scratch.reserve(16);
+}
+
 int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t bpp, int run,
                          bool sequential_fast, void *d_out, uint32_t *adler)
 {
-    HIP_TRY(c.p_sums.reserve(static_cast<size_t>(height) * 16));
-    HIP_TRY(c.p_scratch.reserve(16));
-    if (static_cast<size_t>(height) * 16 > c.hsums_cap) {
-        if (c.h_sums) (void)hipHostFree(c.h_sums);
-        c.h_sums = nullptr; c.hsums_cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c.h_sums), static_cast<size_t>(height) * 16, hipHostMallocDefault));
-        c.hsums_cap = static_cast<size_t>(height) * 16;
-    }
+    if (const int rc = reserve_sums(c, height)) return rc;
     HIP_TRY(pixo_dev::launch_png_filter(d_in, width, height, bpp, run, sequential_fast, d_out,
                                         c.p_sums.as<unsigned long long>(), c.p_scratch.as<int>(), c.stream));
-    HIP_TRY(hipMemcpyAsync(c.h_sums, c.p_sums.p, static_cast<size_t>(height) * 16, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.h_sums.p, c.p_sums.p, static_cast<size_t>(height) * 16, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    *adler = combine_adler(c.h_sums, height, static_cast<uint64_t>(width) * bpp + 1);
+    *adler = combine_adler(c.h_sums.as<unsigned long long>(), height, static_cast<uint64_t>(width) * bpp + 1);
     return PIXO_OK;
 }
 
@@ -72,7 +73,7 @@ int png_filter_in_bands(Context &c, const uint8_t *data, uint32_t width, uint32_
 {
     const size_t row_in = static_cast<size_t>(width) * bpp, row_out = row_in + 1;
     const size_t out_bytes = row_out * height;
-    int rc = c.reserve_hfile(out_bytes);
+    int rc = c.h_file.reserve(out_bytes);
     if (rc) { // (the pinned staging is an optimisation — a 16384x16384 RGBA image wants 1.3 GB of it.  Without it:
               // the whole image in one go, its rows straight into the caller's storage, as before round 3)
         (void)hipGetLastError();
@@ -81,14 +82,7 @@ int png_filter_in_bands(Context &c, const uint8_t *data, uint32_t width, uint32_
         HIP_TRY(hipMemcpy(out, c.p_out.p, out_bytes, hipMemcpyDeviceToHost));
         return PIXO_OK;
     }
-    HIP_TRY(c.p_sums.reserve(static_cast<size_t>(height) * 16));
-    HIP_TRY(c.p_scratch.reserve(16));
-    if (static_cast<size_t>(height) * 16 > c.hsums_cap) {
-        if (c.h_sums) (void)hipHostFree(c.h_sums);
-        c.h_sums = nullptr; c.hsums_cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c.h_sums), static_cast<size_t>(height) * 16, hipHostMallocDefault));
-        c.hsums_cap = static_cast<size_t>(height) * 16;
-    }
+    if ((rc = reserve_sums(c, height))) return rc;
     if (!c.upload_stream) HIP_TRY(hipStreamCreateWithFlags(&c.upload_stream, hipStreamNonBlocking));
     advise_huge(out, out_bytes);
     const uint32_t band_rows = seq ? height : static_cast<uint32_t>(std::max<size_t>(1, (size_t{8} << 20) / row_in));
@@ -99,7 +93,7 @@ int png_filter_in_bands(Context &c, const uint8_t *data, uint32_t width, uint32_
         e = hipEventSynchronize(down[b]);
         const size_t off = static_cast<size_t>(b) * band_rows * row_out;
         const size_t n = std::min(static_cast<size_t>(band_rows) * row_out, out_bytes - off);
-        if (e == hipSuccess) big_copy(out + off, c.h_file + off, n);
+        if (e == hipSuccess) big_copy(out + off, c.h_file.as<uint8_t>() + off, n);
     };
     for (uint32_t b = 0; b < bands && e == hipSuccess; ++b) {
         const uint32_t r0 = b * band_rows, rows = std::min(band_rows, height - r0);
@@ -110,11 +104,11 @@ int png_filter_in_bands(Context &c, const uint8_t *data, uint32_t width, uint32_
         if (e == hipSuccess) e = hipStreamWaitEvent(c.stream, up[b], 0);
         if (e == hipSuccess) e = pixo_dev::launch_png_filter_rows(c.p_in.p, width, height, bpp, run, seq, c.p_out.p, c.p_sums.as<unsigned long long>(),
                                                                   c.p_scratch.as<int>(), r0, rows, c.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c.h_file + r0 * row_out, static_cast<const uint8_t *>(c.p_out.p) + r0 * row_out, rows * row_out, hipMemcpyDeviceToHost, c.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.h_file.as<uint8_t>() + r0 * row_out, static_cast<const uint8_t *>(c.p_out.p) + r0 * row_out, rows * row_out, hipMemcpyDeviceToHost, c.stream);
         if (e == hipSuccess) e = hipEventRecord(down[b], c.stream);
         if (e == hipSuccess && b >= 2) copy_on(b - 2);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(c.h_sums, c.p_sums.p, static_cast<size_t>(height) * 16, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.h_sums.p, c.p_sums.p, static_cast<size_t>(height) * 16, hipMemcpyDeviceToHost, c.stream);
     for (uint32_t b = bands >= 2 ? bands - 2 : 0; b < bands && e == hipSuccess; ++b) copy_on(b);
     const hipError_t e2 = hipStreamSynchronize(c.stream); // (also after an error: nothing of ours in flight when the events go)
     (void)hipStreamSynchronize(c.upload_stream);
@@ -122,7 +116,7 @@ int png_filter_in_bands(Context &c, const uint8_t *data, uint32_t width, uint32_
     for (hipEvent_t ev : up) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : down) if (ev) (void)hipEventDestroy(ev);
     if (e != hipSuccess) return hip_fail(e, "PNG filter stage in bands");
-    *adler = combine_adler(c.h_sums, height, row_out);
+    *adler = combine_adler(c.h_sums.as<unsigned long long>(), height, row_out);
     return PIXO_OK;
 }
 } // namespace
@@ -148,8 +142,7 @@ int pixo_hip_png_filter(const uint8_t *data, size_t data_len, uint32_t width, ui
     Context &c = thread_context();
     if ((rc = c.ensure())) return rc;
     PIXO_ON_DEVICE_OF(c);
-    HIP_TRY(c.p_in.reserve((in_bytes + 15) & ~size_t{15}));
-    HIP_TRY(c.p_out.reserve(out_bytes));
+    if ((rc = c.p_in.reserve((in_bytes + 15) & ~size_t{15})) || (rc = c.p_out.reserve(out_bytes))) return rc;
     if (out_bytes < (size_t{4} << 20)) { // small: one copy each way
         HIP_TRY(hipMemcpyAsync(c.p_in.p, data, in_bytes, hipMemcpyHostToDevice, c.stream));
         if ((rc = png_filter_on_device(c, c.p_in.p, width, height, bytes_per_pixel, run, seq, c.p_out.p, adler32))) return rc;

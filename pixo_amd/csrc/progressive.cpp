@@ -27,20 +27,15 @@ static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *
     a.first[0] = 0;
     for (int i = 0; i < 7; ++i) a.first[i + 1] = a.first[i] + size[i];
     const uint64_t n = a.first[7];
-    HIP_TRY(c.e_tables.reserve(pixo_scan::kScanTableUpload * 4));
-    HIP_TRY(c.g_flags.reserve(n * 4));
-    HIP_TRY(c.g_rank.reserve(n * 8));
-    HIP_TRY(c.g_by_rank.reserve(n * 4));
-    HIP_TRY(c.e_len.reserve(n * 4));
-    HIP_TRY(c.e_off.reserve(n * 8));
-    HIP_TRY(c.e_seg_bytes.reserve(8 * 8));
-    HIP_TRY(c.e_seg_off.reserve(8 * 8));
+    int rc;
+    if ((rc = c.e_tables.reserve(pixo_scan::kScanTableUpload * 4)) || (rc = c.g_flags.reserve(n * 4)) || (rc = c.g_rank.reserve(n * 8)) ||
+        (rc = c.g_by_rank.reserve(n * 4)) || (rc = c.e_len.reserve(n * 4)) || (rc = c.e_off.reserve(n * 8)) ||
+        (rc = c.e_seg_bytes.reserve(8 * 8)) || (rc = c.e_seg_off.reserve(8 * 8)))
+        return rc;
     // a block of an AC scan: at most 63 * 26 bits + an end-of-band run of at most 16 + 14 bits
     const size_t tmp_blocks = pd::scan_tile_count(n) + 1, tmp_segs = pd::scan_tile_count(7) + 1;
     const size_t tmp_tiles = pd::scan_tile_count(pd::stuff_tile_count(n * 212 + 64)) + 1;
-    HIP_TRY(c.e_tmp.reserve((tmp_blocks + tmp_segs + tmp_tiles) * 8));
-    HIP_TRY(c.e_totals.reserve(32));
-    { const int rc_t = c.ensure_totals(); if (rc_t) return rc_t; }
+    if ((rc = c.e_tmp.reserve((tmp_blocks + tmp_segs + tmp_tiles) * 8)) || (rc = c.e_totals.reserve(32))) return rc;
     a.tables = c.e_tables.as<uint32_t>();
     a.flags = c.g_flags.as<uint32_t>();
     a.nonempty = c.e_len.as<uint32_t>(); // only the input of the rank prefix sum: the lengths reuse it
@@ -51,7 +46,7 @@ static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *
     pixo_host::pack_scan_tables(h, packed);
     for (uint32_t &w : packed) // progressive.rs:363-381: a symbol the table lacks is coded as (0, 4 bits)
         if ((w >> 16) == 0) w = 4u << 16;
-    { const int rc = upload_scan_tables(c, packed, stream); if (rc) return rc; }
+    if ((rc = upload_scan_tables(c, packed, stream))) return rc;
     uint64_t *totals = c.e_totals.as<uint64_t>();
     HIP_TRY(pd::launch_prog_flags(a, stream));
     HIP_TRY(pd::launch_exclusive_scan(a.nonempty, n, c.g_rank.as<uint64_t>(), c.e_tmp.as<uint64_t>(), totals + 2, stream));
@@ -61,25 +56,25 @@ static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *
     HIP_TRY(pd::launch_prog_segment_sizes(a, c.e_off.as<uint64_t>(), totals, c.e_seg_bytes.as<uint32_t>(), stream));
     HIP_TRY(pd::launch_exclusive_scan(c.e_seg_bytes.as<uint32_t>(), 7, c.e_seg_off.as<uint64_t>(), c.e_tmp.as<uint64_t>() + tmp_blocks,
                                       totals + 1, stream));
-    HIP_TRY(hipMemcpyAsync(c.h_totals, totals, 16, hipMemcpyDeviceToHost, stream));
+    uint64_t *mail = c.mail->totals;
+    HIP_TRY(hipMemcpyAsync(mail, totals, 16, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     sw.lap("prog flags+rank+lengths");
-    const uint64_t total_bits = c.h_totals[0], nbytes = c.h_totals[1];
+    const uint64_t total_bits = mail[0], nbytes = mail[1];
     const size_t stream_bytes = (nbytes / 4 + 2) * 4;
-    HIP_TRY(c.e_stream.reserve(stream_bytes));
+    if ((rc = c.e_stream.reserve(stream_bytes))) return rc;
     HIP_TRY(hipMemsetAsync(c.e_stream.p, 0, stream_bytes, stream));
     HIP_TRY(pd::launch_prog_pack(a, c.e_off.as<uint64_t>(), total_bits, c.e_seg_off.as<uint64_t>(), c.e_stream.as<uint32_t>(), stream));
     const size_t tiles = pd::stuff_tile_count(nbytes);
-    HIP_TRY(c.e_tile_ff.reserve(tiles * 4));
-    HIP_TRY(c.e_tile_base.reserve(tiles * 8));
+    if ((rc = c.e_tile_ff.reserve(tiles * 4)) || (rc = c.e_tile_base.reserve(tiles * 8))) return rc;
     HIP_TRY(pd::launch_ff_tile_count(c.e_stream.as<uint32_t>(), nbytes, c.e_tile_ff.as<uint32_t>(), stream));
     HIP_TRY(pd::launch_exclusive_scan(c.e_tile_ff.as<uint32_t>(), tiles, c.e_tile_base.as<uint64_t>(),
                                       c.e_tmp.as<uint64_t>() + tmp_blocks + tmp_segs, totals + 1, stream));
-    HIP_TRY(hipMemcpyAsync(c.h_totals + 1, totals + 1, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(mail + 1, totals + 1, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     sw.lap("prog pack+ff census");
-    const uint64_t scan_bytes = nbytes + c.h_totals[1];
-    HIP_TRY(c.e_out.reserve(scan_bytes + 16));
+    const uint64_t scan_bytes = nbytes + mail[1];
+    if ((rc = c.e_out.reserve(scan_bytes + 16))) return rc;
     HIP_TRY(pd::launch_stuff(c.e_stream.as<uint32_t>(), nbytes, c.e_tile_base.as<uint64_t>(), c.e_out.as<uint8_t>(), stream));
     const pd::SegmentPlan plan{7, c.e_seg_off.as<uint64_t>()};
     HIP_TRY(pd::launch_segment_out_offsets(plan, nbytes, c.e_stream.as<uint32_t>(), c.e_tile_base.as<uint64_t>(),
@@ -93,9 +88,8 @@ static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *
     const size_t total = head.size() + 7 * 10 + scan_bytes + 2;
     uint8_t *p = pinned_dest; // the caller's pinned storage when the file fits: the seven copies below are its only pass over the bytes
     if (!p || total > dest_cap) {
-        int rc = c.reserve_hfile(total);
-        if (rc) return rc;
-        p = c.h_file;
+        if ((rc = c.h_file.reserve(total))) return rc;
+        p = c.h_file.as<uint8_t>();
     }
     std::memcpy(p, head.data(), head.size());
     size_t pos = head.size();
@@ -162,30 +156,26 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     sg.nsegs = a.nscans;
     sg.var = 1;
     sg.marker_bytes = 10; // room for the next scan's SOS header
-    HIP_TRY(c.e_tables.reserve(pixo_scan::kScanTableUpload * 4));
-    HIP_TRY(c.e_stream.reserve(stream_bytes + 64));
     const size_t state_words = pd::prog_code_state_words(groups);
-    if (state_words * 8 > c.e_code_state.cap) c.code_state_zero_words = 0; // (a new buffer)
-    HIP_TRY(c.e_code_state.reserve(state_words * 8));
     const size_t stuff_words = pd::fused_stuff_state_words(stream_bytes) + 8;
-    HIP_TRY(c.e_stuff_state.reserve(stuff_words * 8));
-    HIP_TRY(c.e_segs.reserve((4 * 8 + 2) * 8));
+    int rc;
+    if ((rc = c.e_tables.reserve(pixo_scan::kScanTableUpload * 4)) || (rc = c.e_stream.reserve(stream_bytes + 64)) ||
+        (rc = c.e_code_state.reserve(state_words * 8)) || (rc = c.e_stuff_state.reserve(stuff_words * 8)) ||
+        (rc = c.e_segs.reserve((4 * 8 + 2) * 8)) || (rc = c.h_segs.reserve(8 * 8))) // (h_segs: the 8 scan ends)
+        return rc;
     unsigned long long *base = c.e_segs.as<unsigned long long>();
     sg.bits = base; sg.layout = base + 8; sg.bytes = base + 2 * 8 + 2; sg.out_end = base + 3 * 8 + 2;
-    { const int rc_s = c.reserve_hsegs(pixo_host::kScanTableWords); if (rc_s) return rc_s; } // (8 scan ends; and the counters' room: see scan_begin)
-    sg.host_out_end = reinterpret_cast<unsigned long long *>(c.h_segs);
-    { const int rc_t = c.ensure_totals(); if (rc_t) return rc_t; }
+    sg.host_out_end = c.h_segs.as<unsigned long long>();
     uint32_t packed[pixo_host::kScanTableWords];
     pixo_host::pack_scan_tables(h, packed);
     for (uint32_t &w : packed) // progressive.rs:363-381: a symbol the table lacks is coded as (0, 4 bits)
         if ((w >> 16) == 0) w = 4u << 16;
-    { const int rc = upload_scan_tables(c, packed, stream); if (rc) return rc; }
+    if ((rc = upload_scan_tables(c, packed, stream))) return rc;
     a.tables = c.e_tables.as<uint32_t>();
-    const bool zero = c.code_state_zero_words >= state_words;
-    c.code_state_zero_words = 0;
-    unsigned long long *mailbox = reinterpret_cast<unsigned long long *>(c.h_totals);
+    const bool zero = c.e_code_state.known >= state_words;
+    c.e_code_state.known = 0;
     HIP_TRY(pd::launch_prog_code(a, sg, c.e_code_state.as<unsigned long long>(), zero, c.e_stream.as<uint32_t>(),
-                                 c.e_stuff_state.as<unsigned long long>(), stuff_words, mailbox, stream, debug().spin_budget));
+                                 c.e_stuff_state.as<unsigned long long>(), stuff_words, mailbox(c), stream, debug().spin_budget));
     // (the scans' layout — bytes and 16 KiB tiles of each — is worked out by the stuffing kernel's workgroups themselves: seg.var)
     // tiles: a guess of 40 bytes per (scan, block) pair + one partial tile per scan; the stuffing kernel says how many there are
     uint64_t first_tile = 0, tiles = pd::stuff_tiles(blocks_all * 40 + 4096) + a.nscans;
@@ -208,9 +198,8 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
             }
         }
         if (!direct_host) {
-            const int rc_f = c.reserve_hfile(guess);
-            if (rc_f) return rc_f;
-            direct_host = direct_dev = c.h_file; direct_cap = c.hfile_cap;
+            if ((rc = c.h_file.reserve(guess))) return rc;
+            direct_host = direct_dev = c.h_file.as<uint8_t>(); direct_cap = c.h_file.cap;
         }
         note_route(route::PROG_DIRECT_SMALL);
     }
@@ -218,22 +207,22 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
         uint8_t *out = nullptr;
         size_t out_cap = 0;
         if (direct_host) { out = direct_dev + body_at; out_cap = direct_cap - body_at - 2; }
-        else { HIP_TRY(c.e_out.reserve(want_cap)); out = c.e_out.as<uint8_t>(); out_cap = c.e_out.cap; }
+        else { if ((rc = c.e_out.reserve(want_cap))) return rc; out = c.e_out.as<uint8_t>(); out_cap = c.e_out.cap; }
         HIP_TRY(pd::launch_stuff_fused(c.e_stream.as<uint32_t>(), c.e_code_state.as<unsigned long long>(), state_words, 0, false,
                                        stream_bytes + 8 * pd::stuff_tile_bytes(), first_tile, tiles, c.e_stuff_state.as<unsigned long long>(),
-                                       /*state_is_zero=*/attempt == 0, out, out_cap, mailbox, stream, nullptr, 0, &sg,
+                                       /*state_is_zero=*/attempt == 0, out, out_cap, mailbox(c), stream, nullptr, 0, &sg,
                                        debug().spin_budget));
-        c.code_state_zero_words = state_words;
+        c.e_code_state.known = state_words;
         HIP_TRY(hipStreamSynchronize(stream));
-        if (c.h_totals[3]) return scan_retry_multipass(c);
-        const uint64_t all_tiles = c.h_totals[2];
+        if (c.mail->totals[3]) return scan_retry_multipass(c);
+        const uint64_t all_tiles = c.mail->totals[2];
         if (all_tiles > first_tile + tiles) { // the guess was short: the tiles behind it, same buffers
             if (attempt > 2) return fail(PIXO_ERR_COMPRESSION, "Compression error: packed stream longer than announced");
             first_tile += tiles;
             tiles = all_tiles - first_tile;
             continue;
         }
-        scan_bytes = c.h_totals[1];
+        scan_bytes = c.mail->totals[1];
         if (scan_bytes > out_cap) { // (unusually large: grow and repeat the stuffing pass only — into device memory)
             if (attempt > 3) return fail(PIXO_ERR_COMPRESSION, "Compression error: stuffed stream larger than announced");
             direct_host = nullptr;
@@ -249,9 +238,10 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     // c.e_out (or the file itself): [scan k0 | 10 | scan k1 | 10 | ...]; c.h_segs[k]: where scan k's bytes end.  The file: head, then
     // per scan of the script its SOS header and (if it has blocks) its bytes, then EOI.
     uint64_t dev_begin[7], dev_end[7];
+    const uint64_t *ends = c.h_segs.as<uint64_t>();
     for (uint32_t k = 0; k < a.nscans; ++k) {
-        dev_end[k] = c.h_segs[k];
-        dev_begin[k] = k ? c.h_segs[k - 1] + sg.marker_bytes : 0;
+        dev_end[k] = ends[k];
+        dev_begin[k] = k ? ends[k - 1] + sg.marker_bytes : 0;
     }
     const size_t payload = static_cast<size_t>(scan_bytes - static_cast<uint64_t>(sg.marker_bytes) * (a.nscans - 1));
     const size_t total = head.size() + 7 * 10 + payload + 2;
@@ -268,9 +258,8 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     }
     uint8_t *p = pinned_dest;
     if (!p || total > dest_cap) {
-        const int rc = c.reserve_hfile(total);
-        if (rc) return rc;
-        p = c.h_file;
+        if ((rc = c.h_file.reserve(total))) return rc;
+        p = c.h_file.as<uint8_t>();
     }
     std::memcpy(p, head.data(), head.size());
     size_t pos = head.size();
@@ -327,8 +316,8 @@ int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr,
     a.marker_bytes = 2;
     a.restart = scan_has_restart_markers(o, g) ? o.restart_interval : 0;
     a.seed_dc[0] = a.seed_dc[1] = a.seed_dc[2] = 0; a.bit_base = 0; a.pad_last = 1;
-    HIP_TRY(c.e_hist.reserve(pixo_host::kScanTableWords * 8));
-    HIP_TRY(c.e_count.reserve(pd::scan_count_scratch_bytes()));
+    int rc;
+    if ((rc = c.e_hist.reserve(pixo_host::kScanTableWords * 8)) || (rc = c.e_count.reserve(pd::scan_count_scratch_bytes()))) return rc;
     HIP_TRY(pd::launch_scan_count(a, c.e_count.as<uint32_t>(), c.e_hist.as<unsigned long long>(), c.stream));
     uint64_t counts[pixo_host::kScanTableWords];
     HIP_TRY(hipMemcpyAsync(counts, c.e_hist.p, sizeof counts, hipMemcpyDeviceToHost, c.stream));
@@ -376,7 +365,7 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
         HIP_TRY(hipEventRecord(c.side_ready, c.stream)); // (the context's stream is ordered behind the pixels' producer)
         HIP_TRY(hipStreamWaitEvent(c.copy_stream, c.side_ready, 0));
         stats_stream = c.copy_stream;
-        HIP_TRY(c.t_plain.reserve((g.y_blocks + 2 * g.c_blocks) * 128));
+        if ((rc = c.t_plain.reserve((g.y_blocks + 2 * g.c_blocks) * 128))) return rc;
         dy = c.t_plain.as<int16_t>(); dcb = dy + g.y_blocks * 64; dcr = dcb + g.c_blocks * 64;
         if ((rc = coeffs_rows(c, d_pixels, o, g, stats_stream, dy, g.gray ? nullptr : dcb, g.gray ? nullptr : dcr, 0, 0))) return rc;
     } else if (need_plain && (rc = coeffs_on_device(c, d_pixels, o, g, c.stream, &dy, &dcb, &dcr))) return rc;
@@ -393,30 +382,28 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
         a.marker_bytes = 2;
         a.restart = scan_has_restart_markers(o, g) ? o.restart_interval : 0;
         a.seed_dc[0] = a.seed_dc[1] = a.seed_dc[2] = 0; a.bit_base = 0; a.pad_last = 1;
-        HIP_TRY(c.e_hist.reserve(pixo_host::kScanTableWords * 8));
-        HIP_TRY(c.e_count.reserve(pd::scan_count_scratch_bytes()));
+        if ((rc = c.e_hist.reserve(pixo_host::kScanTableWords * 8)) || (rc = c.e_count.reserve(pd::scan_count_scratch_bytes()))) return rc;
         HIP_TRY(pd::launch_scan_count(a, c.e_count.as<uint32_t>(), c.e_hist.as<unsigned long long>(), stats_stream));
-        if ((rc = c.reserve_hsegs(pixo_host::kScanTableWords))) return rc;
-        HIP_TRY(hipMemcpyAsync(c.h_segs, c.e_hist.p, pixo_host::kScanTableWords * 8, hipMemcpyDeviceToHost, stats_stream));
+        HIP_TRY(hipMemcpyAsync(c.mail->counts, c.e_hist.p, sizeof c.mail->counts, hipMemcpyDeviceToHost, stats_stream));
         if (!c.stats_done) HIP_TRY(hipEventCreateWithFlags(&c.stats_done, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c.stats_done, stats_stream));
     } else if ((rc = huffman_for_tuple(dy, dcb, dcr, o, g, c, h))) return rc;
     const size_t blocks = g.y_blocks + 2 * g.c_blocks, coef_bytes = blocks * 128;
     if (o.trellis_quant) {
-        HIP_TRY(c.t_raw.reserve((blocks + 63) / 64 * 64 * 256)); // (whole wavefronts of the trellis kernel: jpeg_kernels.hpp)
-        if ((rc = c.reserve_coef(coef_bytes))) return rc;
+        if ((rc = c.t_raw.reserve((blocks + 63) / 64 * 64 * 256))) return rc; // (whole wavefronts of the trellis kernel: jpeg_kernels.hpp)
+        if ((rc = c.d_coef.reserve(coef_bytes))) return rc;
         float *ry = c.t_raw.as<float>(), *rcb = ry + g.y_blocks * 64, *rcr = rcb + g.c_blocks * 64;
-        dy = static_cast<int16_t *>(c.d_coef); dcb = dy + g.y_blocks * 64; dcr = dcb + g.c_blocks * 64;
+        dy = c.d_coef.as<int16_t>(); dcb = dy + g.y_blocks * 64; dcr = dcb + g.c_blocks * 64;
         HIP_TRY(pd::launch_jpeg_coeffs(d_pixels, o.width, o.height, g.gray, g.s420, 1, ry, g.gray ? nullptr : rcb,
                                        g.gray ? nullptr : rcr, qt, c.stream, /*raw_f32=*/true));
         // one launch over the whole tuple (the planes are contiguous): luminance steps, then chrominance steps
-        HIP_TRY(c.t_trail.reserve(pd::trellis_scratch_bytes(blocks)));
+        if ((rc = c.t_trail.reserve(pd::trellis_scratch_bytes(blocks)))) return rc;
         HIP_TRY(pd::launch_trellis(ry, qt + 128, qt + 192, dy, blocks, g.y_blocks, c.t_trail.p, c.stream));
     }
     if (late_tables) { // the counts have arrived (the search is still running): tables, exactly like optimized_from_counts
         HIP_TRY(hipEventSynchronize(c.stats_done));
         uint64_t dc[2][12], ac[2][256];
-        split_counts(c.h_segs, dc, ac);
+        split_counts(c.mail->counts, dc, ac);
         h = pixo_host::HuffSet::optimized(dc, ac, !g.gray);
     }
     if (debug().host_entropy) note_route(route::HOST_ENTROPY);
@@ -425,10 +412,10 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
         pixo_host::file_headers(head, o, h);
         return device_progressive_scans(dy, dcb, dcr, g, h, c, head, file, file_len, pinned_dest, dest_cap);
     }
-    if ((rc = c.reserve_hcoef(coef_bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.h_coef, dy, coef_bytes, hipMemcpyDeviceToHost, c.stream));
+    if ((rc = c.h_coef.reserve(coef_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c.h_coef.p, dy, coef_bytes, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    const int16_t *hy = static_cast<const int16_t *>(c.h_coef), *hcb = hy + g.y_blocks * 64, *hcr = hcb + g.c_blocks * 64;
+    const int16_t *hy = c.h_coef.as<const int16_t>(), *hcb = hy + g.y_blocks * 64, *hcr = hcb + g.c_blocks * 64;
     pixo_host::encode_progressive_file(hy, hcb, hcr, o, h, spill);
     *file = spill.data();
     *file_len = spill.size();

@@ -20,19 +20,19 @@ int coeffs_to_pinned(Context &c, const uint8_t *pixels, const pixo_jpeg_options 
     if (rc) return rc;
     const size_t px_bytes = static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3);
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128;
-    if ((rc = c.reserve_px((px_bytes + 15) & ~size_t{15}))) return rc;
-    if ((rc = c.reserve_coef(coef_bytes))) return rc;
-    if ((rc = c.reserve_hcoef(coef_bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.d_px, pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
-    int16_t *dy = static_cast<int16_t *>(c.d_coef);
+    if ((rc = c.d_px.reserve((px_bytes + 15) & ~size_t{15}))) return rc;
+    if ((rc = c.d_coef.reserve(coef_bytes))) return rc;
+    if ((rc = c.h_coef.reserve(coef_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(c.d_px.p, pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
+    int16_t *dy = c.d_coef.as<int16_t>();
     int16_t *dcb = dy + g.y_blocks * 64;
     int16_t *dcr = dcb + g.c_blocks * 64;
-    HIP_TRY(pixo_dev::launch_jpeg_coeffs(c.d_px, o.width, o.height, g.gray, g.s420, 1, dy,
+    HIP_TRY(pixo_dev::launch_jpeg_coeffs(c.d_px.p, o.width, o.height, g.gray, g.s420, 1, dy,
                                          g.gray ? nullptr : dcb, g.gray ? nullptr : dcr,
                                          qt_all + (o.quality - 1) * pixo_host::kDeviceQtFloats, c.stream));
-    HIP_TRY(hipMemcpyAsync(c.h_coef, c.d_coef, coef_bytes, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.h_coef.p, c.d_coef.p, coef_bytes, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    *y = static_cast<const int16_t *>(c.h_coef);
+    *y = c.h_coef.as<const int16_t>();
     *cb = *y + g.y_blocks * 64;
     *cr = *cb + g.c_blocks * 64;
     return PIXO_OK;
@@ -43,9 +43,9 @@ int coeffs_to_pinned(Context &c, const uint8_t *pixels, const pixo_jpeg_options 
 int coeffs_reserve(Context &c, const pixo_host::Geometry &g, int16_t **dy, int16_t **dcb, int16_t **dcr)
 {
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128;
-    const int rc = c.reserve_coef(coef_bytes);
+    const int rc = c.d_coef.reserve(coef_bytes);
     if (rc) return rc;
-    *dy = static_cast<int16_t *>(c.d_coef);
+    *dy = c.d_coef.as<int16_t>();
     *dcb = *dy + g.y_blocks * 64;
     *dcr = *dcb + g.c_blocks * 64;
     return PIXO_OK;
@@ -92,29 +92,28 @@ bool scan_has_restart_markers(const pixo_jpeg_options &o, const pixo_host::Geome
 // tables, image after image: one small copy less on the stream per file).
 int upload_scan_tables(Context &c, const uint32_t (&packed)[pixo_host::kScanTableWords], hipStream_t stream)
 {
-    if (c.tables_valid && c.tables_stream == stream && std::memcmp(c.tables_held, packed, sizeof packed) == 0) return PIXO_OK;
-    c.tables_valid = false;
+    if (c.e_tables.known && c.tables_stream == stream && std::memcmp(c.tables_held, packed, sizeof packed) == 0) return PIXO_OK;
+    c.e_tables.known = 0;
     std::memcpy(c.tables_held, packed, sizeof packed);
     for (int i = 0; i < pixo_scan::kWalkWords; ++i) // the same tables in the form of the flat walk (jpeg_scan_block.h)
         c.tables_held[pixo_scan::kTableWords + i] = pixo_scan::walk_table_word(packed, i);
     // (from pinned words: the copy is a plain DMA, not the runtime's staging of pageable memory.  The staging words are free again:
     // every entry point ends with the stream synchronised, and a call uploads its tables once per stream)
-    if (!c.h_tables) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c.h_tables), sizeof c.tables_held, hipHostMallocDefault));
-    std::memcpy(c.h_tables, c.tables_held, sizeof c.tables_held);
-    HIP_TRY(hipMemcpyAsync(c.e_tables.p, c.h_tables, sizeof c.tables_held, hipMemcpyHostToDevice, stream));
-    c.tables_valid = true;
+    std::memcpy(c.mail->tables, c.tables_held, sizeof c.tables_held);
+    HIP_TRY(hipMemcpyAsync(c.e_tables.p, c.mail->tables, sizeof c.tables_held, hipMemcpyHostToDevice, stream));
+    c.e_tables.known = 1;
     c.tables_stream = stream;
     return PIXO_OK;
 }
 
 // The single-pass kernels bound their waits (jpeg_scan_fused.hip): a launch that gave up says so in the pinned mailbox
-// (h_totals[3]); its outputs are garbage.  The caller of the step that notices gets kRetryMultipass back and codes the scan
+// (totals[3]); its outputs are garbage.  The caller of the step that notices gets kRetryMultipass back and codes the scan
 // again with t_force_multipass set (RetryMultipass below): the multi-pass kernels wait for nothing but kernel boundaries.
 thread_local bool t_force_multipass = false;
 std::atomic<uint64_t> g_lookback_fallbacks{0};
 int scan_retry_multipass(Context &c)
 {
-    c.code_state_zero_words = 0; // (the descriptors and the flag are dirty: the next single-pass launch starts with a memset)
+    c.e_code_state.known = 0; // (the descriptors and the flag are dirty: the next single-pass launch starts with a memset)
     g_lookback_fallbacks.fetch_add(1, std::memory_order_relaxed);
     note_route(route::FALLBACK);
     return kRetryMultipass;
@@ -167,8 +166,11 @@ int scan_begin(Context &c, ScanJob &j, const int16_t *dy, const int16_t *dcb, co
     const bool single_pass = !debug().multipass_entropy && !t_force_multipass;
     j.segmented = single_pass && j.nseg > 0 && seg_blocks >= kMinSegBlocks && seg_blocks <= 0xFFFFFFFFull;
     j.fused = single_pass && (j.nseg == 0 || j.segmented);
-    HIP_TRY(c.e_tables.reserve(pixo_scan::kScanTableUpload * 4));
-    HIP_TRY(c.e_hist.reserve(pixo_host::kScanTableWords * 8));
+    int rc;
+    if ((rc = c.e_tables.reserve(pixo_scan::kScanTableUpload * 4))) return rc;
+    if ((rc = c.e_hist.reserve(pixo_host::kScanTableWords * 8))) return rc;
+    // where every segment ends, for the single-pass tuple kernels and for the fused pixel -> scan kernel (scan_from_pixels)
+    if (j.nseg && (j.segmented || pixels_code_usable(j, o, g, batch)) && (rc = c.h_segs.reserve(j.nseg * 8))) return rc;
     if (j.segmented) {
         pd::SegArgs &sg = j.seg;
         sg.nsegs = j.nseg;
@@ -178,47 +180,40 @@ int scan_begin(Context &c, ScanJob &j, const int16_t *dy, const int16_t *dcb, co
         sg.marker_bytes = a.marker_bytes ? 2u : j.seg_gap; // RSTn, or the gap a batch wants between its files' scans
         sg.rst_markers = a.marker_bytes ? 1u : 0u;
         j.stream_cap = static_cast<size_t>(sg.stream_words) * 4 * j.nseg;
-        HIP_TRY(c.e_stream.reserve(j.stream_cap + 64));
+        if ((rc = c.e_stream.reserve(j.stream_cap + 64))) return rc;
         const size_t state_words = pd::fused_code_state_words_seg(j.nseg, seg_blocks);
-        if (state_words * 8 > c.e_code_state.cap) c.code_state_zero_words = 0; // (a new buffer)
-        HIP_TRY(c.e_code_state.reserve(state_words * 8));
+        if ((rc = c.e_code_state.reserve(state_words * 8))) return rc;
         j.code_state_words = state_words;
         // every segment's last tile is partial: one tile more per segment than the bytes alone would need
-        HIP_TRY(c.e_stuff_state.reserve((pd::fused_stuff_state_words(j.stream_cap) + j.nseg) * 8));
-        HIP_TRY(c.e_segs.reserve((4 * j.nseg + 2) * 8));
+        if ((rc = c.e_stuff_state.reserve((pd::fused_stuff_state_words(j.stream_cap) + j.nseg) * 8))) return rc;
+        if ((rc = c.e_segs.reserve((4 * j.nseg + 2) * 8))) return rc;
         unsigned long long *base = c.e_segs.as<unsigned long long>();
         sg.bits = base;
         sg.layout = base + j.nseg;
         sg.bytes = base + 2 * j.nseg + 2;
         sg.out_end = base + 3 * j.nseg + 2;
-        // (room for the optimised-tables counters as well: scan_count / pixels_count reserve theirs AFTER this address has been handed out)
-        { const int rc_s = c.reserve_hsegs(std::max<size_t>(j.nseg, pixo_host::kScanTableWords)); if (rc_s) return rc_s; }
-        sg.host_out_end = reinterpret_cast<unsigned long long *>(c.h_segs);
-        { const int rc_t = c.ensure_totals(); if (rc_t) return rc_t; }
+        sg.host_out_end = c.h_segs.as<unsigned long long>();
         a.tables = c.e_tables.as<uint32_t>();
         a.pad_last = 1;
         return PIXO_OK;
     }
     if (j.fused) { // a block has at most 1665 bits: the packed stream has at most n * 209 bytes (+ slack the kernels read into)
         j.stream_cap = static_cast<size_t>(j.n) * 209 + 64;
-        HIP_TRY(c.e_stream.reserve(j.stream_cap));
-        if (pd::fused_code_state_words(j.n) * 8 > c.e_code_state.cap) c.code_state_zero_words = 0; // (a new buffer)
-        HIP_TRY(c.e_code_state.reserve(pd::fused_code_state_words(j.n) * 8));
+        if ((rc = c.e_stream.reserve(j.stream_cap))) return rc;
+        if ((rc = c.e_code_state.reserve(pd::fused_code_state_words(j.n) * 8))) return rc;
         j.code_state_words = pd::fused_code_state_words(j.n);
-        HIP_TRY(c.e_stuff_state.reserve(pd::fused_stuff_state_words(j.stream_cap) * 8));
-        { const int rc_t = c.ensure_totals(); if (rc_t) return rc_t; }
+        if ((rc = c.e_stuff_state.reserve(pd::fused_stuff_state_words(j.stream_cap) * 8))) return rc;
         a.tables = c.e_tables.as<uint32_t>();
         return PIXO_OK;
     }
-    HIP_TRY(c.e_len.reserve((j.n ? j.n : 1) * 4));
-    HIP_TRY(c.e_off.reserve((j.n ? j.n : 1) * 8));
+    if ((rc = c.e_len.reserve((j.n ? j.n : 1) * 4))) return rc;
+    if ((rc = c.e_off.reserve((j.n ? j.n : 1) * 8))) return rc;
     // scratch of the three prefix sums (blocks, restart segments, 0xFF tiles), reserved before any launch:
     // a block has at most 1665 bits, so the packed stream has at most n * 209 + 3 * nseg bytes
     j.tmp_blocks = pd::scan_tile_count(j.n) + 1; j.tmp_segs = pd::scan_tile_count(j.nseg ? j.nseg : 1) + 1;
     j.tmp_tiles = pd::scan_tile_count(pd::stuff_tile_count(j.n * 209 + 3 * j.nseg + 8)) + 1;
-    HIP_TRY(c.e_tmp.reserve((j.tmp_blocks + j.tmp_segs + j.tmp_tiles) * 8));
-    HIP_TRY(c.e_totals.reserve(16));
-    { const int rc_t = c.ensure_totals(); if (rc_t) return rc_t; }
+    if ((rc = c.e_tmp.reserve((j.tmp_blocks + j.tmp_segs + j.tmp_tiles) * 8))) return rc;
+    if ((rc = c.e_totals.reserve(16))) return rc;
     a.tables = c.e_tables.as<uint32_t>();
     return PIXO_OK;
 }
@@ -234,14 +229,13 @@ void split_counts(const uint64_t counts[pixo_host::kScanTableWords], uint64_t dc
 // count_block statistics of the pass (src/jpeg/mod.rs:826-860) gathered on the device: [class][12 DC + 256 AC].
 int scan_count(Context &c, ScanJob &j, hipStream_t stream, uint64_t counts[pixo_host::kScanTableWords])
 {
-    HIP_TRY(c.e_count.reserve(pixo_dev::scan_count_scratch_bytes()));
+    if (const int rc = c.e_count.reserve(pixo_dev::scan_count_scratch_bytes())) return rc;
     HIP_TRY(pixo_dev::launch_scan_count(j.a, c.e_count.as<uint32_t>(), c.e_hist.as<unsigned long long>(), stream));
     // (into the context's pinned words and from there to the caller's array: a copy to pageable memory goes through the runtime's
     // staging buffer and costs a small optimised-tables file about ten microseconds)
-    { const int rc = c.reserve_hsegs(pixo_host::kScanTableWords); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(c.h_segs, c.e_hist.p, pixo_host::kScanTableWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(c.mail->counts, c.e_hist.p, sizeof c.mail->counts, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    std::memcpy(counts, c.h_segs, pixo_host::kScanTableWords * 8);
+    std::memcpy(counts, c.mail->counts, sizeof c.mail->counts);
     return PIXO_OK;
 }
 
@@ -254,13 +248,12 @@ int pixels_count(Context &c, const pixo_jpeg_options &o, const pixo_host::Geomet
     { const int rc = device_tables(c.device, &qt_all); if (rc) return rc; }
     const uint32_t restart = scan_has_restart_markers(o, g) ? o.restart_interval : 0;
     const pd::PixelsCodePlan plan = pd::pixels_code_plan(o.width, o.height, g.s420, 1, restart, g.gray);
-    HIP_TRY(c.e_count.reserve(pd::pixels_count_scratch_bytes(plan)));
+    if (const int rc = c.e_count.reserve(pd::pixels_count_scratch_bytes(plan))) return rc;
     HIP_TRY(pd::launch_pixels_count(d_pixels, o.width, o.height, g.gray, g.s420, plan, qt_all + (o.quality - 1) * pixo_host::kDeviceQtFloats, c.e_count.p,
                                     c.e_hist.as<unsigned long long>(), stream));
-    { const int rc = c.reserve_hsegs(pixo_host::kScanTableWords); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(c.h_segs, c.e_hist.p, pixo_host::kScanTableWords * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(c.mail->counts, c.e_hist.p, sizeof c.mail->counts, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    std::memcpy(counts, c.h_segs, pixo_host::kScanTableWords * 8);
+    std::memcpy(counts, c.mail->counts, sizeof c.mail->counts);
     return PIXO_OK;
 }
 
@@ -301,31 +294,31 @@ int scan_lengths(Context &c, ScanJob &j, const pixo_jpeg_options &o, const pixo_
     note_route(route::TWO_KERNEL | (j.segmented ? route::SEGMENTED_TUPLE : 0) | (j.fused ? route::SINGLE_PASS_TUPLE : route::MULTI_PASS));
     if (j.segmented) { // every segment packed into its own stream from bit 0; always chained with the stuffing kernel
         const size_t state_words = pd::fused_code_state_words_seg(j.seg.nsegs, j.seg.blocks);
-        const bool zero = c.code_state_zero_words >= state_words;
-        c.code_state_zero_words = 0;
+        const bool zero = c.e_code_state.known >= state_words;
+        c.e_code_state.known = 0;
         HIP_TRY(pd::launch_scan_code(j.a, c.e_code_state.as<unsigned long long>(), zero, c.e_stream.as<uint32_t>(),
                                      c.e_stuff_state.as<unsigned long long>(), pd::fused_stuff_state_words(j.stream_cap) + j.nseg,
-                                     reinterpret_cast<unsigned long long *>(c.h_totals), stream, nullptr, &j.seg, debug().spin_budget));
+                                     mailbox(c), stream, nullptr, &j.seg, debug().spin_budget));
         HIP_TRY(pd::launch_seg_layout(j.seg, const_cast<unsigned long long *>(j.seg.layout), const_cast<unsigned long long *>(j.seg.bytes),
-                                      reinterpret_cast<unsigned long long *>(c.h_totals), stream));
+                                      mailbox(c), stream));
         if (wait) { // (a caller that wants the lengths now: none of the product's paths; kept for symmetry)
             HIP_TRY(hipStreamSynchronize(stream));
-            if (c.h_totals[3]) return scan_retry_multipass(c);
+            if (c.mail->totals[3]) return scan_retry_multipass(c);
         }
         return PIXO_OK;
     }
     if (j.fused) { // lengths, prefix and packing in one pass; the stream starts at bit 0 whatever the band's offset will be
-        const bool zero = c.code_state_zero_words >= pd::fused_code_state_words(j.n);
-        c.code_state_zero_words = 0; // (dirty from here until a stuffing launch has cleaned it)
+        const bool zero = c.e_code_state.known >= pd::fused_code_state_words(j.n);
+        c.e_code_state.known = 0; // (dirty from here until a stuffing launch has cleaned it)
         // chained with the stuffing kernel (!wait): this launch also zeroes that kernel's descriptors
         HIP_TRY(pd::launch_scan_code(j.a, c.e_code_state.as<unsigned long long>(), zero, c.e_stream.as<uint32_t>(),
                                      wait ? nullptr : c.e_stuff_state.as<unsigned long long>(),
-                                     wait ? 0 : pd::fused_stuff_state_words(j.stream_cap), reinterpret_cast<unsigned long long *>(c.h_totals), stream,
+                                     wait ? 0 : pd::fused_stuff_state_words(j.stream_cap), mailbox(c), stream,
                                      nullptr, nullptr, debug().spin_budget));
         if (!wait) return PIXO_OK; // (the caller chains the stuffing kernel and synchronises once)
         HIP_TRY(hipStreamSynchronize(stream)); // (the kernel wrote the length into the pinned mailbox itself)
-        if (c.h_totals[3]) return scan_retry_multipass(c);
-        j.total_bits = c.h_totals[0];
+        if (c.mail->totals[3]) return scan_retry_multipass(c);
+        j.total_bits = c.mail->totals[0];
         j.nbytes = (j.total_bits + 7) / 8;
         return PIXO_OK;
     }
@@ -333,18 +326,18 @@ int scan_lengths(Context &c, ScanJob &j, const pixo_jpeg_options &o, const pixo_
     HIP_TRY(pd::launch_exclusive_scan(c.e_len.as<uint32_t>(), j.n, c.e_off.as<uint64_t>(), c.e_tmp.as<uint64_t>(),
                                       c.e_totals.as<uint64_t>(), stream));
     if (j.nseg) { // restart markers: byte-aligned segments, each followed by two marker bytes
-        HIP_TRY(c.e_seg_bytes.reserve(j.nseg * 8));
-        HIP_TRY(c.e_seg_off.reserve(j.nseg * 8));
+        if (const int rc = c.e_seg_bytes.reserve(j.nseg * 8)) return rc;
+        if (const int rc = c.e_seg_off.reserve(j.nseg * 8)) return rc;
         HIP_TRY(pd::launch_segment_sizes(j.a, c.e_off.as<uint64_t>(), c.e_totals.as<uint64_t>(), j.nseg, c.e_seg_bytes.as<uint32_t>(), stream));
         HIP_TRY(pd::launch_exclusive_scan(c.e_seg_bytes.as<uint32_t>(), j.nseg, c.e_seg_off.as<uint64_t>(),
                                           c.e_tmp.as<uint64_t>() + j.tmp_blocks, c.e_totals.as<uint64_t>() + 1, stream));
         j.plan.nsegments = j.nseg;
         j.plan.seg_byte_off = c.e_seg_off.as<uint64_t>();
     }
-    HIP_TRY(hipMemcpyAsync(c.h_totals, c.e_totals.p, 16, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(c.mail->totals, c.e_totals.p, 16, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream)); // `packed` may go out of scope after this, too
-    j.total_bits = c.h_totals[0];
-    j.nbytes = j.nseg ? c.h_totals[1] : (j.total_bits + 7) / 8; // bytes of the packed (unstuffed) stream
+    j.total_bits = c.mail->totals[0];
+    j.nbytes = j.nseg ? c.mail->totals[1] : (j.total_bits + 7) / 8; // bytes of the packed (unstuffed) stream
     return PIXO_OK;
 }
 
@@ -373,16 +366,16 @@ bool pixels_code_usable(const ScanJob &j, const pixo_jpeg_options &o, const pixo
 static int output_window(Context &c, HostTarget *host, size_t want_cap, uint8_t **out, size_t *out_cap)
 {
     if (!host) {
-        HIP_TRY(c.e_out.reserve(want_cap));
+        if (const int rc = c.e_out.reserve(want_cap)) return rc;
         *out = c.e_out.as<uint8_t>();
         *out_cap = c.e_out.cap;
         return PIXO_OK;
     }
     if (host->grow) {
-        const int rc = c.reserve_hfile(host->before + want_cap + host->after);
+        const int rc = c.h_file.reserve(host->before + want_cap + host->after);
         if (rc) return rc;
-        host->p = c.h_file + host->before;
-        host->cap = c.hfile_cap - host->before - host->after;
+        host->p = c.h_file.as<uint8_t>() + host->before;
+        host->cap = c.h_file.cap - host->before - host->after;
     }
     *out = host->p;
     *out_cap = host->cap;
@@ -405,21 +398,21 @@ int scan_from_pixels(Context &c, ScanJob &j, const pixo_jpeg_options &o, const p
     const uint32_t gap = !segs ? 0u : (restart ? 2u : j.seg_gap); // RSTn, or what a batch wants between its files' scans
     const bool rst = segs && restart != 0;
     note_route((segs ? route::FUSED_SEGMENTED : route::FUSED) | (host ? route::FUSED_DIRECT : 0));
-    if (segs) { // (where every segment ends: the kernel's pinned mailbox, like the single-pass tuple kernels')
-        if ((rc = c.reserve_hsegs(plan.segments))) return rc;
+    if (segs) { // (where every segment ends: c.h_segs, reserved by scan_begin, like the single-pass tuple kernels')
+        if (c.h_segs.cap < plan.segments * 8) return fail(PIXO_ERR_COMPRESSION, "Compression error: segments of the scan not reserved");
         j.pc_seg = true;
         j.seg.marker_bytes = gap;
     }
     // two state blocks: this launch's must be zero, and the launch zeroes the other one (the launch before it used that) on the side
-    if (c.e_pc_state.cap < 2 * words * 8 || c.pc_half_words != words) {
-        HIP_TRY(c.e_pc_state.reserve(2 * words * 8));
+    if ((rc = c.e_pc_state.reserve(2 * words * 8))) return rc;
+    if (c.e_pc_state.known != words) {
         HIP_TRY(hipMemsetAsync(c.e_pc_state.p, 0, 2 * words * 8, stream));
-        c.pc_half_words = words;
+        c.e_pc_state.known = words;
         c.pc_flip = 0;
     }
     // groups of several 6 KiB rounds park their blocks here (jpeg_pixels_code.hip).  NOT in d_coef: the tuple pointers the caller
     // derived from it must stay valid for the multi-pass retry, and a hipFree would synchronise the device in the middle of the call
-    HIP_TRY(c.e_pc_spill.reserve(static_cast<size_t>(plan.groups) * 192 * 128));
+    if ((rc = c.e_pc_spill.reserve(static_cast<size_t>(plan.groups) * 192 * 128))) return rc;
     size_t want_cap = std::max<size_t>(j.stream_cap / 4, 4096) + static_cast<size_t>(plan.segments) * gap;
     for (int attempt = 0;; ++attempt) {
         uint8_t *out = nullptr;
@@ -430,14 +423,14 @@ int scan_from_pixels(Context &c, ScanJob &j, const pixo_jpeg_options &o, const p
         c.pc_flip ^= 1;
         HIP_TRY(pd::launch_pixels_code(d_pixels, o.width, o.height, g.gray, g.s420, plan, gap, rst, qt_all + (o.quality - 1) * pixo_host::kDeviceQtFloats,
                                        c.e_tables.as<uint32_t>(), mine, /*state_is_zero=*/true, other, words, out, out_cap,
-                                       reinterpret_cast<unsigned long long *>(c.h_totals), segs ? reinterpret_cast<unsigned long long *>(c.h_segs) : nullptr,
+                                       mailbox(c), segs ? c.h_segs.as<unsigned long long>() : nullptr,
                                        nullptr, true, c.e_pc_spill.p, stream, debug().spin_budget));
         if (!wait) return PIXO_OK;
         HIP_TRY(hipStreamSynchronize(stream));
-        if (c.h_totals[3]) { c.pc_half_words = 0; return scan_retry_multipass(c); } // (both blocks are memset before the next use)
-        j.total_bits = c.h_totals[0];
-        j.scan_bytes = c.h_totals[1];
-        j.nbytes = segs ? 0 : c.h_totals[2];
+        if (c.mail->totals[3]) { c.e_pc_state.known = 0; return scan_retry_multipass(c); } // (both blocks are memset before the next use)
+        j.total_bits = c.mail->totals[0];
+        j.scan_bytes = c.mail->totals[1];
+        j.nbytes = segs ? 0 : c.mail->totals[2];
         if (j.scan_bytes > out_cap) { // (nothing was stored beyond the capacity: more room, the same kernel again)
             if (host && !host->grow) return PIXO_OK; // (the caller's storage is what it is: the caller reports the size needed)
             if (attempt > 1) return fail(PIXO_ERR_COMPRESSION, "Compression error: scan larger than announced");
@@ -468,22 +461,22 @@ int scan_stuff_segmented(Context &c, ScanJob &j, hipStream_t stream)
     uint64_t first_tile = 0, tiles = per_seg * j.nseg;
     size_t want_cap = std::max<size_t>(j.stream_cap / 4, 4096);
     for (int attempt = 0;; ++attempt) {
-        HIP_TRY(c.e_out.reserve(want_cap));
+        if (const int rc = c.e_out.reserve(want_cap)) return rc;
         HIP_TRY(pd::launch_stuff_fused(c.e_stream.as<uint32_t>(), c.e_code_state.as<unsigned long long>(), code_words, 0, false,
                                        j.stream_cap + j.nseg * pd::stuff_tile_bytes(), first_tile, tiles, c.e_stuff_state.as<unsigned long long>(),
                                        /*state_is_zero=*/attempt == 0, c.e_out.as<uint8_t>(), c.e_out.cap,
-                                       reinterpret_cast<unsigned long long *>(c.h_totals), stream, nullptr, 0, &j.seg, debug().spin_budget));
-        c.code_state_zero_words = code_words;
+                                       mailbox(c), stream, nullptr, 0, &j.seg, debug().spin_budget));
+        c.e_code_state.known = code_words;
         HIP_TRY(hipStreamSynchronize(stream));
-        if (c.h_totals[3]) return scan_retry_multipass(c);
-        const uint64_t all_tiles = c.h_totals[2];
+        if (c.mail->totals[3]) return scan_retry_multipass(c);
+        const uint64_t all_tiles = c.mail->totals[2];
         if (all_tiles > first_tile + tiles) { // the guess was short: the tiles behind it, same buffers
             if (attempt > 2) return fail(PIXO_ERR_COMPRESSION, "Compression error: packed stream longer than announced");
             first_tile += tiles;
             tiles = all_tiles - first_tile;
             continue;
         }
-        j.scan_bytes = c.h_totals[1];
+        j.scan_bytes = c.mail->totals[1];
         if (j.scan_bytes > c.e_out.cap) { // (unusually many 0xFF bytes: grow and repeat the stuffing pass only)
             if (attempt > 2) return fail(PIXO_ERR_COMPRESSION, "Compression error: stuffed stream larger than announced");
             note_route(route::RESTUFF_GROW);
@@ -520,9 +513,9 @@ int scan_stuff_fused(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_b
         HIP_TRY(pd::launch_stuff_fused(c.e_stream.as<uint32_t>(), c.e_code_state.as<unsigned long long>(), j.code_state_words,
                                        shift, j.band, j.stream_cap, first_tile, tiles, c.e_stuff_state.as<unsigned long long>(),
                                        /*state_is_zero=*/chained && attempt == 0, out, out_cap,
-                                       reinterpret_cast<unsigned long long *>(c.h_totals), stream, nullptr, 0, nullptr, debug().spin_budget));
-        c.code_state_zero_words = j.code_state_words;
-        // (no read-back copies: both kernels store their totals into the pinned mailbox h_totals — [0] bits of the scan,
+                                       mailbox(c), stream, nullptr, 0, nullptr, debug().spin_budget));
+        c.e_code_state.known = j.code_state_words;
+        // (no read-back copies: both kernels store their totals into the pinned mailbox — [0] bits of the scan,
         // [1] stuffed bytes, [2] packed bytes — which the host reads after the synchronisation below)
         uint32_t edge[3] = {0, 0, 0}; // band: stream word 0 (head bits) and the two words around the tail bits
         if (j.band) {
@@ -531,8 +524,8 @@ int scan_stuff_fused(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_b
             HIP_TRY(hipMemcpyAsync(&edge[1], c.e_stream.as<uint32_t>() + (tail_at >> 5), 8, hipMemcpyDeviceToHost, stream));
         }
         HIP_TRY(hipStreamSynchronize(stream));
-        if (c.h_totals[3]) return scan_retry_multipass(c);
-        j.total_bits = c.h_totals[0];
+        if (c.mail->totals[3]) return scan_retry_multipass(c);
+        j.total_bits = c.mail->totals[0];
         const uint64_t packed = j.band ? (j.total_bits - j.head_bits) / 8 : (j.total_bits + 7) / 8;
         if (pd::stuff_tiles(packed) > first_tile + tiles) { // the guess was short: the tiles behind it, same buffers
             if (attempt > 2) return fail(PIXO_ERR_COMPRESSION, "Compression error: packed stream longer than announced");
@@ -540,8 +533,8 @@ int scan_stuff_fused(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_b
             tiles = pd::stuff_tiles(packed) - first_tile;
             continue;
         }
-        j.scan_bytes = c.h_totals[1];
-        j.nbytes = c.h_totals[2];
+        j.scan_bytes = c.mail->totals[1];
+        j.nbytes = c.mail->totals[2];
         if (j.scan_bytes > out_cap) { // (first call with unusually many 0xFF bytes: grow and repeat the stuffing pass only)
             if (host && !host->grow) return PIXO_OK; // (the caller's storage is what it is: the caller reports the size needed)
             if (attempt > 2) return fail(PIXO_ERR_COMPRESSION, "Compression error: stuffed stream larger than announced");
@@ -582,25 +575,25 @@ int scan_pack(Context &c, ScanJob &j, hipStream_t stream, uint64_t band_bit_offs
         word_off = 1;
     }
     const size_t stream_bytes = j.band ? ((stream_bits + 31) / 32 + 2) * 4 : (j.nbytes / 4 + 2) * 4;
-    HIP_TRY(c.e_stream.reserve(stream_bytes));
+    if (const int rc = c.e_stream.reserve(stream_bytes)) return rc;
     HIP_TRY(hipMemsetAsync(c.e_stream.p, 0, stream_bytes, stream));
     if (j.n) HIP_TRY(pd::launch_scan_pack(j.a, c.e_off.as<uint64_t>(), j.total_bits, j.nseg ? &j.plan : nullptr, c.e_stream.as<uint32_t>(), stream));
     const uint32_t *body = c.e_stream.as<uint32_t>() + word_off;
     const size_t tiles = pd::stuff_tile_count(j.nbytes);
-    HIP_TRY(c.e_tile_ff.reserve((tiles ? tiles : 1) * 4));
-    HIP_TRY(c.e_tile_base.reserve((tiles ? tiles : 1) * 8));
+    if (const int rc = c.e_tile_ff.reserve((tiles ? tiles : 1) * 4)) return rc;
+    if (const int rc = c.e_tile_base.reserve((tiles ? tiles : 1) * 8)) return rc;
     if (tiles) HIP_TRY(pd::launch_ff_tile_count(body, j.nbytes, c.e_tile_ff.as<uint32_t>(), stream));
     HIP_TRY(pd::launch_exclusive_scan(c.e_tile_ff.as<uint32_t>(), tiles, c.e_tile_base.as<uint64_t>(),
                                       c.e_tmp.as<uint64_t>() + j.tmp_blocks + j.tmp_segs, c.e_totals.as<uint64_t>() + 1, stream));
-    HIP_TRY(hipMemcpyAsync(c.h_totals + 1, c.e_totals.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(c.mail->totals + 1, c.e_totals.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, stream));
     uint32_t edge[2] = {0, 0}; // band: word 0 (head bits) and the word holding the tail bits
     if (j.band) {
         HIP_TRY(hipMemcpyAsync(&edge[0], c.e_stream.p, 4, hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipMemcpyAsync(&edge[1], c.e_stream.as<uint32_t>() + 1 + j.nbytes / 4, 4, hipMemcpyDeviceToHost, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));
-    j.scan_bytes = j.nbytes + c.h_totals[1];
-    HIP_TRY(c.e_out.reserve(j.scan_bytes ? j.scan_bytes : 1));
+    j.scan_bytes = j.nbytes + c.mail->totals[1];
+    if (const int rc = c.e_out.reserve(j.scan_bytes ? j.scan_bytes : 1)) return rc;
     if (tiles) HIP_TRY(pd::launch_stuff(body, j.nbytes, c.e_tile_base.as<uint64_t>(), c.e_out.as<uint8_t>(), stream));
     if (j.nseg) HIP_TRY(pd::launch_restart_markers(j.a, c.e_off.as<uint64_t>(), j.plan, c.e_stream.as<uint32_t>(), c.e_tile_base.as<uint64_t>(),
                                                    c.e_out.as<uint8_t>(), stream));
@@ -638,8 +631,8 @@ extern "C" int pixo_hip_debug_scan_device_async_batch(const void *d_pixels, cons
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const pixo_host::Geometry g = pixo_host::geometry(options->width, options->height, options->color_type, options->subsampling);
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128 * batch;
-    if ((rc = c->reserve_coef(coef_bytes))) return rc;
-    int16_t *dy = static_cast<int16_t *>(c->d_coef), *dcb = dy + g.y_blocks * 64 * batch, *dcr = dcb + g.c_blocks * 64 * batch;
+    if ((rc = c->d_coef.reserve(coef_bytes))) return rc;
+    int16_t *dy = c->d_coef.as<int16_t>(), *dcb = dy + g.y_blocks * 64 * batch, *dcr = dcb + g.c_blocks * 64 * batch;
     ScanJob j;
     if (batch > 1) { // (the gap a batch leaves between two scans: EOI + the next file's headers)
         std::vector<uint8_t> probe_head;
@@ -661,21 +654,21 @@ extern "C" int pixo_hip_debug_scan_device_async_batch(const void *d_pixels, cons
     if (j.segmented) { // (the product's first guess of the stuffing grid: scan_stuff_segmented)
         const size_t code_words = pd::fused_code_state_words_seg(j.seg.nsegs, j.seg.blocks);
         const uint64_t per_seg = pd::stuff_tiles(static_cast<uint64_t>(j.seg.blocks) * 64 + 4096);
-        HIP_TRY(c->e_out.reserve(std::max<size_t>(j.stream_cap / 4, 4096)));
+        if ((rc = c->e_out.reserve(std::max<size_t>(j.stream_cap / 4, 4096)))) return rc;
         HIP_TRY(pd::launch_stuff_fused(c->e_stream.as<uint32_t>(), c->e_code_state.as<unsigned long long>(), code_words, 0, false,
                                        j.stream_cap + j.nseg * pd::stuff_tile_bytes(), 0, per_seg * j.nseg, c->e_stuff_state.as<unsigned long long>(),
-                                       /*state_is_zero=*/true, c->e_out.as<uint8_t>(), c->e_out.cap, reinterpret_cast<unsigned long long *>(c->h_totals), stream,
+                                       /*state_is_zero=*/true, c->e_out.as<uint8_t>(), c->e_out.cap, mailbox(*c), stream,
                                        nullptr, 0, &j.seg, debug().spin_budget));
-        c->code_state_zero_words = code_words;
+        c->e_code_state.known = code_words;
         return PIXO_OK;
     }
     const size_t want_cap = std::max<size_t>(j.stream_cap / 4, 4096);
-    HIP_TRY(c->e_out.reserve(want_cap));
+    if ((rc = c->e_out.reserve(want_cap))) return rc;
     const uint64_t tiles = pd::stuff_tiles(std::min<uint64_t>(j.stream_cap, j.n * 64 + 4096));
     HIP_TRY(pd::launch_stuff_fused(c->e_stream.as<uint32_t>(), c->e_code_state.as<unsigned long long>(), j.code_state_words, 0, false, j.stream_cap, 0,
                                    tiles, c->e_stuff_state.as<unsigned long long>(), /*state_is_zero=*/true, c->e_out.as<uint8_t>(), c->e_out.cap,
-                                   reinterpret_cast<unsigned long long *>(c->h_totals), stream, nullptr, 0, nullptr, debug().spin_budget));
-    c->code_state_zero_words = j.code_state_words;
+                                   mailbox(*c), stream, nullptr, 0, nullptr, debug().spin_budget));
+    c->e_code_state.known = j.code_state_words;
     return PIXO_OK;
 }
 extern "C" int pixo_hip_debug_scan_device_async(const void *d_pixels, const pixo_jpeg_options *options, void *stream_, int *form)

@@ -145,10 +145,10 @@ def test_bands_over_devices():
 # ---- grow pairs: a small call, then one that grows the buffer on a route that handed an earlier pointer to a kernel ----
 # (buffer, first call, second call, a route the second call must take)
 GROW_PAIRS = [
-    ("reserve_px / reserve_coef / reserve_hcoef", case(64, 64, "encode", ct=0, ss=0, opt=True),
+    ("d_px / d_coef / h_coef", case(64, 64, "encode", ct=0, ss=0, opt=True),
      case(1500, 1100, "encode", ct=0, ss=0, opt=True), "TWO_KERNEL"),
-    ("reserve_hfile (fused, direct)", case(32, 32, "encode_device"), case(1800, 1200, "encode_device", q=100), "RESTUFF_GROW"),
-    ("reserve_hsegs (segments, optimised tables)", case(64, 64, "encode_device", restart=4),
+    ("h_file (fused, direct)", case(32, 32, "encode_device"), case(1800, 1200, "encode_device", q=100), "RESTUFF_GROW"),
+    ("h_segs (segments, optimised tables)", case(64, 64, "encode_device", restart=4),
      case(1200, 900, "encode_device", restart=75, opt=True), "SEGMENTED_TUPLE"),
     ("e_out (segmented tuple)", case(64, 64, "encode_device", ct=0, ss=0, restart=12),
      case(1600, 1200, "encode_device", ct=0, ss=0, q=100, restart=200), "SEGMENTED_TUPLE"),
