@@ -14,6 +14,10 @@
 //   pixo::jpeg::encode                 jpeg/mod.rs:88   pixo::jpeg::encode
 //   pixo::jpeg::encode_into            jpeg/mod.rs:328  pixo::jpeg::encode_into
 //   (wasm) encode_jpeg                 wasm.rs:113      pixo::encode_jpeg
+//   pixo::resize::ResizeAlgorithm      resize.rs:33     pixo::resize::ResizeAlgorithm
+//   pixo::resize::ResizeOptions + builder resize.rs:65  pixo::resize::ResizeOptions / ResizeOptionsBuilder
+//   pixo::resize::resize / resize_into resize.rs:165    pixo::resize::resize / resize_into
+//   (wasm) resizeImage                 wasm.rs:183      pixo::resize_image
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -189,6 +193,93 @@ namespace filter {
 }
 } // namespace filter
 } // namespace png
+
+namespace resize {
+// resize.rs:33-45; Default = Bilinear
+enum class ResizeAlgorithm : uint8_t { Nearest = 0, Bilinear = 1, Lanczos3 = 2 };
+
+class ResizeOptionsBuilder;
+
+// resize.rs:65-79
+struct ResizeOptions {
+    uint32_t src_width = 0, src_height = 0;
+    uint32_t dst_width = 0, dst_height = 0;
+    ColorType color_type = ColorType::Rgba;
+    ResizeAlgorithm algorithm = ResizeAlgorithm::Bilinear;
+    static ResizeOptionsBuilder builder(uint32_t src_width, uint32_t src_height);
+    pixo_resize_options c() const
+    {
+        pixo_resize_options o;
+        o.src_width = src_width; o.src_height = src_height;
+        o.dst_width = dst_width; o.dst_height = dst_height;
+        o.color_type = (uint8_t)color_type; o.algorithm = (uint8_t)algorithm;
+        return o;
+    }
+};
+
+// resize.rs:94-150: the destination defaults to the source size, the colour type to Rgba, the algorithm to Bilinear
+class ResizeOptionsBuilder {
+  public:
+    ResizeOptionsBuilder(uint32_t src_width, uint32_t src_height)
+    {
+        o_.src_width = o_.dst_width = src_width;
+        o_.src_height = o_.dst_height = src_height;
+    }
+    ResizeOptionsBuilder &dst(uint32_t width, uint32_t height) { o_.dst_width = width; o_.dst_height = height; return *this; }
+    ResizeOptionsBuilder &color_type(ColorType c) { o_.color_type = c; return *this; }
+    ResizeOptionsBuilder &algorithm(ResizeAlgorithm a) { o_.algorithm = a; return *this; }
+    [[nodiscard]] ResizeOptions build() const { return o_; }
+
+  private:
+    ResizeOptions o_;
+};
+inline ResizeOptionsBuilder ResizeOptions::builder(uint32_t src_width, uint32_t src_height) { return ResizeOptionsBuilder(src_width, src_height); }
+
+// pixo::resize::resize_into (resize.rs:182): `output` is cleared and resized to the result
+inline void resize_into(std::vector<uint8_t> &output, const uint8_t *data, size_t len, const ResizeOptions &options)
+{
+    const pixo_resize_options c = options.c();
+    size_t n = 0;
+    output.clear();
+    int rc = pixo_hip_resize_into(output.data(), 0, data, len, &c, &n); // (the checks, and the length needed)
+    if (rc == PIXO_ERR_BUFFER_TOO_SMALL) {
+        output.resize(n);
+        rc = pixo_hip_resize_into(output.data(), output.size(), data, len, &c, &n);
+    }
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+}
+// pixo::resize::resize (resize.rs:165)
+[[nodiscard]] inline std::vector<uint8_t> resize(const uint8_t *data, size_t len, const ResizeOptions &options)
+{
+    std::vector<uint8_t> out;
+    resize_into(out, data, len, options);
+    return out;
+}
+[[nodiscard]] inline std::vector<uint8_t> resize(const std::vector<uint8_t> &data, const ResizeOptions &options)
+{
+    return resize(data.data(), data.size(), options);
+}
+// device pixels -> device pixels, enqueued on `stream` (a hipStream_t)
+inline void resize_device(const void *d_src, const ResizeOptions &options, void *d_dst, void *stream = nullptr)
+{
+    const pixo_resize_options c = options.c();
+    const int rc = pixo_hip_resize_device(d_src, &c, d_dst, stream);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+}
+} // namespace resize
+
+// The reference's flat wasm export `resizeImage` (src/wasm.rs:183-201), same seven arguments.
+[[nodiscard]] inline std::vector<uint8_t> resize_image(const uint8_t *data, size_t len, uint32_t src_width, uint32_t src_height,
+                                                       uint32_t dst_width, uint32_t dst_height, uint8_t color_type, uint8_t algorithm)
+{
+    uint8_t *buf = nullptr;
+    size_t n = 0;
+    const int rc = pixo_hip_resize_image(data, len, src_width, src_height, dst_width, dst_height, color_type, algorithm, &buf, &n);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    std::vector<uint8_t> out(buf, buf + n);
+    pixo_hip_free(buf);
+    return out;
+}
 
 // The reference's flat wasm export (src/wasm.rs:113-142), same seven arguments.
 [[nodiscard]] inline std::vector<uint8_t> encode_jpeg(const uint8_t *data, size_t len, uint32_t width, uint32_t height,

@@ -227,6 +227,61 @@ int pixo_hip_png_filter_async(const void *d_data, uint32_t width, uint32_t heigh
 uint32_t pixo_hip_png_adler32_from_row_sums(const uint64_t *row_sums, uint32_t width, uint32_t height,
                                             uint32_t bytes_per_pixel);
 
+/* ---- resize (pixo::resize, src/resize.rs) ------------------------------------------------ */
+
+/* pixo::resize::ResizeAlgorithm in declaration order (src/resize.rs:33-45). */
+enum { PIXO_RESIZE_NEAREST = 0, PIXO_RESIZE_BILINEAR = 1, PIXO_RESIZE_LANCZOS3 = 2 };
+#define PIXO_RESIZE_MAX_DIMENSION (1u << 24)
+
+/* Mirrors `pixo::resize::ResizeOptions` (src/resize.rs:65-79).  The builder's defaults are
+ * dst = src, PIXO_RGBA, PIXO_RESIZE_BILINEAR. */
+typedef struct {
+    uint32_t src_width, src_height;
+    uint32_t dst_width, dst_height;
+    uint8_t color_type; /* PIXO_GRAY .. PIXO_RGBA: 1-4 bytes per pixel */
+    uint8_t algorithm;  /* PIXO_RESIZE_* */
+} pixo_resize_options;
+
+/* Replaces `pixo::resize::resize(data, &options)` (src/resize.rs:165): host pixels in, dst_width *
+ * dst_height * bytes-per-pixel bytes out, byte for byte the reference's — also for Lanczos3, whose
+ * two passes keep the reference's u8 intermediate and whose weights use the reference's sinf.
+ * *out is released with pixo_hip_free.  Checks, in the reference's order: source size, destination
+ * size (PIXO_ERR_INVALID_DIMENSIONS), a dimension above 2^24 (PIXO_ERR_IMAGE_TOO_LARGE), data length
+ * (PIXO_ERR_INVALID_DATA_LENGTH). */
+int pixo_hip_resize(const uint8_t *data, size_t data_len, const pixo_resize_options *options,
+                    uint8_t **out, size_t *out_len);
+
+/* Replaces `pixo::resize::resize_into(&mut output, data, &options)` (src/resize.rs:182): writes into
+ * caller storage of `capacity` bytes; *out_len receives the bytes needed, also on
+ * PIXO_ERR_BUFFER_TOO_SMALL. */
+int pixo_hip_resize_into(uint8_t *output, size_t capacity, const uint8_t *data, size_t data_len,
+                         const pixo_resize_options *options, size_t *out_len);
+
+/* Same on DEVICE pointers of the current HIP device: d_src holds the source pixels, d_dst receives
+ * the resized ones.  Asynchronous: the kernels are enqueued on `stream` (a hipStream_t, NULL =
+ * default stream) behind what the caller enqueued on its producer stream
+ * (pixo_hip_set_producer_stream), so with producer stream = `stream` the output can be handed
+ * straight to pixo_hip_jpeg_encode_device or pixo_hip_png_filter_device.  The Lanczos3 intermediate
+ * and tables live in the calling thread's context. */
+int pixo_hip_resize_device(const void *d_src, const pixo_resize_options *options, void *d_dst,
+                           void *stream);
+
+/* The flat shape of the wasm export `resizeImage(data, src_width, src_height, dst_width, dst_height,
+ * color_type, algorithm)` (src/wasm.rs:183-201): colour type, then algorithm are checked first
+ * (PIXO_ERR_INVALID_COLOR_ARG), with the export's messages. */
+int pixo_hip_resize_image(const uint8_t *data, size_t data_len, uint32_t src_width, uint32_t src_height,
+                          uint32_t dst_width, uint32_t dst_height, uint8_t color_type, uint8_t algorithm,
+                          uint8_t **out, size_t *out_len);
+
+/* The Lanczos3 contribution table of one axis (precompute_contributions, src/resize.rs:419-462),
+ * computed on the HOST, no GPU needed: for destination index d the taps are source indices
+ * starts[d] .. starts[d] + counts[d], their normalised weights packed end to end in `weights`.
+ * starts and counts have `dst` entries; `capacity` is the number of floats `weights` holds.  *total
+ * receives the number of weights, also on PIXO_ERR_BUFFER_TOO_SMALL (null arrays with capacity 0: a
+ * size query). */
+int pixo_hip_resize_contributions(uint32_t src, uint32_t dst, uint32_t *starts, uint32_t *counts,
+                                  float *weights, size_t capacity, size_t *total);
+
 /* ---- multi-GPU band sharding -------------------------------------- */
 
 /* Splits the image into `parts` contiguous MCU-row bands; band `index` covers pixel

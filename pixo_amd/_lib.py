@@ -22,13 +22,22 @@ class JpegOptionsC(C.Structure):
     ]
 
 
+class ResizeOptionsC(C.Structure):
+    """pixo_resize_options (include/pixo_hip.h)"""
+    _fields_ = [
+        ("src_width", C.c_uint32), ("src_height", C.c_uint32), ("dst_width", C.c_uint32), ("dst_height", C.c_uint32),
+        ("color_type", C.c_uint8), ("algorithm", C.c_uint8),
+    ]
+
+
 # every symbol include/pixo_hip.h declares
 SYMBOLS = [
     "pixo_jpeg_options_from_preset", "pixo_hip_jpeg_encode", "pixo_hip_jpeg_encode_into",
     "pixo_hip_encode_jpeg", "pixo_hip_coeff_geometry", "pixo_hip_jpeg_coeffs",
     "pixo_hip_jpeg_coeffs_device", "pixo_hip_jpeg_coeffs_integer", "pixo_hip_jpeg_coeffs_integer_device", "pixo_hip_jpeg_entropy_encode", "pixo_hip_jpeg_entropy_encode_device",
     "pixo_hip_jpeg_encode_device", "pixo_hip_jpeg_encode_device_into", "pixo_hip_jpeg_encode_batch_device", "pixo_hip_jpeg_encode_batch_device_into", "pixo_hip_debug_lookback_fallbacks", "pixo_hip_debug_routes", "pixo_hip_debug_dispatch_gate", "pixo_hip_debug_stream_copy", "pixo_hip_debug_stream_io", "pixo_hip_debug_engine_clock", "pixo_hip_debug_scan_device_async", "pixo_hip_debug_scan_device_async_batch", "pixo_hip_png_filter", "pixo_hip_png_filter_device", "pixo_hip_png_filter_async",
-    "pixo_hip_png_adler32_from_row_sums", "pixo_hip_band",
+    "pixo_hip_png_adler32_from_row_sums", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
+    "pixo_hip_resize_contributions", "pixo_hip_band",
     "pixo_hip_band_encoder_create", "pixo_hip_band_encoder_destroy", "pixo_hip_band_encoder_rows",
     "pixo_hip_band_encoder_coeffs", "pixo_hip_band_encoder_count", "pixo_hip_band_encoder_lengths",
     "pixo_hip_band_encoder_pack", "pixo_hip_band_encoder_pack_device", "pixo_hip_band_encoder_copy_body",
@@ -115,6 +124,13 @@ def load():
     L.pixo_hip_png_adler32_from_row_sums.restype = C.c_uint32
     L.pixo_hip_png_filter_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
                                              C.c_void_p, C.POINTER(C.c_uint32)]
+    roptp = C.POINTER(ResizeOptionsC)
+    L.pixo_hip_resize.argtypes = [C.c_void_p, C.c_size_t, roptp, u8pp, szp]
+    L.pixo_hip_resize_into.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, roptp, szp]
+    L.pixo_hip_resize_device.argtypes = [C.c_void_p, roptp, C.c_void_p, C.c_void_p]
+    L.pixo_hip_resize_image.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
+                                        u8pp, szp]
+    L.pixo_hip_resize_contributions.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp]
     L.pixo_hip_band.argtypes = [C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32, C.c_uint32,
                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), szp, szp, szp, szp]
     i16p, u64p = C.POINTER(C.c_int16), C.POINTER(C.c_uint64)

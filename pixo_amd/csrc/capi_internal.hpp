@@ -10,6 +10,7 @@
 //   jpeg_api.cpp     the extern "C" JPEG entry points
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
 //   png_api.cpp      the extern "C" PNG row-filter entry points
+//   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -196,6 +197,15 @@ struct Context {
     Buf t_plain;                        // preset 2, small images: the plain quantiser's tuple of the statistics pass on the second stream
     Buf g_flags, g_rank, g_by_rank;     // progressive scans: band flags, rank among non-empty blocks and its inverse
     Buf h_file{Buf::Mem::Pinned, Buf::Grow::Headroom}; // the finished file lands here
+    // resize (resize_api.cpp)
+    Buf r_in{Buf::Mem::Device, Buf::Grow::Exact}, r_out{Buf::Mem::Device, Buf::Grow::Exact}; // host entries: pixels up, resized pixels down
+    Buf r_mid;                                          // Lanczos3: the u8 intermediate between the passes (src_h rows, padded)
+    Buf r_tables;                                       // ... both axes' contribution tables; known: 1 = they are those of r_dims
+    Buf r_stage{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here on the host, uploaded from here
+    uint32_t r_dims[4] = {0, 0, 0, 0};                  // src_w, dst_w, src_h, dst_h of the tables held
+    uint32_t r_max_span = 0;                            // ... the widest source span of one horizontal tile
+    size_t r_v_at = 0;                                  // ... where the vertical axis starts in r_tables
+    hipEvent_t r_done = nullptr;                        // the last Lanczos3 job (it reads r_tables, writes r_mid) has run
 
     // Small results for the host, one field per purpose: pinned, allocated once with the stream (ensure).
     struct Mailbox {

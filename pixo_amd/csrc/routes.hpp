@@ -45,6 +45,9 @@ enum : uint64_t {
     PROG_MULTI_PASS = 1ull << 33,  // progressive scans by the multi-pass kernels
     PIECES_REDO = 1ull << 34,      // a scan in pieces outgrew its guesses (0xFF bytes, dense content) and was coded again in one piece
     PNG_REGS512 = 1ull << 35,      // PNG filter kernel: adaptive strategies, rows of 16-32 KiB in the registers of 512 threads
+    RESIZE_NEAREST = 1ull << 36,   // resize: the nearest form of the point kernel (resize.hip)
+    RESIZE_BILINEAR = 1ull << 37,  // ... its bilinear form
+    RESIZE_LANCZOS3 = 1ull << 38,  // ... the two Lanczos3 passes
 };
 }
 

@@ -1,0 +1,153 @@
+"""`pixo::resize` on the MI355X (reference src/resize.rs): nearest, bilinear and Lanczos3, byte for byte the reference's.
+Mirrors `ResizeAlgorithm`, `ResizeOptions` and its builder, `resize`, `resize_into`, and the wasm export `resizeImage`
+(src/wasm.rs:183-201) as `resize_image`.  No CPU fallback."""
+import ctypes as C
+import enum
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+from .color import ColorType
+from .error import from_status
+
+MAX_DIMENSION = 1 << 24
+
+# this module's bits of the route record (pixo_hip_debug_routes; pixo_amd/csrc/routes.hpp)
+ROUTES = {"RESIZE_NEAREST": 36, "RESIZE_BILINEAR": 37, "RESIZE_LANCZOS3": 38}
+ROUTE_RESIZE_NEAREST, ROUTE_RESIZE_BILINEAR, ROUTE_RESIZE_LANCZOS3 = (1 << b for b in ROUTES.values())
+
+
+class ResizeAlgorithm(enum.IntEnum):
+    Nearest = 0
+    Bilinear = 1  # the default
+    Lanczos3 = 2
+
+
+@dataclass(frozen=True)
+class ResizeOptions:
+    src_width: int
+    src_height: int
+    dst_width: int
+    dst_height: int
+    color_type: ColorType = ColorType.Rgba
+    algorithm: ResizeAlgorithm = ResizeAlgorithm.Bilinear
+
+    @staticmethod
+    def builder(src_width: int, src_height: int) -> "ResizeOptionsBuilder":
+        return ResizeOptionsBuilder(src_width, src_height)
+
+    def output_len(self) -> int:
+        return self.dst_width * self.dst_height * ColorType(self.color_type).bytes_per_pixel()
+
+    def _c(self) -> _lib.ResizeOptionsC:
+        return _lib.ResizeOptionsC(self.src_width, self.src_height, self.dst_width, self.dst_height,
+                                   int(self.color_type), int(self.algorithm))
+
+
+class ResizeOptionsBuilder:
+    """resize.rs:94-150: destination defaults to the source size, colour type to Rgba, algorithm to Bilinear."""
+
+    def __init__(self, src_width: int, src_height: int):
+        self._v = dict(src_width=src_width, src_height=src_height, dst_width=src_width, dst_height=src_height,
+                       color_type=ColorType.Rgba, algorithm=ResizeAlgorithm.Bilinear)
+
+    def dst(self, width: int, height: int) -> "ResizeOptionsBuilder":
+        self._v.update(dst_width=width, dst_height=height)
+        return self
+
+    def color_type(self, color_type) -> "ResizeOptionsBuilder":
+        self._v["color_type"] = ColorType(color_type)
+        return self
+
+    def algorithm(self, algorithm) -> "ResizeOptionsBuilder":
+        self._v["algorithm"] = ResizeAlgorithm(algorithm)
+        return self
+
+    def build(self) -> ResizeOptions:
+        return ResizeOptions(**self._v)
+
+
+def _raise(status):
+    raise from_status(status, _lib.load().pixo_hip_last_error().decode())
+
+
+def _flat(data) -> np.ndarray:
+    return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+
+
+def resize(data, options: ResizeOptions) -> bytes:
+    """Host pixels -> the resized pixels."""
+    L = _lib.load()
+    px = _flat(data)
+    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    o = options._c()
+    rc = L.pixo_hip_resize(px.ctypes.data, px.size, C.byref(o), C.byref(out), C.byref(n))
+    if rc:
+        _raise(rc)
+    try:
+        return _lib.file_bytes(L, out, n.value)
+    finally:
+        L.pixo_hip_free(out)
+
+
+def resize_into(output, data, options: ResizeOptions) -> int:
+    """Writes into `output` (a writable uint8 numpy array); returns the bytes written.  BufferTooSmall carries the bytes
+    needed in `.needed`."""
+    L = _lib.load()
+    px = _flat(data)
+    assert output.dtype == np.uint8 and output.flags["C_CONTIGUOUS"] and output.flags["WRITEABLE"]
+    n = C.c_size_t()
+    o = options._c()
+    rc = L.pixo_hip_resize_into(output.ctypes.data, output.size, px.ctypes.data, px.size, C.byref(o), C.byref(n))
+    if rc:
+        e = from_status(rc, L.pixo_hip_last_error().decode())
+        e.needed = n.value
+        raise e
+    return n.value
+
+
+def resize_device(d_src, options: ResizeOptions, d_dst, stream=0) -> None:
+    """Device pixels (torch tensor / raw pointer) -> d_dst.  Enqueue only: the kernels run on `stream` behind the work of the
+    producer stream (jpeg.set_producer_stream)."""
+    L = _lib.load()
+
+    def ptr(x):
+        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+    o = options._c()
+    rc = L.pixo_hip_resize_device(ptr(d_src), C.byref(o), ptr(d_dst), C.c_void_p(stream) if stream else None)
+    if rc:
+        _raise(rc)
+
+
+def resize_image(data, src_width, src_height, dst_width, dst_height, color_type: int, algorithm: int) -> bytes:
+    """The wasm export `resizeImage`: seven flat arguments, its error strings."""
+    L = _lib.load()
+    px = _flat(data)
+    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    if not (0 <= color_type <= 255 and 0 <= algorithm <= 255):
+        raise ValueError("color_type and algorithm are u8")
+    rc = L.pixo_hip_resize_image(px.ctypes.data, px.size, src_width, src_height, dst_width, dst_height, color_type, algorithm,
+                                 C.byref(out), C.byref(n))
+    if rc:
+        _raise(rc)
+    try:
+        return _lib.file_bytes(L, out, n.value)
+    finally:
+        L.pixo_hip_free(out)
+
+
+def contributions(src: int, dst: int):
+    """The Lanczos3 table of one axis, computed on the host (no GPU): (starts u32[dst], counts u32[dst], weights f32[total])."""
+    L = _lib.load()
+    total = C.c_size_t()
+    rc = L.pixo_hip_resize_contributions(src, dst, None, None, None, 0, C.byref(total))
+    if rc and rc != -9:
+        _raise(rc)
+    starts, counts = np.empty(dst, np.uint32), np.empty(dst, np.uint32)
+    weights = np.empty(max(total.value, 1), np.float32)
+    rc = L.pixo_hip_resize_contributions(src, dst, starts.ctypes.data, counts.ctypes.data, weights.ctypes.data, total.value, C.byref(total))
+    if rc:
+        _raise(rc)
+    return starts, counts, weights[:total.value]

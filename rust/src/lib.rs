@@ -66,6 +66,14 @@ struct COptions {
     optimize_huffman: u8, progressive: u8, trellis_quant: u8,
 }
 
+/// `pixo_resize_options` (include/pixo_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy)]
+struct CResizeOptions {
+    src_width: u32, src_height: u32, dst_width: u32, dst_height: u32,
+    color_type: u8, algorithm: u8,
+}
+
 const PIXO_ERR_BUFFER_TOO_SMALL: c_int = -9;
 
 extern "C" {
@@ -80,6 +88,10 @@ extern "C" {
                             subsampling_420: c_int, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     fn pixo_hip_png_filter(data: *const u8, len: usize, width: u32, height: u32, bytes_per_pixel: u32, strategy: u8, flags: u32,
                            out: *mut u8, out_capacity: usize, adler32: *mut u32) -> c_int;
+    fn pixo_hip_resize_into(output: *mut u8, capacity: usize, data: *const u8, len: usize, options: *const CResizeOptions,
+                            out_len: *mut usize) -> c_int;
+    fn pixo_hip_resize_image(data: *const u8, len: usize, src_width: u32, src_height: u32, dst_width: u32, dst_height: u32,
+                             color_type: u8, algorithm: u8, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     fn pixo_hip_free(p: *mut u8);
     fn pixo_hip_copy_file(dst: *mut u8, src: *const u8, n: usize);
     fn pixo_hip_last_error() -> *const c_char;
@@ -267,6 +279,94 @@ pub fn encode_jpeg(data: &[u8], width: u32, height: u32, color_type: u8, quality
     -> std::result::Result<Vec<u8>, String> {
     let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
     let rc = unsafe { pixo_hip_encode_jpeg(data.as_ptr(), data.len(), width, height, color_type, quality, preset, subsampling_420 as c_int, &mut p, &mut n) };
+    if rc != 0 { return Err(last_error()); }
+    let mut out = Vec::<u8>::with_capacity(n);
+    unsafe {
+        pixo_hip_copy_file(out.as_mut_ptr(), p, n);
+        out.set_len(n);
+        pixo_hip_free(p);
+    }
+    Ok(out)
+}
+
+/// `pixo::resize` (`src/resize.rs`): nearest, bilinear and Lanczos3 on the device, byte for byte the reference's.
+pub mod resize {
+    use super::*;
+
+    const MAX_DIMENSION: u32 = 1 << 24;
+
+    /// `src/resize.rs:33-45`
+    #[derive(Debug, Clone, Copy, PartialEq, Eq, Default)]
+    pub enum ResizeAlgorithm { Nearest, #[default] Bilinear, Lanczos3 }
+
+    /// `src/resize.rs:65-79`
+    #[derive(Debug, Clone, Copy, PartialEq, Eq)]
+    pub struct ResizeOptions {
+        pub src_width: u32, pub src_height: u32,
+        pub dst_width: u32, pub dst_height: u32,
+        pub color_type: ColorType,
+        pub algorithm: ResizeAlgorithm,
+    }
+    impl ResizeOptions {
+        pub fn builder(src_width: u32, src_height: u32) -> ResizeOptionsBuilder { ResizeOptionsBuilder::new(src_width, src_height) }
+    }
+
+    /// `src/resize.rs:94-150`: destination = source, Rgba, Bilinear unless set.
+    #[derive(Debug, Clone)]
+    pub struct ResizeOptionsBuilder { options: ResizeOptions }
+    impl ResizeOptionsBuilder {
+        pub fn new(src_width: u32, src_height: u32) -> Self {
+            Self { options: ResizeOptions { src_width, src_height, dst_width: src_width, dst_height: src_height,
+                                            color_type: ColorType::Rgba, algorithm: ResizeAlgorithm::default() } }
+        }
+        pub fn dst(mut self, width: u32, height: u32) -> Self { self.options.dst_width = width; self.options.dst_height = height; self }
+        pub fn color_type(mut self, v: ColorType) -> Self { self.options.color_type = v; self }
+        pub fn algorithm(mut self, v: ResizeAlgorithm) -> Self { self.options.algorithm = v; self }
+        #[must_use] pub fn build(self) -> ResizeOptions { self.options }
+    }
+
+    /// `src/resize.rs:213-262`: the library makes the same checks in the same order; its status is turned back into the variant.
+    fn error_of(rc: c_int, data_len: usize, o: &ResizeOptions) -> Error {
+        let bpp = o.color_type as usize + 1;
+        match rc {
+            -1 if o.src_width == 0 || o.src_height == 0 => Error::InvalidDimensions { width: o.src_width, height: o.src_height },
+            -1 => Error::InvalidDimensions { width: o.dst_width, height: o.dst_height },
+            -4 => Error::ImageTooLarge { width: o.src_width.max(o.dst_width), height: o.src_height.max(o.dst_height), max: MAX_DIMENSION },
+            -2 => Error::InvalidDataLength { expected: o.src_width as usize * o.src_height as usize * bpp, actual: data_len },
+            _ => Error::CompressionError(last_error().trim_start_matches("Compression error: ").to_string()),
+        }
+    }
+
+    /// `pixo::resize::resize_into(&mut output, data, &options)`: `output` is cleared and reused.
+    pub fn resize_into(output: &mut Vec<u8>, data: &[u8], options: &ResizeOptions) -> Result<()> {
+        let c = CResizeOptions { src_width: options.src_width, src_height: options.src_height, dst_width: options.dst_width,
+                                 dst_height: options.dst_height, color_type: options.color_type as u8, algorithm: options.algorithm as u8 };
+        output.clear();
+        let mut n = 0usize;
+        let mut rc = unsafe { pixo_hip_resize_into(output.as_mut_ptr(), output.capacity(), data.as_ptr(), data.len(), &c, &mut n) };
+        if rc == PIXO_ERR_BUFFER_TOO_SMALL {
+            output.reserve(n);
+            rc = unsafe { pixo_hip_resize_into(output.as_mut_ptr(), output.capacity(), data.as_ptr(), data.len(), &c, &mut n) };
+        }
+        if rc != 0 { return Err(error_of(rc, data.len(), options)); }
+        unsafe { output.set_len(n) };
+        Ok(())
+    }
+
+    /// `pixo::resize::resize(data, &options)`
+    pub fn resize(data: &[u8], options: &ResizeOptions) -> Result<Vec<u8>> {
+        let mut output = Vec::new();
+        resize_into(&mut output, data, options)?;
+        Ok(output)
+    }
+}
+
+/// The reference's flat wasm export `resizeImage` (`src/wasm.rs:183-201`), same seven arguments, through
+/// `pixo_hip_resize_image`; errors as the reference's strings.
+pub fn resize_image(data: &[u8], src_width: u32, src_height: u32, dst_width: u32, dst_height: u32, color_type: u8, algorithm: u8)
+    -> std::result::Result<Vec<u8>, String> {
+    let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
+    let rc = unsafe { pixo_hip_resize_image(data.as_ptr(), data.len(), src_width, src_height, dst_width, dst_height, color_type, algorithm, &mut p, &mut n) };
     if rc != 0 { return Err(last_error()); }
     let mut out = Vec::<u8>::with_capacity(n);
     unsafe {
