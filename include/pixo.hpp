@@ -192,6 +192,58 @@ namespace filter {
     return out;
 }
 } // namespace filter
+
+// The fields of pixo::png::PngOptions (src/png/mod.rs:41-100) that shape the bytes handed to DEFLATE, plus the ones the
+// presets set for the caller's DEFLATE and chunk writing (carried, unused here).  No quantisation.
+struct PngOptions {
+    uint32_t width = 0, height = 0;
+    ColorType color_type = ColorType::Rgba;
+    uint8_t compression_level = 2;
+    FilterStrategy filter_strategy = FilterStrategy::AdaptiveFast;
+    bool optimize_alpha = false, reduce_color_type = false, strip_metadata = false, reduce_palette = false, optimal_compression = false;
+    uint32_t flags = 0; // PIXO_PNG_NO_RAYON
+
+    // mod.rs:129-198
+    static PngOptions from_preset(uint32_t width, uint32_t height, uint8_t preset)
+    {
+        pixo_png_options c;
+        pixo_hip_png_options_from_preset(&c, width, height, preset);
+        PngOptions o;
+        o.width = c.width; o.height = c.height;
+        o.compression_level = c.compression_level;
+        o.filter_strategy = static_cast<FilterStrategy>(c.filter_strategy);
+        o.optimize_alpha = c.optimize_alpha; o.reduce_color_type = c.reduce_color_type; o.reduce_palette = c.reduce_palette;
+        o.strip_metadata = c.strip_metadata; o.optimal_compression = c.optimal_compression;
+        return o;
+    }
+    static PngOptions fast(uint32_t w, uint32_t h) { return from_preset(w, h, 0); }
+    static PngOptions balanced(uint32_t w, uint32_t h) { return from_preset(w, h, 1); }
+    static PngOptions max(uint32_t w, uint32_t h) { return from_preset(w, h, 2); }
+    pixo_png_options to_c() const
+    {
+        return pixo_png_options{width, height, (uint8_t)color_type, (uint8_t)filter_strategy, optimize_alpha, reduce_color_type,
+                                reduce_palette, compression_level, optimal_compression, strip_metadata, flags};
+    }
+};
+
+// What `encode_into` hands to its DEFLATE (`filtered`, mod.rs:561) after maybe_reduce_color_type and
+// maybe_optimize_alpha, and what it writes into IHDR / PLTE / tRNS for it (mod.rs:526-547).
+struct Prepared {
+    std::vector<uint8_t> stream;
+    pixo_png_layout layout;
+    uint32_t adler32 = 0;
+};
+[[nodiscard]] inline Prepared prepare(const uint8_t *data, size_t len, const PngOptions &options)
+{
+    Prepared p;
+    p.stream.resize((size_t)options.height * ((size_t)options.width * bytes_per_pixel(options.color_type) + 1));
+    const pixo_png_options c = options.to_c();
+    size_t n = 0;
+    const int rc = pixo_hip_png_prepare(data, len, &c, p.stream.data(), p.stream.size(), &n, &p.layout, &p.adler32);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    p.stream.resize(n);
+    return p;
+}
 } // namespace png
 
 namespace resize {

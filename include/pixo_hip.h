@@ -227,6 +227,65 @@ int pixo_hip_png_filter_async(const void *d_data, uint32_t width, uint32_t heigh
 uint32_t pixo_hip_png_adler32_from_row_sums(const uint64_t *row_sums, uint32_t width, uint32_t height,
                                             uint32_t bytes_per_pixel);
 
+/* ---- PNG reductions + filters: the prepared stream (src/png/mod.rs:513-568) -------------- */
+
+/* The prepared stream: the bytes `pixo::png::encode_into` hands to its DEFLATE (`filtered`, mod.rs:561) for given
+ * pixels and options — after maybe_reduce_color_type (:683-836: palette of <= 256 colours in modified-Zeng order at
+ * 1/2/4/8 bits, RGBA -> RGB / GrayAlpha / Gray, RGB -> Gray, gray bit depth), maybe_optimize_alpha (:633-671) and
+ * apply_filters_with_row_bytes — together with the layout a caller needs to write IHDR / PLTE / tRNS around its
+ * own DEFLATE of them.  Quantisation (lossy) is not part of this path. */
+
+/* The fields of pixo::png::PngOptions (mod.rs:64-100) that shape the prepared stream.  compression_level,
+ * optimal_compression and strip_metadata concern the caller's DEFLATE and chunk writing: they are carried (the presets set
+ * them) and read by nothing here. */
+typedef struct pixo_png_options {
+    uint32_t width;
+    uint32_t height;
+    uint8_t color_type;        /* PIXO_GRAY .. PIXO_RGBA */
+    uint8_t filter_strategy;   /* enum pixo_png_filter_strategy */
+    uint8_t optimize_alpha;
+    uint8_t reduce_color_type;
+    uint8_t reduce_palette;
+    uint8_t compression_level;
+    uint8_t optimal_compression;
+    uint8_t strip_metadata;
+    uint32_t flags;            /* PIXO_PNG_NO_RAYON */
+} pixo_png_options;
+
+/* PngOptions::{fast,balanced,max,from_preset} (mod.rs:129-198): 0 fast, 2 max, every other value balanced.
+ * color_type is PIXO_RGBA, flags 0. */
+void pixo_hip_png_options_from_preset(pixo_png_options *out, uint32_t width, uint32_t height, uint8_t preset);
+
+/* What the reference writes around the IDAT data for the prepared stream (mod.rs:526-547). */
+typedef struct pixo_png_layout {
+    uint8_t color_type_byte;   /* IHDR colour type: 0 gray, 2 RGB, 3 palette, 4 gray + alpha, 6 RGBA */
+    uint8_t bit_depth;         /* IHDR bit depth: 1, 2, 4 or 8 */
+    uint8_t bytes_per_pixel;   /* the filters' distance to the "left" byte */
+    uint8_t has_trns;          /* a tRNS chunk with all palette_len alphas follows PLTE (some alpha != 255) */
+    uint32_t row_bytes;        /* bytes of a row without its filter byte; the stream has height * (row_bytes + 1) */
+    uint32_t palette_len;      /* 0: no PLTE */
+    uint8_t palette[256][4];   /* RGBA, final order */
+} pixo_png_layout;
+
+/* Host pixels -> prepared stream in `out`, its layout and the zlib Adler-32 of the stream.  *out_len receives the
+ * stream's length, also on PIXO_ERR_BUFFER_TOO_SMALL; height * (width * bytes-per-pixel + 1) is always enough.
+ * Checks in the reference's order (mod.rs:446-467): dimensions, a dimension above 2^24, data length.  With
+ * optimize_alpha, reduce_color_type and reduce_palette all off this is pixo_hip_png_filter.  Synchronous. */
+int pixo_hip_png_prepare(const uint8_t *data, size_t data_len, const pixo_png_options *options, uint8_t *out,
+                         size_t out_capacity, size_t *out_len, pixo_png_layout *layout, uint32_t *adler32);
+
+/* The same for pixels in HBM on the current HIP device: the stream is left in d_out, which must hold the unreduced
+ * size height * (width * bytes-per-pixel + 1).  Ordered after the producer stream like every entry that takes device
+ * pixels; synchronous, because what the image turns out to be (a palette? how many colours?) is decided on the host
+ * from a few hundred bytes to a few hundred KB of statistics. */
+int pixo_hip_png_prepare_device(const void *d_pixels, const pixo_png_options *options, void *d_out,
+                                pixo_png_layout *layout, size_t *out_len, uint32_t *adler32);
+
+/* The host part of the palette case (optimize_palette_order, mod.rs:909-1099), no GPU needed: from the histogram
+ * counts[n] of the indices into the sorted colour keys and their n x n co-occurrence matrix (:940-977, row major;
+ * the diagonal is never read) to the final order — order_out[k] is the sorted-key index of palette entry k. */
+int pixo_hip_png_palette_order(const uint32_t *counts, const uint32_t *matrix, uint32_t n, uint8_t *order_out);
+
 /* ---- resize (pixo::resize, src/resize.rs) ------------------------------------------------ */
 
 /* pixo::resize::ResizeAlgorithm in declaration order (src/resize.rs:33-45). */

@@ -30,13 +30,32 @@ class ResizeOptionsC(C.Structure):
     ]
 
 
+class PngOptionsC(C.Structure):
+    """pixo_png_options (include/pixo_hip.h)"""
+    _fields_ = [
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("color_type", C.c_uint8), ("filter_strategy", C.c_uint8), ("optimize_alpha", C.c_uint8),
+        ("reduce_color_type", C.c_uint8), ("reduce_palette", C.c_uint8), ("compression_level", C.c_uint8),
+        ("optimal_compression", C.c_uint8), ("strip_metadata", C.c_uint8), ("flags", C.c_uint32),
+    ]
+
+
+class PngLayoutC(C.Structure):
+    """pixo_png_layout (include/pixo_hip.h)"""
+    _fields_ = [
+        ("color_type_byte", C.c_uint8), ("bit_depth", C.c_uint8), ("bytes_per_pixel", C.c_uint8), ("has_trns", C.c_uint8),
+        ("row_bytes", C.c_uint32), ("palette_len", C.c_uint32), ("palette", (C.c_uint8 * 4) * 256),
+    ]
+
+
 # every symbol include/pixo_hip.h declares
 SYMBOLS = [
     "pixo_jpeg_options_from_preset", "pixo_hip_jpeg_encode", "pixo_hip_jpeg_encode_into",
     "pixo_hip_encode_jpeg", "pixo_hip_coeff_geometry", "pixo_hip_jpeg_coeffs",
     "pixo_hip_jpeg_coeffs_device", "pixo_hip_jpeg_coeffs_integer", "pixo_hip_jpeg_coeffs_integer_device", "pixo_hip_jpeg_entropy_encode", "pixo_hip_jpeg_entropy_encode_device",
     "pixo_hip_jpeg_encode_device", "pixo_hip_jpeg_encode_device_into", "pixo_hip_jpeg_encode_batch_device", "pixo_hip_jpeg_encode_batch_device_into", "pixo_hip_debug_lookback_fallbacks", "pixo_hip_debug_routes", "pixo_hip_debug_dispatch_gate", "pixo_hip_debug_stream_copy", "pixo_hip_debug_stream_io", "pixo_hip_debug_engine_clock", "pixo_hip_debug_scan_device_async", "pixo_hip_debug_scan_device_async_batch", "pixo_hip_png_filter", "pixo_hip_png_filter_device", "pixo_hip_png_filter_async",
-    "pixo_hip_png_adler32_from_row_sums", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
+    "pixo_hip_png_adler32_from_row_sums", "pixo_hip_png_options_from_preset", "pixo_hip_png_prepare", "pixo_hip_png_prepare_device",
+    "pixo_hip_png_palette_order", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
     "pixo_hip_resize_contributions", "pixo_hip_band",
     "pixo_hip_band_encoder_create", "pixo_hip_band_encoder_destroy", "pixo_hip_band_encoder_rows",
     "pixo_hip_band_encoder_coeffs", "pixo_hip_band_encoder_count", "pixo_hip_band_encoder_lengths",
@@ -124,6 +143,12 @@ def load():
     L.pixo_hip_png_adler32_from_row_sums.restype = C.c_uint32
     L.pixo_hip_png_filter_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
                                              C.c_void_p, C.POINTER(C.c_uint32)]
+    poptp, playp = C.POINTER(PngOptionsC), C.POINTER(PngLayoutC)
+    L.pixo_hip_png_options_from_preset.argtypes = [poptp, C.c_uint32, C.c_uint32, C.c_uint8]
+    L.pixo_hip_png_options_from_preset.restype = None
+    L.pixo_hip_png_prepare.argtypes = [C.c_void_p, C.c_size_t, poptp, C.c_void_p, C.c_size_t, szp, playp, C.POINTER(C.c_uint32)]
+    L.pixo_hip_png_prepare_device.argtypes = [C.c_void_p, poptp, C.c_void_p, playp, szp, C.POINTER(C.c_uint32)]
+    L.pixo_hip_png_palette_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     roptp = C.POINTER(ResizeOptionsC)
     L.pixo_hip_resize.argtypes = [C.c_void_p, C.c_size_t, roptp, u8pp, szp]
     L.pixo_hip_resize_into.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, roptp, szp]

@@ -10,6 +10,7 @@
 //   jpeg_api.cpp     the extern "C" JPEG entry points
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
 //   png_api.cpp      the extern "C" PNG row-filter entry points
+//   png_reduce_api.cpp  the extern "C" PNG prepare entry points: reductions (png_reduce.hip), palette ordering, then the filter
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
 #pragma once
 #include <hip/hip_runtime.h>
@@ -193,6 +194,11 @@ struct Context {
     uint32_t batch_per_block = 0;  // ... of the last batch (1 + bytes per block; 0: none yet): whether sub-batches pay, jpeg_api.cpp
     Buf p_in, p_out, p_sums, p_scratch; // PNG filter stage
     Buf h_sums{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... p_sums copied to the host
+    // PNG reductions (png_reduce_api.cpp)
+    Buf q_work{Buf::Mem::Device, Buf::Grow::Exact};  // one PngWork: analysis, key lookup table, index map, histogram, pair counts
+    Buf h_qwork{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... its host side: results come down into it, tables go up from it
+    Buf q_index{Buf::Mem::Device, Buf::Grow::Exact}; // palette case: the index image (sorted-key order), 1 byte per pixel
+    Buf q_rows{Buf::Mem::Device, Buf::Grow::Exact};  // the reduced rows the filter kernel reads
     Buf t_raw, t_trail;                 // progressive + trellis: unquantised DCT blocks (f32), Viterbi back-pointers
     Buf t_plain;                        // preset 2, small images: the plain quantiser's tuple of the statistics pass on the second stream
     Buf g_flags, g_rank, g_by_rank;     // progressive scans: band flags, rank among non-empty blocks and its inverse
@@ -431,6 +437,12 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
                           const PixelSource *src);
 int device_tuple_to_malloc(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
                            const pixo_host::Geometry &g, Context &c, uint8_t **out, size_t *out_len);
+
+// ---- PNG (png_api.cpp) -----------------------------------------------------------------------------------------------
+int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast);
+// filter kernel + checksum on the context's stream; returns after the checksum has been combined
+int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t bpp, int run, bool sequential_fast,
+                         void *d_out, uint32_t *adler);
 
 // ---- preset 2 (progressive.cpp) -----------------------------------------------------------------------------------
 int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,

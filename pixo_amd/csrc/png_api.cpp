@@ -7,9 +7,10 @@
 
 using namespace pixo_capi;
 
-namespace {
-// Argument checks shared by the two PNG entries; resolves the strategy the reference would run.
-int png_plan(uint32_t width, uint32_t height, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast)
+namespace pixo_capi {
+// Argument checks shared by the PNG entries; resolves the strategy the reference would run.  `area` is the image's
+// PIXEL count: rows of packed samples are filtered as width = row bytes, bpp = 1, but the small-image rule counts pixels.
+int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast)
 {
     if (width == 0 || height == 0)
         return fail(PIXO_ERR_INVALID_DIMENSIONS, "Invalid image dimensions: " + std::to_string(width) + "x" + std::to_string(height));
@@ -17,13 +18,19 @@ int png_plan(uint32_t width, uint32_t height, uint32_t bpp, uint8_t strategy, ui
         return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format");
     if (strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
     int s = strategy;
-    const uint64_t area = static_cast<uint64_t>(width) * height;
     const bool adaptive = s == PIXO_PNG_ADAPTIVE || s == PIXO_PNG_ADAPTIVE_FAST || s == PIXO_PNG_BIGRAMS;
     if (area <= 4096 && adaptive) s = PIXO_PNG_SUB; // src/png/filter.rs:76-86
     // the stateful AdaptiveFast runs wherever the reference does not take its rayon path (:94-112)
     *sequential_fast = s == PIXO_PNG_ADAPTIVE_FAST && ((flags & PIXO_PNG_NO_RAYON) || height <= 32);
     *run = s;
     return PIXO_OK;
+}
+} // namespace pixo_capi
+
+namespace {
+int png_plan(uint32_t width, uint32_t height, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast)
+{
+    return pixo_capi::png_plan(width, height, static_cast<uint64_t>(width) * height, bpp, strategy, flags, run, sequential_fast);
 }
 
 // zlib Adler-32 of the filtered stream from the per-row sums (A = byte sum, B = sum of
@@ -48,8 +55,10 @@ int reserve_sums(Context &c, uint32_t height)
     return c.p_scratch.reserve(16);
 }
 
-int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t bpp, int run,
-                         bool sequential_fast, void *d_out, uint32_t *adler)
+} // namespace
+
+int pixo_capi::png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t bpp, int run,
+                                    bool sequential_fast, void *d_out, uint32_t *adler)
 {
     if (const int rc = reserve_sums(c, height)) return rc;
     HIP_TRY(pixo_dev::launch_png_filter(d_in, width, height, bpp, run, sequential_fast, d_out,
@@ -60,6 +69,7 @@ int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t 
     return PIXO_OK;
 }
 
+namespace {
 // A large image from host pixels to caller storage, band by band (round 3).  Rows are independent once the row above is on
 // the device, so: the calling thread uploads bands of ~8 MiB back to back on the upload stream (a pageable source blocks it
 // for the copy's duration anyway); each band's kernel and the download of its filtered rows into the context's PINNED

@@ -7,6 +7,7 @@ import enum
 import numpy as np
 
 from . import _lib
+from .color import ColorType
 from .error import from_status
 
 
@@ -80,3 +81,151 @@ def adler32_from_row_sums(row_sums, width, height, bytes_per_pixel):
     a = np.ascontiguousarray(row_sums, dtype=np.uint64)
     assert a.size == 2 * height
     return int(L.pixo_hip_png_adler32_from_row_sums(a.ctypes.data, width, height, bytes_per_pixel)) & 0xFFFFFFFF
+
+
+# ---- the prepared stream: reductions + filters (src/png/mod.rs:513-568) -----------------------------------------------
+
+class PngOptions:
+    """The fields of `pixo::png::PngOptions` (src/png/mod.rs:41-100) that shape the bytes handed to DEFLATE, plus the
+    ones the presets set for the caller's DEFLATE and chunk writing (carried, not used here).  No quantisation."""
+
+    def __init__(self, width=0, height=0, color_type=ColorType.Rgba, compression_level=2,
+                 filter_strategy=FilterStrategy.ADAPTIVE_FAST, optimize_alpha=False, reduce_color_type=False,
+                 strip_metadata=False, reduce_palette=False, optimal_compression=False, flags=0):
+        self.width, self.height, self.color_type = width, height, ColorType(color_type)
+        self.compression_level, self.filter_strategy = compression_level, FilterStrategy(filter_strategy)
+        self.optimize_alpha, self.reduce_color_type, self.reduce_palette = bool(optimize_alpha), bool(reduce_color_type), bool(reduce_palette)
+        self.strip_metadata, self.optimal_compression, self.flags = bool(strip_metadata), bool(optimal_compression), flags
+
+    @classmethod
+    def fast(cls, width, height):
+        return cls(width, height)
+
+    @classmethod
+    def balanced(cls, width, height):
+        return cls(width, height, compression_level=6, filter_strategy=FilterStrategy.ADAPTIVE, optimize_alpha=True,
+                   reduce_color_type=True, strip_metadata=True, reduce_palette=True)
+
+    @classmethod
+    def max(cls, width, height):
+        return cls(width, height, compression_level=9, filter_strategy=FilterStrategy.BIGRAMS, optimize_alpha=True,
+                   reduce_color_type=True, strip_metadata=True, reduce_palette=True, optimal_compression=True)
+
+    @classmethod
+    def from_preset(cls, width, height, preset):
+        return cls.fast(width, height) if preset == 0 else cls.max(width, height) if preset == 2 else cls.balanced(width, height)
+
+    @classmethod
+    def builder(cls, width, height):
+        return PngOptionsBuilder(width, height)
+
+    def to_c(self):
+        return _lib.PngOptionsC(self.width, self.height, int(self.color_type), int(self.filter_strategy), self.optimize_alpha,
+                                self.reduce_color_type, self.reduce_palette, self.compression_level, self.optimal_compression,
+                                self.strip_metadata, self.flags)
+
+    def full_size(self):
+        """Bytes that always hold the prepared stream: the unreduced filtered size."""
+        return filtered_size(self.width, self.height, self.color_type.bytes_per_pixel())
+
+
+class PngOptionsBuilder:
+    """`PngOptionsBuilder` (src/png/mod.rs:220-340) without the quantisation setters."""
+
+    def __init__(self, width, height):
+        self._o = PngOptions(width, height)
+
+    def preset(self, preset):  # keeps dimensions and colour type (mod.rs:327-334)
+        keep = self._o
+        self._o = PngOptions.from_preset(keep.width, keep.height, preset)
+        self._o.color_type, self._o.flags = keep.color_type, keep.flags
+        return self
+
+    def build(self):
+        return self._o
+
+
+def _setter(name, conv):
+    def f(self, value):
+        setattr(self._o, name, conv(value))
+        return self
+    f.__name__ = name
+    return f
+
+
+for _name, _conv in (("color_type", ColorType), ("compression_level", int), ("filter_strategy", FilterStrategy),
+                     ("optimize_alpha", bool), ("reduce_color_type", bool), ("strip_metadata", bool), ("reduce_palette", bool),
+                     ("optimal_compression", bool), ("flags", int)):
+    setattr(PngOptionsBuilder, _name, _setter(_name, _conv))
+
+
+class PngLayout:
+    """What goes around the IDAT data of a prepared stream (pixo_png_layout)."""
+
+    def __init__(self, c):
+        self.color_type_byte, self.bit_depth, self.bytes_per_pixel = c.color_type_byte, c.bit_depth, c.bytes_per_pixel
+        self.row_bytes, self.has_trns = c.row_bytes, bool(c.has_trns)
+        self.palette = [tuple(c.palette[i]) for i in range(c.palette_len)]  # RGBA, final order
+
+    def __repr__(self):
+        return "PngLayout(color_type_byte=%d, bit_depth=%d, bytes_per_pixel=%d, row_bytes=%d, palette=%d entries, has_trns=%s)" % (
+            self.color_type_byte, self.bit_depth, self.bytes_per_pixel, self.row_bytes, len(self.palette), self.has_trns)
+
+
+def prepare(data, options):
+    """Host pixels -> (prepared stream as uint8 array, PngLayout, adler32)."""
+    L = _lib.load()
+    px = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    out = np.empty(max(options.full_size(), 1), np.uint8)
+    o, lay, n, ad = options.to_c(), _lib.PngLayoutC(), C.c_size_t(), C.c_uint32()
+    rc = L.pixo_hip_png_prepare(px.ctypes.data, px.size, C.byref(o), out.ctypes.data, out.size, C.byref(n), C.byref(lay), C.byref(ad))
+    if rc:
+        _raise(rc)
+    return out[:n.value], PngLayout(lay), ad.value
+
+
+def prepare_device(d_pixels, options, d_out):
+    """Device pixels (torch tensor / raw pointer) -> prepared stream in d_out (capacity options.full_size());
+    returns (stream length, PngLayout, adler32)."""
+    L = _lib.load()
+
+    def ptr(x):
+        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+    o, lay, n, ad = options.to_c(), _lib.PngLayoutC(), C.c_size_t(), C.c_uint32()
+    rc = L.pixo_hip_png_prepare_device(ptr(d_pixels), C.byref(o), ptr(d_out), C.byref(lay), C.byref(n), C.byref(ad))
+    if rc:
+        _raise(rc)
+    return n.value, PngLayout(lay), ad.value
+
+
+def palette_order(counts, matrix):
+    """Histogram + co-occurrence matrix of the sorted-key indices -> final order (host only, no GPU)."""
+    L = _lib.load()
+    cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+    m = np.ascontiguousarray(matrix, dtype=np.uint32)
+    n = cnt.size
+    assert m.shape == (n, n)
+    order = np.empty(n, np.uint8)
+    rc = L.pixo_hip_png_palette_order(cnt.ctypes.data, m.ctypes.data, n, order.ctypes.data)
+    if rc:
+        _raise(rc)
+    return order
+
+
+def _chunk(kind, body):
+    import struct
+    import zlib
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+
+def ihdr_plte_trns(layout, width, height):
+    """The IHDR, PLTE and tRNS chunks the reference writes for this layout (src/png/mod.rs:526-547), so that a caller
+    can assemble a file around its own DEFLATE of the prepared stream."""
+    import struct
+    out = _chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, layout.bit_depth, layout.color_type_byte, 0, 0, 0))
+    if layout.palette:
+        out += _chunk(b"PLTE", b"".join(bytes(p[:3]) for p in layout.palette))
+        if layout.has_trns:
+            out += _chunk(b"tRNS", bytes(p[3] for p in layout.palette))
+    return out

@@ -74,6 +74,25 @@ struct CResizeOptions {
     color_type: u8, algorithm: u8,
 }
 
+/// `pixo_png_options` (include/pixo_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy)]
+struct CPngOptions {
+    width: u32, height: u32,
+    color_type: u8, filter_strategy: u8, optimize_alpha: u8, reduce_color_type: u8, reduce_palette: u8,
+    compression_level: u8, optimal_compression: u8, strip_metadata: u8,
+    flags: u32,
+}
+
+/// `pixo_png_layout` (include/pixo_hip.h)
+#[repr(C)]
+#[derive(Clone, Copy)]
+struct CPngLayout {
+    color_type_byte: u8, bit_depth: u8, bytes_per_pixel: u8, has_trns: u8,
+    row_bytes: u32, palette_len: u32,
+    palette: [[u8; 4]; 256],
+}
+
 const PIXO_ERR_BUFFER_TOO_SMALL: c_int = -9;
 
 extern "C" {
@@ -88,6 +107,8 @@ extern "C" {
                             subsampling_420: c_int, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     fn pixo_hip_png_filter(data: *const u8, len: usize, width: u32, height: u32, bytes_per_pixel: u32, strategy: u8, flags: u32,
                            out: *mut u8, out_capacity: usize, adler32: *mut u32) -> c_int;
+    fn pixo_hip_png_prepare(data: *const u8, len: usize, options: *const CPngOptions, out: *mut u8, out_capacity: usize,
+                            out_len: *mut usize, layout: *mut CPngLayout, adler32: *mut u32) -> c_int;
     fn pixo_hip_resize_into(output: *mut u8, capacity: usize, data: *const u8, len: usize, options: *const CResizeOptions,
                             out_len: *mut usize) -> c_int;
     fn pixo_hip_resize_image(data: *const u8, len: usize, src_width: u32, src_height: u32, dst_width: u32, dst_height: u32,
@@ -410,5 +431,73 @@ pub mod png {
             unsafe { out.set_len(n) };
             (out, adler)
         }
+    }
+
+    /// The fields of `pixo::png::PngOptions` (`src/png/mod.rs:41-100`) that shape the bytes handed to DEFLATE, plus the ones
+    /// the presets set for the caller's DEFLATE and chunk writing (carried, unused here).  No quantisation.
+    #[derive(Debug, Clone, Copy)]
+    pub struct PngOptions {
+        pub width: u32, pub height: u32, pub color_type: ColorType, pub compression_level: u8, pub filter_strategy: FilterStrategy,
+        pub optimize_alpha: bool, pub reduce_color_type: bool, pub strip_metadata: bool, pub reduce_palette: bool,
+        pub optimal_compression: bool,
+    }
+
+    impl PngOptions {
+        /// `src/png/mod.rs:129-144`
+        pub fn fast(width: u32, height: u32) -> Self {
+            Self { width, height, color_type: ColorType::Rgba, compression_level: 2, filter_strategy: FilterStrategy::AdaptiveFast,
+                   optimize_alpha: false, reduce_color_type: false, strip_metadata: false, reduce_palette: false, optimal_compression: false }
+        }
+        /// `src/png/mod.rs:151-166`
+        pub fn balanced(width: u32, height: u32) -> Self {
+            Self { compression_level: 6, filter_strategy: FilterStrategy::Adaptive, optimize_alpha: true, reduce_color_type: true,
+                   strip_metadata: true, reduce_palette: true, ..Self::fast(width, height) }
+        }
+        /// `src/png/mod.rs:173-188`
+        pub fn max(width: u32, height: u32) -> Self {
+            Self { compression_level: 9, filter_strategy: FilterStrategy::Bigrams, optimal_compression: true, ..Self::balanced(width, height) }
+        }
+        /// `src/png/mod.rs:191-197`
+        pub fn from_preset(width: u32, height: u32, preset: u8) -> Self {
+            match preset { 0 => Self::fast(width, height), 2 => Self::max(width, height), _ => Self::balanced(width, height) }
+        }
+    }
+
+    /// What `encode_into` writes around the IDAT data (`src/png/mod.rs:526-547`).
+    #[derive(Debug, Clone, PartialEq, Eq)]
+    pub struct PngLayout {
+        pub color_type_byte: u8, pub bit_depth: u8, pub bytes_per_pixel: usize, pub row_bytes: usize,
+        /// RGBA in final order; empty: no PLTE.  `has_trns`: a tRNS chunk with every entry's alpha follows PLTE.
+        pub palette: Vec<[u8; 4]>, pub has_trns: bool,
+    }
+
+    /// The bytes `encode_into` hands to its DEFLATE (`filtered`, `src/png/mod.rs:561`) — after `maybe_reduce_color_type`
+    /// (`:683-836`) and `maybe_optimize_alpha` (`:633-671`) — their layout, and the zlib Adler-32 of the bytes.  Checks in
+    /// the reference's order (`:446-467`).
+    pub fn prepare(data: &[u8], options: &PngOptions) -> Result<(Vec<u8>, PngLayout, u32)> {
+        let c = CPngOptions { width: options.width, height: options.height, color_type: options.color_type as u8,
+                              filter_strategy: options.filter_strategy as u8, optimize_alpha: options.optimize_alpha as u8,
+                              reduce_color_type: options.reduce_color_type as u8, reduce_palette: options.reduce_palette as u8,
+                              compression_level: options.compression_level, optimal_compression: options.optimal_compression as u8,
+                              strip_metadata: options.strip_metadata as u8, flags: 0 };
+        let bpp = options.color_type as usize + 1;
+        let cap = (options.height as usize).saturating_mul((options.width as usize).saturating_mul(bpp) + 1);
+        let cap = if options.width == 0 || options.height == 0 || options.width > (1 << 24) || options.height > (1 << 24) { 0 } else { cap };
+        let mut out = Vec::<u8>::with_capacity(cap);
+        let mut lay = CPngLayout { color_type_byte: 0, bit_depth: 0, bytes_per_pixel: 0, has_trns: 0, row_bytes: 0, palette_len: 0, palette: [[0; 4]; 256] };
+        let (mut n, mut adler) = (0usize, 0u32);
+        let rc = unsafe { pixo_hip_png_prepare(data.as_ptr(), data.len(), &c, out.as_mut_ptr(), cap, &mut n, &mut lay, &mut adler) };
+        match rc {
+            0 => {}
+            -1 => return Err(Error::InvalidDimensions { width: options.width, height: options.height }),
+            -4 => return Err(Error::ImageTooLarge { width: options.width, height: options.height, max: 1 << 24 }),
+            -2 => return Err(Error::InvalidDataLength { expected: options.width as usize * options.height as usize * bpp, actual: data.len() }),
+            _ => return Err(Error::CompressionError(last_error().trim_start_matches("Compression error: ").to_string())),
+        }
+        unsafe { out.set_len(n) };
+        let layout = PngLayout { color_type_byte: lay.color_type_byte, bit_depth: lay.bit_depth, bytes_per_pixel: lay.bytes_per_pixel as usize,
+                                 row_bytes: lay.row_bytes as usize, palette: lay.palette[..lay.palette_len as usize].to_vec(),
+                                 has_trns: lay.has_trns != 0 };
+        Ok((out, layout, adler))
     }
 }
