@@ -66,7 +66,7 @@ void pixo_jpeg_options_from_preset(pixo_jpeg_options *out, uint32_t width, uint3
 /* ---- whole-file encode (host pixels in, JFIF bytes out) ------------------------- */
 
 /* Replaces `pixo::jpeg::encode(data, &options) -> Result<Vec<u8>>` (src/jpeg/mod.rs:88).
- * On success *out is a malloc'd buffer the caller releases with pixo_hip_free(). */
+ * On success *out is a block the caller releases with pixo_hip_free only (never free). */
 int pixo_hip_jpeg_encode(const uint8_t *data, size_t data_len, const pixo_jpeg_options *options,
                          uint8_t **out, size_t *out_len);
 
@@ -147,7 +147,8 @@ int pixo_hip_jpeg_entropy_encode_device(const void *d_y, const void *d_cb, const
                                         size_t *out_len);
 
 /* pixo::jpeg::encode for pixels that are already in HBM (options->width * height * bpp bytes,
- * tightly packed): coefficient kernel + device entropy stage, result in malloc'd host memory.
+ * tightly packed): coefficient kernel + device entropy stage, result in a block the caller releases with
+ * pixo_hip_free only (never free).
  * Same validation and errors as pixo_hip_jpeg_encode.  Ordered after the producer stream (see
  * pixo_hip_set_producer_stream), like every entry point below that takes device pixels. */
 int pixo_hip_jpeg_encode_device(const void *d_pixels, const pixo_jpeg_options *options,
@@ -166,8 +167,8 @@ int pixo_hip_jpeg_encode_device_into(const void *d_pixels, const pixo_jpeg_optio
 
 /* pixo::jpeg::encode for `batch` equally sized images back to back in HBM (config 3: 64 x 1080p):
  * one coefficient launch and ONE pass of the device entropy stage for all of them — every image a byte-aligned
- * segment of the two single-pass entropy kernels — files[i] / lens[i] receive `batch` malloc'd files
- * (pixo_hip_free).  With optimize_huffman, progressive scans or restart markers the images are encoded one by one. */
+ * segment of the two single-pass entropy kernels — files[i] / lens[i] receive `batch` files, each a block the caller
+ * releases with pixo_hip_free only (never free).  With optimize_huffman, progressive scans or restart markers the images are encoded one by one. */
 int pixo_hip_jpeg_encode_batch_device(const void *d_pixels, const pixo_jpeg_options *options, uint32_t batch,
                                       uint8_t **files, size_t *lens);
 

@@ -41,11 +41,10 @@ int pixo_hip_band_encoder_create(const pixo_jpeg_options *options, uint32_t part
     PIXO_REQUIRE(options);
     PIXO_REQUIRE(out);
     *out = nullptr;
-    std::string msg;
-    int rc = pixo_host::validate(*options, false, 0, msg);
-    if (rc) return fail(rc, msg);
+    int rc = checked(*options);
+    if (rc) return rc;
     if (parts == 0 || index >= parts) return fail(PIXO_ERR_COMPRESSION, "Compression error: bad band index");
-    const pixo_host::Geometry whole = pixo_host::geometry(options->width, options->height, options->color_type, options->subsampling);
+    const pixo_host::Geometry whole = geometry_of(*options);
     if (!band_codable(*options, whole))
         return fail(PIXO_ERR_COMPRESSION, "Compression error: bands are entropy-coded on their own only for baseline scans without "
                                           "restart markers (gather the coefficient bands and use pixo_hip_jpeg_entropy_encode_device)");
@@ -60,7 +59,7 @@ int pixo_hip_band_encoder_create(const pixo_jpeg_options *options, uint32_t part
     e->band = *options;
     e->band.height = e->rows ? e->rows : 1;
     e->band.has_restart_interval = 0; e->band.restart_interval = 0;
-    e->g = pixo_host::geometry(e->band.width, e->band.height, e->band.color_type, e->band.subsampling);
+    e->g = geometry_of(e->band);
     if (e->rows == 0) { e->g.y_blocks = e->g.c_blocks = e->g.units = 0; e->g.units_y = 0; }
     e->c = pool().take(device);
     if ((rc = e->c->ensure())) { pool().give(e->c); return rc; }
@@ -100,8 +99,8 @@ int pixo_hip_band_encoder_coeffs(pixo_hip_band_encoder *e, const void *band_pixe
     int rc;
     const void *d_px = band_pixels;
     if (!on_device) { // the band's rows come over this GPU's own PCIe link
-        const size_t px_bytes = static_cast<size_t>(e->band.width) * e->rows * (e->g.gray ? 1 : 3);
-        if ((rc = c.d_px.reserve((px_bytes + 15) & ~size_t{15}))) return rc;
+        const size_t px_bytes = pixel_bytes(e->band, e->g); // (the band's options have its height)
+        if ((rc = reserve_pixels(c, px_bytes))) return rc;
         HIP_TRY(hipMemcpyAsync(c.d_px.p, band_pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
         d_px = c.d_px.p;
     } else if ((rc = order_after_producer(c))) {
@@ -258,8 +257,8 @@ int pixo_hip_jpeg_splice(const pixo_jpeg_options *options, const uint64_t *total
     PIXO_REQUIRE(out);
     PIXO_REQUIRE(out_len);
     std::string msg;
-    int rc = pixo_host::validate(*options, false, 0, msg);
-    if (rc) return fail(rc, msg);
+    int rc = checked(*options);
+    if (rc) return rc;
     pixo_host::HuffSet h;
     if ((rc = tables_for_splice(*options, total_counts, h))) return rc;
     std::vector<uint8_t> v;
@@ -275,8 +274,8 @@ int pixo_hip_jpeg_splice_layout(const pixo_jpeg_options *options, const uint64_t
     PIXO_REQUIRE(file_len);
     PIXO_REQUIRE(body_offsets);
     std::string msg;
-    int rc = pixo_host::validate(*options, false, 0, msg);
-    if (rc) return fail(rc, msg);
+    int rc = checked(*options);
+    if (rc) return rc;
     pixo_host::HuffSet h;
     if ((rc = tables_for_splice(*options, total_counts, h))) return rc;
     pixo_host::SpliceLayout l;
@@ -294,14 +293,14 @@ int pixo_hip_jpeg_splice_finish(const pixo_jpeg_options *options, const uint64_t
     PIXO_REQUIRE(piece_headers);
     PIXO_REQUIRE(file);
     std::string msg;
-    int rc = pixo_host::validate(*options, false, 0, msg);
-    if (rc) return fail(rc, msg);
+    int rc = checked(*options);
+    if (rc) return rc;
     pixo_host::HuffSet h;
     if ((rc = tables_for_splice(*options, total_counts, h))) return rc;
     pixo_host::SpliceLayout l;
     if ((rc = pixo_host::splice_layout(*options, h, piece_headers, parts, l, msg))) return fail(rc, msg);
     if (file_len != l.file_len)
-        return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(l.file_len) + " bytes");
+        return too_small(l.file_len);
     pixo_host::splice_finish(l, file);
     return PIXO_OK;
 }
@@ -310,9 +309,7 @@ int pixo_hip_jpeg_splice_finish(const pixo_jpeg_options *options, const uint64_t
 namespace {
 int band_options(const pixo_jpeg_options *options, uint32_t band_rows_, pixo_jpeg_options *band)
 {
-    std::string msg;
-    int rc = pixo_host::validate(*options, false, 0, msg);
-    if (rc) return fail(rc, msg);
+    if (const int rc = checked(*options)) return rc;
     if (band_rows_ == 0 || band_rows_ > options->height) return fail(PIXO_ERR_COMPRESSION, "Compression error: bad band height");
     *band = *options;
     band->height = band_rows_;
@@ -469,19 +466,19 @@ int pixo_hip_jpeg_encode_multi(const uint8_t *data, size_t data_len, const pixo_
     PIXO_REQUIRE(out_len);
     PIXO_REQUIRE(devices);
     const pixo_jpeg_options &o = *options;
-    std::string msg;
-    int rc = pixo_host::validate(o, true, data_len, msg);
-    if (rc) return fail(rc, msg);
+    int rc = checked(o, true, data_len);
+    if (rc) return rc;
     PIXO_REQUIRE(data);
     if (n_devices == 0 || n_devices > 1024) return fail(PIXO_ERR_COMPRESSION, "Compression error: need 1..1024 devices");
-    const pixo_host::Geometry whole = pixo_host::geometry(o.width, o.height, o.color_type, o.subsampling);
+    const pixo_host::Geometry whole = geometry_of(o);
     if (!band_codable(o, whole)) { // progressive scans / restart markers: one device codes the whole tuple
         DeviceScope on(devices[0]);
         if (on.err != hipSuccess) return hip_fail(on.err, "hipSetDevice");
         const int keep = t_slot.device;
         if ((rc = pixo_hip_set_device(devices[0]))) return rc;
-        rc = pixo_hip_jpeg_encode(data, data_len, options, out, out_len);
-        (void)pixo_hip_set_device(keep);
+        FileResult r;
+        if (!(rc = encode_host_pixels(data, o, FileDest::own_block(), r))) rc = deliver_block(r, out, out_len);
+        (void)pixo_hip_set_device(keep); // (also after an error: the thread's own device comes back)
         return rc;
     }
     const uint32_t parts = n_devices;
@@ -613,15 +610,13 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
     PIXO_REQUIRE(offsets);
     PIXO_REQUIRE(lens);
     const pixo_jpeg_options &o = *options;
-    std::string msg;
-    int rc = pixo_host::validate(o, false, 0, msg);
-    if (rc) return fail(rc, msg);
+    if (const int rc = checked(o)) return rc;
     PIXO_REQUIRE(pixels);
     if (batch == 0) return fail(PIXO_ERR_COMPRESSION, "Compression error: empty batch");
     if (n_devices == 0 || n_devices > 1024) return fail(PIXO_ERR_COMPRESSION, "Compression error: need 1..1024 devices");
     if (arena == nullptr && capacity != 0) return fail(PIXO_ERR_COMPRESSION, "Compression error: null arena with a capacity");
-    const pixo_host::Geometry g = pixo_host::geometry(o.width, o.height, o.color_type, o.subsampling);
-    const size_t image_bytes = static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3);
+    const pixo_host::Geometry g = geometry_of(o);
+    const size_t image_bytes = pixel_bytes(o, g);
     // where the pixels are: in some GPU's memory (images then reach the other GPUs by peer copies, one peer per xGMI link)
     // or in host memory (every GPU fetches its own images over its own PCIe link)
     int src_device = -1;
@@ -651,7 +646,7 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
     }
     PhaseBarrier barrier(parts);
     std::atomic<bool> failed{false};
-    std::atomic<bool> too_small{false};
+    std::atomic<bool> short_arena{false};
     size_t total = 0;
     auto body = [&](unsigned k) {
         Share &sh = shares[k];
@@ -659,13 +654,22 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
         auto hip_step = [&](hipError_t e, const char *what) { if (e != hipSuccess) step(hip_fail(e, what)); };
         BatchWorkerBuffers &buf = t_batch_buffers;
         const int dev = devices[k];
+        const void *local = nullptr; // the share's images in this GPU's memory
+        // the share's files into `dst`, on this worker's context (a share's storage counts as the caller's: a refusal is a retry)
+        auto share_into = [&](uint8_t *dst, size_t cap) {
+            CallerStorageScope storage(dst && cap);
+            Context *c = nullptr;
+            int r = batch_in_range(sh.count);
+            if (!r) r = context_on_current_device(&c);
+            return r ? r : encode_batch_into(*c, local, o, g, sh.count, dst, cap, sh.offs.data(), sh.lens.data());
+        };
         if (sh.count) {
             step(pixo_hip_set_device(dev)); // (binds this worker's library context and the HIP device of this thread)
             if (!sh.rc) hip_step(hipSetDevice(dev), "hipSetDevice");
             if (buf.device != dev) { buf.drop(); buf.device = dev; }
             // ---- the share's images into this GPU's memory
             const uint8_t *src = static_cast<const uint8_t *>(pixels) + static_cast<size_t>(sh.first) * image_bytes;
-            const void *local = src;
+            local = src;
             const size_t px_bytes = static_cast<size_t>(sh.count) * image_bytes;
             if (!sh.rc && src_device != dev) {
                 step(buf.px.reserve(px_bytes));
@@ -678,9 +682,9 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
             sh.offs.assign(sh.count, 0); sh.lens.assign(sh.count, 0);
             if (parts == 1 && !sh.rc) { // one GPU: nothing to place among other shares — the files go straight into the caller's arena, their
                 // way over PCIe overlapping the kernels of the next sub-batch (no device arena, no second pass over the bytes)
-                const int r = pixo_hip_jpeg_encode_batch_device_into(local, options, sh.count, arena, capacity, sh.offs.data(), sh.lens.data());
+                const int r = share_into(arena, capacity);
                 for (uint32_t i = 0; i < sh.count; ++i) { offsets[i] = sh.offs[i]; lens[i] = sh.lens[i]; }
-                if (r == PIXO_ERR_BUFFER_TOO_SMALL) { total = sh.offs[sh.count - 1] + sh.lens[sh.count - 1]; too_small.store(true); }
+                if (r == PIXO_ERR_BUFFER_TOO_SMALL) { total = sh.offs[sh.count - 1] + sh.lens[sh.count - 1]; short_arena.store(true); }
                 else step(r);
                 return;
             }
@@ -690,8 +694,7 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
             for (int attempt = 0; !sh.rc && attempt < 3; ++attempt) {
                 step(buf.arena.reserve(want));
                 if (sh.rc) break;
-                const int r = pixo_hip_jpeg_encode_batch_device_into(local, options, sh.count, buf.arena.as<uint8_t>(), buf.arena.cap,
-                                                                     sh.offs.data(), sh.lens.data());
+                const int r = share_into(buf.arena.as<uint8_t>(), buf.arena.cap);
                 if (r == PIXO_ERR_BUFFER_TOO_SMALL && attempt < 2) { want = sh.offs[sh.count - 1] + sh.lens[sh.count - 1] + 4096; continue; }
                 if (r == PIXO_ERR_BUFFER_TOO_SMALL) // (the sizes changed between three identical calls: not the CALLER's arena that is too small)
                     step(fail(PIXO_ERR_COMPRESSION, "Compression error: a batch share's size changed between identical calls"));
@@ -710,17 +713,17 @@ int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options
                     at += shares[j].lens[i];
                 }
             total = at;
-            if (total > capacity) too_small.store(true);
+            if (total > capacity) short_arena.store(true);
         }
         barrier.arrive();
         // ---- every share's run of files to its final place, over its own GPU's PCIe link, on its own thread
-        if (!failed.load() && !too_small.load() && sh.count && sh.bytes)
+        if (!failed.load() && !short_arena.load() && sh.count && sh.bytes)
             hip_step(hipMemcpy(arena + offsets[sh.first], buf.arena.p, sh.bytes, hipMemcpyDeviceToHost), "device-to-host copy of a batch share's files");
     };
     if (!band_workers_instance().run(parts, body)) return fail(PIXO_ERR_COMPRESSION, "Compression error: could not start the worker threads");
     for (Share &sh : shares)
         if (sh.rc) { const int r = sh.rc; const std::string e = sh.error; return fail(r, e); }
-    if (too_small.load()) return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(total) + " bytes");
+    if (short_arena.load()) return too_small(total);
     return PIXO_OK;
 }
 

@@ -11,11 +11,6 @@ using Form = BaselinePlan::Form;
 using Direct = BaselinePlan::Direct;
 using Upload = BaselinePlan::Upload;
 
-size_t pixel_bytes(const pixo_jpeg_options &o, const pixo_host::Geometry &g)
-{
-    return static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3);
-}
-
 PlanFacts plan_facts(const Context &c, const ScanJob &j, const pixo_jpeg_options &o, const pixo_host::Geometry &g, const PixelSource *src,
                      const FileDest &d, bool dest_gpu_writable)
 {
@@ -55,12 +50,6 @@ void remember_scan(Context &c, uint64_t bytes, uint64_t blocks)
     c.last_scan_blocks = blocks;
 }
 
-int too_small(FileResult &r, size_t total)
-{
-    r.len = total;
-    return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(total) + " bytes");
-}
-
 // Where every image of a batch begins in the stuffed scans (batch + 1 entries).  A copy may still be on its way: the stream is
 // synchronised before they are read.
 int batch_image_starts(Context &c, const ScanJob &j, uint32_t batch, uint64_t scan_bytes, std::vector<uint64_t> &starts)
@@ -88,7 +77,7 @@ int finish_file(Context &c, const FileDest &d, const ScanJob &j, const std::vect
 {
     const size_t hdr = head.size(), total = hdr + scan_bytes + 2;
     const bool fits = d.kind != DestKind::Caller || total <= d.cap;
-    if (placed && !fits) return too_small(r, total); // (stored in place up to the storage's end: nothing to remember)
+    if (placed && !fits) return too_small(total, &r.len); // (stored in place up to the storage's end: nothing to remember)
     if (d.batch == 1) remember_scan(c, scan_bytes, j.n);
     else if (const int rc = batch_image_starts(c, j, d.batch, scan_bytes, r.image_starts)) return rc;
     if (d.kind == DestKind::InHbm) {
@@ -99,7 +88,7 @@ int finish_file(Context &c, const FileDest &d, const ScanJob &j, const std::vect
         r.header_len = hdr;
         return PIXO_OK;
     }
-    if (!fits) return too_small(r, total);
+    if (!fits) return too_small(total, &r.len);
     uint8_t *buf = placed;
     if (!buf) { // copied out of c.e_out: into the caller's storage, a block the caller will own, or the pinned buffer
         bool mine = false;
@@ -269,48 +258,6 @@ int encode_baseline_file(Context &c, const int16_t *dy, const int16_t *dcb, cons
     RetryMultipass scope;
     rc = encode_once(c, dy, dcb, dcr, r.tuple_done ? nullptr : src, o, g, d, dest_dev, r);
     return rc == kRetryMultipass ? fail(PIXO_ERR_COMPRESSION, "Compression error: the entropy kernels could not make progress") : rc;
-}
-
-int device_tuple_to_malloc(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
-                           const pixo_host::Geometry &g, Context &c, uint8_t **out, size_t *out_len)
-{
-    if (debug().host_entropy) note_route(route::HOST_ENTROPY);
-    if (!debug().host_entropy) {
-        if (!o.progressive) {
-            FileResult r;
-            const int rc = encode_baseline_file(c, dy, dcb, dcr, nullptr, o, g, FileDest::own_block(), r);
-            if (rc) return rc;
-            if (r.own_block) { // (already in a block of its own)
-                *out = const_cast<uint8_t *>(r.file);
-                *out_len = r.len;
-                return PIXO_OK;
-            }
-            return deliver(r.file, r.len, out, out_len);
-        }
-        pixo_host::HuffSet h;
-        int rc = huffman_for_tuple(dy, dcb, dcr, o, g, c, h);
-        if (rc) return rc;
-        std::vector<uint8_t> head;
-        pixo_host::file_headers(head, o, h);
-        const uint8_t *file = nullptr;
-        size_t n = 0;
-        if ((rc = device_progressive_scans(dy, dcb, dcr, g, h, c, head, &file, &n))) return rc;
-        return deliver(file, n, out, out_len);
-    }
-    // for experiments, the host twin of the scan coders: host code on a copy of the tuple
-    const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128;
-    int rc = c.h_coef.reserve(coef_bytes);
-    if (rc) return rc;
-    int16_t *hy = c.h_coef.as<int16_t>(), *hcb = hy + g.y_blocks * 64, *hcr = hcb + g.c_blocks * 64;
-    HIP_TRY(hipMemcpyAsync(hy, dy, g.y_blocks * 128, hipMemcpyDeviceToHost, c.stream));
-    if (g.c_blocks) {
-        HIP_TRY(hipMemcpyAsync(hcb, dcb, g.c_blocks * 128, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(hipMemcpyAsync(hcr, dcr, g.c_blocks * 128, hipMemcpyDeviceToHost, c.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    std::vector<uint8_t> v;
-    pixo_host::encode_file(hy, hcb, hcr, o, v);
-    return hand_over(v, out, out_len);
 }
 
 } // namespace pixo_capi

@@ -4,10 +4,12 @@
 //                    outlives threads, device selection, the debug-switch parser
 //   scan_job.cpp     coefficient launches on a context; one pass of the device entropy stage in the steps a band needs
 //   baseline_file.cpp  device tuple / pixels -> whole baseline file: runs the route baseline_plan.hpp chooses, finishes the file
+//   file_route.cpp   pixels or tuple in, a whole file out, to this destination: encode_file (host twin, progressive, baseline),
+//                    the delivery of a FileResult, batches into an arena
 //   pieces.cpp       a scan coded in pieces while the file travels (and the context's copy helper thread)
 //   host_memory.cpp  blocks for files the caller will own (kept large blocks, the pinned pool), copies into fresh memory
-//   progressive.cpp  preset 2: trellis tuple, the seven progressive scans
-//   jpeg_api.cpp     the extern "C" JPEG entry points
+//   progressive.cpp  preset 2: trellis tuple, the seven progressive scans, into a FileDest
+//   jpeg_api.cpp     the extern "C" JPEG entry points: check arguments -> context -> encode_file -> deliver
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
 //   png_api.cpp      the extern "C" PNG row-filter entry points
 //   png_reduce_api.cpp  the extern "C" PNG prepare entry points: reductions (png_reduce.hip), palette ordering, then the filter
@@ -49,6 +51,23 @@ int hip_fail(hipError_t e, const char *what); // pixo::Error::CompressionError(S
 // A null pointer where the contract wants an object is a caller bug the Rust API cannot express; the C ABI
 // answers it with an error instead of a crash.
 #define PIXO_REQUIRE(p) do { if (!(p)) return ::pixo_capi::fail(PIXO_ERR_COMPRESSION, "Compression error: null argument '" #p "'"); } while (0)
+// The argument checks every entry shares, each at the place the entry's own order gives it.
+inline int checked(const pixo_jpeg_options &o, bool with_data = false, size_t data_len = 0) // validation in the reference's order
+{
+    std::string msg;
+    const int rc = pixo_host::validate(o, with_data, data_len, msg);
+    return rc ? fail(rc, msg) : PIXO_OK;
+}
+inline int batch_in_range(uint32_t batch)
+{
+    return batch == 0 || batch > 65535 ? fail(PIXO_ERR_COMPRESSION, "Compression error: batch must be 1..65535") : PIXO_OK;
+}
+// The one home of this string: `needed` also goes to *out_len where the entry promises the size with the refusal.
+inline int too_small(size_t needed, size_t *out_len = nullptr)
+{
+    if (out_len) *out_len = needed;
+    return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(needed) + " bytes");
+}
 
 // ---- debug switches: ONE environment variable, read once ------------------------------------------------------------
 // PIXO_HIP_DEBUG="name[=value],name[=value],..." — A/B experiments and tests only; nothing here changes the bytes of a file.
@@ -232,6 +251,19 @@ struct Context {
 // The totals as the kernels take them
 inline unsigned long long *mailbox(Context &c) { return reinterpret_cast<unsigned long long *>(c.mail->totals); }
 
+// ---- small facts of an image, said once ----------------------------------------------------------------------------------
+inline pixo_host::Geometry geometry_of(const pixo_jpeg_options &o) { return pixo_host::geometry(o.width, o.height, o.color_type, o.subsampling); }
+inline size_t pixel_bytes(const pixo_jpeg_options &o, const pixo_host::Geometry &g) { return static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3); }
+inline int reserve_pixels(Context &c, size_t n) { return c.d_px.reserve((n + 15) & ~size_t{15}); } // (the kernels load 16 bytes at a time)
+// The planes of a tuple that lies in one buffer: Y of every image of the batch, then Cb, then Cr (64 coefficients per block).
+template <class T> struct PlanesOf { T *y, *cb, *cr; };
+using Planes = PlanesOf<int16_t>;
+template <class T> PlanesOf<T> planes_of(T *base, const pixo_host::Geometry &g, size_t batch = 1)
+{
+    T *cb = base + g.y_blocks * 64 * batch;
+    return {base, cb, cb + g.c_blocks * 64 * batch};
+}
+
 // Contexts outlive the threads that use them (context.cpp): a thread that ends parks its context in the pool — no HIP
 // call in a thread-local destructor — and the next thread that needs one adopts it.
 struct ContextPool {
@@ -320,6 +352,19 @@ int coeffs_rows(Context &c, const void *d_pixels, const pixo_jpeg_options &o, co
 int coeffs_on_device(Context &c, const void *d_pixels, const pixo_jpeg_options &o, const pixo_host::Geometry &g, hipStream_t stream,
                      int16_t **dy, int16_t **dcb, int16_t **dcr);
 bool scan_has_restart_markers(const pixo_jpeg_options &o, const pixo_host::Geometry &g);
+// The arguments of a statistics walk over a whole image's tuple (optimised tables: no tables yet, predictors from zero)
+inline pixo_dev::ScanArgs count_args(const pixo_host::Geometry &g, const pixo_jpeg_options &o, const int16_t *dy, const int16_t *dcb, const int16_t *dcr)
+{
+    pixo_dev::ScanArgs a;
+    a.y = dy; a.cb = dcb; a.cr = dcr; a.tables = nullptr;
+    a.mode = g.gray ? 0 : (g.s420 ? 2 : 1);
+    a.nblocks = g.y_blocks + 2 * g.c_blocks;
+    a.blocks_per_mcu = g.gray ? 1 : (g.s420 ? 6 : 3);
+    a.marker_bytes = 2;
+    a.restart = scan_has_restart_markers(o, g) ? o.restart_interval : 0;
+    a.seed_dc[0] = a.seed_dc[1] = a.seed_dc[2] = 0; a.bit_base = 0; a.pad_last = 1;
+    return a;
+}
 
 // ---- the device entropy stage, in the steps a caller may need to interleave with exchanges (scan_job.cpp) ------------
 // One pass over a coefficient tuple in HBM: a whole image, a batch of images (one byte-aligned segment each), or a
@@ -407,7 +452,12 @@ struct FileDest {
                                           // does not fit, nothing is copied there and the result's len says how much is needed
     uint32_t batch = 1, seg_gap = 0;      // InHbm: `batch` (2 or more) equal images back to back, every one a byte-aligned
                                           // segment of ONE scan; seg_gap: bytes to leave free in c.e_out between their scans
-    static FileDest caller(uint8_t *p, size_t cap) { FileDest d; d.kind = DestKind::Caller; d.p = p; d.cap = cap; return d; }
+    // (a null `p` is a size query: nothing is stored, the result's len says how much is needed)
+    static FileDest caller(uint8_t *p, size_t cap)
+    {
+        static uint8_t nowhere;
+        FileDest d; d.kind = DestKind::Caller; d.p = p ? p : &nowhere; d.cap = p ? cap : 0; return d;
+    }
     // OwnBlock: once the size is known the block is allocated and the device-to-host copy goes straight into it; the copy into
     // pageable memory runs at the link's rate, and what it saves is the second pass over the file from the pinned buffer
     // (tools/ubench/upload.cpp: 0.21 ms + a warm 11 MB memcpy, or 1.30 against 1.38 ms for new pages).  Pieces and direct
@@ -427,6 +477,7 @@ struct FileResult {
     std::vector<uint64_t> image_starts;
     bool gaps_left = false;
     bool tuple_done = false;       // the tuple has been computed (a multi-pass retry does not compute it again)
+    std::vector<uint8_t> spill;    // the host twin's file (debug switch host_entropy): `file` points into it
 };
 // The tuple dy / dcb / dcr has been computed (src null), or its place is reserved for src's pixels.
 int encode_baseline_file(Context &c, const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const PixelSource *src,
@@ -435,8 +486,33 @@ int encode_baseline_file(Context &c, const int16_t *dy, const int16_t *dcb, cons
 // nothing of it is kept (code it again in one piece); kRetryMultipass; or an error.
 int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *dst, size_t dst_cap, uint64_t *scan_bytes,
                           const PixelSource *src);
-int device_tuple_to_malloc(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
-                           const pixo_host::Geometry &g, Context &c, uint8_t **out, size_t *out_len);
+
+// ---- pixels or tuple in, a whole file out, to this destination (file_route.cpp) ------------------------------------------
+struct FileSource { // what the file is made from: exactly one of the three
+    const uint8_t *host_px = nullptr;                           // host pixels (uploaded by the route), or
+    const void *d_px = nullptr;                                 // device pixels, or
+    const int16_t *dy = nullptr, *dcb = nullptr, *dcr = nullptr; // a device tuple already computed
+    static FileSource host(const uint8_t *px) { FileSource s; s.host_px = px; return s; }
+    static FileSource device(const void *px) { FileSource s; s.d_px = px; return s; }
+    static FileSource tuple(const void *y, const void *cb, const void *cr) { FileSource s; s.dy = static_cast<const int16_t *>(y); s.dcb = static_cast<const int16_t *>(cb); s.dcr = static_cast<const int16_t *>(cr); return s; }
+};
+// The only place that chooses between the host twin (debug switch host_entropy), the progressive file and the baseline file.
+// `c` is ready, its device current, its stream ordered behind the source's producer.
+int encode_file(Context &c, const FileSource &src, const pixo_jpeg_options &o, const pixo_host::Geometry &g, const FileDest &dest,
+                FileResult &res);
+// A FileResult into what the entry promised.  own_block destinations: a block the caller releases with pixo_hip_free.
+int deliver_block(FileResult &r, uint8_t **out, size_t *out_len);
+// Caller storage, after encode_file returned rc: *out_len (also with PIXO_ERR_BUFFER_TOO_SMALL), then the file unless it
+// already lies in `output`.  copy_threads: the library's copy threads for large files (big_copy) instead of one memcpy.
+int deliver_into(int rc, const FileResult &r, uint8_t *output, size_t capacity, size_t *out_len, bool copy_threads);
+int encode_to_block(Context &c, const FileSource &src, const pixo_jpeg_options &o, const pixo_host::Geometry &g, uint8_t **out,
+                    size_t *out_len); // encode_file to own_block, delivered
+int encode_host_pixels(const uint8_t *data, const pixo_jpeg_options &o, const FileDest &dest, FileResult &res); // encode_file on the thread's context
+// `batch` images back to back in `arena` (host memory of any kind, device memory, or null: sizes only)
+int encode_batch_into(Context &c, const void *d_pixels, const pixo_jpeg_options &o, const pixo_host::Geometry &g, uint32_t batch,
+                      uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens);
+int encode_batch_blocks(Context &c, const void *d_pixels, const pixo_jpeg_options &o, const pixo_host::Geometry &g, uint32_t batch,
+                        uint8_t **files, size_t *lens);
 
 // ---- PNG (png_api.cpp) -----------------------------------------------------------------------------------------------
 int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast);
@@ -447,12 +523,12 @@ int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t 
 // ---- preset 2 (progressive.cpp) -----------------------------------------------------------------------------------
 int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
                       const pixo_host::Geometry &g, Context &c, pixo_host::HuffSet &h);
+// The file is assembled in caller storage the GPU can write (pinned / registered) when it fits there — res.file == dest.p then —
+// and in the context's pinned buffer otherwise: the caller delivers it from there.
 int device_progressive_scans(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_host::Geometry &g,
-                             const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const uint8_t **file,
-                             size_t *file_len, uint8_t *pinned_dest = nullptr, size_t dest_cap = 0);
-// (pinned_dest: caller storage the GPU can write — the file is assembled there when it fits, *file == pinned_dest then)
-int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const pixo_host::Geometry &g, Context &c,
-                        std::vector<uint8_t> &spill, const uint8_t **file, size_t *file_len, uint8_t *pinned_dest = nullptr,
-                        size_t dest_cap = 0);
+                             const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const FileDest &dest, FileResult &res);
+// host_twin: the scans are coded by the host twin on a pinned copy of the tuple, into res.spill
+int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const pixo_host::Geometry &g, Context &c, bool host_twin,
+                        const FileDest &dest, FileResult &res);
 
 } // namespace pixo_capi

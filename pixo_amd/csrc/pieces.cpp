@@ -104,7 +104,7 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
     const bool from_host = src && src->host_px;
     if (from_host) { // pixels still in host memory: pieces sized for the UPLOAD pipeline — about 12 MB of pixels each, so that
         // a band's kernels (tens of microseconds) disappear behind the next band's way over PCIe (>= 100 us)
-        const uint64_t px_bytes = static_cast<uint64_t>(src->o->width) * src->o->height * (src->g->gray ? 1 : 3);
+        const uint64_t px_bytes = pixel_bytes(*src->o, *src->g);
         const uint32_t want = static_cast<uint32_t>(std::min<uint64_t>(kMaxPieces, std::max<uint64_t>(2, px_bytes / (uint64_t{debug().bands_upload_mb} << 20))));
         for (uint32_t k = 0; k < want; ++k) {
             const uint64_t g0 = groups * k / want;
@@ -141,8 +141,7 @@ int device_entropy_pieces(Context &c, ScanJob &j, hipStream_t stream, uint8_t *d
             begin[pieces] = groups;
         } else { // (no common boundaries: the whole image first)
             if (from_host) {
-                const size_t px_bytes = static_cast<size_t>(src->o->width) * src->o->height * (src->g->gray ? 1 : 3);
-                HIP_TRY(hipMemcpyAsync(const_cast<void *>(src->d_px), src->host_px, px_bytes, hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(const_cast<void *>(src->d_px), src->host_px, pixel_bytes(*src->o, *src->g), hipMemcpyHostToDevice, stream));
             }
             const int rc = coeffs_rows(c, src->d_px, *src->o, *src->g, stream, src->dy, src->dcb, src->dcr, 0, 0);
             if (rc) return rc;

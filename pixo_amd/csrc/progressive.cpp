@@ -14,9 +14,41 @@ namespace pixo_capi {
 // stuffed segment — every segment copied from the device straight to its final place — then EOI.  (Round 1 copied the
 // stuffed stream to the host in one piece and spliced it into a std::vector, which the caller copied once more: two
 // extra passes over the file through freshly mapped pages, about half of the 2.3 ms of a 4096x4096 preset-2 file.)
+namespace {
+// Caller storage the GPU can write (pinned / registered), found out once per file: the file is assembled there when it fits.
+struct PinnedDest {
+    uint8_t *host = nullptr, *dev = nullptr; // the caller's address, and the one the GPU stores to
+    size_t cap = 0;
+};
+// Where a file of `total` bytes is assembled: the caller's pinned storage when it fits, else the context's pinned buffer.
+int file_place(Context &c, const PinnedDest &pin, size_t total, uint8_t **p)
+{
+    if (pin.host && total <= pin.cap) { *p = pin.host; return PIXO_OK; }
+    const int rc = c.h_file.reserve(total);
+    *p = c.h_file.as<uint8_t>();
+    return rc;
+}
+int upload_progressive_tables(Context &c, const pixo_host::HuffSet &h, hipStream_t stream)
+{
+    uint32_t packed[pixo_host::kScanTableWords];
+    pixo_host::pack_scan_tables(h, packed);
+    for (uint32_t &w : packed) // progressive.rs:363-381: a symbol the table lacks is coded as (0, 4 bits)
+        if ((w >> 16) == 0) w = 4u << 16;
+    return upload_scan_tables(c, packed, stream);
+}
+// write_sos_progressive (jpeg/mod.rs:650-682) of scan i of simple_progressive_script (progressive.rs:98-110)
+void sos_of_scan(int i, uint8_t sos[10])
+{
+    static const uint8_t script[7][3] = {{0, 0, 0}, {1, 0, 0}, {2, 0, 0}, {0, 1, 10}, {0, 11, 63}, {1, 1, 63}, {2, 1, 63}};
+    const uint8_t v[10] = {0xFF, 0xDA, 0, 8, 1, static_cast<uint8_t>(script[i][0] + 1), static_cast<uint8_t>(script[i][0] == 0 ? 0x00 : 0x11),
+                           script[i][1], script[i][2], 0};
+    std::memcpy(sos, v, 10);
+}
+} // namespace
+
 static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_host::Geometry &g,
-                                              const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const uint8_t **file,
-                                              size_t *file_len, uint8_t *pinned_dest, size_t dest_cap)
+                                              const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const PinnedDest &pin,
+                                              FileResult &r)
 {
     namespace pd = pixo_dev;
     Stopwatch sw;
@@ -42,11 +74,7 @@ static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *
     a.rank = c.g_rank.as<uint64_t>();
     a.by_rank = c.g_by_rank.as<uint32_t>();
 
-    uint32_t packed[pixo_host::kScanTableWords];
-    pixo_host::pack_scan_tables(h, packed);
-    for (uint32_t &w : packed) // progressive.rs:363-381: a symbol the table lacks is coded as (0, 4 bits)
-        if ((w >> 16) == 0) w = 4u << 16;
-    if ((rc = upload_scan_tables(c, packed, stream))) return rc;
+    if ((rc = upload_progressive_tables(c, h, stream))) return rc;
     uint64_t *totals = c.e_totals.as<uint64_t>();
     HIP_TRY(pd::launch_prog_flags(a, stream));
     HIP_TRY(pd::launch_exclusive_scan(a.nonempty, n, c.g_rank.as<uint64_t>(), c.e_tmp.as<uint64_t>(), totals + 2, stream));
@@ -86,18 +114,12 @@ static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *
     for (int i = 6; i >= 0; --i)
         if (start[i] == ~0ull) start[i] = start[i + 1]; // empty scans at the end of the stream
     const size_t total = head.size() + 7 * 10 + scan_bytes + 2;
-    uint8_t *p = pinned_dest; // the caller's pinned storage when the file fits: the seven copies below are its only pass over the bytes
-    if (!p || total > dest_cap) {
-        if ((rc = c.h_file.reserve(total))) return rc;
-        p = c.h_file.as<uint8_t>();
-    }
+    uint8_t *p = nullptr; // (the caller's pinned storage when the file fits: the seven copies below are its only pass over the bytes)
+    if ((rc = file_place(c, pin, total, &p))) return rc;
     std::memcpy(p, head.data(), head.size());
     size_t pos = head.size();
-    static const uint8_t script[7][3] = {{0, 0, 0}, {1, 0, 0}, {2, 0, 0}, {0, 1, 10}, {0, 11, 63}, {1, 1, 63}, {2, 1, 63}};
-    for (int i = 0; i < 7; ++i) { // write_sos_progressive, jpeg/mod.rs:650-682
-        const uint8_t sos[10] = {0xFF, 0xDA, 0, 8, 1, static_cast<uint8_t>(script[i][0] + 1),
-                                 static_cast<uint8_t>(script[i][0] == 0 ? 0x00 : 0x11), script[i][1], script[i][2], 0};
-        std::memcpy(p + pos, sos, 10);
+    for (int i = 0; i < 7; ++i) {
+        sos_of_scan(i, p + pos);
         pos += 10;
         const size_t n = static_cast<size_t>(start[i + 1] - start[i]);
         if (n) HIP_TRY(hipMemcpyAsync(p + pos, c.e_out.as<uint8_t>() + start[i], n, hipMemcpyDeviceToHost, stream));
@@ -105,19 +127,9 @@ static int device_progressive_scans_multipass(const int16_t *dy, const int16_t *
     }
     p[pos] = 0xFF; p[pos + 1] = 0xD9;
     HIP_TRY(hipStreamSynchronize(stream));
-    *file = p;
-    *file_len = pos + 2;
+    r.file = p; r.len = pos + 2; r.header_len = head.size();
     sw.lap("prog stuff+copy+splice");
     return PIXO_OK;
-}
-
-// write_sos_progressive (jpeg/mod.rs:650-682) of scan i of simple_progressive_script (progressive.rs:98-110)
-static void sos_of_scan(int i, uint8_t sos[10])
-{
-    static const uint8_t script[7][3] = {{0, 0, 0}, {1, 0, 0}, {2, 0, 0}, {0, 1, 10}, {0, 11, 63}, {1, 1, 63}, {2, 1, 63}};
-    const uint8_t v[10] = {0xFF, 0xDA, 0, 8, 1, static_cast<uint8_t>(script[i][0] + 1), static_cast<uint8_t>(script[i][0] == 0 ? 0x00 : 0x11),
-                           script[i][1], script[i][2], 0};
-    std::memcpy(sos, v, 10);
 }
 
 // The same scans in ONE pass over the tuple (round 4): prog_code_kernel (every scan a byte-aligned segment with a packed stream
@@ -128,8 +140,8 @@ static void sos_of_scan(int i, uint8_t sos[10])
 // the multi-pass form above has about twenty launches, three synchronisations and one copy per scan.
 // kRetryMultipass: a look-back gave up waiting (the caller runs the multi-pass form).
 static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_host::Geometry &g,
-                                          const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const uint8_t **file,
-                                          size_t *file_len, uint8_t *pinned_dest, size_t dest_cap)
+                                          const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const PinnedDest &pin,
+                                          FileResult &r)
 {
     namespace pd = pixo_dev;
     Stopwatch sw;
@@ -166,11 +178,7 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     unsigned long long *base = c.e_segs.as<unsigned long long>();
     sg.bits = base; sg.layout = base + 8; sg.bytes = base + 2 * 8 + 2; sg.out_end = base + 3 * 8 + 2;
     sg.host_out_end = c.h_segs.as<unsigned long long>();
-    uint32_t packed[pixo_host::kScanTableWords];
-    pixo_host::pack_scan_tables(h, packed);
-    for (uint32_t &w : packed) // progressive.rs:363-381: a symbol the table lacks is coded as (0, 4 bits)
-        if ((w >> 16) == 0) w = 4u << 16;
-    if ((rc = upload_scan_tables(c, packed, stream))) return rc;
+    if ((rc = upload_progressive_tables(c, h, stream))) return rc;
     a.tables = c.e_tables.as<uint32_t>();
     const bool zero = c.e_code_state.known >= state_words;
     c.e_code_state.known = 0;
@@ -191,12 +199,7 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     size_t direct_cap = 0;
     if (a.nscans == 7 && !debug().no_direct_small && c.last_prog_bytes && c.last_prog_bytes <= kDirectBytes) {
         const size_t guess = body_at + 2 * static_cast<size_t>(c.last_prog_bytes) + 4096;
-        if (pinned_dest && dest_cap >= guess) {
-            const PointerInfo at = pointer_info(pinned_dest);
-            if (at.type == hipMemoryTypeHost && at.device_ptr) {
-                direct_host = pinned_dest; direct_dev = static_cast<uint8_t *>(at.device_ptr); direct_cap = dest_cap;
-            }
-        }
+        if (pin.dev && pin.cap >= guess) { direct_host = pin.host; direct_dev = pin.dev; direct_cap = pin.cap; }
         if (!direct_host) {
             if ((rc = c.h_file.reserve(guess))) return rc;
             direct_host = direct_dev = c.h_file.as<uint8_t>(); direct_cap = c.h_file.cap;
@@ -251,16 +254,12 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
         sos_of_scan(0, p + head.size());
         for (uint32_t k = 1; k < 7; ++k) sos_of_scan(static_cast<int>(k), p + body_at + dev_end[k - 1]);
         p[total - 2] = 0xFF; p[total - 1] = 0xD9;
-        *file = p;
-        *file_len = total;
+        r.file = p; r.len = total; r.header_len = head.size();
         sw.lap("prog headers");
         return PIXO_OK;
     }
-    uint8_t *p = pinned_dest;
-    if (!p || total > dest_cap) {
-        if ((rc = c.h_file.reserve(total))) return rc;
-        p = c.h_file.as<uint8_t>();
-    }
+    uint8_t *p = nullptr;
+    if ((rc = file_place(c, pin, total, &p))) return rc;
     std::memcpy(p, head.data(), head.size());
     size_t pos = head.size();
     size_t file_at[7]; // where scan k's bytes go
@@ -281,23 +280,46 @@ static int device_progressive_scans_fused(const int16_t *dy, const int16_t *dcb,
     HIP_TRY(hipStreamSynchronize(stream));
     for (int i = 0; i < 7; ++i) sos_of_scan(i, p + sos_at[i]); // (after the copies: a run's copy passes over the gaps)
     p[pos] = 0xFF; p[pos + 1] = 0xD9;
-    *file = p;
-    *file_len = pos + 2;
+    r.file = p; r.len = pos + 2; r.header_len = head.size();
     sw.lap("prog copy+headers");
     return PIXO_OK;
 }
 
 int device_progressive_scans(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_host::Geometry &g,
-                             const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const uint8_t **file,
-                             size_t *file_len, uint8_t *pinned_dest, size_t dest_cap)
+                             const pixo_host::HuffSet &h, Context &c, const std::vector<uint8_t> &head, const FileDest &d, FileResult &r)
 {
+    PinnedDest pin;
+    if (d.kind == DestKind::Caller && d.cap) {
+        const PointerInfo at = pointer_info(d.p);
+        if (at.type == hipMemoryTypeHost) { pin.host = d.p; pin.dev = static_cast<uint8_t *>(at.device_ptr); pin.cap = d.cap; }
+    }
     if (!debug().multipass_entropy) {
-        const int rc = device_progressive_scans_fused(dy, dcb, dcr, g, h, c, head, file, file_len, pinned_dest, dest_cap);
+        const int rc = device_progressive_scans_fused(dy, dcb, dcr, g, h, c, head, pin, r);
         if (rc != kRetryMultipass) { if (rc == PIXO_OK) note_route(route::PROG_SINGLE_PASS); return rc; }
     }
     note_route(route::PROG_MULTI_PASS | route::MULTI_PASS);
-    return device_progressive_scans_multipass(dy, dcb, dcr, g, h, c, head, file, file_len, pinned_dest, dest_cap);
+    return device_progressive_scans_multipass(dy, dcb, dcr, g, h, c, head, pin, r);
 }
+
+namespace {
+// The statistics walk over a tuple, enqueued on `stream`; the counts on their way to `counts` (not waited for).
+int enqueue_symbol_counts(Context &c, const pixo_jpeg_options &o, const pixo_host::Geometry &g, const int16_t *dy, const int16_t *dcb,
+                          const int16_t *dcr, hipStream_t stream, uint64_t *counts)
+{
+    namespace pd = pixo_dev;
+    int rc;
+    if ((rc = c.e_hist.reserve(pixo_host::kScanTableWords * 8)) || (rc = c.e_count.reserve(pd::scan_count_scratch_bytes()))) return rc;
+    HIP_TRY(pd::launch_scan_count(count_args(g, o, dy, dcb, dcr), c.e_count.as<uint32_t>(), c.e_hist.as<unsigned long long>(), stream));
+    HIP_TRY(hipMemcpyAsync(counts, c.e_hist.p, pixo_host::kScanTableWords * 8, hipMemcpyDeviceToHost, stream));
+    return PIXO_OK;
+}
+pixo_host::HuffSet tables_from_counts(const uint64_t *counts, bool has_chroma)
+{
+    uint64_t dc[2][12], ac[2][256];
+    split_counts(counts, dc, ac);
+    return pixo_host::HuffSet::optimized(dc, ac, has_chroma);
+}
+} // namespace
 
 // Huffman tables of a file over the device tuple: the standard ones, or (optimize_huffman) those built
 // from the statistics of a baseline walk (build_optimized_huffman_tables, jpeg/mod.rs:684-824) — counted
@@ -305,26 +327,12 @@ int device_progressive_scans(const int16_t *dy, const int16_t *dcb, const int16_
 int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
                       const pixo_host::Geometry &g, Context &c, pixo_host::HuffSet &h)
 {
-    namespace pd = pixo_dev;
     h = pixo_host::HuffSet::standard();
     if (!o.optimize_huffman) return PIXO_OK;
-    pd::ScanArgs a;
-    a.y = dy; a.cb = dcb; a.cr = dcr; a.tables = nullptr;
-    a.mode = g.gray ? 0 : (g.s420 ? 2 : 1);
-    a.nblocks = g.y_blocks + 2 * g.c_blocks;
-    a.blocks_per_mcu = g.gray ? 1 : (g.s420 ? 6 : 3);
-    a.marker_bytes = 2;
-    a.restart = scan_has_restart_markers(o, g) ? o.restart_interval : 0;
-    a.seed_dc[0] = a.seed_dc[1] = a.seed_dc[2] = 0; a.bit_base = 0; a.pad_last = 1;
-    int rc;
-    if ((rc = c.e_hist.reserve(pixo_host::kScanTableWords * 8)) || (rc = c.e_count.reserve(pd::scan_count_scratch_bytes()))) return rc;
-    HIP_TRY(pd::launch_scan_count(a, c.e_count.as<uint32_t>(), c.e_hist.as<unsigned long long>(), c.stream));
     uint64_t counts[pixo_host::kScanTableWords];
-    HIP_TRY(hipMemcpyAsync(counts, c.e_hist.p, sizeof counts, hipMemcpyDeviceToHost, c.stream));
+    if (const int rc = enqueue_symbol_counts(c, o, g, dy, dcb, dcr, c.stream, counts)) return rc;
     HIP_TRY(hipStreamSynchronize(c.stream));
-    uint64_t dc[2][12], ac[2][256];
-    split_counts(counts, dc, ac);
-    h = pixo_host::HuffSet::optimized(dc, ac, !g.gray);
+    h = tables_from_counts(counts, !g.gray);
     return PIXO_OK;
 }
 
@@ -335,11 +343,11 @@ int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr,
 //   tuple    `trellis_quant`: the coefficient kernel in raw mode (unquantised transform) followed by the
 //            trellis kernel; otherwise the ordinary kernel (`trellis_quant` acts nowhere else: a baseline
 //            encode with the flag set is an ordinary baseline encode, encode_scan never reads it);
-//   scans    device_progressive_scans above (PIXO_HIP_HOST_ENTROPY=1: the host twin in jpeg_host.cpp on a
-//            pinned copy of the tuple).
-// Progressive file from device pixels; *file points into the context's pinned buffer (or into `spill`: the host twin).
-int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const pixo_host::Geometry &g, Context &c,
-                        std::vector<uint8_t> &spill, const uint8_t **file, size_t *file_len, uint8_t *pinned_dest, size_t dest_cap)
+//   scans    device_progressive_scans above (host_twin: the host twin in jpeg_host.cpp on a pinned copy of the tuple).
+// Progressive file from device pixels; r.file points into the caller's pinned storage, the context's pinned buffer, or r.spill
+// (the host twin).
+int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const pixo_host::Geometry &g, Context &c, bool host_twin,
+                        const FileDest &dest, FileResult &r)
 {
     namespace pd = pixo_dev;
     int rc;
@@ -349,7 +357,7 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
     const float *qt = qt_all + (o.quality - 1) * pixo_host::kDeviceQtFloats;
     pixo_host::HuffSet h;
     const bool need_plain = o.optimize_huffman || !o.trellis_quant;
-    const bool late_tables = o.optimize_huffman && o.trellis_quant && !debug().host_entropy;
+    const bool late_tables = o.optimize_huffman && o.trellis_quant && !host_twin;
     // Round 5, small images (the trellis kernel's wavefronts — 64 blocks each — do not fill the chip's 1,024 SIMDs: up to 1080p):
     // the statistics run on a SECOND stream beside the raw transform + the search, whose 117 us are the latency of one
     // wavefront's 63 steps whatever the image's size.  (On large images the search keeps every SIMD issuing and kernels beside
@@ -366,7 +374,8 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
         HIP_TRY(hipStreamWaitEvent(c.copy_stream, c.side_ready, 0));
         stats_stream = c.copy_stream;
         if ((rc = c.t_plain.reserve((g.y_blocks + 2 * g.c_blocks) * 128))) return rc;
-        dy = c.t_plain.as<int16_t>(); dcb = dy + g.y_blocks * 64; dcr = dcb + g.c_blocks * 64;
+        const Planes plain = planes_of(c.t_plain.as<int16_t>(), g);
+        dy = plain.y; dcb = plain.cb; dcr = plain.cr;
         if ((rc = coeffs_rows(c, d_pixels, o, g, stats_stream, dy, g.gray ? nullptr : dcb, g.gray ? nullptr : dcr, 0, 0))) return rc;
     } else if (need_plain && (rc = coeffs_on_device(c, d_pixels, o, g, c.stream, &dy, &dcb, &dcr))) return rc;
     // Preset 2 (optimised tables AND trellis): the statistics (plain tuple -> baseline walk -> counts) are enqueued, the counts
@@ -374,17 +383,7 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
     // waits for the counts' event only and builds the tables while the search (0.29 ms for 4096x4096) runs.  Rounds 1-3
     // synchronised, built the tables and only then launched the search: 30 us of idle GPU per file.
     if (late_tables) {
-        pd::ScanArgs a;
-        a.y = dy; a.cb = dcb; a.cr = dcr; a.tables = nullptr;
-        a.mode = g.gray ? 0 : (g.s420 ? 2 : 1);
-        a.nblocks = g.y_blocks + 2 * g.c_blocks;
-        a.blocks_per_mcu = g.gray ? 1 : (g.s420 ? 6 : 3);
-        a.marker_bytes = 2;
-        a.restart = scan_has_restart_markers(o, g) ? o.restart_interval : 0;
-        a.seed_dc[0] = a.seed_dc[1] = a.seed_dc[2] = 0; a.bit_base = 0; a.pad_last = 1;
-        if ((rc = c.e_hist.reserve(pixo_host::kScanTableWords * 8)) || (rc = c.e_count.reserve(pd::scan_count_scratch_bytes()))) return rc;
-        HIP_TRY(pd::launch_scan_count(a, c.e_count.as<uint32_t>(), c.e_hist.as<unsigned long long>(), stats_stream));
-        HIP_TRY(hipMemcpyAsync(c.mail->counts, c.e_hist.p, sizeof c.mail->counts, hipMemcpyDeviceToHost, stats_stream));
+        if ((rc = enqueue_symbol_counts(c, o, g, dy, dcb, dcr, stats_stream, c.mail->counts))) return rc;
         if (!c.stats_done) HIP_TRY(hipEventCreateWithFlags(&c.stats_done, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c.stats_done, stats_stream));
     } else if ((rc = huffman_for_tuple(dy, dcb, dcr, o, g, c, h))) return rc;
@@ -392,33 +391,31 @@ int progressive_to_view(const void *d_pixels, const pixo_jpeg_options &o, const 
     if (o.trellis_quant) {
         if ((rc = c.t_raw.reserve((blocks + 63) / 64 * 64 * 256))) return rc; // (whole wavefronts of the trellis kernel: jpeg_kernels.hpp)
         if ((rc = c.d_coef.reserve(coef_bytes))) return rc;
-        float *ry = c.t_raw.as<float>(), *rcb = ry + g.y_blocks * 64, *rcr = rcb + g.c_blocks * 64;
-        dy = c.d_coef.as<int16_t>(); dcb = dy + g.y_blocks * 64; dcr = dcb + g.c_blocks * 64;
-        HIP_TRY(pd::launch_jpeg_coeffs(d_pixels, o.width, o.height, g.gray, g.s420, 1, ry, g.gray ? nullptr : rcb,
-                                       g.gray ? nullptr : rcr, qt, c.stream, /*raw_f32=*/true));
+        const PlanesOf<float> raw = planes_of(c.t_raw.as<float>(), g);
+        float *ry = raw.y;
+        const Planes t = planes_of(c.d_coef.as<int16_t>(), g);
+        dy = t.y; dcb = t.cb; dcr = t.cr;
+        HIP_TRY(pd::launch_jpeg_coeffs(d_pixels, o.width, o.height, g.gray, g.s420, 1, ry, g.gray ? nullptr : raw.cb,
+                                       g.gray ? nullptr : raw.cr, qt, c.stream, /*raw_f32=*/true));
         // one launch over the whole tuple (the planes are contiguous): luminance steps, then chrominance steps
         if ((rc = c.t_trail.reserve(pd::trellis_scratch_bytes(blocks)))) return rc;
         HIP_TRY(pd::launch_trellis(ry, qt + 128, qt + 192, dy, blocks, g.y_blocks, c.t_trail.p, c.stream));
     }
     if (late_tables) { // the counts have arrived (the search is still running): tables, exactly like optimized_from_counts
         HIP_TRY(hipEventSynchronize(c.stats_done));
-        uint64_t dc[2][12], ac[2][256];
-        split_counts(c.mail->counts, dc, ac);
-        h = pixo_host::HuffSet::optimized(dc, ac, !g.gray);
+        h = tables_from_counts(c.mail->counts, !g.gray);
     }
-    if (debug().host_entropy) note_route(route::HOST_ENTROPY);
-    if (!debug().host_entropy) {
+    if (!host_twin) {
         std::vector<uint8_t> head;
         pixo_host::file_headers(head, o, h);
-        return device_progressive_scans(dy, dcb, dcr, g, h, c, head, file, file_len, pinned_dest, dest_cap);
+        return device_progressive_scans(dy, dcb, dcr, g, h, c, head, dest, r);
     }
     if ((rc = c.h_coef.reserve(coef_bytes))) return rc;
     HIP_TRY(hipMemcpyAsync(c.h_coef.p, dy, coef_bytes, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    const int16_t *hy = c.h_coef.as<const int16_t>(), *hcb = hy + g.y_blocks * 64, *hcr = hcb + g.c_blocks * 64;
-    pixo_host::encode_progressive_file(hy, hcb, hcr, o, h, spill);
-    *file = spill.data();
-    *file_len = spill.size();
+    const PlanesOf<const int16_t> host = planes_of(c.h_coef.as<const int16_t>(), g);
+    pixo_host::encode_progressive_file(host.y, host.cb, host.cr, o, h, r.spill);
+    r.file = r.spill.data(); r.len = r.spill.size();
     return PIXO_OK;
 }
 

@@ -18,23 +18,20 @@ int coeffs_to_pinned(Context &c, const uint8_t *pixels, const pixo_jpeg_options 
     const float *qt_all = nullptr;
     rc = device_tables(c.device, &qt_all);
     if (rc) return rc;
-    const size_t px_bytes = static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3);
+    const size_t px_bytes = pixel_bytes(o, g);
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128;
-    if ((rc = c.d_px.reserve((px_bytes + 15) & ~size_t{15}))) return rc;
+    if ((rc = reserve_pixels(c, px_bytes))) return rc;
     if ((rc = c.d_coef.reserve(coef_bytes))) return rc;
     if ((rc = c.h_coef.reserve(coef_bytes))) return rc;
     HIP_TRY(hipMemcpyAsync(c.d_px.p, pixels, px_bytes, hipMemcpyHostToDevice, c.stream));
-    int16_t *dy = c.d_coef.as<int16_t>();
-    int16_t *dcb = dy + g.y_blocks * 64;
-    int16_t *dcr = dcb + g.c_blocks * 64;
-    HIP_TRY(pixo_dev::launch_jpeg_coeffs(c.d_px.p, o.width, o.height, g.gray, g.s420, 1, dy,
-                                         g.gray ? nullptr : dcb, g.gray ? nullptr : dcr,
+    const Planes d = planes_of(c.d_coef.as<int16_t>(), g);
+    HIP_TRY(pixo_dev::launch_jpeg_coeffs(c.d_px.p, o.width, o.height, g.gray, g.s420, 1, d.y,
+                                         g.gray ? nullptr : d.cb, g.gray ? nullptr : d.cr,
                                          qt_all + (o.quality - 1) * pixo_host::kDeviceQtFloats, c.stream));
     HIP_TRY(hipMemcpyAsync(c.h_coef.p, c.d_coef.p, coef_bytes, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    *y = c.h_coef.as<const int16_t>();
-    *cb = *y + g.y_blocks * 64;
-    *cr = *cb + g.c_blocks * 64;
+    const PlanesOf<const int16_t> host = planes_of(c.h_coef.as<const int16_t>(), g);
+    *y = host.y; *cb = host.cb; *cr = host.cr;
     return PIXO_OK;
 }
 
@@ -45,9 +42,8 @@ int coeffs_reserve(Context &c, const pixo_host::Geometry &g, int16_t **dy, int16
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128;
     const int rc = c.d_coef.reserve(coef_bytes);
     if (rc) return rc;
-    *dy = c.d_coef.as<int16_t>();
-    *dcb = *dy + g.y_blocks * 64;
-    *dcr = *dcb + g.c_blocks * 64;
+    const Planes t = planes_of(c.d_coef.as<int16_t>(), g);
+    *dy = t.y; *dcb = t.cb; *dcr = t.cr;
     return PIXO_OK;
 }
 // The coefficient kernel over MCU rows [row0, row0 + rows) of the image — a sub-image of the same width whose blocks
@@ -621,18 +617,18 @@ extern "C" int pixo_hip_debug_scan_device_async_batch(const void *d_pixels, cons
     namespace pd = pixo_dev;
     PIXO_REQUIRE(d_pixels);
     PIXO_REQUIRE(options);
-    std::string msg;
-    int rc = pixo_host::validate(*options, false, 0, msg);
-    if (rc) return fail(rc, msg);
+    int rc = checked(*options);
+    if (rc) return rc;
     if (options->progressive || options->optimize_huffman) return fail(PIXO_ERR_COMPRESSION, "Compression error: pixo_hip_debug_scan_device_async measures baseline scans with standard tables");
-    if (batch == 0 || batch > 65535) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch must be 1..65535");
+    if ((rc = batch_in_range(batch))) return rc;
     Context *c = nullptr;
     if ((rc = context_on_current_device(&c))) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const pixo_host::Geometry g = pixo_host::geometry(options->width, options->height, options->color_type, options->subsampling);
+    const pixo_host::Geometry g = geometry_of(*options);
     const size_t coef_bytes = (g.y_blocks + 2 * g.c_blocks) * 128 * batch;
     if ((rc = c->d_coef.reserve(coef_bytes))) return rc;
-    int16_t *dy = c->d_coef.as<int16_t>(), *dcb = dy + g.y_blocks * 64 * batch, *dcr = dcb + g.c_blocks * 64 * batch;
+    const Planes t = planes_of(c->d_coef.as<int16_t>(), g, batch);
+    int16_t *dy = t.y, *dcb = t.cb, *dcr = t.cr;
     ScanJob j;
     if (batch > 1) { // (the gap a batch leaves between two scans: EOI + the next file's headers)
         std::vector<uint8_t> probe_head;
