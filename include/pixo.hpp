@@ -193,8 +193,8 @@ namespace filter {
 }
 } // namespace filter
 
-// The fields of pixo::png::PngOptions (src/png/mod.rs:41-100) that shape the bytes handed to DEFLATE, plus the ones the
-// presets set for the caller's DEFLATE and chunk writing (carried, unused here).  No quantisation.
+// The fields of pixo::png::PngOptions (src/png/mod.rs:41-100).  compression_level selects the zlib header's FLEVEL; the
+// device DEFLATE has one effort, so optimal_compression compresses the same way (pixo_hip.h).  No quantisation.
 struct PngOptions {
     uint32_t width = 0, height = 0;
     ColorType color_type = ColorType::Rgba;
@@ -243,6 +243,24 @@ struct Prepared {
     if (rc != PIXO_OK) throw Error::from_status(rc);
     p.stream.resize(n);
     return p;
+}
+
+// pixo::png::encode_with_options: a finished PNG file.  The chunks around IDAT are the reference's byte for byte; the IDAT
+// body is the device DEFLATE of the prepared stream (contract: pixo_hip.h).
+[[nodiscard]] inline std::vector<uint8_t> encode(const uint8_t *data, size_t len, const PngOptions &options)
+{
+    const pixo_png_options c = options.to_c();
+    uint8_t *file = nullptr;
+    size_t n = 0;
+    const int rc = pixo_hip_png_encode(data, len, &c, &file, &n);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    std::vector<uint8_t> out(file, file + n);
+    pixo_hip_free(file);
+    return out;
+}
+[[nodiscard]] inline std::vector<uint8_t> encode(const std::vector<uint8_t> &data, const PngOptions &options)
+{
+    return encode(data.data(), data.size(), options);
 }
 } // namespace png
 

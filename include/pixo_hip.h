@@ -233,12 +233,14 @@ uint32_t pixo_hip_png_adler32_from_row_sums(const uint64_t *row_sums, uint32_t w
 /* The prepared stream: the bytes `pixo::png::encode_into` hands to its DEFLATE (`filtered`, mod.rs:561) for given
  * pixels and options — after maybe_reduce_color_type (:683-836: palette of <= 256 colours in modified-Zeng order at
  * 1/2/4/8 bits, RGBA -> RGB / GrayAlpha / Gray, RGB -> Gray, gray bit depth), maybe_optimize_alpha (:633-671) and
- * apply_filters_with_row_bytes — together with the layout a caller needs to write IHDR / PLTE / tRNS around its
- * own DEFLATE of them.  Quantisation (lossy) is not part of this path. */
+ * apply_filters_with_row_bytes — together with the layout of the IHDR / PLTE / tRNS chunks that go around them.
+ * pixo_hip_png_encode (below) compresses the stream on the device and writes the file; the prepare entries are for callers
+ * that want the stream itself.  Quantisation (lossy) is not part of this path. */
 
-/* The fields of pixo::png::PngOptions (mod.rs:64-100) that shape the prepared stream.  compression_level,
- * optimal_compression and strip_metadata concern the caller's DEFLATE and chunk writing: they are carried (the presets set
- * them) and read by nothing here. */
+/* The fields of pixo::png::PngOptions (mod.rs:64-100).  The prepare entries read the ones that shape the prepared stream.
+ * pixo_hip_png_encode also reads compression_level: clamped to 1..9, it selects the FLEVEL bits of the zlib header as in the
+ * reference.  The device compressor has ONE effort: optimal_compression is accepted and compresses the same way, and
+ * strip_metadata changes nothing, because the files written here hold no chunk it would strip. */
 typedef struct pixo_png_options {
     uint32_t width;
     uint32_t height;
@@ -286,6 +288,34 @@ int pixo_hip_png_prepare_device(const void *d_pixels, const pixo_png_options *op
  * counts[n] of the indices into the sorted colour keys and their n x n co-occurrence matrix (:940-977, row major;
  * the diagonal is never read) to the final order — order_out[k] is the sorted-key index of palette entry k. */
 int pixo_hip_png_palette_order(const uint32_t *counts, const uint32_t *matrix, uint32_t n, uint8_t *order_out);
+
+/* ---- PNG whole files: DEFLATE, CRC-32 and chunk writing on the device ------------------------ */
+
+/* The contract differs from the JPEG side: the IDAT body is this library's own DEFLATE, not the reference's bytes.
+ *   - Byte for byte the reference's: signature, IHDR, PLTE, tRNS, IEND (mod.rs:513-630), the two zlib header bytes for
+ *     the compression level (deflate.rs:1642-1658), the Adler-32 trailer, the split into IDAT chunks of 256 KiB.
+ *   - The IDAT chunks concatenated are a valid zlib stream that inflates to the prepared stream pixo_hip_png_prepare
+ *     returns for the same options.
+ *   - Deterministic: the same input gives the same bytes on every run.
+ *   - The zlib stream is never larger than len + 5 * ceil(len / 65535) + 6 bytes (all blocks stored).
+ * `out` blocks are released with pixo_hip_free, as those of the JPEG entries. */
+
+/* Host bytes -> zlib stream (header, DEFLATE blocks of at most 65,535 input bytes each, Adler-32).  level: 1..9 after
+ * clamping, header bits only.  hint_bpp / hint_row: two distances the match search tries at every position besides 1 and
+ * its hash table's — for a filtered PNG stream the bytes per pixel and row_bytes + 1; 0 or a value beyond the data or the
+ * 32 KiB window: not tried.  len == 0 gives the reference's empty stream (header, empty fixed block, Adler-32 of nothing). */
+int pixo_hip_zlib_compress(const uint8_t *data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row,
+                           uint8_t **out, size_t *out_len);
+/* The same for bytes in HBM on the current HIP device, into d_out in HBM.  capacity must be at least the stored bound
+ * above, 8 for len == 0 (PIXO_ERR_BUFFER_TOO_SMALL with *out_len = that size otherwise).  Synchronous. */
+int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row,
+                                  void *d_out, size_t capacity, size_t *out_len);
+/* pixo::png::encode_with_options: pixels in, a finished PNG file out.  Prepare, DEFLATE, compaction and CRC-32 run
+ * without the stream leaving the device; only the finished file is copied out.  Checks: those of pixo_hip_png_prepare, in
+ * the same order. */
+int pixo_hip_png_encode(const uint8_t *data, size_t data_len, const pixo_png_options *options, uint8_t **out, size_t *out_len);
+/* The same for pixels in HBM on the current HIP device (ordered after the producer stream); the file lands on the host. */
+int pixo_hip_png_encode_device(const void *d_pixels, const pixo_png_options *options, uint8_t **out, size_t *out_len);
 
 /* ---- resize (pixo::resize, src/resize.rs) ------------------------------------------------ */
 

@@ -13,6 +13,7 @@
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
 //   png_api.cpp      the extern "C" PNG row-filter entry points
 //   png_reduce_api.cpp  the extern "C" PNG prepare entry points: reductions (png_reduce.hip), palette ordering, then the filter
+//   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, device DEFLATE (png_deflate.hip), chunks
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
 #pragma once
 #include <hip/hip_runtime.h>
@@ -218,6 +219,13 @@ struct Context {
     Buf h_qwork{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... its host side: results come down into it, tables go up from it
     Buf q_index{Buf::Mem::Device, Buf::Grow::Exact}; // palette case: the index image (sorted-key order), 1 byte per pixel
     Buf q_rows{Buf::Mem::Device, Buf::Grow::Exact};  // the reduced rows the filter kernel reads
+    // device DEFLATE (png_encode_api.cpp, png_deflate.hip)
+    Buf z_tok{Buf::Mem::Device, Buf::Grow::Exact};   // a token per input byte, 65,536 u32 per chunk
+    Buf z_slots{Buf::Mem::Device, Buf::Grow::Exact}; // a slot per chunk: its block before compaction
+    Buf z_info;                                      // per chunk: block bytes, form, Adler sums; behind them the blocks' offsets (u64)
+    Buf z_stream;                                    // the zlib stream: plain, or as IDAT bodies with room for their frames
+    Buf z_crc;                                       // CRC-32 of every 4 KiB piece of the stream
+    Buf h_zinfo{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... z_info / z_crc copied to the host
     Buf t_raw, t_trail;                 // progressive + trellis: unquantised DCT blocks (f32), Viterbi back-pointers
     Buf t_plain;                        // preset 2, small images: the plain quantiser's tuple of the statistics pass on the second stream
     Buf g_flags, g_rank, g_by_rank;     // progressive scans: band flags, rank among non-empty blocks and its inverse
@@ -519,6 +527,12 @@ int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8
 // filter kernel + checksum on the context's stream; returns after the checksum has been combined
 int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t bpp, int run, bool sequential_fast,
                          void *d_out, uint32_t *adler);
+
+// ---- PNG prepare (png_reduce_api.cpp) --------------------------------------------------------------------------------
+int png_check_options(const pixo_png_options *o, size_t *in_bytes); // the checks of pixo_hip_png_prepare that need no data
+// d_px: width * height * bpp bytes on the context's device; reductions + filters, the stream is left in d_out
+int png_prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, void *d_out, pixo_png_layout *layout, size_t *out_len,
+                          uint32_t *adler);
 
 // ---- preset 2 (progressive.cpp) -----------------------------------------------------------------------------------
 int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,

@@ -1,0 +1,357 @@
+// png_deflate.hip — DEFLATE on the device for the PNG whole-file path.
+//
+// The stream is cut into chunks of at most 65,535 bytes; one workgroup of 1024 lanes turns one chunk into one DEFLATE block
+// in the chunk's slot.  Every block but the last is followed by an empty stored block (000, pad, 00 00 FF FF), so every
+// block starts on a byte boundary and joining them is a byte compaction.  Per chunk:
+//   1. match finding, one position per lane and sub-step of 1024 positions: a 4-byte hash table in LDS (latest position,
+//      filled with atomicMax after all lanes of the sub-step have looked up, so the result does not depend on scheduling),
+//      seeded with the 32 KiB in front of the chunk, plus the distances 1, hint_bpp, hint_row tried explicitly;
+//   2. greedy parse over next[p] = p + max(len[p], 1): every lane resolves where each position of its 64-position segment
+//      leaves the segment (in LDS, back to front), ONE lane then hops from segment to segment (at most 1024 hops), and
+//      every lane walks its own segment from the entry it was given — tokens compacted in place, histograms by LDS atomics;
+//   3. code lengths (literal/length and distance trees on one lane each), dynamic header, sizes of the three forms;
+//   4. token bit lengths, exclusive scan, LSB-first packing into LDS with atomicOr, vector stores to the slot.
+// Only vector stores write device memory.
+#include <hip/hip_runtime.h>
+
+#include "png_deflate.hpp"
+
+namespace pixo_dev {
+using namespace pixo_pngz;
+
+namespace {
+constexpr uint32_t kThreads = 1024, kSeg = 64, kHashBits = 14, kNoEntry = 0xFFFF;
+static_assert(kThreads * kSeg >= kZChunk, "a lane per segment");
+
+__device__ __forceinline__ uint32_t load_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ uint64_t load_u64(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
+__device__ __forceinline__ uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashBits); }
+
+// bytes that agree at p and q (q < p), at most max_len; reads p[0..max_len) only
+__device__ __forceinline__ uint32_t match_length(const uint8_t *p, const uint8_t *q, uint32_t max_len)
+{
+    uint32_t k = 0;
+    while (k + 8 <= max_len) {
+        const uint64_t x = load_u64(p + k) ^ load_u64(q + k);
+        if (x) return k + (static_cast<uint32_t>(__builtin_ctzll(x)) >> 3);
+        k += 8;
+    }
+    while (k < max_len && p[k] == q[k]) ++k;
+    return k;
+}
+
+struct ChunkShared {
+    union {
+        uint32_t hash[1u << kHashBits]; // position - window start + 1 of the latest occurrence, 0: none
+        uint16_t exit[65536];           // parse: where the path from p leaves p's segment
+        uint32_t out[32768];            // the block being packed
+    } big;
+    uint16_t entry[kThreads];
+    uint32_t scan[kThreads];
+    uint32_t lit_freq[kLitTable], dist_freq[kDistTable];
+    uint16_t lit_code[kLitTable], dist_code[kDistTable];
+    uint8_t lit_len[kLitTable], dist_len[kDistTable];
+    uint8_t fix_lit_len[kLitTable], fix_dist_len[kDistTable];
+    HuffWork work[2];
+    uint8_t header[kHeaderBytes];
+    unsigned long long sum_a, sum_b;
+    uint32_t mode, header_bits, block_bytes;
+};
+
+__global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *__restrict__ data, uint64_t len, uint32_t hint_bpp,
+                                                                 uint32_t hint_row, uint32_t *__restrict__ tok_all,
+                                                                 uint8_t *__restrict__ slots, ZChunkInfo *__restrict__ info)
+{
+    __shared__ ChunkShared s;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t chunk = blockIdx.x;
+    const uint64_t c0 = chunk * kZChunk;
+    const uint32_t n = static_cast<uint32_t>(len - c0 < kZChunk ? len - c0 : kZChunk); // 1..65535
+    const bool last = c0 + n == len;
+    const uint64_t wstart = c0 > kWindow ? c0 - kWindow : 0;
+    uint32_t *tok = tok_all + chunk * kZTokStride;
+    uint8_t *slot = slots + chunk * kZSlot;
+
+    for (uint32_t i = tid; i < (1u << kHashBits); i += kThreads) s.big.hash[i] = 0;
+    if (tid < kLitTable) s.lit_freq[tid] = tid == 256 ? 1u : 0u; // the end-of-block symbol
+    if (tid < kDistTable) s.dist_freq[tid] = 0;
+    if (tid == 0) { s.sum_a = 0; s.sum_b = 0; }
+    __syncthreads();
+
+    { // Adler-32 partial sums of the chunk
+        unsigned long long a = 0, b = 0;
+        for (uint32_t p = tid; p < n; p += kThreads) { const uint32_t v = data[c0 + p]; a += v; b += static_cast<unsigned long long>(n - p) * v; }
+        for (int off = 32; off; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+        if ((tid & 63) == 0) { atomicAdd(&s.sum_a, a); atomicAdd(&s.sum_b, b); }
+    }
+    // the window in front of the chunk
+    for (uint64_t a = wstart + tid; a < c0; a += kThreads)
+        if (a + 4 <= len) atomicMax(&s.big.hash[hash4(load_u32(data + a))], static_cast<uint32_t>(a - wstart) + 1);
+    __syncthreads();
+
+    // ---- 1. the best match at every position ----
+    for (uint32_t base = 0; base < n; base += kThreads) {
+        const uint32_t p = base + tid;
+        const bool active = p < n;
+        const uint64_t a = c0 + p;
+        uint32_t best_len = 0, best_dist = 0, hv = 0;
+        bool hashed = false;
+        if (active) {
+            const uint32_t max_len = n - p < kMaxMatch ? n - p : kMaxMatch;
+            uint32_t cand = 0;
+            if (p + 4 <= n) { hashed = true; hv = hash4(load_u32(data + a)); cand = s.big.hash[hv]; }
+            auto attempt = [&](uint64_t d) {
+                if (d == 0 || d > kWindow || d > a || best_len == max_len) return;
+                const uint32_t l = match_length(data + a, data + a - d, max_len);
+                if (l > best_len || (l == best_len && d < best_dist)) { best_len = l; best_dist = static_cast<uint32_t>(d); }
+            };
+            if (max_len >= kMinMatch) {
+                attempt(1);
+                if (hint_bpp > 1) attempt(hint_bpp);
+                if (cand) attempt(a - (wstart + cand - 1));
+                if (hint_row > 1 && hint_row != hint_bpp) attempt(hint_row);
+            }
+            if (best_len < kMinMatch || (best_len == kMinMatch && best_dist > 4096)) best_len = 0; // dearer than its literals
+        }
+        __syncthreads(); // every lane of the sub-step has looked up
+        if (hashed) atomicMax(&s.big.hash[hv], static_cast<uint32_t>(a - wstart) + 1);
+        if (active) tok[p] = best_len ? token_match(best_len, best_dist) : data[a];
+        __syncthreads();
+    }
+
+    // ---- 2. greedy parse ----
+    for (uint32_t p = tid; p < n; p += kThreads) {
+        const uint32_t l = token_len(tok[p]);
+        const uint32_t e = p + (l ? l : 1);
+        s.big.exit[p] = static_cast<uint16_t>(e < n ? e : n);
+    }
+    s.entry[tid] = kNoEntry;
+    __syncthreads();
+    const uint32_t lo = tid * kSeg, hi = lo + kSeg < n ? lo + kSeg : n;
+    for (uint32_t p = hi; p > lo; --p) { // (hi <= lo: nothing of the chunk in this segment)
+        const uint32_t e = s.big.exit[p - 1];
+        if (e < hi) s.big.exit[p - 1] = s.big.exit[e];
+    }
+    __syncthreads();
+    if (tid == 0)
+        for (uint32_t pos = 0; pos < n; pos = s.big.exit[pos]) s.entry[pos / kSeg] = static_cast<uint16_t>(pos);
+    __syncthreads();
+    uint32_t count = 0; // tokens of this lane's segment, compacted to tok[lo .. lo + count)
+    if (s.entry[tid] != kNoEntry) {
+        for (uint32_t pos = s.entry[tid]; pos < hi;) {
+            const uint32_t t = tok[pos];
+            const uint32_t l = token_len(t);
+            if (l) {
+                uint32_t sym, eb, ev;
+                length_symbol(l, &sym, &eb, &ev);
+                atomicAdd(&s.lit_freq[sym], 1u);
+                distance_symbol(t & 0xFFFF, &sym, &eb, &ev);
+                atomicAdd(&s.dist_freq[sym], 1u);
+            } else {
+                atomicAdd(&s.lit_freq[t & 255], 1u);
+            }
+            tok[lo + count++] = t; // lo + count <= pos: behind the read
+            pos += l ? l : 1;
+        }
+    }
+    __syncthreads();
+
+    // ---- 3. codes and the form of the block ----
+    if (tid == 0) huffman_lengths(s.lit_freq, kLitSyms, 15, s.lit_len, s.work[0]);
+    if (tid == 64) huffman_lengths(s.dist_freq, kDistSyms, 15, s.dist_len, s.work[1]);
+    if (tid == 128) fixed_lengths(s.fix_lit_len, s.fix_dist_len);
+    __syncthreads();
+    if (tid == 0) {
+        s.lit_len[286] = s.lit_len[287] = 0;
+        s.dist_len[30] = s.dist_len[31] = 0;
+        BitWriter bw(s.header);
+        dynamic_header(bw, last, s.lit_len, s.dist_len, s.work[0]);
+        const uint32_t head = bw.bit_count();
+        bw.flush();
+        const uint32_t dyn = head + body_bits(s.lit_freq, s.dist_freq, s.lit_len, s.dist_len);
+        const uint32_t fix = 3 + body_bits(s.lit_freq, s.dist_freq, s.fix_lit_len, s.fix_dist_len);
+        // bytes in the slot: a block that is not the last is followed by the empty stored block
+        const uint32_t dyn_bytes = last ? (dyn + 7) / 8 : (dyn + 3 + 7) / 8 + 4;
+        const uint32_t fix_bytes = last ? (fix + 7) / 8 : (fix + 3 + 7) / 8 + 4;
+        const uint32_t stored_bytes = n + 5;
+        uint32_t mode = 0, bytes = stored_bytes;
+        if (fix_bytes < bytes) { mode = 1; bytes = fix_bytes; }
+        if (dyn_bytes < bytes) { mode = 2; bytes = dyn_bytes; }
+        s.mode = mode;
+        s.block_bytes = bytes;
+        s.header_bits = mode == 2 ? head : 3;
+        if (mode == 1) { s.header[0] = static_cast<uint8_t>((last ? 1u : 0u) | 2u); } // BFINAL, BTYPE = 01
+        info[chunk] = ZChunkInfo{bytes, mode, s.sum_a, s.sum_b};
+    }
+    __syncthreads();
+    const uint32_t mode = s.mode, block_bytes = s.block_bytes;
+    const uint32_t words = (block_bytes + 3) / 4; // <= kZSlot / 4
+    uint32_t *slot_words = reinterpret_cast<uint32_t *>(slot);
+    if (mode == 0) { // stored: BFINAL + 00, LEN, NLEN, the bytes
+        for (uint32_t w = tid; w < words; w += kThreads) {
+            uint32_t v = 0;
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t i = 4 * w + k;
+                uint32_t byte = 0;
+                if (i == 0) byte = last ? 1u : 0u;
+                else if (i == 1) byte = n & 255;
+                else if (i == 2) byte = n >> 8;
+                else if (i == 3) byte = ~n & 255;
+                else if (i == 4) byte = (~n >> 8) & 255;
+                else if (i < n + 5) byte = data[c0 + i - 5];
+                v |= byte << (8 * k);
+            }
+            slot_words[w] = v;
+        }
+        return;
+    }
+    if (mode == 1 && tid < kLitTable) s.lit_len[tid] = s.fix_lit_len[tid];
+    if (mode == 1 && tid < kDistTable) s.dist_len[tid] = s.fix_dist_len[tid];
+    __syncthreads();
+    if (tid == 0) canonical_codes(s.lit_len, kLitTable, s.lit_code);
+    if (tid == 64) canonical_codes(s.dist_len, kDistTable, s.dist_code);
+
+    // ---- 4. pack ----
+    uint32_t bits = 0;
+    for (uint32_t j = 0; j < count; ++j) bits += token_bits(tok[lo + j], s.lit_len, s.dist_len);
+    s.scan[tid] = bits;
+    for (uint32_t w = tid; w < words + 1; w += kThreads) s.big.out[w] = 0; // words + 1 <= 32768
+    __syncthreads();
+    for (uint32_t step = 1; step < kThreads; step <<= 1) { // inclusive scan
+        const uint32_t add = tid >= step ? s.scan[tid - step] : 0;
+        __syncthreads();
+        s.scan[tid] += add;
+        __syncthreads();
+    }
+    const uint32_t header_bits = s.header_bits;
+    const uint32_t body_end = header_bits + s.scan[kThreads - 1]; // where the end-of-block symbol goes
+    for (uint32_t i = tid; i < (header_bits + 7) / 8; i += kThreads) atomicOr(&s.big.out[i >> 2], static_cast<uint32_t>(s.header[i]) << (8 * (i & 3)));
+    auto put = [&](uint32_t at, uint64_t v) { // v: at most 48 bits
+        const uint32_t w = at >> 5, sh = at & 31;
+        const uint32_t w0 = static_cast<uint32_t>(v << sh);
+        const uint64_t rest = sh ? v >> (32 - sh) : v >> 32;
+        if (w0) atomicOr(&s.big.out[w], w0);
+        if (static_cast<uint32_t>(rest)) atomicOr(&s.big.out[w + 1], static_cast<uint32_t>(rest));
+        if (rest >> 32) atomicOr(&s.big.out[w + 2], static_cast<uint32_t>(rest >> 32));
+    };
+    const CodeTables codes{s.lit_code, s.lit_len, s.dist_code, s.dist_len};
+    uint32_t at = header_bits + s.scan[tid] - bits;
+    for (uint32_t j = 0; j < count; ++j) {
+        uint64_t v;
+        const uint32_t k = token_code(tok[lo + j], codes, &v);
+        put(at, v);
+        at += k;
+    }
+    if (tid == 0) {
+        put(body_end, s.lit_code[256]);
+        if (!last) { // 000 and the padding are zero bits already; LEN = 0, NLEN = FFFF
+            const uint32_t i = (body_end + s.lit_len[256] + 3 + 7) / 8 + 2;
+            atomicOr(&s.big.out[i >> 2], 0xFFu << (8 * (i & 3)));
+            atomicOr(&s.big.out[(i + 1) >> 2], 0xFFu << (8 * ((i + 1) & 3)));
+        }
+    }
+    __syncthreads();
+    for (uint32_t w = tid; w < words; w += kThreads) slot_words[w] = s.big.out[w];
+}
+
+// offsets[c] = bytes of the blocks before c; offsets[chunks] = all of them
+__global__ __launch_bounds__(1024) void deflate_scan_kernel(const ZChunkInfo *__restrict__ info, uint64_t chunks, unsigned long long *__restrict__ offsets)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (chunks + 1023) / 1024;
+    const uint64_t c_lo = tid * per < chunks ? tid * per : chunks, c_hi = c_lo + per < chunks ? c_lo + per : chunks;
+    unsigned long long sum = 0;
+    for (uint64_t c = c_lo; c < c_hi; ++c) sum += info[c].bytes;
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t step = 1; step < 1024; step <<= 1) {
+        const unsigned long long add = tid >= step ? part[tid - step] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    unsigned long long at = part[tid] - sum;
+    for (uint64_t c = c_lo; c < c_hi; ++c) { offsets[c] = at; at += info[c].bytes; }
+    if (tid == 1023) offsets[chunks] = part[1023];
+}
+
+__device__ __forceinline__ uint64_t framed_offset(uint64_t s, bool framed) { return framed ? s + 8 + 12 * (s / kIdatBytes) : s; }
+
+__global__ __launch_bounds__(256) void deflate_compact_kernel(const uint8_t *__restrict__ slots, const ZChunkInfo *__restrict__ info,
+                                                              const unsigned long long *__restrict__ offsets, uint64_t chunks, uint32_t header,
+                                                              uint32_t adler, uint8_t *__restrict__ dst, bool framed)
+{
+    const uint32_t tid = threadIdx.x;
+    const uint64_t c = blockIdx.x;
+    const uint8_t *src = slots + c * kZSlot;
+    const uint64_t start = 2 + offsets[c], end = start + info[c].bytes;
+    if (c == 0 && tid < 2) dst[framed_offset(tid, framed)] = static_cast<uint8_t>(header >> (8 * tid));
+    if (c == chunks - 1 && tid < 4) dst[framed_offset(end + tid, framed)] = static_cast<uint8_t>(adler >> (8 * (3 - tid))); // big endian
+    // stream offsets that are multiples of 4 are 4-byte aligned addresses when the destination's first one is: an aligned
+    // word never crosses an IDAT boundary (a multiple of 4) and never belongs to two blocks
+    const bool aligned = (reinterpret_cast<uintptr_t>(dst + framed_offset(0, framed)) & 3) == 0;
+    uint64_t first = (start + 3) & ~uint64_t{3}, lastw = end & ~uint64_t{3};
+    if (!aligned || first >= lastw) first = lastw = end; // bytes only
+    for (uint64_t sb = start + tid; sb < first; sb += 256) dst[framed_offset(sb, framed)] = src[sb - start];
+    for (uint64_t sw = first + 4 * static_cast<uint64_t>(tid); sw < lastw; sw += 4 * 256)
+        *reinterpret_cast<uint32_t *>(dst + framed_offset(sw, framed)) = load_u32(src + (sw - start));
+    for (uint64_t sb = lastw + tid; sb < end; sb += 256) dst[framed_offset(sb, framed)] = src[sb - start];
+}
+
+// Slicing by 4: one aligned word of the stream per step
+__global__ __launch_bounds__(64) void deflate_crc_kernel(const uint8_t *__restrict__ dst, uint64_t stream_len, uint32_t *__restrict__ crcs)
+{
+    __shared__ uint32_t table[4][256];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < 256; i += 64) {
+        uint32_t v = crc32_table_entry(i);
+        table[0][i] = v;
+        for (int k = 1; k < 4; ++k) { v = crc32_table_entry(v & 255) ^ (v >> 8); table[k][i] = v; }
+    }
+    __syncthreads();
+    const uint64_t piece = static_cast<uint64_t>(blockIdx.x) * 64 + tid;
+    const uint64_t s0 = piece * kCrcPiece;
+    if (s0 >= stream_len) return;
+    const uint64_t s1 = s0 + kCrcPiece < stream_len ? s0 + kCrcPiece : stream_len;
+    const uint8_t *p = dst + framed_offset(s0, true); // a piece lies inside one IDAT chunk
+    const uint32_t nbytes = static_cast<uint32_t>(s1 - s0);
+    uint32_t crc = 0xFFFFFFFFu, i = 0;
+    for (; i + 4 <= nbytes; i += 4) {
+        crc ^= *reinterpret_cast<const uint32_t *>(p + i);
+        crc = table[3][crc & 255] ^ table[2][(crc >> 8) & 255] ^ table[1][(crc >> 16) & 255] ^ table[0][crc >> 24];
+    }
+    for (; i < nbytes; ++i) crc = table[0][(crc ^ p[i]) & 255] ^ (crc >> 8);
+    crcs[piece] = ~crc;
+}
+} // namespace
+
+hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t *d_tok,
+                                 uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream)
+{
+    const uint64_t chunks = z_chunks(len);
+    if (chunks == 0 || chunks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(deflate_chunk_kernel, dim3(static_cast<uint32_t>(chunks)), dim3(kThreads), 0, stream,
+                       static_cast<const uint8_t *>(d_data), len, hint_bpp, hint_row, d_tok, d_slots, d_info);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(1024), 0, stream, d_info, chunks, d_offsets);
+    return hipGetLastError();
+}
+
+hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_info, const unsigned long long *d_offsets,
+                                  uint64_t chunks, uint32_t header, uint32_t adler, uint8_t *d_dst, bool framed, hipStream_t stream)
+{
+    hipLaunchKernelGGL(deflate_compact_kernel, dim3(static_cast<uint32_t>(chunks)), dim3(256), 0, stream, d_slots, d_info, d_offsets,
+                       chunks, header, adler, d_dst, framed);
+    return hipGetLastError();
+}
+
+hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_t *d_crc, hipStream_t stream)
+{
+    const uint64_t pieces = (stream_len + kCrcPiece - 1) / kCrcPiece;
+    hipLaunchKernelGGL(deflate_crc_kernel, dim3(static_cast<uint32_t>((pieces + 63) / 64)), dim3(64), 0, stream, d_dst, stream_len, d_crc);
+    return hipGetLastError();
+}
+
+} // namespace pixo_dev

@@ -1,0 +1,41 @@
+// png_deflate.hpp — host-callable launchers of the device DEFLATE (png_deflate.hip): bytes in HBM -> a zlib stream in
+// HBM, optionally laid out as the bodies of 256 KiB IDAT chunks with room for their frames, and the CRC-32 of its pieces.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+#include "png_deflate_math.h"
+
+namespace pixo_dev {
+
+constexpr uint32_t kZChunk = 65535;       // input bytes per DEFLATE block: a stored block's LEN is 16 bits
+constexpr uint32_t kZSlot = 65552;        // bytes of a block's slot (chunk + 5 for the stored form, rounded up to 16)
+constexpr uint32_t kZTokStride = 65536;   // u32 tokens per chunk in the token scratch
+constexpr uint32_t kIdatBytes = 256 * 1024; // src/png/mod.rs:621
+constexpr uint32_t kCrcPiece = 4096;      // bytes of the stream one CRC value covers (divides kIdatBytes)
+
+struct ZChunkInfo {
+    uint32_t bytes; // of the block in its slot, the trailing empty stored block included
+    uint32_t mode;  // 0 stored, 1 fixed, 2 dynamic
+    unsigned long long sum_a, sum_b; // Adler-32 partial sums of the chunk: sum of bytes, sum of (n - i) * byte_i
+};
+
+inline uint64_t z_chunks(uint64_t len) { return (len + kZChunk - 1) / kZChunk; }
+// Where byte s of the zlib stream lies in a destination: framed = the body of IDAT chunk s / 256 KiB, each chunk
+// preceded by 8 bytes (length, type) and followed by 4 (CRC).
+inline uint64_t z_framed_size(uint64_t stream_len) { return stream_len + 12 * ((stream_len + kIdatBytes - 1) / kIdatBytes); }
+
+// One workgroup per chunk: match finding, greedy parse, Huffman codes, the smallest of stored / fixed / dynamic into the
+// chunk's slot; then the exclusive scan of the block lengths.  d_tok: z_chunks * kZTokStride u32; d_slots: z_chunks *
+// kZSlot bytes; d_info: z_chunks entries; d_offsets: z_chunks + 1 u64 (the last: the sum of all block bytes).
+// hint_bpp / hint_row: distances tried at every position besides 1 and the hash table's (0 or out of range: not tried).
+hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t *d_tok,
+                                 uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream);
+// The 2 header bytes, the blocks at their final offsets and the 4 checksum bytes into d_dst.
+hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_info, const unsigned long long *d_offsets,
+                                  uint64_t chunks, uint32_t header, uint32_t adler, uint8_t *d_dst, bool framed, hipStream_t stream);
+// zlib.crc32 of every kCrcPiece bytes of a framed stream of stream_len bytes (d_dst + 8 is 4-byte aligned).
+hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_t *d_crc, hipStream_t stream);
+
+} // namespace pixo_dev

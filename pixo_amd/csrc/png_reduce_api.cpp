@@ -249,6 +249,13 @@ int prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, v
 }
 } // namespace
 
+int pixo_capi::png_check_options(const pixo_png_options *o, size_t *in_bytes) { return check_options(o, in_bytes); }
+int pixo_capi::png_prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, void *d_out, pixo_png_layout *layout,
+                                     size_t *out_len, uint32_t *adler)
+{
+    return prepare_on_device(c, d_px, o, d_out, layout, out_len, adler);
+}
+
 extern "C" {
 
 void pixo_hip_png_options_from_preset(pixo_png_options *out, uint32_t width, uint32_t height, uint8_t preset)

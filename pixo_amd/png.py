@@ -1,6 +1,6 @@
-"""PNG row filters + Adler-32 on the MI355X: the bytes the reference's
-`apply_filters` (src/png/filter.rs:51-206) hands to its DEFLATE, and the zlib wrapper's checksum
-of them.  Mirrors `pixo::png::FilterStrategy` (src/png/mod.rs:345-364).  No CPU fallback."""
+"""PNG on the MI355X: row filters + Adler-32, the reductions in front of them, and whole files —
+`encode` compresses the prepared stream on the device and returns a finished PNG.  Mirrors
+`pixo::png` (src/png/mod.rs).  No CPU fallback."""
 import ctypes as C
 import enum
 
@@ -86,8 +86,8 @@ def adler32_from_row_sums(row_sums, width, height, bytes_per_pixel):
 # ---- the prepared stream: reductions + filters (src/png/mod.rs:513-568) -----------------------------------------------
 
 class PngOptions:
-    """The fields of `pixo::png::PngOptions` (src/png/mod.rs:41-100) that shape the bytes handed to DEFLATE, plus the
-    ones the presets set for the caller's DEFLATE and chunk writing (carried, not used here).  No quantisation."""
+    """The fields of `pixo::png::PngOptions` (src/png/mod.rs:41-100).  `compression_level` selects the zlib header's
+    FLEVEL; the device DEFLATE has one effort, so `optimal_compression` compresses the same way.  No quantisation."""
 
     def __init__(self, width=0, height=0, color_type=ColorType.Rgba, compression_level=2,
                  filter_strategy=FilterStrategy.ADAPTIVE_FAST, optimize_alpha=False, reduce_color_type=False,
@@ -220,8 +220,8 @@ def _chunk(kind, body):
 
 
 def ihdr_plte_trns(layout, width, height):
-    """The IHDR, PLTE and tRNS chunks the reference writes for this layout (src/png/mod.rs:526-547), so that a caller
-    can assemble a file around its own DEFLATE of the prepared stream."""
+    """The IHDR, PLTE and tRNS chunks the reference writes for this layout (src/png/mod.rs:526-547): what `encode` puts
+    in front of its IDAT chunks, for callers that assemble a file around a prepared stream themselves."""
     import struct
     out = _chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, layout.bit_depth, layout.color_type_byte, 0, 0, 0))
     if layout.palette:
@@ -229,3 +229,64 @@ def ihdr_plte_trns(layout, width, height):
         if layout.has_trns:
             out += _chunk(b"tRNS", bytes(p[3] for p in layout.palette))
     return out
+
+
+# ---- whole files: DEFLATE, CRC-32 and chunk writing on the device -----------------------------------------------------
+
+def _take(L, p, n):
+    try:
+        return _lib.file_bytes(L, p, n.value)
+    finally:
+        L.pixo_hip_free(p)
+
+
+def stored_bound(n):
+    """Bytes that always hold the zlib stream of n bytes."""
+    return n + 5 * ((n + 65534) // 65535) + 6
+
+
+def zlib_compress(data, level=6, bpp=0, row=0):
+    """Host bytes -> zlib stream (bytes), compressed on the device.  level: header bits only; bpp / row: distances the
+    match search tries besides 1 and its hash table's (0: none)."""
+    L = _lib.load()
+    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    rc = L.pixo_hip_zlib_compress(a.ctypes.data if a.size else None, a.size, level, bpp, row, C.byref(p), C.byref(n))
+    if rc:
+        _raise(rc)
+    return _take(L, p, n)
+
+
+def zlib_compress_device(d_data, length, d_out, capacity, level=6, bpp=0, row=0):
+    """Device bytes -> zlib stream in d_out (capacity >= stored_bound(length)); returns the stream's length."""
+    L = _lib.load()
+
+    def ptr(x):
+        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+    n = C.c_size_t()
+    rc = L.pixo_hip_zlib_compress_device(ptr(d_data), length, level, bpp, row, ptr(d_out), capacity, C.byref(n))
+    if rc:
+        _raise(rc)
+    return n.value
+
+
+def encode(data, options):
+    """Host pixels -> a finished PNG file (bytes): `pixo::png::encode_with_options`."""
+    L = _lib.load()
+    px = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    o, p, n = options.to_c(), C.POINTER(C.c_uint8)(), C.c_size_t()
+    rc = L.pixo_hip_png_encode(px.ctypes.data, px.size, C.byref(o), C.byref(p), C.byref(n))
+    if rc:
+        _raise(rc)
+    return _take(L, p, n)
+
+
+def encode_device(d_pixels, options):
+    """Device pixels (torch tensor / raw pointer) -> a finished PNG file on the host (bytes)."""
+    L = _lib.load()
+    o, p, n = options.to_c(), C.POINTER(C.c_uint8)(), C.c_size_t()
+    rc = L.pixo_hip_png_encode_device(d_pixels.data_ptr() if hasattr(d_pixels, "data_ptr") else int(d_pixels), C.byref(o), C.byref(p), C.byref(n))
+    if rc:
+        _raise(rc)
+    return _take(L, p, n)
