@@ -6,6 +6,8 @@ points fails loudly.
 import ctypes as C
 import os
 
+from .error import from_status
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIXO_HIP_LIB lets kernel A/B experiments (tools/ab_build.sh) point at another build of the
 # same C ABI; the default is the in-tree library.
@@ -216,3 +218,22 @@ def file_bytes(L, ptr, n: int) -> bytes:
     b = _bytes_new(None, n)
     L.pixo_hip_copy_file(C.cast(C.c_char_p(b), C.c_void_p), ptr, n)
     return b
+
+
+def ptr(x):
+    """A device address: that of a torch tensor, or the raw pointer itself."""
+    return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+
+
+def check(rc):
+    """A status other than PIXO_OK raises the error it stands for (error.py), with the library's message."""
+    if rc:
+        raise from_status(rc, load().pixo_hip_last_error().decode())
+
+
+def take(L, p, n) -> bytes:
+    """The block of n (a c_size_t) bytes the library handed over, as bytes; the block goes back to the library."""
+    try:
+        return file_bytes(L, p, n.value)
+    finally:
+        L.pixo_hip_free(p)

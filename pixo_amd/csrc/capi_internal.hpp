@@ -12,8 +12,8 @@
 //   jpeg_api.cpp     the extern "C" JPEG entry points: check arguments -> context -> encode_file -> deliver
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
 //   png_api.cpp      the extern "C" PNG row-filter entry points
-//   png_reduce_api.cpp  the extern "C" PNG prepare entry points: reductions (png_reduce.hip), palette ordering, then the filter
-//   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, device DEFLATE (png_deflate.hip), chunks
+//   png_reduce_api.cpp  the extern "C" PNG prepare entry points: png_check_options, reductions (png_reduce.hip), palette ordering, the filter
+//   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, a ZlibJob (png_deflate.hip), file head and IDAT frames
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,6 +68,17 @@ inline int too_small(size_t needed, size_t *out_len = nullptr)
 {
     if (out_len) *out_len = needed;
     return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(needed) + " bytes");
+}
+// ... and of these three (src/error.rs:50-91), for the entries whose checks are not pixo_host::validate's
+inline std::string dims(uint32_t w, uint32_t h) { return std::to_string(w) + "x" + std::to_string(h); }
+inline int bad_dimensions(uint32_t w, uint32_t h) { return fail(PIXO_ERR_INVALID_DIMENSIONS, "Invalid image dimensions: " + dims(w, h)); }
+inline int too_large(uint32_t w, uint32_t h, uint32_t max)
+{
+    return fail(PIXO_ERR_IMAGE_TOO_LARGE, "Image " + dims(w, h) + " exceeds maximum dimension " + std::to_string(max));
+}
+inline int bad_length(size_t expected, size_t got)
+{
+    return fail(PIXO_ERR_INVALID_DATA_LENGTH, "Invalid pixel data length: expected " + std::to_string(expected) + " bytes, got " + std::to_string(got));
 }
 
 // ---- debug switches: ONE environment variable, read once ------------------------------------------------------------
@@ -262,7 +273,15 @@ inline unsigned long long *mailbox(Context &c) { return reinterpret_cast<unsigne
 // ---- small facts of an image, said once ----------------------------------------------------------------------------------
 inline pixo_host::Geometry geometry_of(const pixo_jpeg_options &o) { return pixo_host::geometry(o.width, o.height, o.color_type, o.subsampling); }
 inline size_t pixel_bytes(const pixo_jpeg_options &o, const pixo_host::Geometry &g) { return static_cast<size_t>(o.width) * o.height * (g.gray ? 1 : 3); }
-inline int reserve_pixels(Context &c, size_t n) { return c.d_px.reserve((n + 15) & ~size_t{15}); } // (the kernels load 16 bytes at a time)
+inline uint32_t bytes_per_pixel(uint8_t color_type) { return color_type + 1u; } // PIXO_GRAY 1, PIXO_GRAY_ALPHA 2, PIXO_RGB 3, PIXO_RGBA 4
+inline int reserve16(Buf &b, size_t n) { return b.reserve((n + 15) & ~size_t{15}); } // what kernels read as pixels: they load 16 bytes at a time
+inline int reserve_pixels(Context &c, size_t n) { return reserve16(c.d_px, n); }
+inline int upload(Context &c, Buf &b, const void *host, size_t n) // host bytes into `b`, on the context's stream
+{
+    if (const int rc = reserve16(b, n)) return rc;
+    HIP_TRY(hipMemcpyAsync(b.p, host, n, hipMemcpyHostToDevice, c.stream));
+    return PIXO_OK;
+}
 // The planes of a tuple that lies in one buffer: Y of every image of the batch, then Cb, then Cr (64 coefficients per block).
 template <class T> struct PlanesOf { T *y, *cb, *cr; };
 using Planes = PlanesOf<int16_t>;
@@ -293,6 +312,11 @@ Context &thread_context();
 #define PIXO_ON_DEVICE_OF(ctx)                                    \
     ::pixo_capi::DeviceScope device_scope_((ctx).device);         \
     if (device_scope_.err != hipSuccess) return ::pixo_capi::hip_fail(device_scope_.err, "hipSetDevice")
+// The preamble of an entry point that works on the thread's own context: declares it as `c`, ready, its device current
+#define PIXO_THREAD_CONTEXT(c)                                \
+    ::pixo_capi::Context &c = ::pixo_capi::thread_context();  \
+    if (const int ensure_rc_ = c.ensure()) return ensure_rc_; \
+    PIXO_ON_DEVICE_OF(c)
 
 // Device-pointer entry points run on the context's own stream.  What the caller enqueued before the call — on the stream
 // it named with pixo_hip_set_producer_stream, by default the NULL stream — is ordered in front of it with an event.
@@ -523,16 +547,21 @@ int encode_batch_blocks(Context &c, const void *d_pixels, const pixo_jpeg_option
                         uint8_t **files, size_t *lens);
 
 // ---- PNG (png_api.cpp) -----------------------------------------------------------------------------------------------
+// Argument checks shared by the PNG entries; resolves the strategy the reference would run.  `area` is the image's PIXEL count:
+// rows of packed samples are filtered as width = row bytes, bpp = 1, but the small-image rule counts pixels.
 int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast);
 // filter kernel + checksum on the context's stream; returns after the checksum has been combined
 int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t bpp, int run, bool sequential_fast,
                          void *d_out, uint32_t *adler);
 
 // ---- PNG prepare (png_reduce_api.cpp) --------------------------------------------------------------------------------
-int png_check_options(const pixo_png_options *o, size_t *in_bytes); // the checks of pixo_hip_png_prepare that need no data
+// The prepare and whole-file entries' checks in the reference's order; with_data: the host pixels' length too (one that passes IS the input size)
+int png_check_options(const pixo_png_options *o, bool with_data = false, size_t data_len = 0);
+// How the filters saw the rows (packed and palette rows: as one-byte pixels): what a match search behind them is told.
+struct PngFilterView { uint32_t bpp, row; }; // bytes per filter pixel, bytes per filtered row
 // d_px: width * height * bpp bytes on the context's device; reductions + filters, the stream is left in d_out
 int png_prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, void *d_out, pixo_png_layout *layout, size_t *out_len,
-                          uint32_t *adler);
+                          uint32_t *adler, PngFilterView *view = nullptr);
 
 // ---- preset 2 (progressive.cpp) -----------------------------------------------------------------------------------
 int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,

@@ -8,12 +8,9 @@
 using namespace pixo_capi;
 
 namespace pixo_capi {
-// Argument checks shared by the PNG entries; resolves the strategy the reference would run.  `area` is the image's
-// PIXEL count: rows of packed samples are filtered as width = row bytes, bpp = 1, but the small-image rule counts pixels.
 int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast)
 {
-    if (width == 0 || height == 0)
-        return fail(PIXO_ERR_INVALID_DIMENSIONS, "Invalid image dimensions: " + std::to_string(width) + "x" + std::to_string(height));
+    if (width == 0 || height == 0) return bad_dimensions(width, height);
     if (!(bpp == 1 || bpp == 2 || bpp == 3 || bpp == 4 || bpp == 6 || bpp == 8))
         return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format");
     if (strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
@@ -28,11 +25,6 @@ int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8
 } // namespace pixo_capi
 
 namespace {
-int png_plan(uint32_t width, uint32_t height, uint32_t bpp, uint8_t strategy, uint32_t flags, int *run, bool *sequential_fast)
-{
-    return pixo_capi::png_plan(width, height, static_cast<uint64_t>(width) * height, bpp, strategy, flags, run, sequential_fast);
-}
-
 // zlib Adler-32 of the filtered stream from the per-row sums (A = byte sum, B = sum of
 // (row_len - i) * byte_i): s2 += row_len * s1 + B, s1 += A  (mod 65521)
 uint32_t combine_adler(const unsigned long long *sums, uint32_t height, uint64_t out_row_bytes)
@@ -139,26 +131,21 @@ int pixo_hip_png_filter(const uint8_t *data, size_t data_len, uint32_t width, ui
     CallerStorageScope storage(out && out_capacity);
     int run = 0;
     bool seq = false;
-    int rc = png_plan(width, height, bytes_per_pixel, strategy, flags, &run, &seq);
+    int rc = png_plan(width, height, static_cast<uint64_t>(width) * height, bytes_per_pixel, strategy, flags, &run, &seq);
     if (rc) return rc;
     const size_t in_bytes = static_cast<size_t>(width) * height * bytes_per_pixel;
     const size_t out_bytes = static_cast<size_t>(height) * (static_cast<size_t>(width) * bytes_per_pixel + 1);
-    if (data_len != in_bytes)
-        return fail(PIXO_ERR_INVALID_DATA_LENGTH, "Invalid pixel data length: expected " + std::to_string(in_bytes) +
-                                                      " bytes, got " + std::to_string(data_len));
-    if (out_capacity < out_bytes)
-        return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(out_bytes) + " bytes");
+    if (data_len != in_bytes) return bad_length(in_bytes, data_len);
+    if (out_capacity < out_bytes) return too_small(out_bytes);
     if (!data || !out || !adler32) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument");
-    Context &c = thread_context();
-    if ((rc = c.ensure())) return rc;
-    PIXO_ON_DEVICE_OF(c);
-    if ((rc = c.p_in.reserve((in_bytes + 15) & ~size_t{15})) || (rc = c.p_out.reserve(out_bytes))) return rc;
+    PIXO_THREAD_CONTEXT(c);
     if (out_bytes < (size_t{4} << 20)) { // small: one copy each way
-        HIP_TRY(hipMemcpyAsync(c.p_in.p, data, in_bytes, hipMemcpyHostToDevice, c.stream));
+        if ((rc = upload(c, c.p_in, data, in_bytes)) || (rc = c.p_out.reserve(out_bytes))) return rc;
         if ((rc = png_filter_on_device(c, c.p_in.p, width, height, bytes_per_pixel, run, seq, c.p_out.p, adler32))) return rc;
         HIP_TRY(hipMemcpy(out, c.p_out.p, out_bytes, hipMemcpyDeviceToHost));
         return PIXO_OK;
     }
+    if ((rc = reserve16(c.p_in, in_bytes)) || (rc = c.p_out.reserve(out_bytes))) return rc;
     return png_filter_in_bands(c, data, width, height, bytes_per_pixel, run, seq, out, adler32);
 }
 
@@ -168,7 +155,7 @@ int pixo_hip_png_filter_async(const void *d_data, uint32_t width, uint32_t heigh
 {
     int run = 0;
     bool seq = false;
-    int rc = png_plan(width, height, bytes_per_pixel, strategy, flags, &run, &seq);
+    int rc = png_plan(width, height, static_cast<uint64_t>(width) * height, bytes_per_pixel, strategy, flags, &run, &seq);
     if (rc) return rc;
     HIP_TRY(pixo_dev::launch_png_filter(d_data, width, height, bytes_per_pixel, run, seq, d_out,
                                         static_cast<unsigned long long *>(d_row_sums), static_cast<int *>(d_scratch),
@@ -189,7 +176,7 @@ int pixo_hip_png_filter_device(const void *d_data, uint32_t width, uint32_t heig
 {
     int run = 0;
     bool seq = false;
-    int rc = png_plan(width, height, bytes_per_pixel, strategy, flags, &run, &seq);
+    int rc = png_plan(width, height, static_cast<uint64_t>(width) * height, bytes_per_pixel, strategy, flags, &run, &seq);
     if (rc) return rc;
     PIXO_REQUIRE(d_data);
     PIXO_REQUIRE(d_out);

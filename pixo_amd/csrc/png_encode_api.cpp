@@ -37,44 +37,43 @@ uint32_t adler_of_chunks(const pixo_dev::ZChunkInfo *info, uint64_t chunks, uint
     return static_cast<uint32_t>((s2 << 16) | s1);
 }
 
-// len > 0 bytes at d_data on the context's device -> their zlib stream at d_dst (null: c.z_stream).  framed: laid out as
-// IDAT bodies (pixo_dev::z_framed_size) in c.z_stream, and the pieces' CRC-32 are on their way into c.h_zinfo when this
-// returns (same stream: the caller synchronises).  adler_known: the checksum when the caller has it already.
-int zlib_on_device(Context &c, const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row, const uint32_t *adler_known,
-                   uint8_t *d_dst, bool framed, uint64_t *stream_len)
+// One run of the device DEFLATE: len > 0 bytes at d_data on the context's device -> their zlib stream.
+struct ZlibJob {
+    const void *d_data;
+    size_t len;
+    uint8_t level;                   // the header's FLEVEL only
+    uint32_t hint_bpp, hint_row;     // distances the match search tries besides 1 and its hash table's (0: none)
+    void *d_dst = nullptr;           // where the stream goes (null: c.z_stream)
+    const uint32_t *adler = nullptr; // the checksum when the caller has it already (only the total comes down then)
+    bool framed = false;             // as IDAT bodies (z_framed_size) in c.z_stream; their pieces' CRC-32 are then on the way into c.h_zinfo
+};
+int zlib_on_device(Context &c, const ZlibJob &j, uint64_t *stream_len)
 {
-    const uint64_t chunks = pixo_dev::z_chunks(len), bound = stored_bound(len);
+    const uint64_t chunks = pixo_dev::z_chunks(j.len), bound = stored_bound(j.len);
     const size_t info_bytes = chunks * sizeof(pixo_dev::ZChunkInfo), off_bytes = (chunks + 1) * sizeof(unsigned long long);
-    const size_t crc_bytes = framed ? static_cast<size_t>((bound + pixo_dev::kCrcPiece - 1) / pixo_dev::kCrcPiece) * 4 : 0;
+    const size_t crc_bytes = j.framed ? static_cast<size_t>((bound + pixo_dev::kCrcPiece - 1) / pixo_dev::kCrcPiece) * 4 : 0;
     int rc;
     if ((rc = c.z_tok.reserve(chunks * pixo_dev::kZTokStride * sizeof(uint32_t))) || (rc = c.z_slots.reserve(chunks * pixo_dev::kZSlot)) ||
         (rc = c.z_info.reserve(info_bytes + off_bytes)) || (rc = c.h_zinfo.reserve(std::max(info_bytes + off_bytes, crc_bytes))))
         return rc;
-    if (!d_dst && (rc = c.z_stream.reserve(pixo_dev::z_framed_size(bound) + 16))) return rc;
-    if (framed && (rc = c.z_crc.reserve(crc_bytes))) return rc;
+    if (!j.d_dst && (rc = c.z_stream.reserve(pixo_dev::z_framed_size(bound) + 16))) return rc;
+    if (j.framed && (rc = c.z_crc.reserve(crc_bytes))) return rc;
     auto *d_info = c.z_info.as<pixo_dev::ZChunkInfo>();
     auto *d_off = reinterpret_cast<unsigned long long *>(c.z_info.as<uint8_t>() + info_bytes);
-    HIP_TRY(pixo_dev::launch_deflate_chunks(d_data, len, hint_bpp, hint_row, c.z_tok.as<uint32_t>(), c.z_slots.as<uint8_t>(), d_info, d_off, c.stream));
-    uint32_t adler = 0;
-    unsigned long long blocks = 0;
-    if (adler_known) { // only the total comes down
-        HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, d_off + chunks, sizeof(blocks), hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(hipStreamSynchronize(c.stream));
-        blocks = *c.h_zinfo.as<unsigned long long>();
-        adler = *adler_known;
-    } else {
-        HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, d_info, info_bytes + off_bytes, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(hipStreamSynchronize(c.stream));
-        blocks = reinterpret_cast<const unsigned long long *>(c.h_zinfo.as<uint8_t>() + info_bytes)[chunks];
-        adler = adler_of_chunks(c.h_zinfo.as<pixo_dev::ZChunkInfo>(), chunks, len);
-    }
+    HIP_TRY(pixo_dev::launch_deflate_chunks(j.d_data, j.len, j.hint_bpp, j.hint_row, c.z_tok.as<uint32_t>(), c.z_slots.as<uint8_t>(), d_info, d_off, c.stream));
+    // The blocks' total, the last word of z_info, comes down: alone when the checksum is known, behind all the checksum is made from otherwise
+    const size_t all = info_bytes + off_bytes, down = j.adler ? sizeof(unsigned long long) : all;
+    HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, c.z_info.as<uint8_t>() + all - down, down, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    const unsigned long long blocks = *reinterpret_cast<const unsigned long long *>(c.h_zinfo.as<uint8_t>() + down - sizeof(unsigned long long));
+    const uint32_t adler = j.adler ? *j.adler : adler_of_chunks(c.h_zinfo.as<pixo_dev::ZChunkInfo>(), chunks, j.len);
     *stream_len = 2 + blocks + 4;
     if (*stream_len > bound) return fail(PIXO_ERR_COMPRESSION, "Compression error: device DEFLATE exceeded the stored bound");
     uint8_t head[2];
-    zlib_header(level, head);
-    uint8_t *dst = d_dst ? d_dst : c.z_stream.as<uint8_t>();
-    HIP_TRY(pixo_dev::launch_deflate_compact(c.z_slots.as<uint8_t>(), d_info, d_off, chunks, head[0] | (uint32_t{head[1]} << 8), adler, dst, framed, c.stream));
-    if (framed) {
+    zlib_header(j.level, head);
+    uint8_t *dst = j.d_dst ? static_cast<uint8_t *>(j.d_dst) : c.z_stream.as<uint8_t>();
+    HIP_TRY(pixo_dev::launch_deflate_compact(c.z_slots.as<uint8_t>(), d_info, d_off, chunks, head[0] | (uint32_t{head[1]} << 8), adler, dst, j.framed, c.stream));
+    if (j.framed) {
         HIP_TRY(pixo_dev::launch_deflate_crc(dst, *stream_len, c.z_crc.as<uint32_t>(), c.stream));
         const size_t pieces = static_cast<size_t>((*stream_len + pixo_dev::kCrcPiece - 1) / pixo_dev::kCrcPiece);
         HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, c.z_crc.p, pieces * 4, hipMemcpyDeviceToHost, c.stream));
@@ -89,26 +88,14 @@ void empty_zlib(uint8_t level, uint8_t out[8]) // deflate.rs: header, an empty f
     out[4] = 0; out[5] = 0; out[6] = 0; out[7] = 1;
 }
 
-// Pixels on the context's device -> the finished file in a block the caller owns.
-int png_file(Context &c, const void *d_px, const pixo_png_options &o, uint8_t **out, size_t *out_len)
+// Everything in front of the first IDAT chunk: signature, IHDR, and for a palette image PLTE and tRNS (mod.rs:513-547).
+// strip_metadata: there is no ancillary chunk to strip (tRNS is kept by the reference as well).
+std::vector<uint8_t> png_head(uint32_t width, uint32_t height, const pixo_png_layout &layout)
 {
-    const uint32_t in_bpp = o.color_type == PIXO_GRAY ? 1u : o.color_type == PIXO_GRAY_ALPHA ? 2u : o.color_type == PIXO_RGB ? 3u : 4u;
-    int rc = c.p_out.reserve(static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) * in_bpp + 1));
-    if (rc) return rc;
-    pixo_png_layout layout;
-    size_t len = 0;
-    uint32_t adler = 0;
-    if ((rc = png_prepare_on_device(c, d_px, o, c.p_out.p, &layout, &len, &adler))) return rc;
-    const bool bytewise = layout.bit_depth < 8 || layout.color_type_byte == 3;
-    uint64_t stream_len = 0;
-    if ((rc = zlib_on_device(c, c.p_out.p, len, o.compression_level, bytewise ? 1u : layout.bytes_per_pixel, layout.row_bytes + 1, &adler, nullptr,
-                             true, &stream_len)))
-        return rc;
-
     std::vector<uint8_t> head{0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     uint8_t ihdr[13] = {0};
-    put_be32(ihdr, o.width);
-    put_be32(ihdr + 4, o.height);
+    put_be32(ihdr, width);
+    put_be32(ihdr + 4, height);
     ihdr[8] = layout.bit_depth;
     ihdr[9] = layout.color_type_byte;
     append_chunk(head, "IHDR", ihdr, 13);
@@ -121,21 +108,19 @@ int png_file(Context &c, const void *d_px, const pixo_png_options &o, uint8_t **
         append_chunk(head, "PLTE", plte, 3 * layout.palette_len);
         if (layout.has_trns) append_chunk(head, "tRNS", trns, layout.palette_len);
     }
-    const uint64_t idats = (stream_len + pixo_dev::kIdatBytes - 1) / pixo_dev::kIdatBytes;
-    const size_t framed = static_cast<size_t>(pixo_dev::z_framed_size(stream_len)), file_len = head.size() + framed + 12;
-    if ((rc = c.h_file.reserve(file_len))) return rc;
-    uint8_t *file = c.h_file.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(file + head.size(), c.z_stream.p, framed, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream)); // (the pieces' CRC-32 have arrived as well)
-    std::memcpy(file, head.data(), head.size());
+    return head;
+}
 
-    // every IDAT chunk: length, type, [body], the CRC of type + body joined from the pieces' values (x^n mod P)
-    const uint32_t *piece_crc = c.h_zinfo.as<uint32_t>();
+// The frames around a stream that lies at `idat` as IDAT bodies (pixo_dev::z_framed_size), and IEND behind the last.  Every
+// chunk: length, type, [body], the CRC of type + body joined from its 4 KiB pieces' values (x^n mod P).
+void frame_idats(uint8_t *idat, uint64_t stream_len, const uint32_t *piece_crc)
+{
     const uint32_t type_crc = crc32_bytes(0, reinterpret_cast<const uint8_t *>("IDAT"), 4), shift_piece = crc32_x_pow(8ull * pixo_dev::kCrcPiece);
     const uint32_t pieces_per_idat = pixo_dev::kIdatBytes / pixo_dev::kCrcPiece;
+    const uint64_t idats = (stream_len + pixo_dev::kIdatBytes - 1) / pixo_dev::kIdatBytes;
     for (uint64_t k = 0; k < idats; ++k) {
         const uint64_t s0 = k * pixo_dev::kIdatBytes, body = std::min<uint64_t>(pixo_dev::kIdatBytes, stream_len - s0);
-        uint8_t *frame = file + head.size() + s0 + 12 * k;
+        uint8_t *frame = idat + s0 + 12 * k;
         put_be32(frame, static_cast<uint32_t>(body));
         std::memcpy(frame + 4, "IDAT", 4);
         uint32_t crc = type_crc;
@@ -147,8 +132,33 @@ int png_file(Context &c, const void *d_px, const pixo_png_options &o, uint8_t **
     }
     std::vector<uint8_t> iend;
     append_chunk(iend, "IEND", nullptr, 0);
-    std::memcpy(file + head.size() + framed, iend.data(), 12);
-    // strip_metadata: the file has no ancillary chunk to strip (tRNS is kept by the reference as well)
+    std::memcpy(idat + pixo_dev::z_framed_size(stream_len), iend.data(), 12);
+}
+
+// Pixels on the context's device -> the finished file in a block the caller owns: prepare, DEFLATE, copy, frame, deliver.
+int png_file(Context &c, const void *d_px, const pixo_png_options &o, uint8_t **out, size_t *out_len)
+{
+    int rc = c.p_out.reserve(static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) * bytes_per_pixel(o.color_type) + 1));
+    if (rc) return rc;
+    pixo_png_layout layout;
+    size_t len = 0;
+    uint32_t adler = 0;
+    PngFilterView view;
+    if ((rc = png_prepare_on_device(c, d_px, o, c.p_out.p, &layout, &len, &adler, &view))) return rc;
+    ZlibJob job{c.p_out.p, len, o.compression_level, view.bpp, view.row};
+    job.adler = &adler;
+    job.framed = true;
+    uint64_t stream_len = 0;
+    if ((rc = zlib_on_device(c, job, &stream_len))) return rc;
+
+    const std::vector<uint8_t> head = png_head(o.width, o.height, layout);
+    const size_t framed = static_cast<size_t>(pixo_dev::z_framed_size(stream_len)), file_len = head.size() + framed + 12;
+    if ((rc = c.h_file.reserve(file_len))) return rc;
+    uint8_t *file = c.h_file.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(file + head.size(), c.z_stream.p, framed, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream)); // (the pieces' CRC-32 have arrived as well)
+    std::memcpy(file, head.data(), head.size());
+    frame_idats(file + head.size(), stream_len, c.h_zinfo.as<uint32_t>());
     return deliver(file, file_len, out, out_len);
 }
 
@@ -166,15 +176,11 @@ int pixo_hip_zlib_compress(const uint8_t *data, size_t len, uint8_t level, uint3
         return deliver(e, 8, out, out_len);
     }
     PIXO_REQUIRE(data);
-    Context &c = thread_context();
-    int rc = c.ensure();
+    PIXO_THREAD_CONTEXT(c);
+    int rc = upload(c, c.p_in, data, len);
     if (rc) return rc;
-    PIXO_ON_DEVICE_OF(c);
-    if ((rc = c.p_in.reserve((len + 15) & ~size_t{15}))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.p_in.p, data, len, hipMemcpyHostToDevice, c.stream));
     uint64_t n = 0;
-    if ((rc = zlib_on_device(c, c.p_in.p, len, level, hint_bpp, hint_row, nullptr, nullptr, false, &n))) return rc;
-    if ((rc = c.h_file.reserve(n))) return rc;
+    if ((rc = zlib_on_device(c, ZlibJob{c.p_in.p, len, level, hint_bpp, hint_row}, &n)) || (rc = c.h_file.reserve(n))) return rc;
     HIP_TRY(hipMemcpyAsync(c.h_file.p, c.z_stream.p, n, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     return deliver(c.h_file.as<uint8_t>(), n, out, out_len);
@@ -200,7 +206,7 @@ int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level,
     }
     PIXO_REQUIRE(d_data);
     uint64_t n = 0;
-    if ((rc = zlib_on_device(*c, d_data, len, level, hint_bpp, hint_row, nullptr, static_cast<uint8_t *>(d_out), false, &n))) return rc;
+    if ((rc = zlib_on_device(*c, ZlibJob{d_data, len, level, hint_bpp, hint_row, d_out}, &n))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     *out_len = n;
     return PIXO_OK;
@@ -208,29 +214,20 @@ int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level,
 
 int pixo_hip_png_encode(const uint8_t *data, size_t data_len, const pixo_png_options *options, uint8_t **out, size_t *out_len)
 {
-    size_t in_bytes = 0;
-    int rc = png_check_options(options, &in_bytes);
+    int rc = png_check_options(options, true, data_len);
     if (rc) return rc;
-    if (data_len != in_bytes)
-        return fail(PIXO_ERR_INVALID_DATA_LENGTH, "Invalid pixel data length: expected " + std::to_string(in_bytes) + " bytes, got " + std::to_string(data_len));
-    if (options->filter_strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
     PIXO_REQUIRE(data);
     PIXO_REQUIRE(out);
     PIXO_REQUIRE(out_len);
-    Context &c = thread_context();
-    if ((rc = c.ensure())) return rc;
-    PIXO_ON_DEVICE_OF(c);
-    if ((rc = c.p_in.reserve((in_bytes + 15) & ~size_t{15}))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.p_in.p, data, in_bytes, hipMemcpyHostToDevice, c.stream));
+    PIXO_THREAD_CONTEXT(c);
+    if ((rc = upload(c, c.p_in, data, data_len))) return rc;
     return png_file(c, c.p_in.p, *options, out, out_len);
 }
 
 int pixo_hip_png_encode_device(const void *d_pixels, const pixo_png_options *options, uint8_t **out, size_t *out_len)
 {
-    size_t in_bytes = 0;
-    int rc = png_check_options(options, &in_bytes);
+    int rc = png_check_options(options);
     if (rc) return rc;
-    if (options->filter_strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
     PIXO_REQUIRE(d_pixels);
     PIXO_REQUIRE(out);
     PIXO_REQUIRE(out_len);

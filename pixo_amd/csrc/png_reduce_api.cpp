@@ -22,7 +22,6 @@ struct PngWork {
     uint32_t pairs[256 * 256];  // [a * n + b], a < b: adjacent pixel pairs with the indices {a, b}
 };
 
-uint32_t bytes_per_pixel(uint8_t ct) { return ct == PIXO_GRAY ? 1u : ct == PIXO_GRAY_ALPHA ? 2u : ct == PIXO_RGB ? 3u : 4u; }
 uint8_t png_color_type_byte(uint8_t ct) { return ct == PIXO_GRAY ? 0 : ct == PIXO_GRAY_ALPHA ? 4 : ct == PIXO_RGB ? 2 : 6; }
 
 // optimize_palette_order's three steps on the statistics instead of the index image.  order[k] = sorted-key index of
@@ -91,19 +90,6 @@ void palette_order(const uint32_t *counts, const uint32_t *matrix, uint32_t n, s
     order = remap;
 }
 
-int check_options(const pixo_png_options *o, size_t *in_bytes)
-{
-    PIXO_REQUIRE(o);
-    if (o->width == 0 || o->height == 0)
-        return fail(PIXO_ERR_INVALID_DIMENSIONS, "Invalid image dimensions: " + std::to_string(o->width) + "x" + std::to_string(o->height));
-    if (o->width > kPngMaxDimension || o->height > kPngMaxDimension)
-        return fail(PIXO_ERR_IMAGE_TOO_LARGE, "Image " + std::to_string(o->width) + "x" + std::to_string(o->height) +
-                                                  " exceeds maximum dimension " + std::to_string(kPngMaxDimension));
-    if (o->color_type > PIXO_RGBA) return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format");
-    *in_bytes = static_cast<size_t>(o->width) * o->height * bytes_per_pixel(o->color_type);
-    return PIXO_OK;
-}
-
 // The palette case: index image, statistics, order on the host, packed rows.  an: the analysis on the host.
 int reduce_to_palette(Context &c, const void *d_px, const pixo_png_options &o, PngWork *host, PngWork *dev, pixo_png_layout *layout,
                       ConvertArgs *conv)
@@ -121,8 +107,7 @@ int reduce_to_palette(Context &c, const void *d_px, const pixo_png_options &o, P
         host->lookup[s] = kSlotUsed | (static_cast<uint64_t>(i) << 32) | keys[i];
     }
     const uint64_t pixels = static_cast<uint64_t>(o.width) * o.height;
-    int rc = c.q_index.reserve((pixels + 15) & ~uint64_t{15});
-    if (rc) return rc;
+    if (const int rc = reserve16(c.q_index, pixels)) return rc;
     HIP_TRY(hipMemcpyAsync(dev->lookup, host->lookup, sizeof(host->lookup), hipMemcpyHostToDevice, c.stream));
     HIP_TRY(pixo_dev::launch_png_index(d_px, pixels, bytes_per_pixel(o.color_type), dev->lookup, c.q_index.as<uint8_t>(), dev->hist, c.stream));
     std::vector<uint32_t> order(n);
@@ -157,9 +142,22 @@ int reduce_to_palette(Context &c, const void *d_px, const pixo_png_options &o, P
     return PIXO_OK;
 }
 
-// d_px: width * height * bpp bytes on the context's device; the stream is left in d_out.
-int prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, void *d_out, pixo_png_layout *layout, size_t *out_len,
-                      uint32_t *adler)
+} // namespace
+
+int pixo_capi::png_check_options(const pixo_png_options *o, bool with_data, size_t data_len)
+{
+    PIXO_REQUIRE(o);
+    if (o->width == 0 || o->height == 0) return bad_dimensions(o->width, o->height);
+    if (o->width > kPngMaxDimension || o->height > kPngMaxDimension) return too_large(o->width, o->height, kPngMaxDimension);
+    if (o->color_type > PIXO_RGBA) return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format");
+    const size_t want = static_cast<size_t>(o->width) * o->height * bytes_per_pixel(o->color_type);
+    if (with_data && data_len != want) return bad_length(want, data_len);
+    if (o->filter_strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
+    return PIXO_OK;
+}
+
+int pixo_capi::png_prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, void *d_out, pixo_png_layout *layout,
+                                     size_t *out_len, uint32_t *adler, PngFilterView *view)
 {
     const uint8_t ct = o.color_type;
     const uint32_t spp = bytes_per_pixel(ct);
@@ -232,6 +230,7 @@ int prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, v
     // The filters see packed and palette rows as row_bytes one-byte pixels; the small-image rule counts PIXELS (filter.rs:77).
     const bool bytewise = layout->bit_depth < 8 || layout->color_type_byte == 3;
     const uint32_t f_width = bytewise ? layout->row_bytes : o.width, f_bpp = bytewise ? 1u : layout->bytes_per_pixel;
+    if (view) *view = {f_bpp, layout->row_bytes + 1};
     int run = 0;
     bool seq = false;
     int rc = png_plan(f_width, o.height, pixels, f_bpp, o.filter_strategy, o.flags, &run, &seq);
@@ -241,19 +240,11 @@ int prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, v
         conv.width = o.width;
         conv.height = o.height;
         conv.row_bytes = layout->row_bytes;
-        if ((rc = c.q_rows.reserve((static_cast<size_t>(layout->row_bytes) * o.height + 15) & ~size_t{15}))) return rc;
+        if ((rc = reserve16(c.q_rows, static_cast<size_t>(layout->row_bytes) * o.height))) return rc;
         HIP_TRY(pixo_dev::launch_png_convert(conv, conv_src, dev->map, c.q_rows.p, c.stream));
         rows = c.q_rows.p;
     }
     return png_filter_on_device(c, rows, f_width, o.height, f_bpp, run, seq, d_out, adler);
-}
-} // namespace
-
-int pixo_capi::png_check_options(const pixo_png_options *o, size_t *in_bytes) { return check_options(o, in_bytes); }
-int pixo_capi::png_prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, void *d_out, pixo_png_layout *layout,
-                                     size_t *out_len, uint32_t *adler)
-{
-    return prepare_on_device(c, d_px, o, d_out, layout, out_len, adler);
 }
 
 extern "C" {
@@ -276,24 +267,17 @@ int pixo_hip_png_prepare(const uint8_t *data, size_t data_len, const pixo_png_op
                          size_t *out_len, pixo_png_layout *layout, uint32_t *adler32)
 {
     CallerStorageScope storage(out && out_capacity);
-    size_t in_bytes = 0;
-    int rc = check_options(options, &in_bytes);
+    int rc = png_check_options(options, true, data_len);
     if (rc) return rc;
-    if (data_len != in_bytes)
-        return fail(PIXO_ERR_INVALID_DATA_LENGTH, "Invalid pixel data length: expected " + std::to_string(in_bytes) + " bytes, got " + std::to_string(data_len));
-    if (options->filter_strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
     PIXO_REQUIRE(data);
     PIXO_REQUIRE(out_len);
     PIXO_REQUIRE(layout);
     PIXO_REQUIRE(adler32);
     const size_t full = static_cast<size_t>(options->height) * (static_cast<size_t>(options->width) * bytes_per_pixel(options->color_type) + 1);
-    Context &c = thread_context();
-    if ((rc = c.ensure())) return rc;
-    PIXO_ON_DEVICE_OF(c);
-    if ((rc = c.p_in.reserve((in_bytes + 15) & ~size_t{15})) || (rc = c.p_out.reserve(full))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.p_in.p, data, in_bytes, hipMemcpyHostToDevice, c.stream));
-    if ((rc = prepare_on_device(c, c.p_in.p, *options, c.p_out.p, layout, out_len, adler32))) return rc;
-    if (!out || out_capacity < *out_len) return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(*out_len) + " bytes");
+    PIXO_THREAD_CONTEXT(c);
+    if ((rc = upload(c, c.p_in, data, data_len)) || (rc = c.p_out.reserve(full))) return rc;
+    if ((rc = png_prepare_on_device(c, c.p_in.p, *options, c.p_out.p, layout, out_len, adler32))) return rc;
+    if (!out || out_capacity < *out_len) return too_small(*out_len);
     HIP_TRY(hipMemcpy(out, c.p_out.p, *out_len, hipMemcpyDeviceToHost));
     return PIXO_OK;
 }
@@ -301,10 +285,8 @@ int pixo_hip_png_prepare(const uint8_t *data, size_t data_len, const pixo_png_op
 int pixo_hip_png_prepare_device(const void *d_pixels, const pixo_png_options *options, void *d_out, pixo_png_layout *layout,
                                 size_t *out_len, uint32_t *adler32)
 {
-    size_t in_bytes = 0;
-    int rc = check_options(options, &in_bytes);
+    int rc = png_check_options(options);
     if (rc) return rc;
-    if (options->filter_strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
     PIXO_REQUIRE(d_pixels);
     PIXO_REQUIRE(d_out);
     PIXO_REQUIRE(layout);
@@ -312,7 +294,7 @@ int pixo_hip_png_prepare_device(const void *d_pixels, const pixo_png_options *op
     PIXO_REQUIRE(adler32);
     Context *c = nullptr;
     if ((rc = context_on_current_device(&c))) return rc;
-    return prepare_on_device(*c, d_pixels, *options, d_out, layout, out_len, adler32);
+    return png_prepare_on_device(*c, d_pixels, *options, d_out, layout, out_len, adler32);
 }
 
 int pixo_hip_png_palette_order(const uint32_t *counts, const uint32_t *matrix, uint32_t n, uint8_t *order_out)

@@ -12,23 +12,16 @@ using namespace pixo_capi;
 
 namespace {
 
-uint32_t bytes_per_pixel(uint8_t color_type) { return color_type + 1u; } // Gray 1, GrayAlpha 2, Rgb 3, Rgba 4
-
-std::string dims(uint32_t w, uint32_t h) { return std::to_string(w) + "x" + std::to_string(h); }
-
 // resize_impl's checks (src/resize.rs:213-262), before any work.  data_len is checked unless `device` (a device pointer
 // carries no length).
 int resize_plan(const pixo_resize_options *o, bool device, size_t data_len, size_t *in_bytes, size_t *out_bytes)
 {
     PIXO_REQUIRE(o);
-    if (o->src_width == 0 || o->src_height == 0)
-        return fail(PIXO_ERR_INVALID_DIMENSIONS, "Invalid image dimensions: " + dims(o->src_width, o->src_height));
-    if (o->dst_width == 0 || o->dst_height == 0)
-        return fail(PIXO_ERR_INVALID_DIMENSIONS, "Invalid image dimensions: " + dims(o->dst_width, o->dst_height));
+    if (o->src_width == 0 || o->src_height == 0) return bad_dimensions(o->src_width, o->src_height);
+    if (o->dst_width == 0 || o->dst_height == 0) return bad_dimensions(o->dst_width, o->dst_height);
     const uint32_t M = RZ_MAX_DIMENSION;
     if (o->src_width > M || o->src_height > M || o->dst_width > M || o->dst_height > M)
-        return fail(PIXO_ERR_IMAGE_TOO_LARGE, "Image " + dims(std::max(o->src_width, o->dst_width), std::max(o->src_height, o->dst_height)) +
-                                                  " exceeds maximum dimension " + std::to_string(M));
+        return too_large(std::max(o->src_width, o->dst_width), std::max(o->src_height, o->dst_height), M);
     // (the C struct can carry codes the reference's enums cannot: answered like the flat entry's own checks)
     if (o->color_type > PIXO_RGBA)
         return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid color type: " + std::to_string(o->color_type) +
@@ -39,10 +32,7 @@ int resize_plan(const pixo_resize_options *o, bool device, size_t data_len, size
     const size_t bpp = bytes_per_pixel(o->color_type);
     *in_bytes = static_cast<size_t>(o->src_width) * o->src_height * bpp; // (2^24 * 2^24 * 4 fits 64 bits)
     *out_bytes = static_cast<size_t>(o->dst_width) * o->dst_height * bpp;
-    if (!device && data_len != *in_bytes)
-        return fail(PIXO_ERR_INVALID_DATA_LENGTH, "Invalid pixel data length: expected " + std::to_string(*in_bytes) + " bytes, got " +
-                                                      std::to_string(data_len));
-    return PIXO_OK;
+    return !device && data_len != *in_bytes ? bad_length(*in_bytes, data_len) : PIXO_OK;
 }
 
 // ---- contribution tables ----------------------------------------------------------------------------------------------------
@@ -141,12 +131,9 @@ int resize_on_device(Context &c, const uint8_t *d_src, const pixo_resize_options
 // Host pixels -> host storage of the caller's (out_bytes checked by the caller)
 int resize_host(const uint8_t *data, size_t in_bytes, const pixo_resize_options &o, uint8_t *out, size_t out_bytes)
 {
-    Context &c = thread_context();
+    PIXO_THREAD_CONTEXT(c);
     int rc;
-    if ((rc = c.ensure())) return rc;
-    PIXO_ON_DEVICE_OF(c);
-    if ((rc = c.r_in.reserve((in_bytes + 15) & ~size_t{15})) || (rc = c.r_out.reserve((out_bytes + 15) & ~size_t{15}))) return rc;
-    HIP_TRY(hipMemcpyAsync(c.r_in.p, data, in_bytes, hipMemcpyHostToDevice, c.stream));
+    if ((rc = upload(c, c.r_in, data, in_bytes)) || (rc = reserve16(c.r_out, out_bytes))) return rc;
     if ((rc = resize_on_device(c, c.r_in.as<uint8_t>(), o, c.r_out.as<uint8_t>(), c.stream))) return rc;
     HIP_TRY(hipMemcpyAsync(out, c.r_out.p, out_bytes, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
@@ -166,7 +153,7 @@ int pixo_hip_resize_into(uint8_t *output, size_t capacity, const uint8_t *data, 
     int rc = resize_plan(options, false, data_len, &in_bytes, &out_bytes);
     if (rc) return rc;
     *out_len = out_bytes;
-    if (capacity < out_bytes) return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(out_bytes) + " bytes");
+    if (capacity < out_bytes) return too_small(out_bytes);
     PIXO_REQUIRE(data);
     PIXO_REQUIRE(output);
     return resize_host(data, in_bytes, *options, output, out_bytes);
@@ -222,9 +209,8 @@ int pixo_hip_resize_contributions(uint32_t src, uint32_t dst, uint32_t *starts, 
                                   size_t *total)
 {
     PIXO_REQUIRE(total);
-    if (src == 0 || dst == 0) return fail(PIXO_ERR_INVALID_DIMENSIONS, "Invalid image dimensions: " + dims(src, dst));
-    if (src > RZ_MAX_DIMENSION || dst > RZ_MAX_DIMENSION)
-        return fail(PIXO_ERR_IMAGE_TOO_LARGE, "Image " + dims(src, dst) + " exceeds maximum dimension " + std::to_string(RZ_MAX_DIMENSION));
+    if (src == 0 || dst == 0) return bad_dimensions(src, dst);
+    if (src > RZ_MAX_DIMENSION || dst > RZ_MAX_DIMENSION) return too_large(src, dst, RZ_MAX_DIMENSION);
     *total = axis_weights(src, dst);
     if (capacity < *total) return fail(PIXO_ERR_BUFFER_TOO_SMALL, "output buffer too small: need " + std::to_string(*total) + " weights");
     PIXO_REQUIRE(starts);

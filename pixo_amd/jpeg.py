@@ -131,10 +131,6 @@ class JpegOptionsBuilder:
         return dataclasses.replace(self._o)
 
 
-def _raise(status):
-    raise from_status(status, _lib.load().pixo_hip_last_error().decode())
-
-
 def _as_u8(data):
     a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
     if a.dtype != np.uint8:
@@ -149,12 +145,8 @@ def encode(data, options: JpegOptions) -> bytes:
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     oc = options._c()
     rc = L.pixo_hip_jpeg_encode(px.ctypes.data, px.size, C.byref(oc), C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def encode_into(output: bytearray, data, options: JpegOptions) -> None:
@@ -180,7 +172,7 @@ def encode_into_buffer(buffer: np.ndarray, data, options: JpegOptions) -> int:
     rc = L.pixo_hip_jpeg_encode_into(buffer.ctypes.data, buffer.size, px.ctypes.data, px.size, C.byref(oc), C.byref(n))
     if rc:
         try:
-            _raise(rc)
+            _lib.check(rc)
         except error.BufferTooSmall as e:
             e.needed = n.value
             raise
@@ -195,12 +187,8 @@ def encode_jpeg(data, width, height, color_type, quality, preset, subsampling_42
     rc = L.pixo_hip_encode_jpeg(px.ctypes.data, px.size, width, height, color_type & 0xFF,
                                 quality & 0xFF, preset & 0xFF, int(bool(subsampling_420)),
                                 C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def coefficient_geometry(width, height, color_type=ColorType.Rgb, subsampling=Subsampling.S420):
@@ -208,8 +196,7 @@ def coefficient_geometry(width, height, color_type=ColorType.Rgb, subsampling=Su
     L = _lib.load()
     yb, cb = C.c_size_t(), C.c_size_t()
     rc = L.pixo_hip_coeff_geometry(width, height, int(color_type), int(subsampling), C.byref(yb), C.byref(cb))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return yb.value, cb.value
 
 
@@ -229,8 +216,7 @@ def coefficients(data, options: JpegOptions):
     rc = L.pixo_hip_jpeg_coeffs(px.ctypes.data, options.width, options.height, int(options.color_type),
                                 int(options.subsampling), int(options.quality), y.ctypes.data, yb,
                                 cb.ctypes.data, cr.ctypes.data, cbn)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return y, cb, cr
 
 
@@ -240,16 +226,10 @@ def coefficients_device(d_pixels, width, height, color_type, subsampling, qualit
     `.data_ptr()` (torch tensors); `stream` is a hipStream_t handle (int), 0 = default."""
     L = _lib.load()
 
-    def ptr(x):
-        if x is None:
-            return None
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-
-    rc = L.pixo_hip_jpeg_coeffs_device(ptr(d_pixels), width, height, int(color_type), int(subsampling),
-                                       int(quality), batch, ptr(d_y), ptr(d_cb), ptr(d_cr),
+    rc = L.pixo_hip_jpeg_coeffs_device(_dev_ptr(d_pixels), width, height, int(color_type), int(subsampling),
+                                       int(quality), batch, _dev_ptr(d_y), _dev_ptr(d_cb), _dev_ptr(d_cr),
                                        C.c_void_p(stream) if stream else None)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
 
 
 def coefficients_integer(data, options: JpegOptions):
@@ -267,8 +247,7 @@ def coefficients_integer(data, options: JpegOptions):
     rc = L.pixo_hip_jpeg_coeffs_integer(px.ctypes.data, options.width, options.height, int(options.color_type),
                                         int(options.subsampling), int(options.quality), y.ctypes.data, yb,
                                         cb.ctypes.data, cr.ctypes.data, cbn)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return y, cb, cr
 
 
@@ -283,18 +262,12 @@ def entropy_encode(y, cb, cr, options: JpegOptions) -> bytes:
     oc = options._c()
     rc = L.pixo_hip_jpeg_entropy_encode(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, C.byref(oc),
                                         C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def _dev_ptr(x):
-    if x is None:
-        return None
-    return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+    return None if x is None else _lib.ptr(x)
 
 
 def entropy_encode_device(d_y, d_cb, d_cr, options: JpegOptions) -> bytes:
@@ -306,12 +279,8 @@ def entropy_encode_device(d_y, d_cb, d_cr, options: JpegOptions) -> bytes:
     oc = options._c()
     rc = L.pixo_hip_jpeg_entropy_encode_device(_dev_ptr(d_y), _dev_ptr(d_cb), _dev_ptr(d_cr), C.byref(oc),
                                                C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def encode_device(d_pixels, options: JpegOptions) -> bytes:
@@ -320,12 +289,8 @@ def encode_device(d_pixels, options: JpegOptions) -> bytes:
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     oc = options._c()
     rc = L.pixo_hip_jpeg_encode_device(_dev_ptr(d_pixels), C.byref(oc), C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def encode_device_into(buffer, d_pixels, options: JpegOptions) -> int:
@@ -343,7 +308,7 @@ def encode_device_into(buffer, d_pixels, options: JpegOptions) -> int:
     rc = L.pixo_hip_jpeg_encode_device_into(_dev_ptr(d_pixels), C.byref(oc), ptr, cap, C.byref(n))
     if rc:
         try:
-            _raise(rc)
+            _lib.check(rc)
         except error.BufferTooSmall as e:
             e.needed = n.value
             raise
@@ -358,8 +323,7 @@ def encode_batch_device(d_pixels, options: JpegOptions, batch: int):
     lens = (C.c_size_t * batch)()
     oc = options._c()
     rc = L.pixo_hip_jpeg_encode_batch_device(_dev_ptr(d_pixels), C.byref(oc), batch, files, lens)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     out = []
     for i in range(batch):
         out.append(_lib.file_bytes(L, files[i], lens[i]))
@@ -375,8 +339,7 @@ def encode_batch_device_raw(d_pixels, options: JpegOptions, batch: int):
     lens = (C.c_size_t * batch)()
     oc = options._c()
     rc = L.pixo_hip_jpeg_encode_batch_device(_dev_ptr(d_pixels), C.byref(oc), batch, files, lens)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return files, lens
 
 
@@ -405,12 +368,11 @@ def encode_batch_device_into(arena, d_pixels, options: JpegOptions, batch: int):
         return list(offsets), list(lens)
     if rc == -9:  # (offsets / lens were filled in: the size a second attempt needs)
         try:
-            _raise(rc)
+            _lib.check(rc)
         except error.BufferTooSmall as e:
             e.needed = int(offsets[batch - 1] + lens[batch - 1]) if batch else 0
             raise
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return list(offsets), list(lens)
 
 
@@ -452,40 +414,32 @@ def encode_batch_multi(arena, pixels, options: JpegOptions, batch: int, devices)
         return list(offsets), list(lens)
     if rc == -9:
         try:
-            _raise(rc)
+            _lib.check(rc)
         except error.BufferTooSmall as e:
             e.needed = int(offsets[batch - 1] + lens[batch - 1]) if batch else 0
             raise
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return list(offsets), list(lens)
 
 
 def debug_stream_copy(d_in, d_out, nbytes, stream=0):
     """MEASUREMENT only (`pixo_hip_debug_stream_copy`): a plain device copy in the coefficient kernel's launch shape."""
-    def ptr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-    rc = _lib.load().pixo_hip_debug_stream_copy(ptr(d_in), ptr(d_out), int(nbytes), C.c_void_p(stream) if stream else None)
-    if rc:
-        _raise(rc)
+    rc = _lib.load().pixo_hip_debug_stream_copy(_lib.ptr(d_in), _lib.ptr(d_out), int(nbytes), C.c_void_p(stream) if stream else None)
+    _lib.check(rc)
 
 
 def debug_engine_clock(stream=0) -> float:
     """MEASUREMENT only (`pixo_hip_debug_engine_clock`): the engine clock in Hz under full vector load."""
     hz = C.c_double(0.0)
     rc = _lib.load().pixo_hip_debug_engine_clock(C.c_void_p(stream) if stream else None, C.byref(hz))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return hz.value
 
 
 def debug_stream_io(d_in, d_out, workgroups, loads, stores, stream=0):
     """MEASUREMENT only (`pixo_hip_debug_stream_io`): `workgroups` x 192 threads, each `loads` 16-byte loads then `stores` 16-byte stores."""
-    def ptr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-    rc = _lib.load().pixo_hip_debug_stream_io(ptr(d_in), ptr(d_out), int(workgroups), int(loads), int(stores), C.c_void_p(stream) if stream else None)
-    if rc:
-        _raise(rc)
+    rc = _lib.load().pixo_hip_debug_stream_io(_lib.ptr(d_in), _lib.ptr(d_out), int(workgroups), int(loads), int(stores), C.c_void_p(stream) if stream else None)
+    _lib.check(rc)
 
 
 def debug_scan_device_async(d_pixels, options: JpegOptions, stream=0, batch=1) -> int:
@@ -499,8 +453,7 @@ def debug_scan_device_async(d_pixels, options: JpegOptions, stream=0, batch=1) -
         rc = L.pixo_hip_debug_scan_device_async(_dev_ptr(d_pixels), C.byref(oc), C.c_void_p(stream) if stream else None, C.byref(form))
     else:
         rc = L.pixo_hip_debug_scan_device_async_batch(_dev_ptr(d_pixels), C.byref(oc), int(batch), C.c_void_p(stream) if stream else None, C.byref(form))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return form.value
 
 
@@ -551,20 +504,12 @@ def band(width, height, color_type, subsampling, parts, index):
     yo, yb, co, cbk = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
     rc = L.pixo_hip_band(width, height, int(color_type), int(subsampling), parts, index,
                          C.byref(r0), C.byref(r1), C.byref(yo), C.byref(yb), C.byref(co), C.byref(cbk))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return dict(row_begin=r0.value, row_end=r1.value, y_offset=yo.value, y_blocks=yb.value,
                 c_offset=co.value, c_blocks=cbk.value)
 
 
 COUNT_WORDS = 536  # PIXO_HIP_COUNT_WORDS: [class][12 DC categories + 256 AC run/size symbols]
-
-
-def _take(L, out, n):
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
 
 
 def _dc3(values):
@@ -590,8 +535,7 @@ class BandEncoder:
         self._h = C.c_void_p()
         oc = options._c()
         rc = L.pixo_hip_band_encoder_create(C.byref(oc), parts, index, device, C.byref(self._h))
-        if rc:
-            _raise(rc)
+        _lib.check(rc)
         r0, r1 = C.c_uint32(), C.c_uint32()
         L.pixo_hip_band_encoder_rows(self._h, C.byref(r0), C.byref(r1))
         self.row_begin, self.row_end = r0.value, r1.value
@@ -614,15 +558,13 @@ class BandEncoder:
         else:
             px = _as_u8(band_pixels)
             rc = self._L.pixo_hip_band_encoder_coeffs(self._h, px.ctypes.data if px.size else None, 0, last)
-        if rc:
-            _raise(rc)
+        _lib.check(rc)
         return [int(v) for v in last]
 
     def count(self, prev_dc):
         out = np.zeros(COUNT_WORDS, np.uint64)
         rc = self._L.pixo_hip_band_encoder_count(self._h, _dc3(prev_dc), out.ctypes.data_as(C.POINTER(C.c_uint64)))
-        if rc:
-            _raise(rc)
+        _lib.check(rc)
         return out
 
     def lengths(self, prev_dc, total_counts=None) -> int:
@@ -631,8 +573,7 @@ class BandEncoder:
         rc = self._L.pixo_hip_band_encoder_lengths(self._h, _dc3(prev_dc),
                                                    tc.ctypes.data_as(C.POINTER(C.c_uint64)) if tc is not None else None,
                                                    C.byref(bits))
-        if rc:
-            _raise(rc)
+        _lib.check(rc)
         return bits.value
 
     def pack_device(self, bit_offset: int):
@@ -641,8 +582,7 @@ class BandEncoder:
         hdr = (C.c_uint8 * 16)()
         n = C.c_size_t()
         rc = self._L.pixo_hip_band_encoder_pack_device(self._h, bit_offset, hdr, None, C.byref(n))
-        if rc:
-            _raise(rc)
+        _lib.check(rc)
         return bytes(hdr), n.value
 
     def copy_body(self, dst) -> None:
@@ -655,15 +595,13 @@ class BandEncoder:
         else:
             ptr = int(dst)
         rc = self._L.pixo_hip_band_encoder_copy_body(self._h, ptr)
-        if rc:
-            _raise(rc)
+        _lib.check(rc)
 
     def pack(self, bit_offset: int) -> bytes:
         out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
         rc = self._L.pixo_hip_band_encoder_pack(self._h, bit_offset, C.byref(out), C.byref(n))
-        if rc:
-            _raise(rc)
-        return _take(self._L, out, n)
+        _lib.check(rc)
+        return _lib.take(self._L, out, n)
 
 
 def _band_host_args(y, cb, cr):
@@ -681,8 +619,7 @@ def band_count_host(y, cb, cr, options: JpegOptions, band_rows: int, prev_dc):
     oc = options._c()
     rc = L.pixo_hip_jpeg_band_count_host(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, C.byref(oc), band_rows, _dc3(prev_dc),
                                          out.ctypes.data_as(C.POINTER(C.c_uint64)))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return out
 
 
@@ -694,8 +631,7 @@ def band_bits_host(y, cb, cr, options: JpegOptions, band_rows: int, prev_dc, tot
     oc = options._c()
     rc = L.pixo_hip_jpeg_band_bits_host(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, C.byref(oc), band_rows, _dc3(prev_dc),
                                         tc.ctypes.data_as(C.POINTER(C.c_uint64)) if tc is not None else None, C.byref(bits))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return bits.value
 
 
@@ -708,9 +644,8 @@ def band_piece_host(y, cb, cr, options: JpegOptions, band_rows: int, prev_dc, bi
     rc = L.pixo_hip_jpeg_band_piece_host(y.ctypes.data, cb.ctypes.data, cr.ctypes.data, C.byref(oc), band_rows, _dc3(prev_dc),
                                          tc.ctypes.data_as(C.POINTER(C.c_uint64)) if tc is not None else None, bit_offset,
                                          C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    return _take(L, out, n)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def splice(options: JpegOptions, pieces, total_counts=None) -> bytes:
@@ -725,9 +660,8 @@ def splice(options: JpegOptions, pieces, total_counts=None) -> bytes:
     oc = options._c()
     rc = L.pixo_hip_jpeg_splice(C.byref(oc), tc.ctypes.data_as(C.POINTER(C.c_uint64)) if tc is not None else None, ptrs, lens,
                                 n_parts, C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    return _take(L, out, n)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def splice_layout(options: JpegOptions, headers, total_counts=None):
@@ -741,8 +675,7 @@ def splice_layout(options: JpegOptions, headers, total_counts=None):
     oc = options._c()
     rc = L.pixo_hip_jpeg_splice_layout(C.byref(oc), tc.ctypes.data_as(C.POINTER(C.c_uint64)) if tc is not None else None,
                                        blob.ctypes.data, n_parts, C.byref(flen), offs)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return flen.value, list(offs)
 
 
@@ -756,8 +689,7 @@ def splice_finish(options: JpegOptions, headers, file, file_len, total_counts=No
     oc = options._c()
     rc = L.pixo_hip_jpeg_splice_finish(C.byref(oc), tc.ctypes.data_as(C.POINTER(C.c_uint64)) if tc is not None else None,
                                        blob.ctypes.data, len(headers), ptr, file_len)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
 
 
 def encode_multi(data, options: JpegOptions, devices) -> bytes:
@@ -769,9 +701,8 @@ def encode_multi(data, options: JpegOptions, devices) -> bytes:
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     oc = options._c()
     rc = L.pixo_hip_jpeg_encode_multi(px.ctypes.data, px.size, C.byref(oc), devs, len(devices), C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    return _take(L, out, n)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def set_producer_stream(stream) -> None:
@@ -813,8 +744,7 @@ def device_count() -> int:
 
 def set_device(device: int) -> None:
     rc = _lib.load().pixo_hip_set_device(device)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
 
 
 def trim() -> None:

@@ -8,11 +8,6 @@ import numpy as np
 
 from . import _lib
 from .color import ColorType
-from .error import from_status
-
-
-def _raise(status):
-    raise from_status(status, _lib.load().pixo_hip_last_error().decode())
 
 
 class FilterStrategy(enum.IntEnum):
@@ -42,8 +37,7 @@ def apply_filters(data, width, height, bytes_per_pixel, strategy=FilterStrategy.
     ad = C.c_uint32()
     rc = L.pixo_hip_png_filter(px.ctypes.data, px.size, width, height, bytes_per_pixel, int(strategy), flags,
                                out.ctypes.data, out.size, C.byref(ad))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return out, ad.value
 
 
@@ -51,13 +45,9 @@ def apply_filters_device(d_data, width, height, bytes_per_pixel, d_out, strategy
     """Device pixels (torch tensor / raw pointer) -> filtered stream written to d_out; returns adler32."""
     L = _lib.load()
 
-    def ptr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-
     ad = C.c_uint32()
-    rc = L.pixo_hip_png_filter_device(ptr(d_data), width, height, bytes_per_pixel, int(strategy), flags, ptr(d_out), C.byref(ad))
-    if rc:
-        _raise(rc)
+    rc = L.pixo_hip_png_filter_device(_lib.ptr(d_data), width, height, bytes_per_pixel, int(strategy), flags, _lib.ptr(d_out), C.byref(ad))
+    _lib.check(rc)
     return ad.value
 
 
@@ -67,13 +57,9 @@ def apply_filters_async(d_data, width, height, bytes_per_pixel, d_out, d_row_sum
     them with `adler32_from_row_sums`."""
     L = _lib.load()
 
-    def ptr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-
-    rc = L.pixo_hip_png_filter_async(ptr(d_data), width, height, bytes_per_pixel, int(strategy), flags, ptr(d_out),
-                                     ptr(d_row_sums), ptr(d_scratch), C.c_void_p(stream) if stream else None)
-    if rc:
-        _raise(rc)
+    rc = L.pixo_hip_png_filter_async(_lib.ptr(d_data), width, height, bytes_per_pixel, int(strategy), flags, _lib.ptr(d_out),
+                                     _lib.ptr(d_row_sums), _lib.ptr(d_scratch), C.c_void_p(stream) if stream else None)
+    _lib.check(rc)
 
 
 def adler32_from_row_sums(row_sums, width, height, bytes_per_pixel):
@@ -179,8 +165,7 @@ def prepare(data, options):
     out = np.empty(max(options.full_size(), 1), np.uint8)
     o, lay, n, ad = options.to_c(), _lib.PngLayoutC(), C.c_size_t(), C.c_uint32()
     rc = L.pixo_hip_png_prepare(px.ctypes.data, px.size, C.byref(o), out.ctypes.data, out.size, C.byref(n), C.byref(lay), C.byref(ad))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return out[:n.value], PngLayout(lay), ad.value
 
 
@@ -189,13 +174,9 @@ def prepare_device(d_pixels, options, d_out):
     returns (stream length, PngLayout, adler32)."""
     L = _lib.load()
 
-    def ptr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-
     o, lay, n, ad = options.to_c(), _lib.PngLayoutC(), C.c_size_t(), C.c_uint32()
-    rc = L.pixo_hip_png_prepare_device(ptr(d_pixels), C.byref(o), ptr(d_out), C.byref(lay), C.byref(n), C.byref(ad))
-    if rc:
-        _raise(rc)
+    rc = L.pixo_hip_png_prepare_device(_lib.ptr(d_pixels), C.byref(o), _lib.ptr(d_out), C.byref(lay), C.byref(n), C.byref(ad))
+    _lib.check(rc)
     return n.value, PngLayout(lay), ad.value
 
 
@@ -208,8 +189,7 @@ def palette_order(counts, matrix):
     assert m.shape == (n, n)
     order = np.empty(n, np.uint8)
     rc = L.pixo_hip_png_palette_order(cnt.ctypes.data, m.ctypes.data, n, order.ctypes.data)
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return order
 
 
@@ -233,13 +213,6 @@ def ihdr_plte_trns(layout, width, height):
 
 # ---- whole files: DEFLATE, CRC-32 and chunk writing on the device -----------------------------------------------------
 
-def _take(L, p, n):
-    try:
-        return _lib.file_bytes(L, p, n.value)
-    finally:
-        L.pixo_hip_free(p)
-
-
 def stored_bound(n):
     """Bytes that always hold the zlib stream of n bytes."""
     return n + 5 * ((n + 65534) // 65535) + 6
@@ -252,22 +225,17 @@ def zlib_compress(data, level=6, bpp=0, row=0):
     a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     rc = L.pixo_hip_zlib_compress(a.ctypes.data if a.size else None, a.size, level, bpp, row, C.byref(p), C.byref(n))
-    if rc:
-        _raise(rc)
-    return _take(L, p, n)
+    _lib.check(rc)
+    return _lib.take(L, p, n)
 
 
 def zlib_compress_device(d_data, length, d_out, capacity, level=6, bpp=0, row=0):
     """Device bytes -> zlib stream in d_out (capacity >= stored_bound(length)); returns the stream's length."""
     L = _lib.load()
 
-    def ptr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-
     n = C.c_size_t()
-    rc = L.pixo_hip_zlib_compress_device(ptr(d_data), length, level, bpp, row, ptr(d_out), capacity, C.byref(n))
-    if rc:
-        _raise(rc)
+    rc = L.pixo_hip_zlib_compress_device(_lib.ptr(d_data), length, level, bpp, row, _lib.ptr(d_out), capacity, C.byref(n))
+    _lib.check(rc)
     return n.value
 
 
@@ -277,16 +245,14 @@ def encode(data, options):
     px = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     o, p, n = options.to_c(), C.POINTER(C.c_uint8)(), C.c_size_t()
     rc = L.pixo_hip_png_encode(px.ctypes.data, px.size, C.byref(o), C.byref(p), C.byref(n))
-    if rc:
-        _raise(rc)
-    return _take(L, p, n)
+    _lib.check(rc)
+    return _lib.take(L, p, n)
 
 
 def encode_device(d_pixels, options):
     """Device pixels (torch tensor / raw pointer) -> a finished PNG file on the host (bytes)."""
     L = _lib.load()
     o, p, n = options.to_c(), C.POINTER(C.c_uint8)(), C.c_size_t()
-    rc = L.pixo_hip_png_encode_device(d_pixels.data_ptr() if hasattr(d_pixels, "data_ptr") else int(d_pixels), C.byref(o), C.byref(p), C.byref(n))
-    if rc:
-        _raise(rc)
-    return _take(L, p, n)
+    rc = L.pixo_hip_png_encode_device(_lib.ptr(d_pixels), C.byref(o), C.byref(p), C.byref(n))
+    _lib.check(rc)
+    return _lib.take(L, p, n)

@@ -68,10 +68,6 @@ class ResizeOptionsBuilder:
         return ResizeOptions(**self._v)
 
 
-def _raise(status):
-    raise from_status(status, _lib.load().pixo_hip_last_error().decode())
-
-
 def _flat(data) -> np.ndarray:
     return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
 
@@ -83,12 +79,8 @@ def resize(data, options: ResizeOptions) -> bytes:
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     o = options._c()
     rc = L.pixo_hip_resize(px.ctypes.data, px.size, C.byref(o), C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def resize_into(output, data, options: ResizeOptions) -> int:
@@ -112,13 +104,9 @@ def resize_device(d_src, options: ResizeOptions, d_dst, stream=0) -> None:
     producer stream (jpeg.set_producer_stream)."""
     L = _lib.load()
 
-    def ptr(x):
-        return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
-
     o = options._c()
-    rc = L.pixo_hip_resize_device(ptr(d_src), C.byref(o), ptr(d_dst), C.c_void_p(stream) if stream else None)
-    if rc:
-        _raise(rc)
+    rc = L.pixo_hip_resize_device(_lib.ptr(d_src), C.byref(o), _lib.ptr(d_dst), C.c_void_p(stream) if stream else None)
+    _lib.check(rc)
 
 
 def resize_image(data, src_width, src_height, dst_width, dst_height, color_type: int, algorithm: int) -> bytes:
@@ -130,12 +118,8 @@ def resize_image(data, src_width, src_height, dst_width, dst_height, color_type:
         raise ValueError("color_type and algorithm are u8")
     rc = L.pixo_hip_resize_image(px.ctypes.data, px.size, src_width, src_height, dst_width, dst_height, color_type, algorithm,
                                  C.byref(out), C.byref(n))
-    if rc:
-        _raise(rc)
-    try:
-        return _lib.file_bytes(L, out, n.value)
-    finally:
-        L.pixo_hip_free(out)
+    _lib.check(rc)
+    return _lib.take(L, out, n)
 
 
 def contributions(src: int, dst: int):
@@ -144,10 +128,9 @@ def contributions(src: int, dst: int):
     total = C.c_size_t()
     rc = L.pixo_hip_resize_contributions(src, dst, None, None, None, 0, C.byref(total))
     if rc and rc != -9:
-        _raise(rc)
+        _lib.check(rc)
     starts, counts = np.empty(dst, np.uint32), np.empty(dst, np.uint32)
     weights = np.empty(max(total.value, 1), np.float32)
     rc = L.pixo_hip_resize_contributions(src, dst, starts.ctypes.data, counts.ctypes.data, weights.ctypes.data, total.value, C.byref(total))
-    if rc:
-        _raise(rc)
+    _lib.check(rc)
     return starts, counts, weights[:total.value]
