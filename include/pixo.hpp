@@ -194,7 +194,15 @@ namespace filter {
 } // namespace filter
 
 // The fields of pixo::png::PngOptions (src/png/mod.rs:41-100).  compression_level selects the zlib header's FLEVEL; the
-// device DEFLATE has one effort, so optimal_compression compresses the same way (pixo_hip.h).  No quantisation.
+// device DEFLATE has one effort, so optimal_compression compresses the same way (pixo_hip.h).
+enum class QuantizationMode : uint8_t { Off = PIXO_PNG_QUANT_OFF, Auto = PIXO_PNG_QUANT_AUTO, Force = PIXO_PNG_QUANT_FORCE };
+// pixo::png::QuantizationOptions: Off, 256 colours, no dithering by default
+struct QuantizationOptions {
+    QuantizationMode mode = QuantizationMode::Off;
+    uint16_t max_colors = 256;
+    bool dithering = false;
+    pixo_png_quantization to_c() const { return pixo_png_quantization{(uint8_t)mode, (uint8_t)dithering, max_colors}; }
+};
 struct PngOptions {
     uint32_t width = 0, height = 0;
     ColorType color_type = ColorType::Rgba;
@@ -202,6 +210,7 @@ struct PngOptions {
     FilterStrategy filter_strategy = FilterStrategy::AdaptiveFast;
     bool optimize_alpha = false, reduce_color_type = false, strip_metadata = false, reduce_palette = false, optimal_compression = false;
     uint32_t flags = 0; // PIXO_PNG_NO_RAYON
+    QuantizationOptions quantization; // travels beside pixo_png_options (pixo_png_quantization)
 
     // mod.rs:129-198
     static PngOptions from_preset(uint32_t width, uint32_t height, uint8_t preset)
@@ -219,6 +228,12 @@ struct PngOptions {
     static PngOptions fast(uint32_t w, uint32_t h) { return from_preset(w, h, 0); }
     static PngOptions balanced(uint32_t w, uint32_t h) { return from_preset(w, h, 1); }
     static PngOptions max(uint32_t w, uint32_t h) { return from_preset(w, h, 2); }
+    static PngOptions from_preset_with_lossless(uint32_t w, uint32_t h, uint8_t preset, bool lossless) // mod.rs:203-213
+    {
+        PngOptions o = from_preset(w, h, preset);
+        if (!lossless) o.quantization = QuantizationOptions{QuantizationMode::Auto, 256, true};
+        return o;
+    }
     pixo_png_options to_c() const
     {
         return pixo_png_options{width, height, (uint8_t)color_type, (uint8_t)filter_strategy, optimize_alpha, reduce_color_type,
@@ -247,16 +262,23 @@ struct Prepared {
 
 // pixo::png::encode_with_options: a finished PNG file.  The chunks around IDAT are the reference's byte for byte; the IDAT
 // body is the device DEFLATE of the prepared stream (contract: pixo_hip.h).
-[[nodiscard]] inline std::vector<uint8_t> encode(const uint8_t *data, size_t len, const PngOptions &options)
+// ... with quantisation (mod.rs:469-511): the reference's gate decides between the indexed file and the lossless one
+[[nodiscard]] inline std::vector<uint8_t> encode(const uint8_t *data, size_t len, const PngOptions &options, const QuantizationOptions &quantization)
 {
     const pixo_png_options c = options.to_c();
+    const pixo_png_quantization q = quantization.to_c();
     uint8_t *file = nullptr;
     size_t n = 0;
-    const int rc = pixo_hip_png_encode(data, len, &c, &file, &n);
+    const int rc = quantization.mode == QuantizationMode::Off ? pixo_hip_png_encode(data, len, &c, &file, &n) : pixo_hip_png_encode_lossy(data, len, &c, &q, &file, &n);
     if (rc != PIXO_OK) throw Error::from_status(rc);
     std::vector<uint8_t> out(file, file + n);
     pixo_hip_free(file);
     return out;
+}
+// ... with the options' own `quantization` (Off by default: the lossless file)
+[[nodiscard]] inline std::vector<uint8_t> encode(const uint8_t *data, size_t len, const PngOptions &options)
+{
+    return encode(data, len, options, options.quantization);
 }
 [[nodiscard]] inline std::vector<uint8_t> encode(const std::vector<uint8_t> &data, const PngOptions &options)
 {

@@ -235,7 +235,8 @@ uint32_t pixo_hip_png_adler32_from_row_sums(const uint64_t *row_sums, uint32_t w
  * 1/2/4/8 bits, RGBA -> RGB / GrayAlpha / Gray, RGB -> Gray, gray bit depth), maybe_optimize_alpha (:633-671) and
  * apply_filters_with_row_bytes — together with the layout of the IHDR / PLTE / tRNS chunks that go around them.
  * pixo_hip_png_encode (below) compresses the stream on the device and writes the file; the prepare entries are for callers
- * that want the stream itself.  Quantisation (lossy) is not part of this path. */
+ * that want the stream itself.  Quantisation (lossy) has entries of its own: pixo_hip_png_quantize and
+ * pixo_hip_png_encode_lossy, below. */
 
 /* The fields of pixo::png::PngOptions (mod.rs:64-100).  The prepare entries read the ones that shape the prepared stream.
  * pixo_hip_png_encode also reads compression_level: clamped to 1..9, it selects the FLEVEL bits of the zlib header as in the
@@ -316,6 +317,53 @@ int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level,
 int pixo_hip_png_encode(const uint8_t *data, size_t data_len, const pixo_png_options *options, uint8_t **out, size_t *out_len);
 /* The same for pixels in HBM on the current HIP device (ordered after the producer stream); the file lands on the host. */
 int pixo_hip_png_encode_device(const void *d_pixels, const pixo_png_options *options, uint8_t **out, size_t *out_len);
+
+/* ---- PNG lossy mode: palette quantisation and dithering on the device ------------------------- */
+
+/* pixo::png::QuantizationMode / QuantizationOptions (src/png/mod.rs).  The options travel in a struct of their own:
+ * pixo_png_options keeps its 20 bytes. */
+enum { PIXO_PNG_QUANT_OFF = 0, PIXO_PNG_QUANT_AUTO = 1, PIXO_PNG_QUANT_FORCE = 2 };
+typedef struct pixo_png_quantization {
+    uint8_t mode;        /* PIXO_PNG_QUANT_* */
+    uint8_t dithering;   /* Floyd-Steinberg on r, g, b (alpha is not dithered) */
+    uint16_t max_colors; /* min(max_colors, 256) everywhere; 0 behaves as 1 */
+} pixo_png_quantization;
+
+/* What encode_into does before it writes an indexed file (mod.rs:469-492): the gate — Off never, Force for RGB and RGBA, Auto
+ * also needs max_colors < sampled colours <= 32 * max_colors (should_quantize_auto, :1708-1762) — then quantize_image
+ * (:1505-1701): strided histogram, median cut, two k-means rounds, the 64^3 nearest-entry table, and one lookup per pixel or
+ * Floyd-Steinberg dithering.  Index for index and entry for entry the reference's, with one stated exception: above 8,192
+ * sampled colours the reference keeps the 8,192 most frequent by an unstable sort; here colours of equal count are kept by
+ * ascending key (r<<24 | g<<16 | b<<8 | a).
+ * *applied = 0: the gate declined and nothing else is written.  Otherwise width * height indices (8 bits each) go to
+ * indices_out (PIXO_ERR_BUFFER_TOO_SMALL when indices_capacity is less), the palette's RGBA entries to palette_out,
+ * their number to *palette_len, and *trns_len says how many alphas a tRNS chunk holds: up to the last one that is not 255
+ * (maybe_trim_transparency, :1888-1902), 0 for none.  Checks: those of pixo_hip_png_prepare in its order, then a null
+ * `quantization`.  Synchronous. */
+int pixo_hip_png_quantize(const uint8_t *data, size_t data_len, const pixo_png_options *options,
+                          const pixo_png_quantization *quantization, uint8_t *indices_out, size_t indices_capacity,
+                          uint8_t (*palette_out)[4], uint32_t *palette_len, uint32_t *trns_len, uint8_t *applied);
+/* The same for pixels in HBM on the current HIP device; the indices are left in d_indices (width * height bytes in HBM).
+ * Only the sampled colour keys (at most about 0.5 MB) and the k-means sums cross to the host. */
+int pixo_hip_png_quantize_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                                 void *d_indices, uint8_t (*palette_out)[4], uint32_t *palette_len, uint32_t *trns_len,
+                                 uint8_t *applied);
+/* pixo::png::encode_with_options with quantisation: when the gate declines, exactly the bytes of pixo_hip_png_encode;
+ * otherwise the indexed file of encode_indexed_into (:1814-1886): IHDR with bit depth 8 and colour type 3, PLTE, the trimmed
+ * tRNS, the indices filtered as one-byte pixels — Adaptive, AdaptiveFast, MinSum and Bigrams become None, every other strategy
+ * is kept — and the IDAT chunks of pixo_hip_png_encode's contract. */
+int pixo_hip_png_encode_lossy(const uint8_t *data, size_t data_len, const pixo_png_options *options,
+                              const pixo_png_quantization *quantization, uint8_t **out, size_t *out_len);
+int pixo_hip_png_encode_lossy_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                                     uint8_t **out, size_t *out_len);
+/* Tests and tools: how the dither ran in this process so far — launches of the chained form, calls served band by band
+ * (debug switch spin_budget=0, images of one band, or after a give-up), chained launches in which a band gave up waiting
+ * (each also counts in pixo_hip_debug_lookback_fallbacks).  Null pointers are skipped. */
+int pixo_hip_debug_png_dither_stats(uint64_t *chained_launches, uint64_t *band_by_band_calls, uint64_t *gave_up);
+/* The host part of the quantiser, no GPU needed: median cut (median_cut_palette, :1301-1333, before its k-means) of n <= 8,192
+ * colours (keys r<<24 | g<<16 | b<<8 | a) with their counts into at most min(max_colors, 256) entries, in box order. */
+int pixo_hip_png_median_cut(const uint32_t *colors, const uint32_t *counts, uint32_t n, uint32_t max_colors,
+                            uint8_t (*palette_out)[4], uint32_t *palette_len);
 
 /* ---- resize (pixo::resize, src/resize.rs) ------------------------------------------------ */
 

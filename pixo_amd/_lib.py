@@ -50,6 +50,11 @@ class PngLayoutC(C.Structure):
     ]
 
 
+class PngQuantizationC(C.Structure):
+    """pixo_png_quantization (include/pixo_hip.h)"""
+    _fields_ = [("mode", C.c_uint8), ("dithering", C.c_uint8), ("max_colors", C.c_uint16)]
+
+
 # every symbol include/pixo_hip.h declares
 SYMBOLS = [
     "pixo_jpeg_options_from_preset", "pixo_hip_jpeg_encode", "pixo_hip_jpeg_encode_into",
@@ -58,7 +63,8 @@ SYMBOLS = [
     "pixo_hip_jpeg_encode_device", "pixo_hip_jpeg_encode_device_into", "pixo_hip_jpeg_encode_batch_device", "pixo_hip_jpeg_encode_batch_device_into", "pixo_hip_debug_lookback_fallbacks", "pixo_hip_debug_routes", "pixo_hip_debug_dispatch_gate", "pixo_hip_debug_stream_copy", "pixo_hip_debug_stream_io", "pixo_hip_debug_engine_clock", "pixo_hip_debug_scan_device_async", "pixo_hip_debug_scan_device_async_batch", "pixo_hip_png_filter", "pixo_hip_png_filter_device", "pixo_hip_png_filter_async",
     "pixo_hip_png_adler32_from_row_sums", "pixo_hip_png_options_from_preset", "pixo_hip_png_prepare", "pixo_hip_png_prepare_device",
     "pixo_hip_png_palette_order", "pixo_hip_zlib_compress", "pixo_hip_zlib_compress_device", "pixo_hip_png_encode",
-    "pixo_hip_png_encode_device", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
+    "pixo_hip_png_encode_device", "pixo_hip_png_quantize", "pixo_hip_png_quantize_device", "pixo_hip_png_encode_lossy",
+    "pixo_hip_png_encode_lossy_device", "pixo_hip_debug_png_dither_stats", "pixo_hip_png_median_cut", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
     "pixo_hip_resize_contributions", "pixo_hip_band",
     "pixo_hip_band_encoder_create", "pixo_hip_band_encoder_destroy", "pixo_hip_band_encoder_rows",
     "pixo_hip_band_encoder_coeffs", "pixo_hip_band_encoder_count", "pixo_hip_band_encoder_lengths",
@@ -156,6 +162,13 @@ def load():
     L.pixo_hip_zlib_compress_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, szp]
     L.pixo_hip_png_encode.argtypes = [C.c_void_p, C.c_size_t, poptp, u8pp, szp]
     L.pixo_hip_png_encode_device.argtypes = [C.c_void_p, poptp, u8pp, szp]
+    qoptp, u32p = C.POINTER(PngQuantizationC), C.POINTER(C.c_uint32)
+    L.pixo_hip_png_quantize.argtypes = [C.c_void_p, C.c_size_t, poptp, qoptp, C.c_void_p, C.c_size_t, C.c_void_p, u32p, u32p, C.POINTER(C.c_uint8)]
+    L.pixo_hip_png_quantize_device.argtypes = [C.c_void_p, poptp, qoptp, C.c_void_p, C.c_void_p, u32p, u32p, C.POINTER(C.c_uint8)]
+    L.pixo_hip_png_encode_lossy.argtypes = [C.c_void_p, C.c_size_t, poptp, qoptp, u8pp, szp]
+    L.pixo_hip_png_encode_lossy_device.argtypes = [C.c_void_p, poptp, qoptp, u8pp, szp]
+    L.pixo_hip_debug_png_dither_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
+    L.pixo_hip_png_median_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, u32p]
     roptp = C.POINTER(ResizeOptionsC)
     L.pixo_hip_resize.argtypes = [C.c_void_p, C.c_size_t, roptp, u8pp, szp]
     L.pixo_hip_resize_into.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, roptp, szp]

@@ -14,6 +14,7 @@
 //   png_api.cpp      the extern "C" PNG row-filter entry points
 //   png_reduce_api.cpp  the extern "C" PNG prepare entry points: png_check_options, reductions (png_reduce.hip), palette ordering, the filter
 //   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, a ZlibJob (png_deflate.hip), file head and IDAT frames
+//   png_quantize_api.cpp  PNG lossy mode: gate, histogram and median cut on the host, the kernels of png_quantize.hip, the extern "C" quantize entries
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
 #pragma once
 #include <hip/hip_runtime.h>
@@ -237,6 +238,13 @@ struct Context {
     Buf z_stream;                                    // the zlib stream: plain, or as IDAT bodies with room for their frames
     Buf z_crc;                                       // CRC-32 of every 4 KiB piece of the stream
     Buf h_zinfo{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... z_info / z_crc copied to the host
+    // PNG quantisation (png_quantize_api.cpp, png_quantize.hip); the indices go to q_index
+    Buf k_samples{Buf::Mem::Device, Buf::Grow::Exact};  // the strided colour keys of the histogram and of the gate
+    Buf h_ksamples{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... copied to the host (and sorted there)
+    Buf k_work{Buf::Mem::Device, Buf::Grow::Exact};     // one QuantWork: histogram colours and counts, palette, k-means sums, dither state
+    Buf h_kwork{Buf::Mem::Pinned, Buf::Grow::Exact};    // ... its host side
+    Buf k_lut{Buf::Mem::Device, Buf::Grow::Exact};      // the 64^3 nearest-entry table
+    Buf k_carry{Buf::Mem::Device, Buf::Grow::Exact};    // dither: per band, what its first row receives from the band above (u64 per column)
     Buf t_raw, t_trail;                 // progressive + trellis: unquantised DCT blocks (f32), Viterbi back-pointers
     Buf t_plain;                        // preset 2, small images: the plain quantiser's tuple of the statistics pass on the second stream
     Buf g_flags, g_rank, g_by_rank;     // progressive scans: band flags, rank among non-empty blocks and its inverse
@@ -435,6 +443,7 @@ struct RetryMultipass {
 };
 int scan_retry_multipass(Context &c);
 uint64_t lookback_fallbacks(); // how often that has happened in this process (tests)
+void note_lookback_fallback();  // a kernel with bounded waits gave up and its job ran again in a form that waits for nothing (also: the PNG dither)
 int upload_scan_tables(Context &c, const uint32_t (&packed)[pixo_host::kScanTableWords], hipStream_t stream);
 int scan_begin(Context &c, ScanJob &j, const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,
                const pixo_host::Geometry &g, uint32_t batch, const int16_t *band_seed_dc);
@@ -562,6 +571,14 @@ struct PngFilterView { uint32_t bpp, row; }; // bytes per filter pixel, bytes pe
 // d_px: width * height * bpp bytes on the context's device; reductions + filters, the stream is left in d_out
 int png_prepare_on_device(Context &c, const void *d_px, const pixo_png_options &o, void *d_out, pixo_png_layout *layout, size_t *out_len,
                           uint32_t *adler, PngFilterView *view = nullptr);
+
+// ---- PNG quantisation (png_quantize_api.cpp) ---------------------------------------------------------------------------
+// The reference's gate and quantize_image (mod.rs:469-492) on pixels on the context's device.  *applied false: the gate
+// declined (or the mode is Off, or the pixels are gray) and nothing else is set.  Otherwise width * height indices lie in
+// c.q_index, `layout` describes the 8-bit palette image and *trns_len says how many alphas its tRNS chunk holds (0: none).
+int png_check_quantization(const pixo_png_quantization *quantization); // behind png_check_options' checks: a null struct, an unknown mode
+int png_quantize_on_device(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization &q, bool *applied,
+                           pixo_png_layout *layout, uint32_t *trns_len);
 
 // ---- preset 2 (progressive.cpp) -----------------------------------------------------------------------------------
 int huffman_for_tuple(const int16_t *dy, const int16_t *dcb, const int16_t *dcr, const pixo_jpeg_options &o,

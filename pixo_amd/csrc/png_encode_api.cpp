@@ -1,4 +1,4 @@
-// png_encode_api.cpp — the extern "C" zlib and PNG whole-file entry points: the prepared stream (png_reduce_api.cpp) is
+// png_encode_api.cpp — the extern "C" zlib and PNG whole-file entry points (lossless and quantised): the prepared stream (png_reduce_api.cpp) is
 // compressed where it lies (png_deflate.hip), its blocks are compacted into the bodies of 256 KiB IDAT chunks, the chunks'
 // CRC-32 come from the device in 4 KiB pieces, and only the finished file crosses to the host.  The chunks around IDAT are
 // the reference's byte for byte (src/png/mod.rs:513-630); the IDAT body is this library's own DEFLATE.
@@ -90,7 +90,8 @@ void empty_zlib(uint8_t level, uint8_t out[8]) // deflate.rs: header, an empty f
 
 // Everything in front of the first IDAT chunk: signature, IHDR, and for a palette image PLTE and tRNS (mod.rs:513-547).
 // strip_metadata: there is no ancillary chunk to strip (tRNS is kept by the reference as well).
-std::vector<uint8_t> png_head(uint32_t width, uint32_t height, const pixo_png_layout &layout)
+// trns_len: how many alphas tRNS holds — all of them on the lossless path, trimmed on the quantised one (mod.rs:1888-1902)
+std::vector<uint8_t> png_head(uint32_t width, uint32_t height, const pixo_png_layout &layout, uint32_t trns_len)
 {
     std::vector<uint8_t> head{0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     uint8_t ihdr[13] = {0};
@@ -106,7 +107,7 @@ std::vector<uint8_t> png_head(uint32_t width, uint32_t height, const pixo_png_la
             trns[i] = layout.palette[i][3];
         }
         append_chunk(head, "PLTE", plte, 3 * layout.palette_len);
-        if (layout.has_trns) append_chunk(head, "tRNS", trns, layout.palette_len);
+        if (layout.has_trns) append_chunk(head, "tRNS", trns, trns_len);
     }
     return head;
 }
@@ -135,7 +136,29 @@ void frame_idats(uint8_t *idat, uint64_t stream_len, const uint32_t *piece_crc)
     std::memcpy(idat + pixo_dev::z_framed_size(stream_len), iend.data(), 12);
 }
 
-// Pixels on the context's device -> the finished file in a block the caller owns: prepare, DEFLATE, copy, frame, deliver.
+// A prepared stream of `len` bytes in c.p_out -> the finished file in a block the caller owns: DEFLATE, copy, frame, deliver.
+int png_finish(Context &c, const pixo_png_options &o, const pixo_png_layout &layout, uint32_t trns_len, size_t len, uint32_t adler,
+               const PngFilterView &view, uint8_t **out, size_t *out_len)
+{
+    ZlibJob job{c.p_out.p, len, o.compression_level, view.bpp, view.row};
+    job.adler = &adler;
+    job.framed = true;
+    uint64_t stream_len = 0;
+    int rc = zlib_on_device(c, job, &stream_len);
+    if (rc) return rc;
+
+    const std::vector<uint8_t> head = png_head(o.width, o.height, layout, trns_len);
+    const size_t framed = static_cast<size_t>(pixo_dev::z_framed_size(stream_len)), file_len = head.size() + framed + 12;
+    if ((rc = c.h_file.reserve(file_len))) return rc;
+    uint8_t *file = c.h_file.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(file + head.size(), c.z_stream.p, framed, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream)); // (the pieces' CRC-32 have arrived as well)
+    std::memcpy(file, head.data(), head.size());
+    frame_idats(file + head.size(), stream_len, c.h_zinfo.as<uint32_t>());
+    return deliver(file, file_len, out, out_len);
+}
+
+// Pixels on the context's device -> the finished file: prepare, then png_finish.
 int png_file(Context &c, const void *d_px, const pixo_png_options &o, uint8_t **out, size_t *out_len)
 {
     int rc = c.p_out.reserve(static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) * bytes_per_pixel(o.color_type) + 1));
@@ -145,21 +168,28 @@ int png_file(Context &c, const void *d_px, const pixo_png_options &o, uint8_t **
     uint32_t adler = 0;
     PngFilterView view;
     if ((rc = png_prepare_on_device(c, d_px, o, c.p_out.p, &layout, &len, &adler, &view))) return rc;
-    ZlibJob job{c.p_out.p, len, o.compression_level, view.bpp, view.row};
-    job.adler = &adler;
-    job.framed = true;
-    uint64_t stream_len = 0;
-    if ((rc = zlib_on_device(c, job, &stream_len))) return rc;
+    return png_finish(c, o, layout, layout.palette_len, len, adler, view, out, out_len);
+}
 
-    const std::vector<uint8_t> head = png_head(o.width, o.height, layout);
-    const size_t framed = static_cast<size_t>(pixo_dev::z_framed_size(stream_len)), file_len = head.size() + framed + 12;
-    if ((rc = c.h_file.reserve(file_len))) return rc;
-    uint8_t *file = c.h_file.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(file + head.size(), c.z_stream.p, framed, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream)); // (the pieces' CRC-32 have arrived as well)
-    std::memcpy(file, head.data(), head.size());
-    frame_idats(file + head.size(), stream_len, c.h_zinfo.as<uint32_t>());
-    return deliver(file, file_len, out, out_len);
+// ... with quantisation (mod.rs:469-511): the gate declines -> png_file; otherwise the indices as an 8-bit, one-byte-per-pixel
+// image through the same filter, DEFLATE, CRC and chunk path (encode_indexed_into, :1814-1886).
+int png_file_lossy(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization &q, uint8_t **out, size_t *out_len)
+{
+    bool applied = false;
+    pixo_png_layout layout;
+    uint32_t trns_len = 0;
+    int rc = png_quantize_on_device(c, d_px, o, q, &applied, &layout, &trns_len);
+    if (rc) return rc;
+    if (!applied) return png_file(c, d_px, o, out, out_len);
+    uint8_t strategy = o.filter_strategy; // :1866-1874: palette-aware filtering
+    if (strategy == PIXO_PNG_ADAPTIVE || strategy == PIXO_PNG_ADAPTIVE_FAST || strategy == PIXO_PNG_MINSUM || strategy == PIXO_PNG_BIGRAMS) strategy = PIXO_PNG_NONE;
+    int run = 0;
+    bool seq = false;
+    const size_t len = static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) + 1);
+    if ((rc = png_plan(o.width, o.height, static_cast<uint64_t>(o.width) * o.height, 1, strategy, o.flags, &run, &seq)) || (rc = c.p_out.reserve(len))) return rc;
+    uint32_t adler = 0;
+    if ((rc = png_filter_on_device(c, c.q_index.p, o.width, o.height, 1, run, seq, c.p_out.p, &adler))) return rc;
+    return png_finish(c, o, layout, trns_len, len, adler, PngFilterView{1, o.width + 1}, out, out_len);
 }
 
 } // namespace
@@ -234,6 +264,34 @@ int pixo_hip_png_encode_device(const void *d_pixels, const pixo_png_options *opt
     Context *c = nullptr;
     if ((rc = context_on_current_device(&c))) return rc;
     return png_file(*c, d_pixels, *options, out, out_len);
+}
+
+int pixo_hip_png_encode_lossy(const uint8_t *data, size_t data_len, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                              uint8_t **out, size_t *out_len)
+{
+    int rc = png_check_options(options, true, data_len);
+    if (rc) return rc;
+    PIXO_REQUIRE(data);
+    if ((rc = png_check_quantization(quantization))) return rc;
+    PIXO_REQUIRE(out);
+    PIXO_REQUIRE(out_len);
+    PIXO_THREAD_CONTEXT(c);
+    if ((rc = upload(c, c.p_in, data, data_len))) return rc;
+    return png_file_lossy(c, c.p_in.p, *options, *quantization, out, out_len);
+}
+
+int pixo_hip_png_encode_lossy_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization, uint8_t **out,
+                                     size_t *out_len)
+{
+    int rc = png_check_options(options);
+    if (rc) return rc;
+    PIXO_REQUIRE(d_pixels);
+    if ((rc = png_check_quantization(quantization))) return rc;
+    PIXO_REQUIRE(out);
+    PIXO_REQUIRE(out_len);
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc;
+    return png_file_lossy(*c, d_pixels, *options, *quantization, out, out_len);
 }
 
 } // extern "C"

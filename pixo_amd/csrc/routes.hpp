@@ -16,7 +16,7 @@ enum : uint64_t {
     DENSE_STREAM_RULE = 1ull << 4, // the context's last file was dense: the fused kernel would have served, the two-kernel form did
     SINGLE_PASS_TUPLE = 1ull << 5, // the single-pass tuple coders of jpeg_scan_fused.hip
     MULTI_PASS = 1ull << 6,        // the multi-pass entropy kernels of jpeg_entropy.hip (baseline or progressive)
-    FALLBACK = 1ull << 7,          // a single-pass launch gave up waiting: the job ran again with the multi-pass kernels
+    FALLBACK = 1ull << 7,          // a single-pass launch gave up waiting: the job ran again with the multi-pass kernels (PNG dither: band by band)
     HOST_ENTROPY = 1ull << 8,      // the host twin of the scan coders (debug switch host_entropy)
     PIECES = 1ull << 9,            // a scan coded in pieces while the file travels (device_entropy_pieces)
     HOST_BANDS = 1ull << 10,       // ... with host pixels uploaded in bands

@@ -107,11 +107,15 @@ int upload_scan_tables(Context &c, const uint32_t (&packed)[pixo_host::kScanTabl
 // again with t_force_multipass set (RetryMultipass below): the multi-pass kernels wait for nothing but kernel boundaries.
 thread_local bool t_force_multipass = false;
 std::atomic<uint64_t> g_lookback_fallbacks{0};
+void note_lookback_fallback()
+{
+    g_lookback_fallbacks.fetch_add(1, std::memory_order_relaxed);
+    note_route(route::FALLBACK);
+}
 int scan_retry_multipass(Context &c)
 {
     c.e_code_state.known = 0; // (the descriptors and the flag are dirty: the next single-pass launch starts with a memset)
-    g_lookback_fallbacks.fetch_add(1, std::memory_order_relaxed);
-    note_route(route::FALLBACK);
+    note_lookback_fallback();
     return kRetryMultipass;
 }
 uint64_t lookback_fallbacks() { return g_lookback_fallbacks.load(std::memory_order_relaxed); }

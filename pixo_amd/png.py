@@ -1,6 +1,7 @@
-"""PNG on the MI355X: row filters + Adler-32, the reductions in front of them, and whole files —
-`encode` compresses the prepared stream on the device and returns a finished PNG.  Mirrors
-`pixo::png` (src/png/mod.rs).  No CPU fallback."""
+"""PNG on the MI355X: row filters + Adler-32, the reductions in front of them, whole files —
+`encode` compresses the prepared stream on the device and returns a finished PNG — and the lossy mode:
+palette quantisation and Floyd-Steinberg dithering on the device.  Mirrors `pixo::png` (src/png/mod.rs).
+No CPU fallback."""
 import ctypes as C
 import enum
 
@@ -71,13 +72,38 @@ def adler32_from_row_sums(row_sums, width, height, bytes_per_pixel):
 
 # ---- the prepared stream: reductions + filters (src/png/mod.rs:513-568) -----------------------------------------------
 
+class QuantizationMode(enum.IntEnum):
+    """`pixo::png::QuantizationMode`"""
+    OFF = 0
+    AUTO = 1
+    FORCE = 2
+
+
+class QuantizationOptions:
+    """`pixo::png::QuantizationOptions`: Off, 256 colours, no dithering by default."""
+
+    def __init__(self, mode=QuantizationMode.OFF, max_colors=256, dithering=False):
+        self.mode, self.max_colors, self.dithering = QuantizationMode(mode), int(max_colors), bool(dithering)
+
+    def to_c(self):
+        return _lib.PngQuantizationC(int(self.mode), self.dithering, self.max_colors)
+
+    def __eq__(self, other):
+        return isinstance(other, QuantizationOptions) and (self.mode, self.max_colors, self.dithering) == (other.mode, other.max_colors, other.dithering)
+
+    def __repr__(self):
+        return "QuantizationOptions(mode=%s, max_colors=%d, dithering=%s)" % (self.mode.name, self.max_colors, self.dithering)
+
+
 class PngOptions:
     """The fields of `pixo::png::PngOptions` (src/png/mod.rs:41-100).  `compression_level` selects the zlib header's
-    FLEVEL; the device DEFLATE has one effort, so `optimal_compression` compresses the same way.  No quantisation."""
+    FLEVEL; the device DEFLATE has one effort, so `optimal_compression` compresses the same way.  `quantization` travels
+    beside the C struct (pixo_png_quantization): `encode` takes the lossy entries when its mode is not Off."""
 
     def __init__(self, width=0, height=0, color_type=ColorType.Rgba, compression_level=2,
                  filter_strategy=FilterStrategy.ADAPTIVE_FAST, optimize_alpha=False, reduce_color_type=False,
-                 strip_metadata=False, reduce_palette=False, optimal_compression=False, flags=0):
+                 strip_metadata=False, reduce_palette=False, optimal_compression=False, flags=0, quantization=None):
+        self.quantization = quantization if quantization is not None else QuantizationOptions()
         self.width, self.height, self.color_type = width, height, ColorType(color_type)
         self.compression_level, self.filter_strategy = compression_level, FilterStrategy(filter_strategy)
         self.optimize_alpha, self.reduce_color_type, self.reduce_palette = bool(optimize_alpha), bool(reduce_color_type), bool(reduce_palette)
@@ -102,6 +128,14 @@ class PngOptions:
         return cls.fast(width, height) if preset == 0 else cls.max(width, height) if preset == 2 else cls.balanced(width, height)
 
     @classmethod
+    def from_preset_with_lossless(cls, width, height, preset, lossless):
+        """mod.rs:203-213: not lossless = Auto, 256 colours, dithering on"""
+        o = cls.from_preset(width, height, preset)
+        if not lossless:
+            o.quantization = QuantizationOptions(QuantizationMode.AUTO, 256, True)
+        return o
+
+    @classmethod
     def builder(cls, width, height):
         return PngOptionsBuilder(width, height)
 
@@ -116,7 +150,8 @@ class PngOptions:
 
 
 class PngOptionsBuilder:
-    """`PngOptionsBuilder` (src/png/mod.rs:220-340) without the quantisation setters."""
+    """`PngOptionsBuilder` (src/png/mod.rs:220-340).  Of the quantisation setters it has `quantization_mode`,
+    `quantization_max_colors` and `quantization_dithering` (:297-324)."""
 
     def __init__(self, width, height):
         self._o = PngOptions(width, height)
@@ -125,6 +160,18 @@ class PngOptionsBuilder:
         keep = self._o
         self._o = PngOptions.from_preset(keep.width, keep.height, preset)
         self._o.color_type, self._o.flags = keep.color_type, keep.flags
+        return self
+
+    def quantization_mode(self, mode):
+        self._o.quantization.mode = QuantizationMode(mode)
+        return self
+
+    def quantization_max_colors(self, max_colors):
+        self._o.quantization.max_colors = int(max_colors)
+        return self
+
+    def quantization_dithering(self, dithering):
+        self._o.quantization.dithering = bool(dithering)
         return self
 
     def build(self):
@@ -239,12 +286,21 @@ def zlib_compress_device(d_data, length, d_out, capacity, level=6, bpp=0, row=0)
     return n.value
 
 
+def _lossy(options):
+    return options.quantization.mode != QuantizationMode.OFF
+
+
 def encode(data, options):
-    """Host pixels -> a finished PNG file (bytes): `pixo::png::encode_with_options`."""
+    """Host pixels -> a finished PNG file (bytes): `pixo::png::encode_with_options`.  With `options.quantization` not Off
+    the reference's gate decides between the indexed (lossy) file and this same lossless one."""
     L = _lib.load()
     px = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     o, p, n = options.to_c(), C.POINTER(C.c_uint8)(), C.c_size_t()
-    rc = L.pixo_hip_png_encode(px.ctypes.data, px.size, C.byref(o), C.byref(p), C.byref(n))
+    if _lossy(options):
+        q = options.quantization.to_c()
+        rc = L.pixo_hip_png_encode_lossy(px.ctypes.data, px.size, C.byref(o), C.byref(q), C.byref(p), C.byref(n))
+    else:
+        rc = L.pixo_hip_png_encode(px.ctypes.data, px.size, C.byref(o), C.byref(p), C.byref(n))
     _lib.check(rc)
     return _lib.take(L, p, n)
 
@@ -253,6 +309,68 @@ def encode_device(d_pixels, options):
     """Device pixels (torch tensor / raw pointer) -> a finished PNG file on the host (bytes)."""
     L = _lib.load()
     o, p, n = options.to_c(), C.POINTER(C.c_uint8)(), C.c_size_t()
-    rc = L.pixo_hip_png_encode_device(_lib.ptr(d_pixels), C.byref(o), C.byref(p), C.byref(n))
+    if _lossy(options):
+        q = options.quantization.to_c()
+        rc = L.pixo_hip_png_encode_lossy_device(_lib.ptr(d_pixels), C.byref(o), C.byref(q), C.byref(p), C.byref(n))
+    else:
+        rc = L.pixo_hip_png_encode_device(_lib.ptr(d_pixels), C.byref(o), C.byref(p), C.byref(n))
     _lib.check(rc)
     return _lib.take(L, p, n)
+
+
+# ---- lossy mode: palette quantisation and dithering on the device ------------------------------------------------------
+
+class Quantized:
+    """What `quantize` made of an image: `applied` False when the gate declined (then nothing else is set)."""
+
+    def __init__(self, applied, indices=None, palette=None, trns_len=0):
+        self.applied, self.indices, self.palette, self.trns_len = applied, indices, palette, trns_len
+
+
+def _quantized(applied, indices, pal, n, trns):
+    if not applied.value:
+        return Quantized(False)
+    return Quantized(True, indices, [tuple(int(v) for v in pal[i]) for i in range(n.value)], trns.value)
+
+
+def quantize(data, options):
+    """Host pixels -> Quantized (indices as a uint8 array [height * width], RGBA palette, tRNS length): the reference's
+    gate and `quantize_image` for `options.quantization`."""
+    L = _lib.load()
+    px = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    idx, pal = np.empty(max(options.width * options.height, 1), np.uint8), np.zeros((256, 4), np.uint8)
+    o, q, n, trns, applied = options.to_c(), options.quantization.to_c(), C.c_uint32(), C.c_uint32(), C.c_uint8()
+    rc = L.pixo_hip_png_quantize(px.ctypes.data, px.size, C.byref(o), C.byref(q), idx.ctypes.data, idx.size, pal.ctypes.data,
+                                 C.byref(n), C.byref(trns), C.byref(applied))
+    _lib.check(rc)
+    return _quantized(applied, idx[:options.width * options.height], pal, n, trns)
+
+
+def quantize_device(d_pixels, options, d_indices):
+    """Device pixels (torch tensor / raw pointer) -> indices in d_indices (width * height bytes in HBM); returns Quantized
+    with `indices` None."""
+    L = _lib.load()
+    pal = np.zeros((256, 4), np.uint8)
+    o, q, n, trns, applied = options.to_c(), options.quantization.to_c(), C.c_uint32(), C.c_uint32(), C.c_uint8()
+    rc = L.pixo_hip_png_quantize_device(_lib.ptr(d_pixels), C.byref(o), C.byref(q), _lib.ptr(d_indices), pal.ctypes.data, C.byref(n),
+                                        C.byref(trns), C.byref(applied))
+    _lib.check(rc)
+    return _quantized(applied, None, pal, n, trns)
+
+
+def dither_stats():
+    """(chained launches, calls served band by band, chained launches that gave up) of the dither in this process (tests, tools)."""
+    a, b, g = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    _lib.check(_lib.load().pixo_hip_debug_png_dither_stats(C.byref(a), C.byref(b), C.byref(g)))
+    return a.value, b.value, g.value
+
+
+def median_cut(colors, counts, max_colors):
+    """Colour keys (r<<24 | g<<16 | b<<8 | a) + counts -> the median-cut palette before k-means, RGBA rows (host only, no GPU)."""
+    L = _lib.load()
+    k, cnt = np.ascontiguousarray(colors, dtype=np.uint32), np.ascontiguousarray(counts, dtype=np.uint32)
+    assert k.size == cnt.size
+    pal, n = np.zeros((256, 4), np.uint8), C.c_uint32()
+    rc = L.pixo_hip_png_median_cut(k.ctypes.data, cnt.ctypes.data, k.size, max_colors, pal.ctypes.data, C.byref(n))
+    _lib.check(rc)
+    return pal[:n.value].copy()
