@@ -41,7 +41,7 @@ class Error : public std::runtime_error {
   public:
     enum class Kind {
         InvalidDimensions, InvalidDataLength, InvalidQuality, ImageTooLarge, UnsupportedColorType,
-        CompressionError, InvalidRestartInterval, InvalidColorArgument, BufferTooSmall, Unknown
+        CompressionError, InvalidRestartInterval, InvalidColorArgument, BufferTooSmall, InvalidDecode, UnsupportedDecode, Unknown
     };
     Error(Kind k, const std::string &msg) : std::runtime_error(msg), kind_(k) {}
     Kind kind() const { return kind_; }
@@ -58,6 +58,8 @@ class Error : public std::runtime_error {
         case PIXO_ERR_INVALID_RESTART_INTERVAL: k = Kind::InvalidRestartInterval; break;
         case PIXO_ERR_INVALID_COLOR_ARG: k = Kind::InvalidColorArgument; break;
         case PIXO_ERR_BUFFER_TOO_SMALL: k = Kind::BufferTooSmall; break;
+        case PIXO_ERR_INVALID_DECODE: k = Kind::InvalidDecode; break;
+        case PIXO_ERR_UNSUPPORTED_DECODE: k = Kind::UnsupportedDecode; break;
         default: break;
         }
         return Error(k, pixo_hip_last_error());
@@ -359,6 +361,31 @@ inline void resize_device(const void *d_src, const ResizeOptions &options, void 
     if (rc != PIXO_OK) throw Error::from_status(rc);
 }
 } // namespace resize
+
+namespace decode {
+// decode/png.rs:18-28
+struct PngImage {
+    uint32_t width = 0;
+    uint32_t height = 0;
+    std::vector<uint8_t> pixels;
+    ColorType color_type = ColorType::Rgb;
+};
+// pixo::decode::decode_png (decode/png.rs:101)
+[[nodiscard]] inline PngImage decode_png(const uint8_t *data, size_t len)
+{
+    uint8_t *buf = nullptr;
+    size_t n = 0;
+    PngImage im;
+    uint8_t ct = 0;
+    const int rc = pixo_hip_png_decode(data, len, &buf, &n, &im.width, &im.height, &ct);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    im.pixels.assign(buf, buf + n);
+    pixo_hip_free(buf);
+    im.color_type = static_cast<ColorType>(ct);
+    return im;
+}
+[[nodiscard]] inline PngImage decode_png(const std::vector<uint8_t> &data) { return decode_png(data.data(), data.size()); }
+} // namespace decode
 
 // The reference's flat wasm export `resizeImage` (src/wasm.rs:183-201), same seven arguments.
 [[nodiscard]] inline std::vector<uint8_t> resize_image(const uint8_t *data, size_t len, uint32_t src_width, uint32_t src_height,

@@ -42,7 +42,9 @@ typedef enum {
     PIXO_ERR_COMPRESSION = -6,             /* Error::CompressionError(String): device/runtime failures */
     PIXO_ERR_INVALID_RESTART_INTERVAL = -7,/* Error::InvalidRestartInterval       */
     PIXO_ERR_INVALID_COLOR_ARG = -8,       /* wasm.rs:122-131 "Invalid color type for JPEG: …" */
-    PIXO_ERR_BUFFER_TOO_SMALL = -9         /* encode_into with a fixed-capacity buffer */
+    PIXO_ERR_BUFFER_TOO_SMALL = -9,        /* encode_into with a fixed-capacity buffer */
+    PIXO_ERR_INVALID_DECODE = -10,         /* Error::InvalidDecode(String): "Decode error: {msg}" (src/error.rs:83-85) */
+    PIXO_ERR_UNSUPPORTED_DECODE = -11      /* Error::UnsupportedDecode(String): "Unsupported: {msg}" (src/error.rs:86-88) */
 } pixo_status;
 
 /* pixo::jpeg::JpegOptions (src/jpeg/mod.rs:121-140), field for field. */
@@ -528,6 +530,42 @@ int pixo_hip_jpeg_encode_multi(const uint8_t *data, size_t data_len, const pixo_
 int pixo_hip_jpeg_encode_batch_multi(const void *pixels, const pixo_jpeg_options *options, uint32_t batch,
                                      const int *devices, uint32_t n_devices, uint8_t *arena, size_t capacity,
                                      size_t *offsets, size_t *lens);
+
+/* ---- PNG decode ------------------------------------------------------------------------ */
+
+/* Replaces `pixo::decode::decode_png(data) -> Result<PngImage>` (src/decode/png.rs:101-291): a PNG file in host memory ->
+ * 8-bit pixels.  The chunk walk, its checks and the inflate run on the host in the reference's order and with its messages
+ * (PIXO_ERR_INVALID_DECODE / PIXO_ERR_UNSUPPORTED_DECODE, PIXO_ERR_INVALID_DIMENSIONS, PIXO_ERR_IMAGE_TOO_LARGE); row
+ * reconstruction (reconstruct_image / unfilter_row, :294-410) and the conversion to pixels (convert_to_pixels, :430-533) run
+ * on the device.  *color_type: the PIXO_* colour type of the pixels (:271-283: a palette image is PIXO_RGBA only if its tRNS
+ * holds a value other than 255).  On success *pixels is a block of width * height * channels bytes the caller releases with
+ * pixo_hip_free only. */
+int pixo_hip_png_decode(const uint8_t *file, size_t len, uint8_t **pixels, size_t *pixels_len, uint32_t *width, uint32_t *height,
+                        uint8_t *color_type);
+/* The same walk and checks up to "no IDAT data" (src/decode/png.rs:102-260) and the colour-type rule (:271-283), nothing else:
+ * no inflate, no GPU.  What a caller of pixo_hip_png_decode_device allocates from.  (What only the inflated stream can show —
+ * an ill-formed stream, a filter byte above 4, a palette image without PLTE — is left to the decode.) */
+int pixo_hip_png_decode_info(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint8_t *color_type);
+/* decode_png with the pixels left in DEVICE memory: `file` is host memory, d_pixels device memory of `capacity` bytes
+ * (PIXO_ERR_BUFFER_TOO_SMALL, with *width, *height and *color_type set, when that is less than width * height * channels).
+ * Ordered like pixo_hip_resize_device: the upload and the kernels are enqueued on `stream` behind the work of the producer
+ * stream, and the call returns without waiting for them, so the pixels can be handed on that stream to
+ * pixo_hip_resize_device, pixo_hip_jpeg_encode_device or pixo_hip_png_encode_device.  Every error of pixo_hip_png_decode is
+ * reported before anything is enqueued. */
+int pixo_hip_png_decode_device(const uint8_t *file, size_t len, void *d_pixels, size_t capacity, uint32_t *width, uint32_t *height,
+                               uint8_t *color_type, void *stream);
+/* Host only: `inflate_zlib_with_size(data, Some(expected))` (src/decode/inflate.rs:294-352) into `out` (`expected` bytes): the
+ * 6-byte minimum, the three header checks, the blocks, the Adler-32 read from the LAST four bytes of `data`, then the size —
+ * in that order, with the reference's messages.  Never writes past `expected` bytes. */
+int pixo_hip_zlib_inflate(const uint8_t *data, size_t len, uint8_t *out, size_t expected);
+/* Rows a workgroup of the reconstruction kernel walks side by side; a longer run of dependent rows takes several passes
+ * (tests place their pass boundaries by it). */
+uint32_t pixo_hip_png_unfilter_pass_rows(void);
+/* MEASUREMENT only (tools/png_decode_timing.py): pixo_hip_png_decode with its legs timed — ms[0] chunk walk + CRC, [1] inflate,
+ * [2] finding the runs of rows (host clocks), [3] upload, [4] reconstruction kernel, [5] conversion kernel (HIP events),
+ * [6] the whole call; counts[0] segments (rows that do not read the row above start one), [1] rows of the longest,
+ * [2] workgroups launched.  The pixels are released again. */
+int pixo_hip_debug_png_decode_timed(const uint8_t *file, size_t len, double ms[7], uint64_t counts[3]);
 
 /* ---- runtime ----------------------------------------------------------------------- */
 

@@ -65,7 +65,8 @@ SYMBOLS = [
     "pixo_hip_png_palette_order", "pixo_hip_zlib_compress", "pixo_hip_zlib_compress_device", "pixo_hip_png_encode",
     "pixo_hip_png_encode_device", "pixo_hip_png_quantize", "pixo_hip_png_quantize_device", "pixo_hip_png_encode_lossy",
     "pixo_hip_png_encode_lossy_device", "pixo_hip_debug_png_dither_stats", "pixo_hip_png_median_cut", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
-    "pixo_hip_resize_contributions", "pixo_hip_band",
+    "pixo_hip_resize_contributions", "pixo_hip_png_decode", "pixo_hip_png_decode_info", "pixo_hip_png_decode_device", "pixo_hip_zlib_inflate",
+    "pixo_hip_png_unfilter_pass_rows", "pixo_hip_debug_png_decode_timed", "pixo_hip_band",
     "pixo_hip_band_encoder_create", "pixo_hip_band_encoder_destroy", "pixo_hip_band_encoder_rows",
     "pixo_hip_band_encoder_coeffs", "pixo_hip_band_encoder_count", "pixo_hip_band_encoder_lengths",
     "pixo_hip_band_encoder_pack", "pixo_hip_band_encoder_pack_device", "pixo_hip_band_encoder_copy_body",
@@ -176,6 +177,13 @@ def load():
     L.pixo_hip_resize_image.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
                                         u8pp, szp]
     L.pixo_hip_resize_contributions.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp]
+    u8p = C.POINTER(C.c_uint8)
+    L.pixo_hip_png_decode.argtypes = [C.c_void_p, C.c_size_t, u8pp, szp, u32p, u32p, u8p]
+    L.pixo_hip_png_decode_info.argtypes = [C.c_void_p, C.c_size_t, u32p, u32p, u8p]
+    L.pixo_hip_png_decode_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, u32p, u32p, u8p, C.c_void_p]
+    L.pixo_hip_zlib_inflate.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    L.pixo_hip_png_unfilter_pass_rows.restype = C.c_uint32
+    L.pixo_hip_debug_png_decode_timed.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.pixo_hip_band.argtypes = [C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32, C.c_uint32,
                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), szp, szp, szp, szp]
     i16p, u64p = C.POINTER(C.c_int16), C.POINTER(C.c_uint64)

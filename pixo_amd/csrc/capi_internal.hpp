@@ -16,6 +16,8 @@
 //   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, a ZlibJob (png_deflate.hip), file head and IDAT frames
 //   png_quantize_api.cpp  PNG lossy mode: gate, histogram and median cut on the host, the kernels of png_quantize.hip, the extern "C" quantize entries
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
+//   png_decode_api.cpp  the extern "C" PNG decode entry points: chunk walk and checks, the host inflate (png_inflate.cpp), the runs of rows,
+//                    the launches of png_unfilter.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -258,6 +260,14 @@ struct Context {
     uint32_t r_max_span = 0;                            // ... the widest source span of one horizontal tile
     size_t r_v_at = 0;                                  // ... where the vertical axis starts in r_tables
     hipEvent_t r_done = nullptr;                        // the last Lanczos3 job (it reads r_tables, writes r_mid) has run
+    // PNG decode (png_decode_api.cpp, png_unfilter.hip)
+    Buf u_inflated{Buf::Mem::Pinned, Buf::Grow::Exact};  // the inflated stream: the host inflate writes it, the upload reads it
+    Buf u_stream{Buf::Mem::Device, Buf::Grow::Exact};    // ... on the device
+    Buf u_rows{Buf::Mem::Device, Buf::Grow::Exact};      // the reconstructed rows, 16-byte pitched
+    Buf u_out{Buf::Mem::Device, Buf::Grow::Exact};       // host entry: the pixels before they go down
+    Buf u_tables{Buf::Mem::Device, Buf::Grow::Exact};    // the palette table (256 words), behind it the runs of rows
+    Buf h_utables{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here, uploaded from here
+    hipEvent_t u_done = nullptr;                         // the last decode job (it reads all of the above) has run
 
     // Small results for the host, one field per purpose: pinned, allocated once with the stream (ensure).
     struct Mailbox {

@@ -1,0 +1,383 @@
+// png_decode_api.cpp — the extern "C" PNG decode entry points (pixo::decode::decode_png, reference src/decode/png.rs:101-291):
+// the chunk walk and its checks in the reference's order and words, the host inflate (png_inflate.cpp) into pinned memory, the
+// runs of rows that do not read the row above, and the launches of png_unfilter.hip.
+//
+// The order in which a faulty file is refused: signature; per chunk in file order "truncated PNG chunk", its CRC-32, then its
+// own length / field checks; then missing IEND, missing IHDR, zero dimension, dimension above 2^24, compression method, filter
+// method, interlace (Unsupported), bit depth against colour type, no IDAT, whatever inflate raises, Adler-32, size, the first
+// row in row order with a filter byte above 4, a palette image without PLTE.  All of it is known on the host before a kernel starts.
+#include "capi_internal.hpp"
+#include "png_deflate_math.h"
+#include "png_inflate.hpp"
+#include "png_unfilter.hpp"
+
+#include <algorithm>
+
+using namespace pixo_capi;
+using namespace pixo_pngu;
+
+namespace {
+
+int invalid(const std::string &msg) { return fail(PIXO_ERR_INVALID_DECODE, "Decode error: " + msg); }
+int unsupported(const std::string &msg) { return fail(PIXO_ERR_UNSUPPORTED_DECODE, "Unsupported: " + msg); }
+
+// zlib.crc32, eight bytes a step
+struct CrcTables {
+    uint32_t t[8][256];
+    CrcTables()
+    {
+        for (uint32_t i = 0; i < 256; ++i) t[0][i] = pixo_pngz::crc32_table_entry(i);
+        for (uint32_t i = 0; i < 256; ++i)
+            for (int k = 1; k < 8; ++k) t[k][i] = t[0][t[k - 1][i] & 255] ^ (t[k - 1][i] >> 8);
+    }
+};
+uint32_t crc32_fast(const uint8_t *p, size_t n)
+{
+    static const CrcTables T;
+    uint32_t c = 0xFFFFFFFFu;
+    for (; n >= 8; n -= 8, p += 8) {
+        uint32_t lo, hi;
+        std::memcpy(&lo, p, 4);
+        std::memcpy(&hi, p + 4, 4);
+        lo ^= c;
+        c = T.t[7][lo & 255] ^ T.t[6][(lo >> 8) & 255] ^ T.t[5][(lo >> 16) & 255] ^ T.t[4][lo >> 24] ^ T.t[3][hi & 255] ^
+            T.t[2][(hi >> 8) & 255] ^ T.t[1][(hi >> 16) & 255] ^ T.t[0][hi >> 24];
+    }
+    for (; n; --n, ++p) c = T.t[0][(c ^ *p) & 255] ^ (c >> 8);
+    return ~c;
+}
+
+uint32_t be32(const uint8_t *p) { return (uint32_t{p[0]} << 24) | (uint32_t{p[1]} << 16) | (uint32_t{p[2]} << 8) | p[3]; }
+
+// String::from_utf8_lossy of a chunk type: every maximal ill-formed run becomes U+FFFD
+std::string utf8_lossy(const uint8_t *s, size_t n)
+{
+    std::string out;
+    for (size_t i = 0; i < n;) {
+        const uint8_t b = s[i];
+        size_t need = 0;
+        uint8_t lo = 0x80, hi = 0xBF;
+        if (b < 0x80) { out += static_cast<char>(b); ++i; continue; }
+        if (b >= 0xC2 && b <= 0xDF) need = 1;
+        else if (b >= 0xE0 && b <= 0xEF) { need = 2; if (b == 0xE0) lo = 0xA0; if (b == 0xED) hi = 0x9F; }
+        else if (b >= 0xF0 && b <= 0xF4) { need = 3; if (b == 0xF0) lo = 0x90; if (b == 0xF4) hi = 0x8F; }
+        size_t got = 0;
+        while (need && got < need && i + 1 + got < n) {
+            const uint8_t c = s[i + 1 + got];
+            if (c < (got == 0 ? lo : 0x80) || c > (got == 0 ? hi : 0xBF)) break;
+            ++got;
+        }
+        if (need && got == need) out.append(reinterpret_cast<const char *>(s + i), need + 1);
+        else out += "\xEF\xBF\xBD";
+        i += 1 + got;
+    }
+    return out;
+}
+
+const char *color_type_name(uint32_t ct) // {:?} of PngColorType
+{
+    return ct == CT_GRAY ? "Grayscale" : ct == CT_RGB ? "Rgb" : ct == CT_INDEXED ? "Indexed" : ct == CT_GRAY_ALPHA ? "GrayscaleAlpha" : "Rgba";
+}
+
+struct PngFile {
+    bool has_ihdr = false, has_plte = false, has_trns = false;
+    uint32_t width = 0, height = 0;
+    uint8_t depth = 0, color_type = 0, compression = 0, filter = 0, interlace = 0;
+    const uint8_t *plte = nullptr, *trns = nullptr;
+    uint32_t plte_entries = 0, trns_len = 0;
+    // the IDAT bodies: one chunk is read where it lies, several are joined
+    const uint8_t *idat = nullptr;
+    size_t idat_len = 0, idat_chunks = 0;
+    std::vector<uint8_t> joined;
+
+    uint8_t out_color_type() const // png.rs:271-283
+    {
+        if (color_type == CT_GRAY) return PIXO_GRAY;
+        if (color_type == CT_GRAY_ALPHA) return PIXO_GRAY_ALPHA;
+        if (color_type == CT_RGBA) return PIXO_RGBA;
+        return color_type == CT_INDEXED && has_trns && trns_has_alpha(trns, trns_len) ? PIXO_RGBA : PIXO_RGB;
+    }
+    uint64_t row_bytes() const { return pixo_pngu::row_bytes(color_type, depth, width); }
+    size_t pixel_bytes() const { return static_cast<size_t>(width) * height * bytes_per_pixel(out_color_type()); }
+};
+
+// The walk (png.rs:102-205) and the checks behind it up to "no IDAT data" (:207-260).  join: the IDAT bodies are wanted.
+int png_walk(const uint8_t *data, size_t len, bool join, PngFile &f)
+{
+    static const uint8_t kSignature[8] = {0x89, 0x50, 0x4E, 0x47, 0x0D, 0x0A, 0x1A, 0x0A};
+    if (len < 8 || std::memcmp(data, kSignature, 8) != 0) return invalid("not a PNG file");
+    size_t pos = 8;
+    bool seen_iend = false;
+    while (pos + 12 <= len) {
+        const size_t length = be32(data + pos);
+        const uint8_t *type = data + pos + 4, *body = data + pos + 8;
+        if (length > len - pos - 12) return invalid("truncated PNG chunk"); // (pos + 12 <= len)
+        if (be32(body + length) != crc32_fast(type, 4 + length)) return invalid("CRC mismatch in " + utf8_lossy(type, 4) + " chunk");
+        if (!std::memcmp(type, "IHDR", 4)) {
+            if (length != 13) return invalid("invalid IHDR length");
+            const uint8_t ct = body[9];
+            if (ct != CT_GRAY && ct != CT_RGB && ct != CT_INDEXED && ct != CT_GRAY_ALPHA && ct != CT_RGBA)
+                return invalid("invalid PNG color type: " + std::to_string(ct));
+            f.has_ihdr = true;
+            f.width = be32(body); f.height = be32(body + 4);
+            f.depth = body[8]; f.color_type = ct; f.compression = body[10]; f.filter = body[11]; f.interlace = body[12];
+        } else if (!std::memcmp(type, "PLTE", 4)) {
+            if (length % 3 != 0) return invalid("invalid PLTE length");
+            f.has_plte = true; f.plte = body; f.plte_entries = static_cast<uint32_t>(length / 3);
+        } else if (!std::memcmp(type, "tRNS", 4)) {
+            f.has_trns = true; f.trns = body; f.trns_len = static_cast<uint32_t>(length);
+        } else if (!std::memcmp(type, "IDAT", 4)) {
+            if (join && length) {
+                if (f.idat_chunks == 1) f.joined.assign(f.idat, f.idat + f.idat_len);
+                if (f.idat_chunks >= 1) f.joined.insert(f.joined.end(), body, body + length);
+                else f.idat = body;
+                ++f.idat_chunks;
+            }
+            f.idat_len += length;
+        } else if (!std::memcmp(type, "IEND", 4)) {
+            seen_iend = true;
+            break;
+        }
+        pos += 12 + length;
+    }
+    if (f.idat_chunks > 1) f.idat = f.joined.data();
+    if (!seen_iend) return invalid("missing IEND chunk");
+    if (!f.has_ihdr) return invalid("missing IHDR chunk");
+    if (f.width == 0 || f.height == 0) return bad_dimensions(f.width, f.height);
+    const uint32_t M = 1u << 24;
+    if (f.width > M || f.height > M) return too_large(f.width, f.height, M);
+    if (f.compression != 0) return invalid("unsupported compression method");
+    if (f.filter != 0) return invalid("unsupported filter method");
+    if (f.interlace != 0) return unsupported("Adam7 interlaced images not supported");
+    if (!depth_valid(f.color_type, f.depth))
+        return invalid("invalid bit depth " + std::to_string(f.depth) + " for color type " + color_type_name(f.color_type));
+    if (f.idat_len == 0) return invalid("no IDAT data");
+    return PIXO_OK;
+}
+
+int inflate_status(pixo_inflate::Kind k, const std::string &msg)
+{
+    return k == pixo_inflate::OK ? PIXO_OK : k == pixo_inflate::UNSUPPORTED ? unsupported(msg) : invalid(msg);
+}
+
+// The rows that do not read the row above (row 0, filter None or Sub) cut the image into segments; consecutive segments are
+// joined into runs of at least kUnfilterPassRows rows (a run of short segments fills a wavefront's lanes), a run per workgroup.
+struct Runs {
+    std::vector<uint32_t> pairs; // (first row, rows)
+    uint64_t segments = 0, longest_segment = 0;
+};
+// *bad_row: the first row whose filter byte is above 4 (height: none)
+Runs find_runs(const uint8_t *stream, uint32_t height, uint64_t row_bytes, uint32_t *bad_row)
+{
+    Runs r;
+    *bad_row = height;
+    uint32_t run_at = 0, seg_at = 0;
+    for (uint32_t y = 0; y < height; ++y) {
+        const uint8_t ft = stream[static_cast<size_t>(y) * (row_bytes + 1)];
+        if (ft > FILTER_PAETH) { *bad_row = y; return r; }
+        if (y > 0 && ft <= FILTER_SUB) {
+            ++r.segments;
+            r.longest_segment = std::max<uint64_t>(r.longest_segment, y - seg_at);
+            seg_at = y;
+            if (y - run_at >= pixo_dev::kUnfilterPassRows) {
+                r.pairs.push_back(run_at);
+                r.pairs.push_back(y - run_at);
+                run_at = y;
+            }
+        }
+    }
+    ++r.segments;
+    r.longest_segment = std::max<uint64_t>(r.longest_segment, height - seg_at);
+    r.pairs.push_back(run_at);
+    r.pairs.push_back(height - run_at);
+    return r;
+}
+
+struct DecodeStats { // of the calling thread's last decode (tools/png_decode_timing.py)
+    uint64_t segments = 0, longest_segment = 0, runs = 0;
+    double walk_ms = 0, inflate_ms = 0, runs_ms = 0, upload_ms = 0, unfilter_ms = 0, convert_ms = 0;
+};
+thread_local DecodeStats t_stats;
+struct Legs { // timed: events around the three device legs
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Legs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Everything behind the walk: inflate into the context's pinned buffer, the checks that need the stream, upload, the two kernels
+// on `s`, the pixels left at d_out (device memory of f.pixel_bytes() bytes).  Enqueue only; c.u_done is recorded behind the job.
+int decode_on_device(Context &c, const PngFile &f, uint8_t *d_out, hipStream_t s, Legs *legs = nullptr)
+{
+    const uint64_t row = f.row_bytes(), pitch = pixo_dev::unfilter_pitch(row);
+    const size_t expected = static_cast<size_t>(f.height) * (row + 1); // (2^24 rows of at most 2^27 + 1 bytes: fits 64 bits)
+    // the job before may still be reading the pinned buffers this one is about to write
+    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(c.u_done));
+    int rc;
+    if ((rc = c.u_inflated.reserve(expected))) return rc;
+    uint8_t *stream = c.u_inflated.as<uint8_t>();
+    auto t0 = std::chrono::steady_clock::now();
+    std::string msg;
+    if ((rc = inflate_status(pixo_inflate::inflate_zlib(f.idat, f.idat_len, stream, expected, &msg), msg))) return rc;
+    t_stats.inflate_ms = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    uint32_t bad_row = 0;
+    const Runs runs = find_runs(stream, f.height, row, &bad_row);
+    if (bad_row < f.height) return invalid("invalid filter type: " + std::to_string(stream[static_cast<size_t>(bad_row) * (row + 1)]));
+    if (f.color_type == CT_INDEXED && !f.has_plte) return invalid("missing PLTE chunk");
+    t_stats.runs_ms = ms_since(t0);
+    t_stats.segments = runs.segments; t_stats.longest_segment = runs.longest_segment; t_stats.runs = runs.pairs.size() / 2;
+
+    // everything is reserved before any address is handed out
+    const size_t table_bytes = 256 * sizeof(uint32_t), runs_bytes = runs.pairs.size() * sizeof(uint32_t);
+    if ((rc = c.u_stream.reserve(pixo_dev::unfilter_stream_alloc(f.height, row))) || (rc = c.u_rows.reserve(static_cast<size_t>(f.height) * pitch)) ||
+        (rc = c.h_utables.reserve(table_bytes + runs_bytes)) || (rc = c.u_tables.reserve(table_bytes + runs_bytes)))
+        return rc;
+    uint32_t *tables = c.h_utables.as<uint32_t>();
+    const bool rgba = f.out_color_type() == PIXO_RGBA;
+    for (uint32_t i = 0; i < 256; ++i) // (tRNS counts only where it holds a value other than 255: png.rs:501)
+        tables[i] = f.color_type == CT_INDEXED ? palette_rgba(f.plte, f.plte_entries, f.trns, rgba ? f.trns_len : 0, i) : 0;
+    std::memcpy(tables + 256, runs.pairs.data(), runs_bytes);
+
+    if (legs) for (hipEvent_t &e : legs->e) HIP_TRY(hipEventCreate(&e));
+    if (legs) HIP_TRY(hipEventRecord(legs->e[0], s));
+    HIP_TRY(hipMemcpyAsync(c.u_stream.p, stream, expected, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(c.u_tables.p, tables, table_bytes + runs_bytes, hipMemcpyHostToDevice, s));
+    if (legs) HIP_TRY(hipEventRecord(legs->e[1], s));
+    pixo_dev::UnfilterArgs u;
+    u.stream = c.u_stream.as<uint8_t>(); u.rows = c.u_rows.as<uint8_t>();
+    u.row_bytes = row; u.pitch = pitch; u.bpp = filter_unit(f.color_type, f.depth);
+    u.runs = c.u_tables.as<uint32_t>() + 256; u.n_runs = static_cast<uint32_t>(runs.pairs.size() / 2);
+    HIP_TRY(pixo_dev::launch_png_unfilter(u, s));
+    if (legs) HIP_TRY(hipEventRecord(legs->e[2], s));
+    pixo_dev::UnconvertArgs v;
+    v.rows = u.rows; v.pitch = pitch; v.out = d_out; v.width = f.width; v.height = f.height;
+    v.form = convert_of(f.color_type, f.depth); v.depth = f.depth; v.out_bpp = bytes_per_pixel(f.out_color_type());
+    v.table = c.u_tables.as<uint32_t>();
+    HIP_TRY(pixo_dev::launch_png_convert(v, s));
+    if (legs) HIP_TRY(hipEventRecord(legs->e[3], s));
+    HIP_TRY(hipEventRecord(c.u_done, s));
+    return PIXO_OK;
+}
+
+void report(const PngFile &f, uint32_t *width, uint32_t *height, uint8_t *color_type)
+{
+    *width = f.width; *height = f.height; *color_type = f.out_color_type();
+}
+
+// Host file -> a block of the pinned pool the caller owns
+int decode_to_block(const uint8_t *file, size_t len, uint8_t **pixels, size_t *pixels_len, uint32_t *width, uint32_t *height, uint8_t *color_type,
+                    double *legs_ms)
+{
+    PngFile f;
+    auto t0 = std::chrono::steady_clock::now();
+    int rc = png_walk(file, len, true, f);
+    if (rc) return rc;
+    t_stats.walk_ms = ms_since(t0);
+    PIXO_THREAD_CONTEXT(c);
+    const size_t n = f.pixel_bytes();
+    if ((rc = reserve16(c.u_out, n))) return rc;
+    Legs legs;
+    if ((rc = decode_on_device(c, f, c.u_out.as<uint8_t>(), c.stream, legs_ms ? &legs : nullptr))) return rc;
+    uint8_t *block = pool_take(n);
+    if (!block) block = alloc_file(n);
+    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    hipError_t e = hipMemcpyAsync(block, c.u_out.p, n, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { free_file(block); return hip_fail(e, "png decode"); }
+    if (legs_ms) {
+        float ms = 0;
+        for (int i = 0; i < 3; ++i) {
+            HIP_TRY(hipEventElapsedTime(&ms, legs.e[i], legs.e[i + 1]));
+            (i == 0 ? t_stats.upload_ms : i == 1 ? t_stats.unfilter_ms : t_stats.convert_ms) = ms;
+        }
+    }
+    report(f, width, height, color_type);
+    *pixels = block;
+    *pixels_len = n;
+    return PIXO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pixo_hip_png_decode(const uint8_t *file, size_t len, uint8_t **pixels, size_t *pixels_len, uint32_t *width, uint32_t *height, uint8_t *color_type)
+{
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(pixels);
+    PIXO_REQUIRE(pixels_len);
+    PIXO_REQUIRE(width);
+    PIXO_REQUIRE(height);
+    PIXO_REQUIRE(color_type);
+    return decode_to_block(file, len, pixels, pixels_len, width, height, color_type, nullptr);
+}
+
+int pixo_hip_png_decode_info(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint8_t *color_type)
+{
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(width);
+    PIXO_REQUIRE(height);
+    PIXO_REQUIRE(color_type);
+    PngFile f;
+    const int rc = png_walk(file, len, false, f);
+    if (rc) return rc;
+    report(f, width, height, color_type);
+    return PIXO_OK;
+}
+
+int pixo_hip_png_decode_device(const uint8_t *file, size_t len, void *d_pixels, size_t capacity, uint32_t *width, uint32_t *height,
+                               uint8_t *color_type, void *stream)
+{
+    CallerStorageScope storage(d_pixels != nullptr && capacity != 0);
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(width);
+    PIXO_REQUIRE(height);
+    PIXO_REQUIRE(color_type);
+    PngFile f;
+    int rc = png_walk(file, len, true, f);
+    if (rc) return rc;
+    report(f, width, height, color_type);
+    if (capacity < f.pixel_bytes()) return too_small(f.pixel_bytes());
+    PIXO_REQUIRE(d_pixels);
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    return decode_on_device(*c, f, static_cast<uint8_t *>(d_pixels), s);
+}
+
+int pixo_hip_zlib_inflate(const uint8_t *data, size_t len, uint8_t *out, size_t expected)
+{
+    PIXO_REQUIRE(data);
+    if (expected) PIXO_REQUIRE(out);
+    std::string msg;
+    return inflate_status(pixo_inflate::inflate_zlib(data, len, out, expected, &msg), msg);
+}
+
+uint32_t pixo_hip_png_unfilter_pass_rows(void) { return pixo_dev::kUnfilterPassRows; }
+
+int pixo_hip_debug_png_decode_timed(const uint8_t *file, size_t len, double ms[7], uint64_t counts[3])
+{
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(ms);
+    PIXO_REQUIRE(counts);
+    uint8_t *pixels = nullptr;
+    size_t n = 0;
+    uint32_t w = 0, h = 0;
+    uint8_t ct = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = decode_to_block(file, len, &pixels, &n, &w, &h, &ct, ms);
+    if (rc) return rc;
+    const double whole = ms_since(t0);
+    free_file(pixels);
+    const DecodeStats &t = t_stats;
+    ms[0] = t.walk_ms; ms[1] = t.inflate_ms; ms[2] = t.runs_ms; ms[3] = t.upload_ms; ms[4] = t.unfilter_ms; ms[5] = t.convert_ms; ms[6] = whole;
+    counts[0] = t.segments; counts[1] = t.longest_segment; counts[2] = t.runs;
+    return PIXO_OK;
+}
+
+} // extern "C"

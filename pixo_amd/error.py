@@ -42,10 +42,18 @@ class BufferTooSmall(Error):
     pass
 
 
+class InvalidDecode(Error):
+    """error.rs:83-85: malformed or corrupt data, `Decode error: {msg}`."""
+
+
+class UnsupportedDecode(Error):
+    """error.rs:86-88: valid data the decoder does not implement, `Unsupported: {msg}`."""
+
+
 _BY_STATUS = {
     -1: InvalidDimensions, -2: InvalidDataLength, -3: InvalidQuality, -4: ImageTooLarge,
     -5: UnsupportedColorType, -6: CompressionError, -7: InvalidRestartInterval,
-    -8: InvalidColorArgument, -9: BufferTooSmall,
+    -8: InvalidColorArgument, -9: BufferTooSmall, -10: InvalidDecode, -11: UnsupportedDecode,
 }
 
 

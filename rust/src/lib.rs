@@ -113,6 +113,8 @@ extern "C" {
                             out_len: *mut usize) -> c_int;
     fn pixo_hip_resize_image(data: *const u8, len: usize, src_width: u32, src_height: u32, dst_width: u32, dst_height: u32,
                              color_type: u8, algorithm: u8, out: *mut *mut u8, out_len: *mut usize) -> c_int;
+    fn pixo_hip_png_decode(file: *const u8, len: usize, pixels: *mut *mut u8, pixels_len: *mut usize, width: *mut u32, height: *mut u32,
+                           color_type: *mut u8) -> c_int;
     fn pixo_hip_free(p: *mut u8);
     fn pixo_hip_copy_file(dst: *mut u8, src: *const u8, n: usize);
     fn pixo_hip_last_error() -> *const c_char;
@@ -379,6 +381,52 @@ pub mod resize {
         let mut output = Vec::new();
         resize_into(&mut output, data, options)?;
         Ok(output)
+    }
+}
+
+/// `pixo::decode` (`src/decode/png.rs`): `decode_png` with the row reconstruction and the conversion to 8-bit pixels on the
+/// device; the chunk walk, its checks and the inflate run on the host in the reference's order and with its messages.
+/// `decode_jpeg` is not provided.
+pub mod decode {
+    use super::*;
+
+    /// `src/decode/png.rs:18-28`
+    #[derive(Debug, Clone)]
+    pub struct PngImage {
+        pub width: u32,
+        pub height: u32,
+        pub pixels: Vec<u8>,
+        pub color_type: ColorType,
+    }
+
+    /// `pixo::decode::decode_png(data)` (`src/decode/png.rs:101`)
+    pub fn decode_png(data: &[u8]) -> Result<PngImage> {
+        let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
+        let (mut width, mut height, mut ct) = (0u32, 0u32, 0u8);
+        let rc = unsafe { pixo_hip_png_decode(data.as_ptr(), data.len(), &mut p, &mut n, &mut width, &mut height, &mut ct) };
+        if rc != 0 {
+            let msg = last_error();
+            return Err(match rc {
+                -10 => Error::InvalidDecode(msg.trim_start_matches("Decode error: ").to_string()),
+                -11 => Error::UnsupportedDecode(msg.trim_start_matches("Unsupported: ").to_string()),
+                // the two variants with fields: the dimensions are the text's "WxH"
+                -1 | -4 => {
+                    let dims = msg.split(|c: char| !(c.is_ascii_digit() || c == 'x')).find(|t| t.contains('x') && t.len() > 2).unwrap_or("0x0");
+                    let mut it = dims.split('x').map(|v| v.parse::<u32>().unwrap_or(0));
+                    let (w, h) = (it.next().unwrap_or(0), it.next().unwrap_or(0));
+                    if rc == -1 { Error::InvalidDimensions { width: w, height: h } } else { Error::ImageTooLarge { width: w, height: h, max: 1 << 24 } }
+                }
+                _ => Error::CompressionError(msg.trim_start_matches("Compression error: ").to_string()),
+            });
+        }
+        let mut pixels = Vec::<u8>::with_capacity(n);
+        unsafe {
+            pixo_hip_copy_file(pixels.as_mut_ptr(), p, n);
+            pixels.set_len(n);
+            pixo_hip_free(p);
+        }
+        let color_type = match ct { 0 => ColorType::Gray, 1 => ColorType::GrayAlpha, 2 => ColorType::Rgb, _ => ColorType::Rgba };
+        Ok(PngImage { width, height, pixels, color_type })
     }
 }
 
