@@ -195,8 +195,12 @@ namespace filter {
 }
 } // namespace filter
 
+// PngOptions::flags: the device DEFLATE's denser effort for the whole-file entries (pixo_hip.h, PIXO_PNG_EFFORT_HIGH)
+constexpr uint32_t kEffortHigh = PIXO_PNG_EFFORT_HIGH;
+
 // The fields of pixo::png::PngOptions (src/png/mod.rs:41-100).  compression_level selects the zlib header's FLEVEL; the
-// device DEFLATE has one effort, so optimal_compression compresses the same way (pixo_hip.h).
+// device DEFLATE has two efforts, but neither knob of the reference selects one: optimal_compression compresses the default
+// way, and the denser effort is flags = kEffortHigh.
 enum class QuantizationMode : uint8_t { Off = PIXO_PNG_QUANT_OFF, Auto = PIXO_PNG_QUANT_AUTO, Force = PIXO_PNG_QUANT_FORCE };
 // pixo::png::QuantizationOptions: Off, 256 colours, no dithering by default
 struct QuantizationOptions {
@@ -211,7 +215,7 @@ struct PngOptions {
     uint8_t compression_level = 2;
     FilterStrategy filter_strategy = FilterStrategy::AdaptiveFast;
     bool optimize_alpha = false, reduce_color_type = false, strip_metadata = false, reduce_palette = false, optimal_compression = false;
-    uint32_t flags = 0; // PIXO_PNG_NO_RAYON
+    uint32_t flags = 0; // PIXO_PNG_NO_RAYON | kEffortHigh (the latter read by the whole-file entries)
     QuantizationOptions quantization; // travels beside pixo_png_options (pixo_png_quantization)
 
     // mod.rs:129-198

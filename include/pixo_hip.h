@@ -201,6 +201,9 @@ enum pixo_png_filter_strategy {
 /* flags */
 #define PIXO_PNG_NO_RAYON 1u /* semantics of a build without the `parallel` feature (wasm): AdaptiveFast is
                                  always the sequential, stateful variant (src/png/filter.rs:147-167) */
+#define PIXO_PNG_EFFORT_HIGH 2u /* whole-file entries only (pixo_hip_png_encode*): the device DEFLATE's second, denser
+                                   effort — hash chains and a one-step lazy parse — for smooth content such as screenshots,
+                                   charts and gradients; see "PNG whole files" below.  Not a reference option. */
 
 /* Replaces pixo::png::filter::apply_filters (src/png/filter.rs:51-206) and the Adler-32 the zlib
  * wrapper computes over its result (src/simd/fallback.rs:8-25, src/compress/deflate.rs:1044):
@@ -242,8 +245,10 @@ uint32_t pixo_hip_png_adler32_from_row_sums(const uint64_t *row_sums, uint32_t w
 
 /* The fields of pixo::png::PngOptions (mod.rs:64-100).  The prepare entries read the ones that shape the prepared stream.
  * pixo_hip_png_encode also reads compression_level: clamped to 1..9, it selects the FLEVEL bits of the zlib header as in the
- * reference.  The device compressor has ONE effort: optimal_compression is accepted and compresses the same way, and
- * strip_metadata changes nothing, because the files written here hold no chunk it would strip. */
+ * reference.  The device compressor has TWO efforts, and the reference's knobs select neither: compression_level and
+ * optimal_compression are accepted and compress the default way at every value, because that keeps every existing
+ * caller's bytes; the denser effort is asked for with PIXO_PNG_EFFORT_HIGH in flags.  strip_metadata changes nothing,
+ * because the files written here hold no chunk it would strip. */
 typedef struct pixo_png_options {
     uint32_t width;
     uint32_t height;
@@ -255,7 +260,7 @@ typedef struct pixo_png_options {
     uint8_t compression_level;
     uint8_t optimal_compression;
     uint8_t strip_metadata;
-    uint32_t flags;            /* PIXO_PNG_NO_RAYON */
+    uint32_t flags;            /* PIXO_PNG_NO_RAYON | PIXO_PNG_EFFORT_HIGH (the latter read by the whole-file entries only) */
 } pixo_png_options;
 
 /* PngOptions::{fast,balanced,max,from_preset} (mod.rs:129-198): 0 fast, 2 max, every other value balanced.
@@ -313,6 +318,19 @@ int pixo_hip_zlib_compress(const uint8_t *data, size_t len, uint8_t level, uint3
  * above, 8 for len == 0 (PIXO_ERR_BUFFER_TOO_SMALL with *out_len = that size otherwise).  Synchronous. */
 int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row,
                                   void *d_out, size_t capacity, size_t *out_len);
+/* The two entries above with the effort of the match search named: 0 is theirs (the latest occurrence of a 4-byte hash,
+ * greedy parse), 1 the high effort PIXO_PNG_EFFORT_HIGH selects for whole files: up to `probes` earlier occurrences along a
+ * hash chain, linked in sub-steps of `substep` positions, and a one-step lazy parse.  Slower (about twice the
+ * time), needs 3 more bytes of device memory per input byte for the links, and writes smooth content much smaller; photographs
+ * and noise change by a few percent at the most (INTEGRATION.md has the measured ranges).  The contract above (inflates to the input, deterministic, stored bound, one byte-aligned block
+ * per 65,535 bytes) holds for both.  Any other effort: PIXO_ERR_INVALID_COLOR_ARG ("Invalid DEFLATE effort: ..."), before
+ * any device work. */
+int pixo_hip_zlib_compress_effort(const uint8_t *data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row,
+                                  uint32_t effort, uint8_t **out, size_t *out_len);
+int pixo_hip_zlib_compress_effort_device(const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row,
+                                         uint32_t effort, void *d_out, size_t capacity, size_t *out_len);
+/* The high effort's two constants (png_deflate.hpp), for tests and models.  Either pointer may be NULL.  No GPU needed. */
+void pixo_hip_png_deflate_effort_params(uint32_t *substep, uint32_t *probes);
 /* pixo::png::encode_with_options: pixels in, a finished PNG file out.  Prepare, DEFLATE, compaction and CRC-32 run
  * without the stream leaving the device; only the finished file is copied out.  Checks: those of pixo_hip_png_prepare, in
  * the same order. */

@@ -62,7 +62,8 @@ SYMBOLS = [
     "pixo_hip_jpeg_coeffs_device", "pixo_hip_jpeg_coeffs_integer", "pixo_hip_jpeg_coeffs_integer_device", "pixo_hip_jpeg_entropy_encode", "pixo_hip_jpeg_entropy_encode_device",
     "pixo_hip_jpeg_encode_device", "pixo_hip_jpeg_encode_device_into", "pixo_hip_jpeg_encode_batch_device", "pixo_hip_jpeg_encode_batch_device_into", "pixo_hip_debug_lookback_fallbacks", "pixo_hip_debug_routes", "pixo_hip_debug_dispatch_gate", "pixo_hip_debug_stream_copy", "pixo_hip_debug_stream_io", "pixo_hip_debug_engine_clock", "pixo_hip_debug_scan_device_async", "pixo_hip_debug_scan_device_async_batch", "pixo_hip_png_filter", "pixo_hip_png_filter_device", "pixo_hip_png_filter_async",
     "pixo_hip_png_adler32_from_row_sums", "pixo_hip_png_options_from_preset", "pixo_hip_png_prepare", "pixo_hip_png_prepare_device",
-    "pixo_hip_png_palette_order", "pixo_hip_zlib_compress", "pixo_hip_zlib_compress_device", "pixo_hip_png_encode",
+    "pixo_hip_png_palette_order", "pixo_hip_zlib_compress", "pixo_hip_zlib_compress_device", "pixo_hip_zlib_compress_effort", "pixo_hip_zlib_compress_effort_device",
+    "pixo_hip_png_deflate_effort_params", "pixo_hip_png_encode",
     "pixo_hip_png_encode_device", "pixo_hip_png_quantize", "pixo_hip_png_quantize_device", "pixo_hip_png_encode_lossy",
     "pixo_hip_png_encode_lossy_device", "pixo_hip_debug_png_dither_stats", "pixo_hip_png_median_cut", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
     "pixo_hip_resize_contributions", "pixo_hip_png_decode", "pixo_hip_png_decode_info", "pixo_hip_png_decode_device", "pixo_hip_zlib_inflate",
@@ -161,6 +162,11 @@ def load():
     L.pixo_hip_png_palette_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.pixo_hip_zlib_compress.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, u8pp, szp]
     L.pixo_hip_zlib_compress_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, szp]
+    if hasattr(L, "pixo_hip_zlib_compress_effort"):  # (absent from A/B builds of older trees: tools/ab/)
+        L.pixo_hip_zlib_compress_effort.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_uint32, u8pp, szp]
+        L.pixo_hip_zlib_compress_effort_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, szp]
+        L.pixo_hip_png_deflate_effort_params.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pixo_hip_png_deflate_effort_params.restype = None
     L.pixo_hip_png_encode.argtypes = [C.c_void_p, C.c_size_t, poptp, u8pp, szp]
     L.pixo_hip_png_encode_device.argtypes = [C.c_void_p, poptp, u8pp, szp]
     qoptp, u32p = C.POINTER(PngQuantizationC), C.POINTER(C.c_uint32)

@@ -236,6 +236,7 @@ struct Context {
     // device DEFLATE (png_encode_api.cpp, png_deflate.hip)
     Buf z_tok{Buf::Mem::Device, Buf::Grow::Exact};   // a token per input byte, 65,536 u32 per chunk
     Buf z_slots{Buf::Mem::Device, Buf::Grow::Exact}; // a slot per chunk: its block before compaction
+    Buf z_prev{Buf::Mem::Device, Buf::Grow::Exact};  // high effort only: a u16 link per position of every chunk and of its window
     Buf z_info;                                      // per chunk: block bytes, form, Adler sums; behind them the blocks' offsets (u64)
     Buf z_stream;                                    // the zlib stream: plain, or as IDAT bodies with room for their frames
     Buf z_crc;                                       // CRC-32 of every 4 KiB piece of the stream

@@ -11,6 +11,14 @@
 //      every lane walks its own segment from the entry it was given — tokens compacted in place, histograms by LDS atomics;
 //   3. code lengths (literal/length and distance trees on one lane each), dynamic header, sizes of the three forms;
 //   4. token bit lengths, exclusive scan, LSB-first packing into LDS with atomicOr, vector stores to the slot.
+// The high effort (template argument) replaces step 1 and changes the next[] of step 2; steps 2 to 4 are the same code:
+//   1a. links: the window and the chunk are walked in sub-steps of kZEffortSubstep positions by ONE wavefront (the hashes
+//       of 16,384 positions at a time are put into LDS by all lanes first): every position reads the head of its hash,
+//       then every position of the sub-step inserts itself; the distance to the head seen is the position's link, a
+//       u16 in global memory.  Links depend on hashes only, never on match lengths;
+//   1b. every position in parallel, as in step 1: distance 1, hint_bpp, up to kZEffortProbes entries along the links, hint_row;
+//   1c. one-step lazy: a position whose successor has a strictly longer match becomes a literal, so next[p] = p + 1 there
+//       and step 2 runs on the tokens as they then are.
 // Only vector stores write device memory.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +29,8 @@ using namespace pixo_pngz;
 
 namespace {
 constexpr uint32_t kThreads = 1024, kSeg = 64, kHashBits = 14, kNoEntry = 0xFFFF;
+constexpr uint32_t kLinkPiece = 16384, kNoHash = 0xFFFF; // high effort: positions whose hashes LDS holds at a time
+static_assert(kLinkPiece % kZEffortSubstep == 0 && kLinkPiece % kThreads == 0 && kWindow % kLinkPiece == 0, "whole sub-steps per piece");
 static_assert(kThreads * kSeg >= kZChunk, "a lane per segment");
 
 __device__ __forceinline__ uint32_t load_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
@@ -45,6 +55,10 @@ struct ChunkShared {
         uint32_t hash[1u << kHashBits]; // position - window start + 1 of the latest occurrence, 0: none
         uint16_t exit[65536];           // parse: where the path from p leaves p's segment
         uint32_t out[32768];            // the block being packed
+        struct {
+            uint32_t head[1u << kHashBits]; // the same table as `hash`
+            uint16_t hash_of[kLinkPiece];   // high effort, links: the hash of every position of the piece, kNoHash: none
+        } link;
     } big;
     uint16_t entry[kThreads];
     uint32_t scan[kThreads];
@@ -58,9 +72,11 @@ struct ChunkShared {
     uint32_t mode, header_bits, block_bytes;
 };
 
+template <bool kHigh>
 __global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *__restrict__ data, uint64_t len, uint32_t hint_bpp,
                                                                  uint32_t hint_row, uint32_t *__restrict__ tok_all,
-                                                                 uint8_t *__restrict__ slots, ZChunkInfo *__restrict__ info)
+                                                                 uint8_t *__restrict__ slots, ZChunkInfo *__restrict__ info,
+                                                                 uint16_t *__restrict__ prev_all)
 {
     __shared__ ChunkShared s;
     const uint32_t tid = threadIdx.x;
@@ -84,42 +100,117 @@ __global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *
         for (int off = 32; off; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
         if ((tid & 63) == 0) { atomicAdd(&s.sum_a, a); atomicAdd(&s.sum_b, b); }
     }
-    // the window in front of the chunk
-    for (uint64_t a = wstart + tid; a < c0; a += kThreads)
-        if (a + 4 <= len) atomicMax(&s.big.hash[hash4(load_u32(data + a))], static_cast<uint32_t>(a - wstart) + 1);
-    __syncthreads();
-
-    // ---- 1. the best match at every position ----
-    for (uint32_t base = 0; base < n; base += kThreads) {
-        const uint32_t p = base + tid;
-        const bool active = p < n;
-        const uint64_t a = c0 + p;
-        uint32_t best_len = 0, best_dist = 0, hv = 0;
-        bool hashed = false;
-        if (active) {
-            const uint32_t max_len = n - p < kMaxMatch ? n - p : kMaxMatch;
-            uint32_t cand = 0;
-            if (p + 4 <= n) { hashed = true; hv = hash4(load_u32(data + a)); cand = s.big.hash[hv]; }
-            auto attempt = [&](uint64_t d) {
-                if (d == 0 || d > kWindow || d > a || best_len == max_len) return;
-                const uint32_t l = match_length(data + a, data + a - d, max_len);
-                if (l > best_len || (l == best_len && d < best_dist)) { best_len = l; best_dist = static_cast<uint32_t>(d); }
-            };
-            if (max_len >= kMinMatch) {
-                attempt(1);
-                if (hint_bpp > 1) attempt(hint_bpp);
-                if (cand) attempt(a - (wstart + cand - 1));
-                if (hint_row > 1 && hint_row != hint_bpp) attempt(hint_row);
-            }
-            if (best_len < kMinMatch || (best_len == kMinMatch && best_dist > 4096)) best_len = 0; // dearer than its literals
-        }
-        __syncthreads(); // every lane of the sub-step has looked up
-        if (hashed) atomicMax(&s.big.hash[hv], static_cast<uint32_t>(a - wstart) + 1);
-        if (active) tok[p] = best_len ? token_match(best_len, best_dist) : data[a];
+    if constexpr (kHigh) {
+        const uint32_t wlen = static_cast<uint32_t>(c0 - wstart), total = wlen + n; // 0 or kWindow; <= kZPrevStride
+        uint16_t *prev = prev_all + chunk * kZPrevStride;
         __syncthreads();
-    }
+        // ---- 1a. links ----
+        for (uint32_t piece = 0; piece < total; piece += kLinkPiece) {
+            for (uint32_t i = tid; i < kLinkPiece; i += kThreads) {
+                const uint32_t r = piece + i;
+                uint32_t hv = kNoHash;
+                if (r < total) { // as in step 1: the window's positions hash while four bytes of the stream are left, the chunk's while four of the chunk are
+                    const uint64_t a = wstart + r;
+                    if (r < wlen ? a + 4 <= len : r - wlen + 4 <= n) hv = hash4(load_u32(data + a));
+                }
+                s.big.link.hash_of[i] = static_cast<uint16_t>(hv);
+            }
+            __syncthreads();
+            if (tid < 64) { // one wavefront: its LDS operations take effect in program order, so no barrier is needed between sub-steps
+                const uint32_t end = total - piece < kLinkPiece ? total - piece : kLinkPiece;
+                for (uint32_t sub = 0; sub < end; sub += kZEffortSubstep) {
+                    uint32_t hv[kZEffortSubstep / 64], seen[kZEffortSubstep / 64];
+#pragma unroll
+                    for (uint32_t j = 0; j < kZEffortSubstep / 64; ++j) {
+                        hv[j] = s.big.link.hash_of[sub + 64 * j + tid];
+                        seen[j] = hv[j] != kNoHash ? __hip_atomic_load(&s.big.link.head[hv[j]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+                    }
+                    __builtin_amdgcn_wave_barrier(); // every look-up of the sub-step is issued before its first insert
+#pragma unroll
+                    for (uint32_t j = 0; j < kZEffortSubstep / 64; ++j) {
+                        const uint32_t r = piece + sub + 64 * j + tid;
+                        if (hv[j] != kNoHash) atomicMax(&s.big.link.head[hv[j]], r + 1);
+                        if (r < total) prev[r] = static_cast<uint16_t>(chain_link(r, seen[j])); // (kWindow itself fits 16 bits)
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+            __syncthreads();
+        }
+        // ---- 1b, 1c. the best match at every position; a position gives way to a longer match at the next ----
+        for (uint32_t base = 0; base < n; base += kThreads) {
+            const uint32_t p = base + tid;
+            const bool active = p < n;
+            const uint64_t a = c0 + p;
+            uint32_t best_len = 0, best_dist = 0;
+            if (active) {
+                const uint32_t max_len = n - p < kMaxMatch ? n - p : kMaxMatch;
+                auto attempt = [&](uint64_t d) {
+                    if (d == 0 || d > kWindow || d > a || best_len == max_len) return;
+                    const uint32_t l = match_length(data + a, data + a - d, max_len);
+                    if (l > best_len || (l == best_len && d < best_dist)) { best_len = l; best_dist = static_cast<uint32_t>(d); }
+                };
+                if (max_len >= kMinMatch) {
+                    attempt(1);
+                    if (hint_bpp > 1) attempt(hint_bpp);
+                    uint32_t dist = 0;
+                    for (uint32_t k = 0; k < kZEffortProbes && best_len < max_len; ++k) {
+                        dist = chain_step(dist, prev[wlen + p - dist]);
+                        if (!dist) break;
+                        attempt(dist);
+                    }
+                    if (hint_row > 1 && hint_row != hint_bpp) attempt(hint_row);
+                }
+                best_len = kept_length(best_len, best_dist);
+            }
+            s.scan[tid] = best_len; // (0 beyond the chunk's end)
+            __syncthreads();
+            if (active) {
+                const uint32_t len_next = tid + 1 < kThreads ? s.scan[tid + 1] : 0; // the last lane's successor: settled by lane 0 of the next round
+                tok[p] = best_len && !lazy_defers(best_len, len_next) ? token_match(best_len, best_dist) : data[a];
+            }
+            __syncthreads(); // tok[base - 1] is written; s.scan is free again
+            if (tid == 0 && base && lazy_defers(token_len(tok[base - 1]), best_len)) tok[base - 1] = data[a - 1];
+        }
+        __syncthreads();
+    } else { // effort 0: step 1 as it has always been
+        // the window in front of the chunk
+        for (uint64_t a = wstart + tid; a < c0; a += kThreads)
+            if (a + 4 <= len) atomicMax(&s.big.hash[hash4(load_u32(data + a))], static_cast<uint32_t>(a - wstart) + 1);
+        __syncthreads();
 
-    // ---- 2. greedy parse ----
+        // ---- 1. the best match at every position ----
+        for (uint32_t base = 0; base < n; base += kThreads) {
+            const uint32_t p = base + tid;
+            const bool active = p < n;
+            const uint64_t a = c0 + p;
+            uint32_t best_len = 0, best_dist = 0, hv = 0;
+            bool hashed = false;
+            if (active) {
+                const uint32_t max_len = n - p < kMaxMatch ? n - p : kMaxMatch;
+                uint32_t cand = 0;
+                if (p + 4 <= n) { hashed = true; hv = hash4(load_u32(data + a)); cand = s.big.hash[hv]; }
+                auto attempt = [&](uint64_t d) {
+                    if (d == 0 || d > kWindow || d > a || best_len == max_len) return;
+                    const uint32_t l = match_length(data + a, data + a - d, max_len);
+                    if (l > best_len || (l == best_len && d < best_dist)) { best_len = l; best_dist = static_cast<uint32_t>(d); }
+                };
+                if (max_len >= kMinMatch) {
+                    attempt(1);
+                    if (hint_bpp > 1) attempt(hint_bpp);
+                    if (cand) attempt(a - (wstart + cand - 1));
+                    if (hint_row > 1 && hint_row != hint_bpp) attempt(hint_row);
+                }
+                if (best_len < kMinMatch || (best_len == kMinMatch && best_dist > 4096)) best_len = 0; // dearer than its literals
+            }
+            __syncthreads(); // every lane of the sub-step has looked up
+            if (hashed) atomicMax(&s.big.hash[hv], static_cast<uint32_t>(a - wstart) + 1);
+            if (active) tok[p] = best_len ? token_match(best_len, best_dist) : data[a];
+            __syncthreads();
+        }
+    } // effort 0
+
+    // ---- 2. parse: greedy over the tokens as they stand (the high effort has made its deferred positions literals) ----
     for (uint32_t p = tid; p < n; p += kThreads) {
         const uint32_t l = token_len(tok[p]);
         const uint32_t e = p + (l ? l : 1);
@@ -326,13 +417,13 @@ __global__ __launch_bounds__(64) void deflate_crc_kernel(const uint8_t *__restri
 }
 } // namespace
 
-hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t *d_tok,
-                                 uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream)
+hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t effort, uint32_t *d_tok,
+                                 uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream)
 {
     const uint64_t chunks = z_chunks(len);
-    if (chunks == 0 || chunks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(deflate_chunk_kernel, dim3(static_cast<uint32_t>(chunks)), dim3(kThreads), 0, stream,
-                       static_cast<const uint8_t *>(d_data), len, hint_bpp, hint_row, d_tok, d_slots, d_info);
+    if (chunks == 0 || chunks > 0x7FFFFFFFull || effort > 1 || (effort && !d_prev)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(effort ? deflate_chunk_kernel<true> : deflate_chunk_kernel<false>, dim3(static_cast<uint32_t>(chunks)), dim3(kThreads), 0, stream,
+                       static_cast<const uint8_t *>(d_data), len, hint_bpp, hint_row, d_tok, d_slots, d_info, d_prev);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(1024), 0, stream, d_info, chunks, d_offsets);

@@ -14,6 +14,17 @@ constexpr uint32_t kZSlot = 65552;        // bytes of a block's slot (chunk + 5 
 constexpr uint32_t kZTokStride = 65536;   // u32 tokens per chunk in the token scratch
 constexpr uint32_t kIdatBytes = 256 * 1024; // src/png/mod.rs:621
 constexpr uint32_t kCrcPiece = 4096;      // bytes of the stream one CRC value covers (divides kIdatBytes)
+// The high effort ("the second finder"): positions whose look-ups come before their inserts, and the
+// entries of a hash chain tried at a position.  Chosen on the MI355X from {64, 256} x {4, 8} (profiles/png_encode_timing.txt).
+#ifndef PIXO_PNG_EFFORT_SUBSTEP
+#define PIXO_PNG_EFFORT_SUBSTEP 64
+#endif
+#ifndef PIXO_PNG_EFFORT_PROBES
+#define PIXO_PNG_EFFORT_PROBES 8
+#endif
+constexpr uint32_t kZEffortSubstep = PIXO_PNG_EFFORT_SUBSTEP, kZEffortProbes = PIXO_PNG_EFFORT_PROBES;
+constexpr uint32_t kZPrevStride = 32768 + 65536; // u16 links per chunk in the link scratch: its window, then the chunk
+static_assert(kZEffortSubstep % 64 == 0 && 32768 % kZEffortSubstep == 0, "whole wavefronts; the window is whole sub-steps");
 
 struct ZChunkInfo {
     uint32_t bytes; // of the block in its slot, the trailing empty stored block included
@@ -30,8 +41,10 @@ inline uint64_t z_framed_size(uint64_t stream_len) { return stream_len + 12 * ((
 // chunk's slot; then the exclusive scan of the block lengths.  d_tok: z_chunks * kZTokStride u32; d_slots: z_chunks *
 // kZSlot bytes; d_info: z_chunks entries; d_offsets: z_chunks + 1 u64 (the last: the sum of all block bytes).
 // hint_bpp / hint_row: distances tried at every position besides 1 and the hash table's (0 or out of range: not tried).
-hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t *d_tok,
-                                 uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream);
+// effort 0: the table's latest occurrence, greedy parse (d_prev is not read).  effort 1: hash chains of kZEffortProbes entries
+// linked in sub-steps of kZEffortSubstep, one-step lazy parse; d_prev: z_chunks * kZPrevStride u16.
+hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t effort, uint32_t *d_tok,
+                                 uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream);
 // The 2 header bytes, the blocks at their final offsets and the 4 checksum bytes into d_dst.
 hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_info, const unsigned long long *d_offsets,
                                   uint64_t chunks, uint32_t header, uint32_t adler, uint8_t *d_dst, bool framed, hipStream_t stream);

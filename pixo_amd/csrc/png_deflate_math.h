@@ -49,6 +49,33 @@ PNGZ_HD uint32_t length_symbol_extra(uint32_t sym) { return sym < 265 || sym == 
 PNGZ_HD uint32_t distance_symbol_extra(uint32_t sym) { return sym < 4 ? 0u : (sym >> 1) - 1; }
 PNGZ_HD uint32_t fixed_literal_length(uint32_t sym) { return sym < 144 ? 8u : sym < 256 ? 9u : sym < 280 ? 7u : 8u; }
 
+// ---- the high-effort finder: links, chains, the lazy rule --------------------------------------------
+// Positions are counted from the start of the chunk's window.  A link is the distance from a position to the head its
+// look-up saw (head: position + 1 of the latest occurrence of the hash in earlier sub-steps, 0: none); 0 ends the chain.
+// A distance beyond the window is not kept: every later entry of the chain lies farther still.
+PNGZ_HD uint32_t chain_link(uint32_t pos, uint32_t head)
+{
+    if (!head) return 0;
+    const uint32_t d = pos + 1 - head; // head <= pos: inserted by an earlier sub-step
+    return d > kWindow ? 0 : d;
+}
+// The next entry of the chain of a position: `dist` is the distance of the entry the link was read at (0: the
+// position itself), `link` that entry's link.  -> the new entry's distance, 0: the chain ends here.
+PNGZ_HD uint32_t chain_step(uint32_t dist, uint32_t link)
+{
+    if (!link || dist + link > kWindow) return 0;
+    return dist + link;
+}
+// What a finder keeps of the best match at a position: nothing below 3 bytes, and no 3 bytes from beyond 4096.
+PNGZ_HD uint32_t kept_length(uint32_t len, uint32_t dist) { return len < kMinMatch || (len == kMinMatch && dist > 4096) ? 0 : len; }
+// One-step lazy parse: the position is given up as a literal when the next one has a strictly longer match
+// (len_next: 0 where there is none, or no next position in the chunk).
+PNGZ_HD bool lazy_defers(uint32_t len_here, uint32_t len_next) { return len_next > len_here; }
+PNGZ_HD uint32_t lazy_next(uint32_t p, uint32_t len_here, uint32_t len_next)
+{
+    return lazy_defers(len_here, len_next) ? p + 1 : p + (len_here ? len_here : 1);
+}
+
 // ---- LSB-first bit writer over bytes ---------------------------------------------------------------------------------
 struct BitWriter {
     uint8_t *p;

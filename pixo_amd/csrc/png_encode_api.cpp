@@ -46,6 +46,7 @@ struct ZlibJob {
     void *d_dst = nullptr;           // where the stream goes (null: c.z_stream)
     const uint32_t *adler = nullptr; // the checksum when the caller has it already (only the total comes down then)
     bool framed = false;             // as IDAT bodies (z_framed_size) in c.z_stream; their pieces' CRC-32 are then on the way into c.h_zinfo
+    uint32_t effort = 0;             // 0: the table's latest occurrence, greedy; 1: hash chains and a lazy parse (PIXO_PNG_EFFORT_HIGH)
 };
 int zlib_on_device(Context &c, const ZlibJob &j, uint64_t *stream_len)
 {
@@ -58,9 +59,11 @@ int zlib_on_device(Context &c, const ZlibJob &j, uint64_t *stream_len)
         return rc;
     if (!j.d_dst && (rc = c.z_stream.reserve(pixo_dev::z_framed_size(bound) + 16))) return rc;
     if (j.framed && (rc = c.z_crc.reserve(crc_bytes))) return rc;
+    if (j.effort && (rc = c.z_prev.reserve(chunks * pixo_dev::kZPrevStride * sizeof(uint16_t)))) return rc;
     auto *d_info = c.z_info.as<pixo_dev::ZChunkInfo>();
     auto *d_off = reinterpret_cast<unsigned long long *>(c.z_info.as<uint8_t>() + info_bytes);
-    HIP_TRY(pixo_dev::launch_deflate_chunks(j.d_data, j.len, j.hint_bpp, j.hint_row, c.z_tok.as<uint32_t>(), c.z_slots.as<uint8_t>(), d_info, d_off, c.stream));
+    HIP_TRY(pixo_dev::launch_deflate_chunks(j.d_data, j.len, j.hint_bpp, j.hint_row, j.effort, c.z_tok.as<uint32_t>(), j.effort ? c.z_prev.as<uint16_t>() : nullptr, c.z_slots.as<uint8_t>(), d_info, d_off,
+                                            c.stream));
     // The blocks' total, the last word of z_info, comes down: alone when the checksum is known, behind all the checksum is made from otherwise
     const size_t all = info_bytes + off_bytes, down = j.adler ? sizeof(unsigned long long) : all;
     HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, c.z_info.as<uint8_t>() + all - down, down, hipMemcpyDeviceToHost, c.stream));
@@ -79,6 +82,11 @@ int zlib_on_device(Context &c, const ZlibJob &j, uint64_t *stream_len)
         HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, c.z_crc.p, pieces * 4, hipMemcpyDeviceToHost, c.stream));
     }
     return PIXO_OK;
+}
+
+int bad_effort(uint32_t effort) // an argument out of its enumeration, as for the resize algorithm
+{
+    return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid DEFLATE effort: " + std::to_string(effort) + " (expected 0 or 1)");
 }
 
 void empty_zlib(uint8_t level, uint8_t out[8]) // deflate.rs: header, an empty fixed block, Adler-32 of nothing
@@ -143,6 +151,7 @@ int png_finish(Context &c, const pixo_png_options &o, const pixo_png_layout &lay
     ZlibJob job{c.p_out.p, len, o.compression_level, view.bpp, view.row};
     job.adler = &adler;
     job.framed = true;
+    job.effort = (o.flags & PIXO_PNG_EFFORT_HIGH) ? 1 : 0;
     uint64_t stream_len = 0;
     int rc = zlib_on_device(c, job, &stream_len);
     if (rc) return rc;
@@ -198,6 +207,13 @@ extern "C" {
 
 int pixo_hip_zlib_compress(const uint8_t *data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row, uint8_t **out, size_t *out_len)
 {
+    return pixo_hip_zlib_compress_effort(data, len, level, hint_bpp, hint_row, 0, out, out_len);
+}
+
+int pixo_hip_zlib_compress_effort(const uint8_t *data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row, uint32_t effort, uint8_t **out,
+                                  size_t *out_len)
+{
+    if (effort > 1) return bad_effort(effort);
     PIXO_REQUIRE(out);
     PIXO_REQUIRE(out_len);
     if (len == 0) {
@@ -210,7 +226,9 @@ int pixo_hip_zlib_compress(const uint8_t *data, size_t len, uint8_t level, uint3
     int rc = upload(c, c.p_in, data, len);
     if (rc) return rc;
     uint64_t n = 0;
-    if ((rc = zlib_on_device(c, ZlibJob{c.p_in.p, len, level, hint_bpp, hint_row}, &n)) || (rc = c.h_file.reserve(n))) return rc;
+    ZlibJob job{c.p_in.p, len, level, hint_bpp, hint_row};
+    job.effort = effort;
+    if ((rc = zlib_on_device(c, job, &n)) || (rc = c.h_file.reserve(n))) return rc;
     HIP_TRY(hipMemcpyAsync(c.h_file.p, c.z_stream.p, n, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     return deliver(c.h_file.as<uint8_t>(), n, out, out_len);
@@ -219,6 +237,13 @@ int pixo_hip_zlib_compress(const uint8_t *data, size_t len, uint8_t level, uint3
 int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row, void *d_out, size_t capacity,
                                   size_t *out_len)
 {
+    return pixo_hip_zlib_compress_effort_device(d_data, len, level, hint_bpp, hint_row, 0, d_out, capacity, out_len);
+}
+
+int pixo_hip_zlib_compress_effort_device(const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row, uint32_t effort, void *d_out,
+                                         size_t capacity, size_t *out_len)
+{
+    if (effort > 1) return bad_effort(effort);
     PIXO_REQUIRE(d_out);
     PIXO_REQUIRE(out_len);
     const uint64_t bound = len ? stored_bound(len) : 8; // (no input: the 8 bytes of the empty stream)
@@ -236,10 +261,18 @@ int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level,
     }
     PIXO_REQUIRE(d_data);
     uint64_t n = 0;
-    if ((rc = zlib_on_device(*c, ZlibJob{d_data, len, level, hint_bpp, hint_row, d_out}, &n))) return rc;
+    ZlibJob job{d_data, len, level, hint_bpp, hint_row, d_out};
+    job.effort = effort;
+    if ((rc = zlib_on_device(*c, job, &n))) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     *out_len = n;
     return PIXO_OK;
+}
+
+void pixo_hip_png_deflate_effort_params(uint32_t *substep, uint32_t *probes)
+{
+    if (substep) *substep = pixo_dev::kZEffortSubstep;
+    if (probes) *probes = pixo_dev::kZEffortProbes;
 }
 
 int pixo_hip_png_encode(const uint8_t *data, size_t data_len, const pixo_png_options *options, uint8_t **out, size_t *out_len)

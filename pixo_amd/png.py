@@ -24,6 +24,7 @@ class FilterStrategy(enum.IntEnum):
 
 
 NO_RAYON = 1  # flags: semantics of a reference build without the `parallel` feature
+EFFORT_HIGH = 2  # flags, read by `encode` / `encode_device`: the device DEFLATE's denser effort (hash chains, lazy parse)
 
 
 def filtered_size(width, height, bytes_per_pixel):
@@ -97,7 +98,9 @@ class QuantizationOptions:
 
 class PngOptions:
     """The fields of `pixo::png::PngOptions` (src/png/mod.rs:41-100).  `compression_level` selects the zlib header's
-    FLEVEL; the device DEFLATE has one effort, so `optimal_compression` compresses the same way.  `quantization` travels
+    FLEVEL and nothing else, and `optimal_compression` compresses the same way: the device DEFLATE has two efforts, but the
+    default one is what every value of the reference's knobs gets, so that existing callers keep their bytes.  The denser
+    effort, for smooth content (screenshots, charts, gradients), is `flags=EFFORT_HIGH`.  `quantization` travels
     beside the C struct (pixo_png_quantization): `encode` takes the lossy entries when its mode is not Off."""
 
     def __init__(self, width=0, height=0, color_type=ColorType.Rgba, compression_level=2,
@@ -265,23 +268,32 @@ def stored_bound(n):
     return n + 5 * ((n + 65534) // 65535) + 6
 
 
-def zlib_compress(data, level=6, bpp=0, row=0):
+def deflate_effort_params():
+    """-> (substep, probes) of the high effort: positions whose look-ups come before their inserts, chain entries tried."""
+    s, k = C.c_uint32(), C.c_uint32()
+    _lib.load().pixo_hip_png_deflate_effort_params(C.byref(s), C.byref(k))
+    return s.value, k.value
+
+
+def zlib_compress(data, level=6, bpp=0, row=0, effort=0):
     """Host bytes -> zlib stream (bytes), compressed on the device.  level: header bits only; bpp / row: distances the
-    match search tries besides 1 and its hash table's (0: none)."""
+    match search tries besides 1 and its hash table's (0: none); effort: 0 the default finder, 1 the high effort that
+    `EFFORT_HIGH` selects for whole files (anything else raises)."""
     L = _lib.load()
     a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
-    rc = L.pixo_hip_zlib_compress(a.ctypes.data if a.size else None, a.size, level, bpp, row, C.byref(p), C.byref(n))
+    rc = L.pixo_hip_zlib_compress_effort(a.ctypes.data if a.size else None, a.size, level, bpp, row, effort, C.byref(p), C.byref(n))
     _lib.check(rc)
     return _lib.take(L, p, n)
 
 
-def zlib_compress_device(d_data, length, d_out, capacity, level=6, bpp=0, row=0):
-    """Device bytes -> zlib stream in d_out (capacity >= stored_bound(length)); returns the stream's length."""
+def zlib_compress_device(d_data, length, d_out, capacity, level=6, bpp=0, row=0, effort=0):
+    """Device bytes -> zlib stream in d_out (capacity >= stored_bound(length)); returns the stream's length.  effort: as
+    for `zlib_compress`."""
     L = _lib.load()
 
     n = C.c_size_t()
-    rc = L.pixo_hip_zlib_compress_device(_lib.ptr(d_data), length, level, bpp, row, _lib.ptr(d_out), capacity, C.byref(n))
+    rc = L.pixo_hip_zlib_compress_effort_device(_lib.ptr(d_data), length, level, bpp, row, effort, _lib.ptr(d_out), capacity, C.byref(n))
     _lib.check(rc)
     return n.value
 

@@ -94,6 +94,9 @@ struct CPngLayout {
 }
 
 const PIXO_ERR_BUFFER_TOO_SMALL: c_int = -9;
+/// `PIXO_PNG_EFFORT_HIGH`: the bit of `pixo_png_options.flags` that asks the whole-file entries for the device DEFLATE's
+/// denser effort (hash chains, one-step lazy parse); `effort = 1` of the two zlib entries below is the same finder.
+pub const PNG_EFFORT_HIGH: u32 = 2;
 
 extern "C" {
     // include/pixo_hip.h
@@ -109,6 +112,12 @@ extern "C" {
                            out: *mut u8, out_capacity: usize, adler32: *mut u32) -> c_int;
     fn pixo_hip_png_prepare(data: *const u8, len: usize, options: *const CPngOptions, out: *mut u8, out_capacity: usize,
                             out_len: *mut usize, layout: *mut CPngLayout, adler32: *mut u32) -> c_int;
+    #[allow(dead_code)]
+    fn pixo_hip_zlib_compress_effort(data: *const u8, len: usize, level: u8, hint_bpp: u32, hint_row: u32, effort: u32,
+                                     out: *mut *mut u8, out_len: *mut usize) -> c_int;
+    #[allow(dead_code)]
+    fn pixo_hip_zlib_compress_effort_device(d_data: *const u8, len: usize, level: u8, hint_bpp: u32, hint_row: u32, effort: u32,
+                                            d_out: *mut u8, capacity: usize, out_len: *mut usize) -> c_int;
     fn pixo_hip_resize_into(output: *mut u8, capacity: usize, data: *const u8, len: usize, options: *const CResizeOptions,
                             out_len: *mut usize) -> c_int;
     fn pixo_hip_resize_image(data: *const u8, len: usize, src_width: u32, src_height: u32, dst_width: u32, dst_height: u32,
