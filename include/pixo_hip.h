@@ -218,7 +218,8 @@ int pixo_hip_png_filter(const uint8_t *data, size_t data_len, uint32_t width, ui
                         size_t out_capacity, uint32_t *adler32);
 
 /* Same on DEVICE pointers of the current HIP device (d_out: height * (row bytes + 1) bytes).
- * Synchronous: returns after the checksum has been combined. */
+ * Synchronous: returns after the checksum has been combined.  The device pointers of this and of every PNG entry below
+ * (d_data, d_pixels, d_out, d_indices) may have any alignment, and the results are the same bytes. */
 int pixo_hip_png_filter_device(const void *d_data, uint32_t width, uint32_t height, uint32_t bytes_per_pixel,
                                uint8_t strategy, uint32_t flags, void *d_out, uint32_t *adler32);
 
@@ -315,7 +316,8 @@ int pixo_hip_png_palette_order(const uint32_t *counts, const uint32_t *matrix, u
 int pixo_hip_zlib_compress(const uint8_t *data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row,
                            uint8_t **out, size_t *out_len);
 /* The same for bytes in HBM on the current HIP device, into d_out in HBM.  capacity must be at least the stored bound
- * above, 8 for len == 0 (PIXO_ERR_BUFFER_TOO_SMALL with *out_len = that size otherwise).  Synchronous. */
+ * above, 8 for len == 0 (PIXO_ERR_BUFFER_TOO_SMALL with *out_len = that size otherwise).  Synchronous.  d_data and d_out
+ * may have any alignment, and the stream is the same bytes, those of pixo_hip_zlib_compress. */
 int pixo_hip_zlib_compress_device(const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row,
                                   void *d_out, size_t capacity, size_t *out_len);
 /* The two entries above with the effort of the match search named: 0 is theirs (the latest occurrence of a 4-byte hash,
@@ -569,7 +571,7 @@ int pixo_hip_png_decode_info(const uint8_t *file, size_t len, uint32_t *width, u
  * Ordered like pixo_hip_resize_device: the upload and the kernels are enqueued on `stream` behind the work of the producer
  * stream, and the call returns without waiting for them, so the pixels can be handed on that stream to
  * pixo_hip_resize_device, pixo_hip_jpeg_encode_device or pixo_hip_png_encode_device.  Every error of pixo_hip_png_decode is
- * reported before anything is enqueued. */
+ * reported before anything is enqueued.  d_pixels may have any alignment, and the pixels are the same bytes. */
 int pixo_hip_png_decode_device(const uint8_t *file, size_t len, void *d_pixels, size_t capacity, uint32_t *width, uint32_t *height,
                                uint8_t *color_type, void *stream);
 /* Host only: `inflate_zlib_with_size(data, Some(expected))` (src/decode/inflate.rs:294-352) into `out` (`expected` bytes): the

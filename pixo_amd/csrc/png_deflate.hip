@@ -441,6 +441,7 @@ hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_in
 hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_t *d_crc, hipStream_t stream)
 {
     const uint64_t pieces = (stream_len + kCrcPiece - 1) / kCrcPiece;
+    if (reinterpret_cast<uintptr_t>(d_dst) % 4) return hipErrorInvalidValue; // word loads at d_dst + 8 + 12 k + a multiple of kCrcPiece
     hipLaunchKernelGGL(deflate_crc_kernel, dim3(static_cast<uint32_t>((pieces + 63) / 64)), dim3(64), 0, stream, d_dst, stream_len, d_crc);
     return hipGetLastError();
 }

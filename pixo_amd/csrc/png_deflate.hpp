@@ -48,7 +48,10 @@ hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint
 // The 2 header bytes, the blocks at their final offsets and the 4 checksum bytes into d_dst.
 hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_info, const unsigned long long *d_offsets,
                                   uint64_t chunks, uint32_t header, uint32_t adler, uint8_t *d_dst, bool framed, hipStream_t stream);
-// zlib.crc32 of every kCrcPiece bytes of a framed stream of stream_len bytes (d_dst + 8 is 4-byte aligned).
+// zlib.crc32 of every kCrcPiece bytes of a framed stream of stream_len bytes.  A piece is read a word at a time from
+// d_dst + 8 + 12 * (IDAT chunks in front) + a multiple of kCrcPiece: d_dst must be 4-byte aligned, or the launch is refused.
+// It is: a framed stream is only ever written to the context's own buffer, a caller's d_out gets the unframed one.
+static_assert(kCrcPiece % 4 == 0 && kIdatBytes % kCrcPiece == 0, "a CRC piece starts on a word of the framed stream and lies inside one IDAT chunk");
 hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_t *d_crc, hipStream_t stream);
 
 } // namespace pixo_dev

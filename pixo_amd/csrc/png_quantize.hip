@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void pngq_map_kernel(const uint8_t *px, u
             const uint32_t idx = (lut && (key & 255u) == 255u) ? lut[cell_of(key >> 24, (key >> 16) & 255, (key >> 8) & 255)] : nearest(pal, n, key);
             out |= idx << (8 * k);
         }
-        if (valid == 4) reinterpret_cast<uint32_t *>(index)[g] = out; // (the index image starts 16-byte aligned)
+        if (valid == 4) reinterpret_cast<uint32_t *>(index)[g] = out; // (the index image is the context's own buffer, never a caller's: launch_pngq_map refuses one that is not 4-byte aligned)
         else
             for (uint32_t k = 0; k < valid; ++k) index[first + k] = (uint8_t)(out >> (8 * k));
     }
@@ -262,6 +262,7 @@ hipError_t launch_pngq_map(const void *d_pixels, uint64_t pixels, uint32_t spp, 
                            uint8_t *d_index, hipStream_t stream)
 {
     if ((spp != 3 && spp != 4) || n == 0 || n > kMaxPalette || pixels == 0) return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(d_index) % 4) return hipErrorInvalidValue; // four indices a store; the pixels may sit anywhere
     const uint8_t *px = static_cast<const uint8_t *>(d_pixels);
     const uint32_t blocks = blocks_for((pixels + 3) / 4);
     if (spp == 4 && reinterpret_cast<uintptr_t>(px) % 4 == 0) pngq_map_kernel<true><<<blocks, kThreads, 0, stream>>>(px, pixels, spp, d_lut, d_palette, n, d_index);
