@@ -290,6 +290,29 @@ struct Prepared {
 {
     return encode(data.data(), data.size(), options);
 }
+// `batch` equally sized images back to back in `data` -> their files, each byte for byte what `encode` makes of its image:
+// one pass of filters, DEFLATE and CRC over all of them (contract: pixo_hip.h).  The options' own `quantization` is passed
+// on when it is not Off.
+[[nodiscard]] inline std::vector<std::vector<uint8_t>> encode_batch(const uint8_t *data, size_t len, const PngOptions &options, uint32_t batch)
+{
+    const pixo_png_options c = options.to_c();
+    const pixo_png_quantization q = options.quantization.to_c();
+    std::vector<uint8_t *> files(batch ? batch : 1, nullptr);
+    std::vector<size_t> lens(batch ? batch : 1, 0);
+    const int rc = pixo_hip_png_encode_batch(data, len, &c, options.quantization.mode == QuantizationMode::Off ? nullptr : &q, batch, files.data(), lens.data());
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    struct Blocks { // (released also when a copy below throws)
+        std::vector<uint8_t *> &files;
+        ~Blocks() { for (uint8_t *f : files) pixo_hip_free(f); }
+    } blocks{files};
+    std::vector<std::vector<uint8_t>> out(batch);
+    for (uint32_t i = 0; i < batch; ++i) out[i].assign(files[i], files[i] + lens[i]);
+    return out;
+}
+[[nodiscard]] inline std::vector<std::vector<uint8_t>> encode_batch(const std::vector<uint8_t> &data, const PngOptions &options, uint32_t batch)
+{
+    return encode_batch(data.data(), data.size(), options, batch);
+}
 } // namespace png
 
 namespace resize {

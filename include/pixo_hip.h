@@ -378,6 +378,33 @@ int pixo_hip_png_encode_lossy(const uint8_t *data, size_t data_len, const pixo_p
                               const pixo_png_quantization *quantization, uint8_t **out, size_t *out_len);
 int pixo_hip_png_encode_lossy_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization,
                                      uint8_t **out, size_t *out_len);
+/* ---- PNG batches: `batch` equally sized images, one pass of filters, DEFLATE and CRC ---------------- */
+
+/* pixo::png::encode_with_options for `batch` equally sized images back to back in HBM on the current HIP device, one
+ * pixo_png_options for all of them; `quantization` may be NULL (lossless).  File i is byte for byte what
+ * pixo_hip_png_encode_device — pixo_hip_png_encode_lossy_device when `quantization` is given — returns for image i with the
+ * same options: every strategy, preset, flag and colour type.  The DEFLATE, its scan, the compaction and the CRC-32 run as one
+ * launch each over all images of a sub-batch (at most 64 MiB of prepared stream and 1024 chunks of 65,535 bytes, every image
+ * counting at least one; at least one image), every image a segment no
+ * match, window or aligned word crosses; with reductions, quantisation and the sequential AdaptiveFast off, so do the filters.
+ * The reductions and the quantiser keep their own host round trips, image by image.
+ * files[i] / lens[i] receive `batch` files, each a block the caller releases with pixo_hip_free; after a failure no block
+ * stays allocated.  Checks, before the thread's context is touched: those of pixo_hip_png_encode_device on `options`, null
+ * d_pixels, batch in 1..65535, `quantization` (when given) as pixo_hip_png_encode_lossy_device checks it, null files, null lens. */
+int pixo_hip_png_encode_batch_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                                     uint32_t batch, uint8_t **files, size_t *lens);
+/* The same, the files back to back without gaps in `arena` — host memory, pageable or pinned — at offsets[i] (offsets[0] = 0),
+ * lens[i] bytes each; both arrays have `batch` entries.  When the files do not fit, offsets / lens are still filled in
+ * (capacity needed = offsets[batch - 1] + lens[batch - 1]) and PIXO_ERR_BUFFER_TOO_SMALL is returned; a null arena with
+ * capacity 0 is a size query (nothing is copied).  A PNG's size is known only after compression: a size query, and a call
+ * whose arena turns out too small, do all of the device work.  An arena that turns out too small may hold the files of the
+ * first sub-batches.  An arena in device memory is refused. */
+int pixo_hip_png_encode_batch_device_into(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                                          uint32_t batch, uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens);
+/* ... and for host pixels: data_len must be batch x width x height x bytes per pixel (checked where pixo_hip_png_encode checks
+ * its length, in front of the filter strategy). */
+int pixo_hip_png_encode_batch(const uint8_t *data, size_t data_len, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                              uint32_t batch, uint8_t **files, size_t *lens);
 /* Tests and tools: how the dither ran in this process so far — launches of the chained form, calls served band by band
  * (debug switch spin_budget=0, images of one band, or after a give-up), chained launches in which a band gave up waiting
  * (each also counts in pixo_hip_debug_lookback_fallbacks).  Null pointers are skipped. */
@@ -603,7 +630,7 @@ void *pixo_hip_get_producer_stream(void);   /* what the calling thread set (to s
  * image needed (a 16384x16384 image: ~2 GB of HBM, ~0.4 GB pinned) until it calls this. */
 int pixo_hip_trim(void);
 /* Tests and A/B tools only: replaces the debug switches read from the environment variable PIXO_HIP_DEBUG
- * ("name[=value],...": trace, host_entropy, multipass_entropy, direct_stores, one_piece, two_kernel_scan, fused_batch, no_side_stats, coef_form=scalar|packed, trellis_form=lane|group, batch_parts=n, piece_groups=n, piece_medium=n,
+ * ("name[=value],...": trace, host_entropy, multipass_entropy, direct_stores, one_piece, two_kernel_scan, fused_batch, no_side_stats, coef_form=scalar|packed, trellis_form=lane|group, batch_parts=n, png_batch_bytes=n, piece_groups=n, piece_medium=n,
  * piece_schedule=a:b:c, copy_threads=n, spin_budget=n, no_bands_upload, bands_upload_min_mb=n, bands_upload_mb=n — pixo_amd/csrc/capi_internal.hpp).  None of
  * them changes the bytes of a file.  NULL = read the environment again.  Not synchronised with calls in flight. */
 int pixo_hip_debug_configure(const char *switches_or_null);

@@ -65,7 +65,8 @@ SYMBOLS = [
     "pixo_hip_png_palette_order", "pixo_hip_zlib_compress", "pixo_hip_zlib_compress_device", "pixo_hip_zlib_compress_effort", "pixo_hip_zlib_compress_effort_device",
     "pixo_hip_png_deflate_effort_params", "pixo_hip_png_encode",
     "pixo_hip_png_encode_device", "pixo_hip_png_quantize", "pixo_hip_png_quantize_device", "pixo_hip_png_encode_lossy",
-    "pixo_hip_png_encode_lossy_device", "pixo_hip_debug_png_dither_stats", "pixo_hip_png_median_cut", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
+    "pixo_hip_png_encode_lossy_device", "pixo_hip_png_encode_batch_device", "pixo_hip_png_encode_batch_device_into", "pixo_hip_png_encode_batch",
+    "pixo_hip_debug_png_dither_stats", "pixo_hip_png_median_cut", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
     "pixo_hip_resize_contributions", "pixo_hip_png_decode", "pixo_hip_png_decode_info", "pixo_hip_png_decode_device", "pixo_hip_zlib_inflate",
     "pixo_hip_png_unfilter_pass_rows", "pixo_hip_debug_png_decode_timed", "pixo_hip_band",
     "pixo_hip_band_encoder_create", "pixo_hip_band_encoder_destroy", "pixo_hip_band_encoder_rows",
@@ -174,6 +175,10 @@ def load():
     L.pixo_hip_png_quantize_device.argtypes = [C.c_void_p, poptp, qoptp, C.c_void_p, C.c_void_p, u32p, u32p, C.POINTER(C.c_uint8)]
     L.pixo_hip_png_encode_lossy.argtypes = [C.c_void_p, C.c_size_t, poptp, qoptp, u8pp, szp]
     L.pixo_hip_png_encode_lossy_device.argtypes = [C.c_void_p, poptp, qoptp, u8pp, szp]
+    if hasattr(L, "pixo_hip_png_encode_batch_device"):  # (absent from A/B builds of older trees: tools/ab/)
+        L.pixo_hip_png_encode_batch_device.argtypes = [C.c_void_p, poptp, qoptp, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), szp]
+        L.pixo_hip_png_encode_batch_device_into.argtypes = [C.c_void_p, poptp, qoptp, C.c_uint32, C.c_void_p, C.c_size_t, szp, szp]
+        L.pixo_hip_png_encode_batch.argtypes = [C.c_void_p, C.c_size_t, poptp, qoptp, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), szp]
     L.pixo_hip_debug_png_dither_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
     L.pixo_hip_png_median_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, u32p]
     roptp = C.POINTER(ResizeOptionsC)

@@ -13,7 +13,8 @@
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
 //   png_api.cpp      the extern "C" PNG row-filter entry points
 //   png_reduce_api.cpp  the extern "C" PNG prepare entry points: png_check_options, reductions (png_reduce.hip), palette ordering, the filter
-//   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, a ZlibJob (png_deflate.hip), file head and IDAT frames
+//   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, a ZlibJob (png_deflate.hip), file head and IDAT frames;
+//                    the PNG batch entries: segments, sub-batches, the batched tail
 //   png_quantize_api.cpp  PNG lossy mode: gate, histogram and median cut on the host, the kernels of png_quantize.hip, the extern "C" quantize entries
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
 //   png_decode_api.cpp  the extern "C" PNG decode entry points: chunk walk and checks, the host inflate (png_inflate.cpp), the runs of rows,
@@ -100,6 +101,9 @@ inline int bad_length(size_t expected, size_t got)
 //   piece_schedule=a:b:c   their relative sizes (default 1:3)
 //   copy_threads=n     threads that copy finished files above 2 MB into fresh host memory (default 8)
 //   spin_budget=n      look-back kernels give up waiting after n polls (default 2^20; tests force the fallback with 0)
+//   png_batch_bytes=n  a sub-batch of pixo_hip_png_encode_batch* holds at most n bytes of prepared stream (and at least one image)
+//                      instead of 64 MiB: tests reach a sub-batch boundary with small images (the limit of 1024 chunks a sub-batch,
+//                      which bounds the scratch, stays)
 //   no_bands_upload    host pixels are uploaded in one copy instead of MCU-row bands pipelined with the kernels
 //   plain_host         no host-memory policy (for embedders that own theirs): pixo_hip_free returns every block to malloc at once
 //                      (no blocks kept for the next large file), fresh blocks are plain malloc, no madvise(MADV_HUGEPAGE) on the
@@ -120,6 +124,7 @@ struct DebugSwitches {
     unsigned copy_threads = 8;
     uint32_t spin_budget = 1u << 20;
     uint32_t batch_parts = 0; // (measurements) sub-batches of pixo_hip_jpeg_encode_batch_device_into, 0 = the library's choice
+    uint64_t png_batch_bytes = 0; // bytes of prepared stream a sub-batch of the PNG batch entries holds at most, 0 = 64 MiB
 };
 const DebugSwitches &debug();
 
@@ -573,10 +578,15 @@ int png_plan(uint32_t width, uint32_t height, uint64_t area, uint32_t bpp, uint8
 // filter kernel + checksum on the context's stream; returns after the checksum has been combined
 int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t bpp, int run, bool sequential_fast,
                          void *d_out, uint32_t *adler);
+// `batch` equal images back to back at d_in in one launch, their streams back to back at d_out; the row sums are on their way
+// to the host when this returns.  Once the stream has been synchronised, png_filter_batch_adler combines image i's.
+int png_filter_batch_begin(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t batch, uint32_t bpp, int run, void *d_out);
+uint32_t png_filter_batch_adler(const Context &c, uint32_t width, uint32_t height, uint32_t bpp, uint32_t image);
 
 // ---- PNG prepare (png_reduce_api.cpp) --------------------------------------------------------------------------------
 // The prepare and whole-file entries' checks in the reference's order; with_data: the host pixels' length too (one that passes IS the input size)
-int png_check_options(const pixo_png_options *o, bool with_data = false, size_t data_len = 0);
+// images: the data are those of a batch of so many equal images back to back
+int png_check_options(const pixo_png_options *o, bool with_data = false, size_t data_len = 0, uint32_t images = 1);
 // How the filters saw the rows (packed and palette rows: as one-byte pixels): what a match search behind them is told.
 struct PngFilterView { uint32_t bpp, row; }; // bytes per filter pixel, bytes per filtered row
 // d_px: width * height * bpp bytes on the context's device; reductions + filters, the stream is left in d_out

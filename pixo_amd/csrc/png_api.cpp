@@ -61,6 +61,22 @@ int pixo_capi::png_filter_on_device(Context &c, const void *d_in, uint32_t width
     return PIXO_OK;
 }
 
+// The batch form (png_encode_api.cpp): one launch over the rows of `batch` images, all row sums on their way down in one
+// copy.  Nothing is waited for here; png_filter_batch_adler reads the sums once the stream has been synchronised.
+int pixo_capi::png_filter_batch_begin(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t batch, uint32_t bpp, int run, void *d_out)
+{
+    const uint64_t rows = static_cast<uint64_t>(height) * batch;
+    if (rows > 0x7FFFFFFFull) return hip_fail(hipErrorInvalidValue, "rows of a PNG batch");
+    if (const int rc = reserve_sums(c, static_cast<uint32_t>(rows))) return rc;
+    HIP_TRY(pixo_dev::launch_png_filter_batch(d_in, width, height, batch, bpp, run, d_out, c.p_sums.as<unsigned long long>(), c.stream));
+    HIP_TRY(hipMemcpyAsync(c.h_sums.p, c.p_sums.p, static_cast<size_t>(rows) * 16, hipMemcpyDeviceToHost, c.stream));
+    return PIXO_OK;
+}
+uint32_t pixo_capi::png_filter_batch_adler(const Context &c, uint32_t width, uint32_t height, uint32_t bpp, uint32_t image)
+{
+    return combine_adler(c.h_sums.as<unsigned long long>() + 2 * static_cast<size_t>(image) * height, height, static_cast<uint64_t>(width) * bpp + 1);
+}
+
 namespace {
 // A large image from host pixels to caller storage, band by band (round 3).  Rows are independent once the row above is on
 // the device, so: the calling thread uploads bands of ~8 MiB back to back on the upload stream (a pageable source blocks it

@@ -72,21 +72,20 @@ struct ChunkShared {
     uint32_t mode, header_bits, block_bytes;
 };
 
+// One chunk of one stream: `data` is the stream's first byte, `len` its bytes, `chunk` the chunk's number in the stream; tok,
+// slot, info and prev are the chunk's own places in the scratch.  The stream is a whole launch's (deflate_chunk_kernel) or one
+// segment of a batch (deflate_chunk_seg_kernel): the window, `last`, the hash seeding and the links never leave it.
 template <bool kHigh>
-__global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *__restrict__ data, uint64_t len, uint32_t hint_bpp,
-                                                                 uint32_t hint_row, uint32_t *__restrict__ tok_all,
-                                                                 uint8_t *__restrict__ slots, ZChunkInfo *__restrict__ info,
-                                                                 uint16_t *__restrict__ prev_all)
+__device__ __forceinline__ void deflate_chunk(const uint8_t *__restrict__ data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint64_t chunk,
+                                              uint32_t *__restrict__ tok, uint8_t *__restrict__ slot, ZChunkInfo *__restrict__ info,
+                                              uint16_t *__restrict__ prev)
 {
     __shared__ ChunkShared s;
     const uint32_t tid = threadIdx.x;
-    const uint64_t chunk = blockIdx.x;
-    const uint64_t c0 = chunk * kZChunk;
-    const uint32_t n = static_cast<uint32_t>(len - c0 < kZChunk ? len - c0 : kZChunk); // 1..65535
-    const bool last = c0 + n == len;
-    const uint64_t wstart = c0 > kWindow ? c0 - kWindow : 0;
-    uint32_t *tok = tok_all + chunk * kZTokStride;
-    uint8_t *slot = slots + chunk * kZSlot;
+    const ChunkSpan span = chunk_span(len, chunk);
+    const uint64_t c0 = span.c0, wstart = span.wstart;
+    const uint32_t n = span.n; // 1..65535
+    const bool last = span.last;
 
     for (uint32_t i = tid; i < (1u << kHashBits); i += kThreads) s.big.hash[i] = 0;
     if (tid < kLitTable) s.lit_freq[tid] = tid == 256 ? 1u : 0u; // the end-of-block symbol
@@ -102,7 +101,6 @@ __global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *
     }
     if constexpr (kHigh) {
         const uint32_t wlen = static_cast<uint32_t>(c0 - wstart), total = wlen + n; // 0 or kWindow; <= kZPrevStride
-        uint16_t *prev = prev_all + chunk * kZPrevStride;
         __syncthreads();
         // ---- 1a. links ----
         for (uint32_t piece = 0; piece < total; piece += kLinkPiece) {
@@ -272,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *
         s.block_bytes = bytes;
         s.header_bits = mode == 2 ? head : 3;
         if (mode == 1) { s.header[0] = static_cast<uint8_t>((last ? 1u : 0u) | 2u); } // BFINAL, BTYPE = 01
-        info[chunk] = ZChunkInfo{bytes, mode, s.sum_a, s.sum_b};
+        *info = ZChunkInfo{bytes, mode, s.sum_a, s.sum_b};
     }
     __syncthreads();
     const uint32_t mode = s.mode, block_bytes = s.block_bytes;
@@ -345,6 +343,30 @@ __global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *
     for (uint32_t w = tid; w < words; w += kThreads) slot_words[w] = s.big.out[w];
 }
 
+template <bool kHigh>
+__global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *__restrict__ data, uint64_t len, uint32_t hint_bpp,
+                                                                 uint32_t hint_row, uint32_t *__restrict__ tok_all,
+                                                                 uint8_t *__restrict__ slots, ZChunkInfo *__restrict__ info,
+                                                                 uint16_t *__restrict__ prev_all)
+{
+    const uint64_t chunk = blockIdx.x;
+    deflate_chunk<kHigh>(data, len, hint_bpp, hint_row, chunk, tok_all + chunk * kZTokStride, slots + chunk * kZSlot, info + chunk,
+                         kHigh ? prev_all + chunk * kZPrevStride : nullptr);
+}
+
+// The batch form: workgroup b finds its segment in the table (png_deflate_math.h seg_of_chunk: uniform loads) and works on
+// chunk b - first_chunk of that segment's stream; the scratch is indexed by b.
+template <bool kHigh>
+__global__ __launch_bounds__(kThreads) void deflate_chunk_seg_kernel(const uint8_t *__restrict__ data, const ZSegment *__restrict__ segs, uint32_t nseg,
+                                                                     uint32_t *__restrict__ tok_all, uint8_t *__restrict__ slots,
+                                                                     ZChunkInfo *__restrict__ info, uint16_t *__restrict__ prev_all)
+{
+    const uint32_t b = blockIdx.x;
+    const ZSegment sg = segs[seg_of_chunk(segs, nseg, b)];
+    deflate_chunk<kHigh>(data + sg.src, sg.len, sg.hint_bpp, sg.hint_row, b - sg.first_chunk, tok_all + static_cast<uint64_t>(b) * kZTokStride,
+                         slots + static_cast<uint64_t>(b) * kZSlot, info + b, kHigh ? prev_all + static_cast<uint64_t>(b) * kZPrevStride : nullptr);
+}
+
 // offsets[c] = bytes of the blocks before c; offsets[chunks] = all of them
 __global__ __launch_bounds__(1024) void deflate_scan_kernel(const ZChunkInfo *__restrict__ info, uint64_t chunks, unsigned long long *__restrict__ offsets)
 {
@@ -367,20 +389,19 @@ __global__ __launch_bounds__(1024) void deflate_scan_kernel(const ZChunkInfo *__
     if (tid == 1023) offsets[chunks] = part[1023];
 }
 
-__device__ __forceinline__ uint64_t framed_offset(uint64_t s, bool framed) { return framed ? s + 8 + 12 * (s / kIdatBytes) : s; }
+__device__ __forceinline__ uint64_t framed_offset(uint64_t s, bool framed) { return framed ? seg_framed_offset(s) : s; }
 
-__global__ __launch_bounds__(256) void deflate_compact_kernel(const uint8_t *__restrict__ slots, const ZChunkInfo *__restrict__ info,
-                                                              const unsigned long long *__restrict__ offsets, uint64_t chunks, uint32_t header,
-                                                              uint32_t adler, uint8_t *__restrict__ dst, bool framed)
+// One chunk's block from its slot to stream bytes [start, end) of the destination; the stream's first chunk also writes the
+// zlib header, its last the checksum.
+__device__ __forceinline__ void compact_chunk(const uint8_t *__restrict__ src, uint64_t start, uint64_t end, bool first_chunk, bool last_chunk,
+                                              uint32_t header, uint32_t adler, uint8_t *__restrict__ dst, bool framed)
 {
     const uint32_t tid = threadIdx.x;
-    const uint64_t c = blockIdx.x;
-    const uint8_t *src = slots + c * kZSlot;
-    const uint64_t start = 2 + offsets[c], end = start + info[c].bytes;
-    if (c == 0 && tid < 2) dst[framed_offset(tid, framed)] = static_cast<uint8_t>(header >> (8 * tid));
-    if (c == chunks - 1 && tid < 4) dst[framed_offset(end + tid, framed)] = static_cast<uint8_t>(adler >> (8 * (3 - tid))); // big endian
+    if (first_chunk && tid < 2) dst[framed_offset(tid, framed)] = static_cast<uint8_t>(header >> (8 * tid));
+    if (last_chunk && tid < 4) dst[framed_offset(end + tid, framed)] = static_cast<uint8_t>(adler >> (8 * (3 - tid))); // big endian
     // stream offsets that are multiples of 4 are 4-byte aligned addresses when the destination's first one is: an aligned
-    // word never crosses an IDAT boundary (a multiple of 4) and never belongs to two blocks
+    // word never crosses an IDAT boundary (a multiple of 4) and never belongs to two blocks.  (A segment of a batch starts
+    // on a multiple of 16 of an aligned buffer, so the test and the argument hold for each segment by itself.)
     const bool aligned = (reinterpret_cast<uintptr_t>(dst + framed_offset(0, framed)) & 3) == 0;
     uint64_t first = (start + 3) & ~uint64_t{3}, lastw = end & ~uint64_t{3};
     if (!aligned || first >= lastw) first = lastw = end; // bytes only
@@ -390,30 +411,95 @@ __global__ __launch_bounds__(256) void deflate_compact_kernel(const uint8_t *__r
     for (uint64_t sb = lastw + tid; sb < end; sb += 256) dst[framed_offset(sb, framed)] = src[sb - start];
 }
 
-// Slicing by 4: one aligned word of the stream per step
-__global__ __launch_bounds__(64) void deflate_crc_kernel(const uint8_t *__restrict__ dst, uint64_t stream_len, uint32_t *__restrict__ crcs)
+__global__ __launch_bounds__(256) void deflate_compact_kernel(const uint8_t *__restrict__ slots, const ZChunkInfo *__restrict__ info,
+                                                              const unsigned long long *__restrict__ offsets, uint64_t chunks, uint32_t header,
+                                                              uint32_t adler, uint8_t *__restrict__ dst, bool framed)
 {
-    __shared__ uint32_t table[4][256];
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t i = tid; i < 256; i += 64) {
+    const uint64_t c = blockIdx.x;
+    const uint64_t start = 2 + offsets[c];
+    compact_chunk(slots + c * kZSlot, start, start + info[c].bytes, c == 0, c == chunks - 1, header, adler, dst, framed);
+}
+
+// The batch forms.  Scan: one workgroup per segment, the offsets restart at every segment (offsets[b]: the bytes of the
+// segment's blocks in front of global chunk b), totals[s]: the bytes of all blocks of segment s.
+__global__ __launch_bounds__(1024) void deflate_scan_seg_kernel(const ZChunkInfo *__restrict__ info, const ZSegment *__restrict__ segs,
+                                                                unsigned long long *__restrict__ offsets, unsigned long long *__restrict__ totals)
+{
+    __shared__ unsigned long long part[1024];
+    const uint32_t tid = threadIdx.x, sg = blockIdx.x;
+    const uint64_t base = segs[sg].first_chunk, chunks = segs[sg + 1].first_chunk - base;
+    const uint64_t per = (chunks + 1023) / 1024;
+    const uint64_t c_lo = tid * per < chunks ? tid * per : chunks, c_hi = c_lo + per < chunks ? c_lo + per : chunks;
+    unsigned long long sum = 0;
+    for (uint64_t c = c_lo; c < c_hi; ++c) sum += info[base + c].bytes;
+    part[tid] = sum;
+    __syncthreads();
+    for (uint32_t step = 1; step < 1024; step <<= 1) {
+        const unsigned long long add = tid >= step ? part[tid - step] : 0;
+        __syncthreads();
+        part[tid] += add;
+        __syncthreads();
+    }
+    unsigned long long at = part[tid] - sum;
+    for (uint64_t c = c_lo; c < c_hi; ++c) { offsets[base + c] = at; at += info[base + c].bytes; }
+    if (tid == 1023) totals[sg] = part[1023];
+}
+
+// Compaction: workgroup b moves global chunk b's block to its segment's own destination, framed.
+__global__ __launch_bounds__(256) void deflate_compact_seg_kernel(const uint8_t *__restrict__ slots, const ZChunkInfo *__restrict__ info,
+                                                                  const unsigned long long *__restrict__ offsets, const ZSegment *__restrict__ segs,
+                                                                  uint32_t nseg, uint32_t header, uint8_t *__restrict__ dst)
+{
+    const uint32_t b = blockIdx.x, sg = seg_of_chunk(segs, nseg, b);
+    const uint64_t start = 2 + offsets[b];
+    compact_chunk(slots + static_cast<uint64_t>(b) * kZSlot, start, start + info[b].bytes, b == segs[sg].first_chunk, b + 1 == segs[sg + 1].first_chunk,
+                  header, segs[sg].adler, dst + segs[sg].dst, true);
+}
+
+// Slicing by 4: one aligned word of the stream per step
+__device__ __forceinline__ void crc_tables(uint32_t (*table)[256])
+{
+    for (uint32_t i = threadIdx.x; i < 256; i += 64) {
         uint32_t v = crc32_table_entry(i);
         table[0][i] = v;
         for (int k = 1; k < 4; ++k) { v = crc32_table_entry(v & 255) ^ (v >> 8); table[k][i] = v; }
     }
     __syncthreads();
-    const uint64_t piece = static_cast<uint64_t>(blockIdx.x) * 64 + tid;
-    const uint64_t s0 = piece * kCrcPiece;
-    if (s0 >= stream_len) return;
-    const uint64_t s1 = s0 + kCrcPiece < stream_len ? s0 + kCrcPiece : stream_len;
-    const uint8_t *p = dst + framed_offset(s0, true); // a piece lies inside one IDAT chunk
-    const uint32_t nbytes = static_cast<uint32_t>(s1 - s0);
+}
+__device__ __forceinline__ uint32_t crc_of_piece(const uint8_t *p, uint32_t nbytes, const uint32_t (*table)[256])
+{
     uint32_t crc = 0xFFFFFFFFu, i = 0;
     for (; i + 4 <= nbytes; i += 4) {
         crc ^= *reinterpret_cast<const uint32_t *>(p + i);
         crc = table[3][crc & 255] ^ table[2][(crc >> 8) & 255] ^ table[1][(crc >> 16) & 255] ^ table[0][crc >> 24];
     }
     for (; i < nbytes; ++i) crc = table[0][(crc ^ p[i]) & 255] ^ (crc >> 8);
-    crcs[piece] = ~crc;
+    return ~crc;
+}
+__global__ __launch_bounds__(64) void deflate_crc_kernel(const uint8_t *__restrict__ dst, uint64_t stream_len, uint32_t *__restrict__ crcs)
+{
+    __shared__ uint32_t table[4][256];
+    crc_tables(table);
+    const uint64_t piece = static_cast<uint64_t>(blockIdx.x) * 64 + threadIdx.x;
+    uint64_t s0;
+    const uint32_t nbytes = piece_span(stream_len, piece, &s0);
+    if (!nbytes) return;
+    crcs[piece] = crc_of_piece(dst + framed_offset(s0, true), nbytes, table); // a piece lies inside one IDAT chunk
+}
+// The batch form: the grid covers every segment's pieces by its stored bound, so that the host need not know the streams'
+// lengths to launch it; a lane reads its segment's real length from the scan's totals, and pieces behind the end write nothing.
+__global__ __launch_bounds__(64) void deflate_crc_seg_kernel(const uint8_t *__restrict__ dst, const ZSegment *__restrict__ segs, uint32_t nseg,
+                                                             const unsigned long long *__restrict__ totals, uint32_t *__restrict__ crcs)
+{
+    __shared__ uint32_t table[4][256];
+    crc_tables(table);
+    const uint64_t g = static_cast<uint64_t>(blockIdx.x) * 64 + threadIdx.x;
+    if (g >= segs[nseg].first_piece) return;
+    const uint32_t sg = seg_of_piece(segs, nseg, static_cast<uint32_t>(g));
+    uint64_t s0;
+    const uint32_t nbytes = piece_span(2 + totals[sg] + 4, g - segs[sg].first_piece, &s0);
+    if (!nbytes) return;
+    crcs[g] = crc_of_piece(dst + segs[sg].dst + framed_offset(s0, true), nbytes, table);
 }
 } // namespace
 
@@ -443,6 +529,29 @@ hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_
     const uint64_t pieces = (stream_len + kCrcPiece - 1) / kCrcPiece;
     if (reinterpret_cast<uintptr_t>(d_dst) % 4) return hipErrorInvalidValue; // word loads at d_dst + 8 + 12 k + a multiple of kCrcPiece
     hipLaunchKernelGGL(deflate_crc_kernel, dim3(static_cast<uint32_t>((pieces + 63) / 64)), dim3(64), 0, stream, d_dst, stream_len, d_crc);
+    return hipGetLastError();
+}
+
+hipError_t launch_deflate_segments(const void *d_data, const ZSegment *d_segs, uint32_t nseg, uint32_t chunks, uint32_t effort, uint32_t *d_tok,
+                                   uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, hipStream_t stream)
+{
+    if (nseg == 0 || chunks == 0 || chunks > 0x7FFFFFFFu || effort > 1 || (effort && !d_prev)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(effort ? deflate_chunk_seg_kernel<true> : deflate_chunk_seg_kernel<false>, dim3(chunks), dim3(kThreads), 0, stream,
+                       static_cast<const uint8_t *>(d_data), d_segs, nseg, d_tok, d_slots, d_info, d_prev);
+    return hipGetLastError();
+}
+
+hipError_t launch_deflate_segments_finish(const uint8_t *d_slots, const ZChunkInfo *d_info, const ZSegment *d_segs, uint32_t nseg, uint32_t chunks,
+                                          uint32_t pieces, uint32_t header, unsigned long long *d_offsets, unsigned long long *d_totals,
+                                          uint8_t *d_dst, uint32_t *d_crc, hipStream_t stream)
+{
+    if (nseg == 0 || chunks == 0 || pieces == 0 || reinterpret_cast<uintptr_t>(d_dst) % kSegAlign) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(deflate_scan_seg_kernel, dim3(nseg), dim3(1024), 0, stream, d_info, d_segs, d_offsets, d_totals);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(deflate_compact_seg_kernel, dim3(chunks), dim3(256), 0, stream, d_slots, d_info, d_offsets, d_segs, nseg, header, d_dst);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(deflate_crc_seg_kernel, dim3((pieces + 63) / 64), dim3(64), 0, stream, d_dst, d_segs, nseg, d_totals, d_crc);
     return hipGetLastError();
 }
 

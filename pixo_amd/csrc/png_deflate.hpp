@@ -54,4 +54,20 @@ hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_in
 static_assert(kCrcPiece % 4 == 0 && kIdatBytes % kCrcPiece == 0, "a CRC piece starts on a word of the framed stream and lies inside one IDAT chunk");
 hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_t *d_crc, hipStream_t stream);
 
+// ---- batches: nseg streams (segments, png_deflate_math.h ZSegment) in one launch each ---------------------------------
+// d_segs: the table of nseg + 1 entries that seg_layout filled in, in device memory; d_data / d_dst: what the segments' src
+// / dst count from.  The scratch is indexed by global chunk as above (`chunks` = d_segs[nseg].first_chunk of them).
+static_assert(pixo_pngz::kSegChunk == kZChunk && pixo_pngz::kSegIdat == kIdatBytes && pixo_pngz::kSegPiece == kCrcPiece, "one set of sizes");
+static_assert(sizeof(pixo_pngz::ZSegment) == 48, "the table's layout is the same on both sides");
+// Every chunk of every segment into its slot: one workgroup per chunk, no chunk looks in front of its segment's first byte.
+hipError_t launch_deflate_segments(const void *d_data, const pixo_pngz::ZSegment *d_segs, uint32_t nseg, uint32_t chunks, uint32_t effort,
+                                   uint32_t *d_tok, uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, hipStream_t stream);
+// Scan (d_offsets: `chunks` u64, restarting at every segment; d_totals: nseg u64, each segment's block bytes), compaction
+// (every segment's header, blocks and d_segs[s].adler as IDAT bodies at d_dst + dst; d_dst 16-byte aligned) and the CRC-32
+// of every 4 KiB piece (d_crc: `pieces` = d_segs[nseg].first_piece words; segment s's values start at first_piece, those
+// behind its stream's end are not written).  d_segs[s].adler must be final by now.
+hipError_t launch_deflate_segments_finish(const uint8_t *d_slots, const ZChunkInfo *d_info, const pixo_pngz::ZSegment *d_segs, uint32_t nseg,
+                                          uint32_t chunks, uint32_t pieces, uint32_t header, unsigned long long *d_offsets,
+                                          unsigned long long *d_totals, uint8_t *d_dst, uint32_t *d_crc, hipStream_t stream);
+
 } // namespace pixo_dev

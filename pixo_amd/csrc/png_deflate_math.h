@@ -318,6 +318,83 @@ PNGZ_HD void zlib_header(uint32_t level, uint8_t out[2])
 // Bytes that always hold the zlib stream of len bytes: stored blocks of 65,535, header and checksum.
 PNGZ_HD uint64_t stored_bound(uint64_t len) { return len + 5 * ((len + 65534) / 65535) + 6; }
 
+// ---- batches: several streams (segments) in one launch ("segments") -----------------------------------
+// A segment is one image's prepared stream.  Its chunks, its window, its blocks' offsets, its zlib header and checksum,
+// its IDAT bodies and its CRC pieces are its own: nothing below ever yields an index outside the segment it names.
+constexpr uint32_t kSegChunk = 65535;       // input bytes per DEFLATE block (png_deflate.hpp kZChunk)
+constexpr uint32_t kSegIdat = 256 * 1024;   // bytes of an IDAT body (kIdatBytes)
+constexpr uint32_t kSegPiece = 4096;        // bytes of the stream one CRC value covers (kCrcPiece)
+constexpr uint32_t kSegAlign = 16;          // every segment's destination starts on a multiple of this
+struct ZSegment {
+    uint64_t src;         // its first byte, counted from the launch's data pointer
+    uint64_t len;         // its bytes, > 0
+    uint64_t dst;         // its framed zlib stream, counted from the launch's destination: a multiple of kSegAlign
+    uint32_t first_chunk; // chunks of the segments in front of it
+    uint32_t first_piece; // CRC pieces of the segments in front of it, each segment counted by its stored bound
+    uint32_t hint_bpp, hint_row;
+    uint32_t adler;       // of the segment's bytes (read by the compaction only)
+    uint32_t reserved;
+};
+PNGZ_HD uint64_t seg_chunks(uint64_t len) { return (len + kSegChunk - 1) / kSegChunk; }
+PNGZ_HD uint64_t seg_framed_size(uint64_t stream_len) { return stream_len + 12 * ((stream_len + kSegIdat - 1) / kSegIdat); }
+PNGZ_HD uint64_t seg_pieces(uint64_t len) { return (stored_bound(len) + kSegPiece - 1) / kSegPiece; } // of the longest stream it can become
+PNGZ_HD uint64_t seg_dst_bytes(uint64_t len) { return (seg_framed_size(stored_bound(len)) + kSegAlign - 1) / kSegAlign * kSegAlign; }
+// Fills in first_chunk, first_piece and dst of segs[0..n) from their len, and the totals into segs[n] (a table has n + 1
+// entries; the last one's src and len are 0).  false: the chunks or pieces do not fit 31 bits.
+PNGZ_HD bool seg_layout(ZSegment *segs, uint32_t n)
+{
+    uint64_t chunk = 0, piece = 0, dst = 0;
+    for (uint32_t s = 0; s <= n; ++s) {
+        if (chunk > 0x7FFFFFFFull || piece > 0x7FFFFFFFull) return false;
+        segs[s].first_chunk = static_cast<uint32_t>(chunk);
+        segs[s].first_piece = static_cast<uint32_t>(piece);
+        segs[s].dst = dst;
+        if (s == n) { segs[s].src = 0; segs[s].len = 0; break; }
+        chunk += seg_chunks(segs[s].len);
+        piece += seg_pieces(segs[s].len);
+        dst += seg_dst_bytes(segs[s].len);
+    }
+    return true;
+}
+// The segment that holds global chunk / piece g (g below the table's total): the last one that starts at or before it.
+// A search of the n + 1 firsts, not a map with an entry per chunk: the table is what the host uploads anyway, a
+// workgroup pays at most 17 uniform loads for it in front of 65,535 bytes of work, and a map would cost the host a loop
+// and an upload that grow with the chunks instead of the images.
+PNGZ_HD uint32_t seg_of_chunk(const ZSegment *segs, uint32_t n, uint32_t g)
+{
+    uint32_t lo = 0, hi = n; // segs[lo].first_chunk <= g < segs[hi].first_chunk
+    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (segs[mid].first_chunk <= g) lo = mid; else hi = mid; }
+    return lo;
+}
+PNGZ_HD uint32_t seg_of_piece(const ZSegment *segs, uint32_t n, uint32_t g)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (segs[mid].first_piece <= g) lo = mid; else hi = mid; }
+    return lo;
+}
+// Chunk `chunk` of a stream of len bytes, all counted from the stream's first byte: where it starts, its bytes, where its
+// 32 KiB window starts (never in front of the stream), whether it is the stream's last.
+struct ChunkSpan { uint64_t c0, wstart; uint32_t n; bool last; };
+PNGZ_HD ChunkSpan chunk_span(uint64_t len, uint64_t chunk)
+{
+    ChunkSpan r;
+    r.c0 = chunk * kSegChunk;
+    r.n = static_cast<uint32_t>(len - r.c0 < kSegChunk ? len - r.c0 : kSegChunk);
+    r.last = r.c0 + r.n == len;
+    r.wstart = r.c0 > kWindow ? r.c0 - kWindow : 0;
+    return r;
+}
+// Piece `piece` of a segment whose zlib stream has stream_len bytes: its first byte in the stream and its bytes (0: the
+// piece lies behind the stream's end and has no value).
+PNGZ_HD uint32_t piece_span(uint64_t stream_len, uint64_t piece, uint64_t *s0)
+{
+    *s0 = piece * kSegPiece;
+    if (*s0 >= stream_len) return 0;
+    return static_cast<uint32_t>(stream_len - *s0 < kSegPiece ? stream_len - *s0 : kSegPiece);
+}
+// Where byte s of a zlib stream lies in its destination as IDAT bodies: 8 bytes in front of every body, 4 behind.
+PNGZ_HD uint64_t seg_framed_offset(uint64_t s) { return s + 8 + 12 * (s / kSegIdat); }
+
 // ---- CRC-32 (reflected 0xEDB88320) -----------------------------------------------------------------------------------
 PNGZ_HD uint32_t crc32_table_entry(uint32_t i)
 {

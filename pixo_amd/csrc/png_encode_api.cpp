@@ -2,8 +2,10 @@
 // compressed where it lies (png_deflate.hip), its blocks are compacted into the bodies of 256 KiB IDAT chunks, the chunks'
 // CRC-32 come from the device in 4 KiB pieces, and only the finished file crosses to the host.  The chunks around IDAT are
 // the reference's byte for byte (src/png/mod.rs:513-630); the IDAT body is this library's own DEFLATE.
+// The batch entries run the same stages over N equal images at once, every image a segment (png_deflate_math.h ZSegment).
 #include "capi_internal.hpp"
 #include "png_deflate.hpp"
+#include "png_filter.hpp"
 
 #include <algorithm>
 #include <vector>
@@ -201,6 +203,296 @@ int png_file_lossy(Context &c, const void *d_px, const pixo_png_options &o, cons
     return png_finish(c, o, layout, trns_len, len, adler, PngFilterView{1, o.width + 1}, out, out_len);
 }
 
+// ---- batches: N equal images, one pass of filters, DEFLATE and CRC ("segments") ------------------------
+// One image's prepared stream in c.p_out, and what its file needs around the IDAT chunks.
+struct PngSegment {
+    size_t src = 0, len = 0; // its first byte counted from c.p_out.p, its bytes
+    PngFilterView view{1, 0};
+    uint32_t adler = 0;
+    pixo_png_layout layout;
+    uint32_t trns_len = 0;
+};
+// Where a batch's files go: blocks the caller owns (files), or back to back into an arena in host memory (offsets).
+struct BatchSink {
+    uint8_t **files = nullptr;
+    uint8_t *arena = nullptr;
+    size_t cap = 0;
+    size_t *offsets = nullptr, *lens = nullptr;
+    bool pinned = false; // the arena is host memory the runtime knows: device-to-host copies go straight into it
+    size_t at = 0;       // arena: the bytes of the files so far
+    uint32_t waits = 0;  // how often the host has waited for the stream (debug switch trace)
+};
+int wait_for(Context &c, BatchSink &sink)
+{
+    ++sink.waits;
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    return PIXO_OK;
+}
+
+// The batched tail of one sub-batch: the segment table, the scratch, the launches.  Host side of the table, the segments'
+// totals and the pieces' CRC-32: c.h_zinfo, in that order.
+struct BatchTail {
+    uint32_t nseg = 0, chunks = 0, pieces = 0, header = 0;
+    size_t table_bytes = 0, info_bytes = 0, off_bytes = 0, totals_bytes = 0;
+    ZSegment *h_table = nullptr;
+    ZSegment *d_table = nullptr;
+    unsigned long long *d_off = nullptr, *d_totals = nullptr;
+    const unsigned long long *h_totals = nullptr;
+    const uint32_t *h_crc = nullptr;
+};
+// Reserves everything, uploads the table and launches the DEFLATE of every chunk of every segment.  The Adler-32 of the
+// segments need not be known yet: the compaction reads them (tail_finish).
+int tail_begin(Context &c, const std::vector<PngSegment> &segs, const pixo_png_options &o, BatchTail &t)
+{
+    const uint32_t effort = (o.flags & PIXO_PNG_EFFORT_HIGH) ? 1 : 0;
+    t.nseg = static_cast<uint32_t>(segs.size());
+    std::vector<ZSegment> table(t.nseg + 1);
+    for (uint32_t i = 0; i < t.nseg; ++i) table[i] = ZSegment{segs[i].src, segs[i].len, 0, 0, 0, segs[i].view.bpp, segs[i].view.row, segs[i].adler, 0};
+    if (!seg_layout(table.data(), t.nseg)) return hip_fail(hipErrorInvalidValue, "chunks of a PNG batch");
+    t.chunks = table[t.nseg].first_chunk;
+    t.pieces = table[t.nseg].first_piece;
+    t.table_bytes = table.size() * sizeof(ZSegment);
+    t.info_bytes = t.chunks * sizeof(pixo_dev::ZChunkInfo);
+    t.off_bytes = t.chunks * sizeof(unsigned long long);
+    t.totals_bytes = t.nseg * sizeof(unsigned long long);
+    int rc;
+    if ((rc = c.z_tok.reserve(static_cast<size_t>(t.chunks) * pixo_dev::kZTokStride * sizeof(uint32_t))) ||
+        (rc = c.z_slots.reserve(static_cast<size_t>(t.chunks) * pixo_dev::kZSlot)) ||
+        (rc = c.z_info.reserve(t.info_bytes + t.off_bytes + t.totals_bytes + t.table_bytes)) ||
+        (rc = c.h_zinfo.reserve(t.table_bytes + t.totals_bytes + static_cast<size_t>(t.pieces) * 4)) ||
+        (rc = c.z_stream.reserve(static_cast<size_t>(table[t.nseg].dst) + 16)) || (rc = c.z_crc.reserve(static_cast<size_t>(t.pieces) * 4)))
+        return rc;
+    if (effort && (rc = c.z_prev.reserve(static_cast<size_t>(t.chunks) * pixo_dev::kZPrevStride * sizeof(uint16_t)))) return rc;
+    uint8_t *d = c.z_info.as<uint8_t>(), *h = c.h_zinfo.as<uint8_t>();
+    t.d_off = reinterpret_cast<unsigned long long *>(d + t.info_bytes);
+    t.d_totals = reinterpret_cast<unsigned long long *>(d + t.info_bytes + t.off_bytes);
+    t.d_table = reinterpret_cast<ZSegment *>(d + t.info_bytes + t.off_bytes + t.totals_bytes);
+    t.h_table = reinterpret_cast<ZSegment *>(h);
+    t.h_totals = reinterpret_cast<const unsigned long long *>(h + t.table_bytes);
+    t.h_crc = reinterpret_cast<const uint32_t *>(h + t.table_bytes + t.totals_bytes);
+    std::memcpy(t.h_table, table.data(), t.table_bytes);
+    uint8_t head[2];
+    zlib_header(o.compression_level, head);
+    t.header = head[0] | (uint32_t{head[1]} << 8);
+    HIP_TRY(hipMemcpyAsync(t.d_table, t.h_table, t.table_bytes, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(pixo_dev::launch_deflate_segments(c.p_out.p, t.d_table, t.nseg, t.chunks, effort, c.z_tok.as<uint32_t>(),
+                                              effort ? c.z_prev.as<uint16_t>() : nullptr, c.z_slots.as<uint8_t>(), c.z_info.as<pixo_dev::ZChunkInfo>(), c.stream));
+    return PIXO_OK;
+}
+// Scan, compaction and CRC over all segments; their totals and piece values come down together.  adlers_late: the segments'
+// checksums became known after tail_begin (the stream has been synchronised since): the table goes up once more.
+int tail_finish(Context &c, const std::vector<PngSegment> &segs, BatchTail &t, bool adlers_late, BatchSink &sink)
+{
+    if (adlers_late) {
+        for (uint32_t i = 0; i < t.nseg; ++i) t.h_table[i].adler = segs[i].adler;
+        HIP_TRY(hipMemcpyAsync(t.d_table, t.h_table, t.table_bytes, hipMemcpyHostToDevice, c.stream));
+    }
+    HIP_TRY(pixo_dev::launch_deflate_segments_finish(c.z_slots.as<uint8_t>(), c.z_info.as<pixo_dev::ZChunkInfo>(), t.d_table, t.nseg, t.chunks, t.pieces,
+                                                     t.header, t.d_off, t.d_totals, c.z_stream.as<uint8_t>(), c.z_crc.as<uint32_t>(), c.stream));
+    HIP_TRY(hipMemcpyAsync(c.h_zinfo.as<uint8_t>() + t.table_bytes, t.d_totals, t.totals_bytes, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.h_zinfo.as<uint8_t>() + t.table_bytes + t.totals_bytes, c.z_crc.p, static_cast<size_t>(t.pieces) * 4, hipMemcpyDeviceToHost, c.stream));
+    return wait_for(c, sink);
+}
+// The framed streams behind their heads, in the caller's blocks or at their arena offsets; frames and IEND by the host.
+// first: the sub-batch's first image in the batch.
+int tail_deliver(Context &c, const std::vector<PngSegment> &segs, const BatchTail &t, const pixo_png_options &o, uint32_t first, BatchSink &sink)
+{
+    struct File { std::vector<uint8_t> head; uint64_t stream_len = 0; size_t framed = 0, len = 0; uint8_t *at = nullptr; bool staged = false; };
+    std::vector<File> f(t.nseg);
+    for (uint32_t i = 0; i < t.nseg; ++i) {
+        f[i].stream_len = 2 + t.h_totals[i] + 4;
+        if (f[i].stream_len > stored_bound(segs[i].len)) return fail(PIXO_ERR_COMPRESSION, "Compression error: device DEFLATE exceeded the stored bound");
+        f[i].head = png_head(o.width, o.height, segs[i].layout, segs[i].trns_len);
+        f[i].framed = static_cast<size_t>(pixo_dev::z_framed_size(f[i].stream_len));
+        f[i].len = f[i].head.size() + f[i].framed + 12;
+        sink.lens[first + i] = f[i].len;
+    }
+    // Blocks: from the pinned pool, the copies go straight into them.  Arena: straight into a pinned one.  Otherwise (the pool
+    // is exhausted, the arena is pageable) through the context's pinned file buffer.
+    size_t stage = 0;
+    if (sink.files) {
+        bool pooled = true;
+        for (uint32_t i = 0; i < t.nseg && pooled; ++i)
+            if (!(sink.files[first + i] = pool_take(f[i].len))) pooled = false;
+        for (uint32_t i = 0; i < t.nseg; ++i) {
+            if (pooled) { f[i].at = sink.files[first + i]; continue; }
+            free_file(sink.files[first + i]);
+            sink.files[first + i] = nullptr;
+            f[i].staged = true;
+            stage += f[i].len;
+        }
+    } else {
+        for (uint32_t i = 0; i < t.nseg; ++i) {
+            sink.offsets[first + i] = sink.at;
+            sink.at += f[i].len;
+        }
+        // (nothing is copied from the sub-batch on that no longer fits: sizes only from there on)
+        for (uint32_t i = 0; i < t.nseg && sink.arena && sink.at <= sink.cap; ++i) {
+            if (sink.pinned) f[i].at = sink.arena + sink.offsets[first + i];
+            else { f[i].staged = true; stage += f[i].len; }
+        }
+    }
+    if (stage) {
+        if (const int rc = c.h_file.reserve(stage)) return rc;
+        size_t at = 0;
+        for (File &x : f)
+            if (x.staged) { x.at = c.h_file.as<uint8_t>() + at; at += x.len; }
+    }
+    hipError_t e = hipSuccess;
+    bool any = false;
+    for (uint32_t i = 0; i < t.nseg && e == hipSuccess; ++i)
+        if (f[i].at) { any = true; e = hipMemcpyAsync(f[i].at + f[i].head.size(), c.z_stream.as<uint8_t>() + t.h_table[i].dst, f[i].framed, hipMemcpyDeviceToHost, c.stream); }
+    for (const File &x : f)
+        if (x.at) std::memcpy(x.at, x.head.data(), x.head.size()); // (while the copies run: they touch other bytes)
+    if (any) { // (also after an error: no copy is in flight when a block goes back)
+        ++sink.waits;
+        const hipError_t idle = hipStreamSynchronize(c.stream);
+        if (e == hipSuccess) e = idle;
+    }
+    if (e != hipSuccess) return hip_fail(e, "device-to-host copy of the PNG batch files");
+    for (uint32_t i = 0; i < t.nseg; ++i) {
+        if (!f[i].at) continue;
+        frame_idats(f[i].at + f[i].head.size(), f[i].stream_len, t.h_crc + t.h_table[i].first_piece);
+        if (!f[i].staged) continue;
+        if (sink.files) {
+            size_t n = 0;
+            if (const int rc = deliver(f[i].at, f[i].len, &sink.files[first + i], &n)) return rc;
+        } else {
+            std::memcpy(sink.arena + sink.offsets[first + i], f[i].at, f[i].len);
+        }
+    }
+    return PIXO_OK;
+}
+
+// One image of a batch the image-by-image way in: its prepared stream at c.p_out + seg.src, by the single entries' own sequence.
+int png_segment_of_image(Context &c, const void *d_img, const pixo_png_options &o, const pixo_png_quantization *q, PngSegment &seg)
+{
+    uint8_t *dst = c.p_out.as<uint8_t>() + seg.src;
+    int rc;
+    if (q) { // png_file_lossy
+        bool applied = false;
+        if ((rc = png_quantize_on_device(c, d_img, o, *q, &applied, &seg.layout, &seg.trns_len))) return rc;
+        if (applied) {
+            uint8_t strategy = o.filter_strategy;
+            if (strategy == PIXO_PNG_ADAPTIVE || strategy == PIXO_PNG_ADAPTIVE_FAST || strategy == PIXO_PNG_MINSUM || strategy == PIXO_PNG_BIGRAMS) strategy = PIXO_PNG_NONE;
+            int run = 0;
+            bool seq = false;
+            if ((rc = png_plan(o.width, o.height, static_cast<uint64_t>(o.width) * o.height, 1, strategy, o.flags, &run, &seq))) return rc;
+            seg.len = static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) + 1);
+            seg.view = PngFilterView{1, o.width + 1};
+            return png_filter_on_device(c, c.q_index.p, o.width, o.height, 1, run, seq, dst, &seg.adler);
+        }
+    }
+    if ((rc = png_prepare_on_device(c, d_img, o, dst, &seg.layout, &seg.len, &seg.adler, &seg.view))) return rc;
+    seg.trns_len = seg.layout.palette_len;
+    return PIXO_OK;
+}
+
+// `batch` images back to back at d_px -> their files into the sink.  Sub-batches run one after the other on the context.  A
+// sub-batch holds at most 64 MiB of prepared stream AND at most kBatchChunks chunks, and always at least one image: the
+// scratch is per CHUNK, not per byte — kZTokStride * 4 + kZSlot = 327,696 bytes for every chunk however short (524,304 with
+// the high effort's links) — and every image has at least one.  1024 chunks: 336 MB of scratch, 537 MB with the high effort,
+// what 64 MiB of stream in full chunks need; a batch of thumbnails reaches the chunk limit long before the byte limit.
+constexpr uint64_t kBatchChunks = 1024;
+int png_batch(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization *q, uint32_t batch, BatchSink &sink)
+{
+    const uint32_t bpp = bytes_per_pixel(o.color_type);
+    const size_t px_bytes = static_cast<size_t>(o.width) * o.height * bpp, full = static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) * bpp + 1);
+    int run = 0;
+    bool seq = false;
+    int rc = png_plan(o.width, o.height, static_cast<uint64_t>(o.width) * o.height, bpp, o.filter_strategy, o.flags, &run, &seq);
+    if (rc) return rc;
+    // The batched way in: the stream is the unreduced rows' and the filters do not depend on row 0's decision.  Everything
+    // else prepares image by image (the reductions' and the quantiser's own round trips stay) in front of the batched tail.
+    const bool filter_batch = !q && !o.optimize_alpha && !o.reduce_color_type && !o.reduce_palette && !seq;
+    const uint64_t limit = debug().png_batch_bytes ? debug().png_batch_bytes : (uint64_t{64} << 20);
+    const uint64_t by_bytes = std::max<uint64_t>(limit / full, 1), by_chunks = std::max<uint64_t>(kBatchChunks / seg_chunks(full), 1);
+    const uint32_t per = static_cast<uint32_t>(std::min<uint64_t>(std::min(by_bytes, by_chunks), batch)); // (a reduced stream is never longer than `full`)
+    note_route(route::PNG_BATCH | (filter_batch ? route::PNG_BATCH_FILTER : 0) | (per < batch ? route::SUB_BATCHES : 0));
+    for (uint32_t first = 0, part = 0; first < batch; first += per, ++part) {
+        const uint32_t nb = std::min(per, batch - first), waits0 = sink.waits;
+        const uint8_t *d_first = static_cast<const uint8_t *>(d_px) + px_bytes * first;
+        if ((rc = c.p_out.reserve(full * nb))) return rc;
+        std::vector<PngSegment> segs(nb);
+        BatchTail tail;
+        Stopwatch watch; // (debug switch trace: wall time between the host's waits)
+        for (uint32_t i = 0; i < nb; ++i) segs[i].src = full * i;
+        if (filter_batch) {
+            for (PngSegment &sg : segs) {
+                std::memset(&sg.layout, 0, sizeof(sg.layout));
+                sg.layout.color_type_byte = o.color_type == PIXO_GRAY ? 0 : o.color_type == PIXO_GRAY_ALPHA ? 4 : o.color_type == PIXO_RGB ? 2 : 6;
+                sg.layout.bit_depth = 8;
+                sg.layout.bytes_per_pixel = static_cast<uint8_t>(bpp);
+                sg.layout.row_bytes = o.width * bpp;
+                sg.len = full;
+                sg.view = PngFilterView{bpp, o.width * bpp + 1};
+            }
+            // filters, row sums on their way down, DEFLATE behind them: one wait for all three, then the checksums on the host
+            if ((rc = png_filter_batch_begin(c, d_first, o.width, o.height, nb, bpp, run, c.p_out.p)) || (rc = tail_begin(c, segs, o, tail)) ||
+                (rc = wait_for(c, sink)))
+                return rc;
+            for (uint32_t i = 0; i < nb; ++i) segs[i].adler = png_filter_batch_adler(c, o.width, o.height, bpp, i);
+            watch.lap("png batch: filters, DEFLATE");
+        } else {
+            for (uint32_t i = 0; i < nb; ++i)
+                if ((rc = png_segment_of_image(c, d_first + px_bytes * i, o, q, segs[i]))) return rc;
+            watch.lap("png batch: images prepared");
+            if ((rc = tail_begin(c, segs, o, tail))) return rc;
+        }
+        if ((rc = tail_finish(c, segs, tail, filter_batch, sink))) return rc;
+        watch.lap(filter_batch ? "png batch: scan, compact, CRC" : "png batch: DEFLATE to CRC");
+        if ((rc = tail_deliver(c, segs, tail, o, first, sink))) return rc;
+        watch.lap("png batch: copies, frames");
+        if (debug().trace)
+            std::fprintf(stderr, "[pixo_hip] png batch: sub-batch %u, %u image(s), %u chunk(s), %s way in, host waits %u%s\n", part, nb, tail.chunks,
+                         filter_batch ? "batched" : "image-by-image", sink.waits - waits0, filter_batch ? "" : " (behind the images' own)");
+    }
+    return PIXO_OK;
+}
+
+int png_batch_blocks(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization *q, uint32_t batch, uint8_t **files, size_t *lens)
+{
+    for (uint32_t i = 0; i < batch; ++i) { files[i] = nullptr; lens[i] = 0; }
+    BatchSink sink;
+    sink.files = files;
+    sink.lens = lens;
+    const int rc = png_batch(c, d_px, o, q, batch, sink);
+    if (rc) {
+        (void)hipStreamSynchronize(c.stream); // (no copy is in flight when the blocks go back)
+        for (uint32_t i = 0; i < batch; ++i) { free_file(files[i]); files[i] = nullptr; lens[i] = 0; }
+    }
+    return rc;
+}
+
+int png_batch_into(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization *q, uint32_t batch, uint8_t *arena,
+                   size_t capacity, size_t *offsets, size_t *lens)
+{
+    for (uint32_t i = 0; i < batch; ++i) { offsets[i] = 0; lens[i] = 0; }
+    BatchSink sink;
+    sink.arena = arena;
+    sink.cap = arena ? capacity : 0;
+    sink.offsets = offsets;
+    sink.lens = lens;
+    const hipMemoryType arena_type = arena ? pointer_info(arena).type : hipMemoryTypeUnregistered;
+    if (arena_type == hipMemoryTypeDevice) return hip_fail(hipErrorInvalidValue, "arena of a PNG batch in device memory (host memory only)");
+    sink.pinned = arena_type == hipMemoryTypeHost;
+    const int rc = png_batch(c, d_px, o, q, batch, sink);
+    if (rc) return rc;
+    return arena && sink.at <= capacity ? PIXO_OK : too_small(sink.at);
+}
+
+// The checks the three batch entries share behind png_check_options, in their order
+int png_batch_checks(const void *pixels, uint32_t batch, const pixo_png_quantization *quantization, const void *files_or_offsets, const void *lens, bool into)
+{
+    PIXO_REQUIRE(pixels);
+    int rc = batch_in_range(batch);
+    if (rc || (quantization && (rc = png_check_quantization(quantization)))) return rc;
+    if (into) { const void *offsets = files_or_offsets; PIXO_REQUIRE(offsets); }
+    else { const void *files = files_or_offsets; PIXO_REQUIRE(files); }
+    PIXO_REQUIRE(lens);
+    return PIXO_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -325,6 +617,38 @@ int pixo_hip_png_encode_lossy_device(const void *d_pixels, const pixo_png_option
     Context *c = nullptr;
     if ((rc = context_on_current_device(&c))) return rc;
     return png_file_lossy(*c, d_pixels, *options, *quantization, out, out_len);
+}
+
+int pixo_hip_png_encode_batch_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization, uint32_t batch,
+                                     uint8_t **files, size_t *lens)
+{
+    int rc = png_check_options(options);
+    if (rc || (rc = png_batch_checks(d_pixels, batch, quantization, files, lens, false))) return rc;
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc;
+    return png_batch_blocks(*c, d_pixels, *options, quantization, batch, files, lens);
+}
+
+int pixo_hip_png_encode_batch_device_into(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                                          uint32_t batch, uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens)
+{
+    CallerStorageScope storage(arena && capacity);
+    int rc = png_check_options(options);
+    if (rc || (rc = png_batch_checks(d_pixels, batch, quantization, offsets, lens, true))) return rc;
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc;
+    return png_batch_into(*c, d_pixels, *options, quantization, batch, arena, capacity, offsets, lens);
+}
+
+int pixo_hip_png_encode_batch(const uint8_t *data, size_t data_len, const pixo_png_options *options, const pixo_png_quantization *quantization,
+                              uint32_t batch, uint8_t **files, size_t *lens)
+{
+    int rc = png_check_options(options, true, data_len, batch);
+    if (rc) return rc;
+    if ((rc = png_batch_checks(data, batch, quantization, files, lens, false))) return rc;
+    PIXO_THREAD_CONTEXT(c);
+    if ((rc = upload(c, c.p_in, data, data_len))) return rc;
+    return png_batch_blocks(c, c.p_in.p, *options, quantization, batch, files, lens);
 }
 
 } // extern "C"

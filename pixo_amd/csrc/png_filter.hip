@@ -309,7 +309,10 @@ __device__ __forceinline__ unsigned long long bigram_score(const uint8_t *row, c
 // K_BIGRAMS (~110).
 // K_REGS512: the same with 512 threads, rows of up to 32 KiB.
 enum { K_GENERAL = 0, K_REGS = 1, K_BIGRAMS = 2, K_REGS512 = 3 };
-template <int BPP, bool FAST, int KIND, int ITERS = kRegIters>
+// BATCH: the rows are those of several images of a.height rows each, back to back (launch_png_filter_batch): the first row
+// of EVERY image has no row above, and no row ever reads another image's.  Everything else — the XCD chunks, late_half, the
+// output and the sums at row y of the launch — is the single image's; the default keeps the single-image instantiations as they were.
+template <int BPP, bool FAST, int KIND, int ITERS = kRegIters, bool BATCH = false>
 __global__ __launch_bounds__(KIND == K_REGS512 ? 2 * kThreads : kThreads) void png_filter_kernel(const Args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
@@ -331,7 +334,7 @@ __global__ __launch_bounds__(KIND == K_REGS512 ? 2 * kThreads : kThreads) void p
     y += a.first_row;
     const int n = (int)a.row_bytes; // < 2^31 (checked by the launcher)
     const uint8_t *row = a.data + (size_t)y * a.row_bytes;
-    const uint8_t *prev = y ? row - a.row_bytes : nullptr;
+    const uint8_t *prev = (BATCH ? y % a.height : y) ? row - a.row_bytes : nullptr;
     constexpr int NT = KIND == K_REGS512 ? 2 * kThreads : kThreads;
     const int ndw = (n + 3) / 4, per_iter = NT * 4;
     int strategy = a.forced ? *a.forced : a.strategy;
@@ -483,7 +486,7 @@ __device__ __forceinline__ void bigram_candidate(const Raw *raw, int n, int ndw,
     if ((tid & 63) == 0) atomicAdd(count, c);
 }
 
-template <int BPP, bool FAST>
+template <int BPP, bool FAST, bool BATCH = false>
 __global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const Args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
@@ -495,7 +498,7 @@ __global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const Args a
     y += a.first_row;
     const int n = (int)a.row_bytes, ndw = (n + 3) / 4, tid = (int)threadIdx.x;
     const uint8_t *row = a.data + (size_t)y * a.row_bytes;
-    const uint8_t *prev = y ? row - a.row_bytes : nullptr;
+    const uint8_t *prev = (BATCH ? y % a.height : y) ? row - a.row_bytes : nullptr;
     uint32_t *bm0 = reinterpret_cast<uint32_t *>(stage + a.bitmap_off), *bm1 = bm0 + 2048, *xch = bm1 + 2048;
     if (tid < 5) cnt[tid] = 0;
     if (tid < 2) acc64[tid] = 0;
@@ -532,41 +535,52 @@ __global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const Args a
     if (tid == 0) { a.row_sums[2 * (size_t)y] = acc64[0]; a.row_sums[2 * (size_t)y + 1] = acc64[1]; }
 }
 
-template <int BPP> hipError_t launch_bpp(const Args &a, uint32_t rows, bool fast, hipStream_t s)
+template <int BPP, bool BATCH = false> hipError_t launch_bpp(const Args &a, uint32_t rows, bool fast, hipStream_t s)
 {
     const uint64_t ndw = (a.row_bytes + 3) / 4;
     namespace r = pixo_capi::route;
     if (a.strategy == PNG_S_BIGRAMS && a.stage_bytes != 0 && ndw <= (uint64_t)kRegIters * kThreads * 4) {
         pixo_capi::note_route(r::PNG_BIGRAMS_REGS);
         const uint32_t lds = a.stage_bytes + 2 * 8192u + 4u * (kRegIters * kThreads + 1); // stage | two bitmaps | exchange array
-        if (fast) hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, true>), dim3(rows), dim3(kThreads), lds, s, a);
-        else hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, false>), dim3(rows), dim3(kThreads), lds, s, a);
+        if (fast) hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, true, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
+        else hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, false, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
     } else if (a.strategy == PNG_S_BIGRAMS) {
         pixo_capi::note_route(r::PNG_BIGRAMS);
         const uint32_t lds = a.stage_bytes + 8192u;
-        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_BIGRAMS>), dim3(rows), dim3(kThreads), lds, s, a);
-        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_BIGRAMS>), dim3(rows), dim3(kThreads), lds, s, a);
+        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_BIGRAMS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
+        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_BIGRAMS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
     } else if (a.strategy > PNG_S_PAETH && !a.forced && ndw <= (uint64_t)kRegIters * 2 * kThreads * 4 && a.stage_bytes != 0) {
         // rows of up to 16 KiB: 256 threads hold them; up to 32 KiB: 512 threads
         if (ndw <= (uint64_t)kRegIters * kThreads * 4) {
             pixo_capi::note_route(r::PNG_REGS);
-            if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
-            else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+            if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+            else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
         } else {
             pixo_capi::note_route(r::PNG_REGS512);
-            if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS512>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
-            else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS512>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
+            if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS512, kRegIters, BATCH>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
+            else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS512, kRegIters, BATCH>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
         }
     } else {
         pixo_capi::note_route(r::PNG_GENERAL);
-        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_GENERAL>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
-        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_GENERAL>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_GENERAL, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_GENERAL, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_rows(const Args &a, uint32_t rows, uint32_t bpp, bool fast, hipStream_t s)
+hipError_t launch_rows(const Args &a, uint32_t rows, uint32_t bpp, bool fast, hipStream_t s, bool batch = false)
 {
+    if (batch) {
+        switch (bpp) {
+        case 1: return launch_bpp<1, true>(a, rows, fast, s);
+        case 2: return launch_bpp<2, true>(a, rows, fast, s);
+        case 3: return launch_bpp<3, true>(a, rows, fast, s);
+        case 4: return launch_bpp<4, true>(a, rows, fast, s);
+        case 6: return launch_bpp<6, true>(a, rows, fast, s);
+        case 8: return launch_bpp<8, true>(a, rows, fast, s);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (bpp) {
     case 1: return launch_bpp<1>(a, rows, fast, s);
     case 2: return launch_bpp<2>(a, rows, fast, s);
@@ -622,6 +636,32 @@ hipError_t launch_png_filter_rows(const void *d_data, uint32_t width, uint32_t h
     }
     a.first_row = first_row;
     return launch_rows(a, rows, bpp, fast, stream);
+}
+
+// `batch` images of image_rows rows back to back at d_data: one launch over batch * image_rows rows; the filtered streams
+// lie back to back at d_out, the sums of image i's row r at d_row_sums[2 * (i * image_rows + r)].  Not for the stateful
+// AdaptiveFast (row 0 of every image would have to decide first).
+hipError_t launch_png_filter_batch(const void *d_data, uint32_t width, uint32_t image_rows, uint32_t batch, uint32_t bpp, int strategy,
+                                   void *d_out, unsigned long long *d_row_sums, hipStream_t stream)
+{
+    const uint64_t rows = (uint64_t)image_rows * batch;
+    if (rows == 0 || rows > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    Args a;
+    a.data = static_cast<const uint8_t *>(d_data);
+    a.out = static_cast<uint8_t *>(d_out);
+    a.row_sums = d_row_sums;
+    a.row_bytes = (uint64_t)width * bpp;
+    if (a.row_bytes >= 0x7FFFFFF0ull) return hipErrorInvalidValue;
+    a.height = image_rows;
+    a.strategy = strategy;
+    const uint64_t stage = 16 + ((a.row_bytes + 15) & ~15ull) + 32; // (as launch_png_filter_rows)
+    a.stage_bytes = stage <= 48 * 1024 ? (uint32_t)stage : 0u;
+    a.bitmap_off = a.stage_bytes;
+    a.forced = nullptr; a.winner0 = nullptr; a.first_row = 0;
+    a.late_half = (rows >= 2048u && whole_chip_device()) ? 1u : 0u;
+    // (an image's first byte is image_rows * row_bytes behind the one before: a multiple of 4 when row_bytes is)
+    const bool fast = reinterpret_cast<uintptr_t>(d_data) % 4 == 0 && a.row_bytes % 4 == 0;
+    return launch_rows(a, (uint32_t)rows, bpp, fast, stream, true);
 }
 
 } // namespace pixo_dev

@@ -22,5 +22,10 @@ hipError_t launch_png_filter(const void *d_data, uint32_t width, uint32_t height
 hipError_t launch_png_filter_rows(const void *d_data, uint32_t width, uint32_t height, uint32_t bpp, int strategy,
                                   bool sequential_fast, void *d_out, unsigned long long *d_row_sums, int *d_scratch,
                                   uint32_t first_row, uint32_t rows, hipStream_t stream);
+// `batch` images of image_rows rows each, back to back at d_data, in one launch: d_out receives their filtered streams back
+// to back, d_row_sums [batch * image_rows][2] every row's sums.  The first row of every image has no row above.  The
+// strategy is what png_plan resolved; the stateful AdaptiveFast is not served here.
+hipError_t launch_png_filter_batch(const void *d_data, uint32_t width, uint32_t image_rows, uint32_t batch, uint32_t bpp, int strategy,
+                                   void *d_out, unsigned long long *d_row_sums, hipStream_t stream);
 
 } // namespace pixo_dev

@@ -144,13 +144,14 @@ int reduce_to_palette(Context &c, const void *d_px, const pixo_png_options &o, P
 
 } // namespace
 
-int pixo_capi::png_check_options(const pixo_png_options *o, bool with_data, size_t data_len)
+int pixo_capi::png_check_options(const pixo_png_options *o, bool with_data, size_t data_len, uint32_t images)
 {
     PIXO_REQUIRE(o);
     if (o->width == 0 || o->height == 0) return bad_dimensions(o->width, o->height);
     if (o->width > kPngMaxDimension || o->height > kPngMaxDimension) return too_large(o->width, o->height, kPngMaxDimension);
     if (o->color_type > PIXO_RGBA) return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format");
-    const size_t want = static_cast<size_t>(o->width) * o->height * bytes_per_pixel(o->color_type);
+    const size_t one = static_cast<size_t>(o->width) * o->height * bytes_per_pixel(o->color_type);
+    const size_t want = images <= 1 || one <= SIZE_MAX / images ? one * images : SIZE_MAX; // (a batch whose bytes do not fit size_t: no length is right)
     if (with_data && data_len != want) return bad_length(want, data_len);
     if (o->filter_strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
     return PIXO_OK;

@@ -48,6 +48,8 @@ enum : uint64_t {
     RESIZE_NEAREST = 1ull << 36,   // resize: the nearest form of the point kernel (resize.hip)
     RESIZE_BILINEAR = 1ull << 37,  // ... its bilinear form
     RESIZE_LANCZOS3 = 1ull << 38,  // ... the two Lanczos3 passes
+    PNG_BATCH = 1ull << 39,        // PNG batch entries: one DEFLATE, scan, compaction and CRC launch over all images of a sub-batch
+    PNG_BATCH_FILTER = 1ull << 40, // ... and one filter launch over all their rows in front of it
 };
 }
 

@@ -23,6 +23,10 @@ class FilterStrategy(enum.IntEnum):
     BIGRAMS = 8
 
 
+# this module's bits of the route record (pixo_hip_debug_routes; pixo_amd/csrc/routes.hpp)
+ROUTES = {"PNG_BATCH": 39, "PNG_BATCH_FILTER": 40, "SUB_BATCHES": 26}
+ROUTE_PNG_BATCH, ROUTE_PNG_BATCH_FILTER, ROUTE_SUB_BATCHES = (1 << b for b in ROUTES.values())
+
 NO_RAYON = 1  # flags: semantics of a reference build without the `parallel` feature
 EFFORT_HIGH = 2  # flags, read by `encode` / `encode_device`: the device DEFLATE's denser effort (hash chains, lazy parse)
 
@@ -328,6 +332,76 @@ def encode_device(d_pixels, options):
         rc = L.pixo_hip_png_encode_device(_lib.ptr(d_pixels), C.byref(o), C.byref(p), C.byref(n))
     _lib.check(rc)
     return _lib.take(L, p, n)
+
+
+# ---- batches: equally sized images, one pass of filters, DEFLATE and CRC ------------------------------------------------
+
+def _quant_arg(options):
+    return C.byref(options.quantization.to_c()) if _lossy(options) else None
+
+
+def _check_batch_pixels(d_pixels, options, batch):
+    """(the C entries take no length for device pixels: whatever carries a size is checked here)"""
+    if hasattr(d_pixels, "numel"):
+        need = batch * options.width * options.height * options.color_type.bytes_per_pixel()
+        have = d_pixels.numel() * d_pixels.element_size()
+        if have != need:
+            raise ValueError("a batch of %d images of %dx%d needs %d bytes of pixels, the tensor holds %d" % (batch, options.width, options.height, need, have))
+
+
+def _take_files(L, files, lens, batch):
+    out = []
+    for i in range(batch):
+        out.append(_lib.file_bytes(L, files[i], lens[i]))
+        L.pixo_hip_free(files[i])
+    return out
+
+
+def encode_batch_device(d_pixels, options, batch):
+    """`batch` equally sized images back to back in HBM (torch tensor / raw pointer) -> list of `batch` PNG files (bytes),
+    each byte for byte what `encode_device` returns for its image.  `options.quantization`, when not Off, is passed on."""
+    L = _lib.load()
+    _check_batch_pixels(d_pixels, options, batch)
+    files, lens, o = (C.POINTER(C.c_uint8) * batch)(), (C.c_size_t * batch)(), options.to_c()
+    _lib.check(L.pixo_hip_png_encode_batch_device(_lib.ptr(d_pixels), C.byref(o), _quant_arg(options), batch, files, lens))
+    return _take_files(L, files, lens, batch)
+
+
+def encode_batch_device_into(arena, d_pixels, options, batch):
+    """The `batch` files back to back in `arena` (a torch uint8 CPU tensor, pinned or not, a numpy uint8 array, or None
+    for a size query — which does the device work: a PNG's size is known only after compression).  Returns (offsets,
+    lens); raises BufferTooSmall (`.needed`) when the files do not fit."""
+    from . import error
+    L = _lib.load()
+    _check_batch_pixels(d_pixels, options, batch)
+    offsets, lens, o = (C.c_size_t * batch)(), (C.c_size_t * batch)(), options.to_c()
+    if arena is None:
+        ptr, cap = None, 0
+    elif hasattr(arena, "data_ptr"):
+        ptr, cap = arena.data_ptr(), arena.numel()
+    else:
+        ptr, cap = arena.ctypes.data, arena.size
+    rc = L.pixo_hip_png_encode_batch_device_into(_lib.ptr(d_pixels), C.byref(o), _quant_arg(options), batch, ptr, cap, offsets, lens)
+    if rc == -9 and arena is None:  # PIXO_ERR_BUFFER_TOO_SMALL: the answer to a size query
+        return list(offsets), list(lens)
+    if rc == -9:
+        try:
+            _lib.check(rc)
+        except error.BufferTooSmall as e:
+            e.needed = int(offsets[batch - 1] + lens[batch - 1]) if batch else 0
+            e.offsets, e.lens = list(offsets), list(lens)
+            raise
+    _lib.check(rc)
+    return list(offsets), list(lens)
+
+
+def encode_batch(data, options, batch):
+    """Host pixels of `batch` equally sized images back to back -> list of `batch` PNG files (bytes)."""
+    L = _lib.load()
+    px = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    files, lens, o = (C.POINTER(C.c_uint8) * batch)(), (C.c_size_t * batch)(), options.to_c()
+    _lib.check(L.pixo_hip_png_encode_batch(px.ctypes.data, px.size, C.byref(o), _quant_arg(options), batch, files, lens))
+    return _take_files(L, files, lens, batch)
 
 
 # ---- lossy mode: palette quantisation and dithering on the device ------------------------------------------------------
