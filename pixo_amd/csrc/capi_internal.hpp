@@ -13,7 +13,7 @@
 //   bands.cpp        one image over several GPUs: band encoder, splice, pixo_hip_jpeg_encode_multi
 //   png_api.cpp      the extern "C" PNG row-filter entry points
 //   png_reduce_api.cpp  the extern "C" PNG prepare entry points: png_check_options, reductions (png_reduce.hip), palette ordering, the filter
-//   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, a ZlibJob (png_deflate.hip), file head and IDAT frames;
+//   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, the DEFLATE tail over a segment table (png_deflate.hip), file head and IDAT frames;
 //                    the PNG batch entries: segments, sub-batches, the batched tail
 //   png_quantize_api.cpp  PNG lossy mode: gate, histogram and median cut on the host, the kernels of png_quantize.hip, the extern "C" quantize entries
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables

@@ -73,8 +73,8 @@ struct ChunkShared {
 };
 
 // One chunk of one stream: `data` is the stream's first byte, `len` its bytes, `chunk` the chunk's number in the stream; tok,
-// slot, info and prev are the chunk's own places in the scratch.  The stream is a whole launch's (deflate_chunk_kernel) or one
-// segment of a batch (deflate_chunk_seg_kernel): the window, `last`, the hash seeding and the links never leave it.
+// slot, info and prev are the chunk's own places in the scratch.  The stream is one segment of the launch's table
+// (deflate_chunk_kernel): the window, `last`, the hash seeding and the links never leave it.
 template <bool kHigh>
 __device__ __forceinline__ void deflate_chunk(const uint8_t *__restrict__ data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint64_t chunk,
                                               uint32_t *__restrict__ tok, uint8_t *__restrict__ slot, ZChunkInfo *__restrict__ info,
@@ -343,50 +343,17 @@ __device__ __forceinline__ void deflate_chunk(const uint8_t *__restrict__ data, 
     for (uint32_t w = tid; w < words; w += kThreads) slot_words[w] = s.big.out[w];
 }
 
+// Workgroup b finds its segment in the table (png_deflate_math.h seg_of_chunk: uniform loads, none for a table of one) and
+// works on chunk b - first_chunk of that segment's stream; the scratch is indexed by b.
 template <bool kHigh>
-__global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *__restrict__ data, uint64_t len, uint32_t hint_bpp,
-                                                                 uint32_t hint_row, uint32_t *__restrict__ tok_all,
-                                                                 uint8_t *__restrict__ slots, ZChunkInfo *__restrict__ info,
-                                                                 uint16_t *__restrict__ prev_all)
-{
-    const uint64_t chunk = blockIdx.x;
-    deflate_chunk<kHigh>(data, len, hint_bpp, hint_row, chunk, tok_all + chunk * kZTokStride, slots + chunk * kZSlot, info + chunk,
-                         kHigh ? prev_all + chunk * kZPrevStride : nullptr);
-}
-
-// The batch form: workgroup b finds its segment in the table (png_deflate_math.h seg_of_chunk: uniform loads) and works on
-// chunk b - first_chunk of that segment's stream; the scratch is indexed by b.
-template <bool kHigh>
-__global__ __launch_bounds__(kThreads) void deflate_chunk_seg_kernel(const uint8_t *__restrict__ data, const ZSegment *__restrict__ segs, uint32_t nseg,
-                                                                     uint32_t *__restrict__ tok_all, uint8_t *__restrict__ slots,
-                                                                     ZChunkInfo *__restrict__ info, uint16_t *__restrict__ prev_all)
+__global__ __launch_bounds__(kThreads) void deflate_chunk_kernel(const uint8_t *__restrict__ data, const ZSegment *__restrict__ segs, uint32_t nseg,
+                                                                 uint32_t *__restrict__ tok_all, uint8_t *__restrict__ slots,
+                                                                 ZChunkInfo *__restrict__ info, uint16_t *__restrict__ prev_all)
 {
     const uint32_t b = blockIdx.x;
     const ZSegment sg = segs[seg_of_chunk(segs, nseg, b)];
     deflate_chunk<kHigh>(data + sg.src, sg.len, sg.hint_bpp, sg.hint_row, b - sg.first_chunk, tok_all + static_cast<uint64_t>(b) * kZTokStride,
                          slots + static_cast<uint64_t>(b) * kZSlot, info + b, kHigh ? prev_all + static_cast<uint64_t>(b) * kZPrevStride : nullptr);
-}
-
-// offsets[c] = bytes of the blocks before c; offsets[chunks] = all of them
-__global__ __launch_bounds__(1024) void deflate_scan_kernel(const ZChunkInfo *__restrict__ info, uint64_t chunks, unsigned long long *__restrict__ offsets)
-{
-    __shared__ unsigned long long part[1024];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t per = (chunks + 1023) / 1024;
-    const uint64_t c_lo = tid * per < chunks ? tid * per : chunks, c_hi = c_lo + per < chunks ? c_lo + per : chunks;
-    unsigned long long sum = 0;
-    for (uint64_t c = c_lo; c < c_hi; ++c) sum += info[c].bytes;
-    part[tid] = sum;
-    __syncthreads();
-    for (uint32_t step = 1; step < 1024; step <<= 1) {
-        const unsigned long long add = tid >= step ? part[tid - step] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    unsigned long long at = part[tid] - sum;
-    for (uint64_t c = c_lo; c < c_hi; ++c) { offsets[c] = at; at += info[c].bytes; }
-    if (tid == 1023) offsets[chunks] = part[1023];
 }
 
 __device__ __forceinline__ uint64_t framed_offset(uint64_t s, bool framed) { return framed ? seg_framed_offset(s) : s; }
@@ -411,18 +378,9 @@ __device__ __forceinline__ void compact_chunk(const uint8_t *__restrict__ src, u
     for (uint64_t sb = lastw + tid; sb < end; sb += 256) dst[framed_offset(sb, framed)] = src[sb - start];
 }
 
-__global__ __launch_bounds__(256) void deflate_compact_kernel(const uint8_t *__restrict__ slots, const ZChunkInfo *__restrict__ info,
-                                                              const unsigned long long *__restrict__ offsets, uint64_t chunks, uint32_t header,
-                                                              uint32_t adler, uint8_t *__restrict__ dst, bool framed)
-{
-    const uint64_t c = blockIdx.x;
-    const uint64_t start = 2 + offsets[c];
-    compact_chunk(slots + c * kZSlot, start, start + info[c].bytes, c == 0, c == chunks - 1, header, adler, dst, framed);
-}
-
-// The batch forms.  Scan: one workgroup per segment, the offsets restart at every segment (offsets[b]: the bytes of the
-// segment's blocks in front of global chunk b), totals[s]: the bytes of all blocks of segment s.
-__global__ __launch_bounds__(1024) void deflate_scan_seg_kernel(const ZChunkInfo *__restrict__ info, const ZSegment *__restrict__ segs,
+// Scan: one workgroup per segment, the offsets restart at every segment (offsets[b]: the bytes of the segment's blocks in
+// front of global chunk b), totals[s]: the bytes of all blocks of segment s.
+__global__ __launch_bounds__(1024) void deflate_scan_kernel(const ZChunkInfo *__restrict__ info, const ZSegment *__restrict__ segs,
                                                                 unsigned long long *__restrict__ offsets, unsigned long long *__restrict__ totals)
 {
     __shared__ unsigned long long part[1024];
@@ -445,15 +403,15 @@ __global__ __launch_bounds__(1024) void deflate_scan_seg_kernel(const ZChunkInfo
     if (tid == 1023) totals[sg] = part[1023];
 }
 
-// Compaction: workgroup b moves global chunk b's block to its segment's own destination, framed.
-__global__ __launch_bounds__(256) void deflate_compact_seg_kernel(const uint8_t *__restrict__ slots, const ZChunkInfo *__restrict__ info,
-                                                                  const unsigned long long *__restrict__ offsets, const ZSegment *__restrict__ segs,
-                                                                  uint32_t nseg, uint32_t header, uint8_t *__restrict__ dst)
+// Compaction: workgroup b moves global chunk b's block to its segment's own destination.
+__global__ __launch_bounds__(256) void deflate_compact_kernel(const uint8_t *__restrict__ slots, const ZChunkInfo *__restrict__ info,
+                                                              const unsigned long long *__restrict__ offsets, const ZSegment *__restrict__ segs,
+                                                              uint32_t nseg, uint32_t header, uint8_t *__restrict__ dst, bool framed)
 {
     const uint32_t b = blockIdx.x, sg = seg_of_chunk(segs, nseg, b);
     const uint64_t start = 2 + offsets[b];
     compact_chunk(slots + static_cast<uint64_t>(b) * kZSlot, start, start + info[b].bytes, b == segs[sg].first_chunk, b + 1 == segs[sg + 1].first_chunk,
-                  header, segs[sg].adler, dst + segs[sg].dst, true);
+                  header, segs[sg].adler, dst + segs[sg].dst, framed);
 }
 
 // Slicing by 4: one aligned word of the stream per step
@@ -476,20 +434,10 @@ __device__ __forceinline__ uint32_t crc_of_piece(const uint8_t *p, uint32_t nbyt
     for (; i < nbytes; ++i) crc = table[0][(crc ^ p[i]) & 255] ^ (crc >> 8);
     return ~crc;
 }
-__global__ __launch_bounds__(64) void deflate_crc_kernel(const uint8_t *__restrict__ dst, uint64_t stream_len, uint32_t *__restrict__ crcs)
-{
-    __shared__ uint32_t table[4][256];
-    crc_tables(table);
-    const uint64_t piece = static_cast<uint64_t>(blockIdx.x) * 64 + threadIdx.x;
-    uint64_t s0;
-    const uint32_t nbytes = piece_span(stream_len, piece, &s0);
-    if (!nbytes) return;
-    crcs[piece] = crc_of_piece(dst + framed_offset(s0, true), nbytes, table); // a piece lies inside one IDAT chunk
-}
-// The batch form: the grid covers every segment's pieces by its stored bound, so that the host need not know the streams'
-// lengths to launch it; a lane reads its segment's real length from the scan's totals, and pieces behind the end write nothing.
-__global__ __launch_bounds__(64) void deflate_crc_seg_kernel(const uint8_t *__restrict__ dst, const ZSegment *__restrict__ segs, uint32_t nseg,
-                                                             const unsigned long long *__restrict__ totals, uint32_t *__restrict__ crcs)
+// The grid covers every segment's pieces by its stored bound, so that the host need not know the streams' lengths to launch
+// it; a lane reads its segment's real length from the scan's totals, and pieces behind the end write nothing.
+__global__ __launch_bounds__(64) void deflate_crc_kernel(const uint8_t *__restrict__ dst, const ZSegment *__restrict__ segs, uint32_t nseg,
+                                                         const unsigned long long *__restrict__ totals, uint32_t *__restrict__ crcs)
 {
     __shared__ uint32_t table[4][256];
     crc_tables(table);
@@ -503,55 +451,27 @@ __global__ __launch_bounds__(64) void deflate_crc_seg_kernel(const uint8_t *__re
 }
 } // namespace
 
-hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t effort, uint32_t *d_tok,
-                                 uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream)
-{
-    const uint64_t chunks = z_chunks(len);
-    if (chunks == 0 || chunks > 0x7FFFFFFFull || effort > 1 || (effort && !d_prev)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(effort ? deflate_chunk_kernel<true> : deflate_chunk_kernel<false>, dim3(static_cast<uint32_t>(chunks)), dim3(kThreads), 0, stream,
-                       static_cast<const uint8_t *>(d_data), len, hint_bpp, hint_row, d_tok, d_slots, d_info, d_prev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(1024), 0, stream, d_info, chunks, d_offsets);
-    return hipGetLastError();
-}
-
-hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_info, const unsigned long long *d_offsets,
-                                  uint64_t chunks, uint32_t header, uint32_t adler, uint8_t *d_dst, bool framed, hipStream_t stream)
-{
-    hipLaunchKernelGGL(deflate_compact_kernel, dim3(static_cast<uint32_t>(chunks)), dim3(256), 0, stream, d_slots, d_info, d_offsets,
-                       chunks, header, adler, d_dst, framed);
-    return hipGetLastError();
-}
-
-hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_t *d_crc, hipStream_t stream)
-{
-    const uint64_t pieces = (stream_len + kCrcPiece - 1) / kCrcPiece;
-    if (reinterpret_cast<uintptr_t>(d_dst) % 4) return hipErrorInvalidValue; // word loads at d_dst + 8 + 12 k + a multiple of kCrcPiece
-    hipLaunchKernelGGL(deflate_crc_kernel, dim3(static_cast<uint32_t>((pieces + 63) / 64)), dim3(64), 0, stream, d_dst, stream_len, d_crc);
-    return hipGetLastError();
-}
-
-hipError_t launch_deflate_segments(const void *d_data, const ZSegment *d_segs, uint32_t nseg, uint32_t chunks, uint32_t effort, uint32_t *d_tok,
-                                   uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, hipStream_t stream)
+hipError_t launch_deflate(const void *d_data, const ZSegment *d_segs, uint32_t nseg, uint32_t chunks, uint32_t effort, uint32_t *d_tok,
+                          uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, hipStream_t stream)
 {
     if (nseg == 0 || chunks == 0 || chunks > 0x7FFFFFFFu || effort > 1 || (effort && !d_prev)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(effort ? deflate_chunk_seg_kernel<true> : deflate_chunk_seg_kernel<false>, dim3(chunks), dim3(kThreads), 0, stream,
+    hipLaunchKernelGGL(effort ? deflate_chunk_kernel<true> : deflate_chunk_kernel<false>, dim3(chunks), dim3(kThreads), 0, stream,
                        static_cast<const uint8_t *>(d_data), d_segs, nseg, d_tok, d_slots, d_info, d_prev);
     return hipGetLastError();
 }
 
-hipError_t launch_deflate_segments_finish(const uint8_t *d_slots, const ZChunkInfo *d_info, const ZSegment *d_segs, uint32_t nseg, uint32_t chunks,
-                                          uint32_t pieces, uint32_t header, unsigned long long *d_offsets, unsigned long long *d_totals,
-                                          uint8_t *d_dst, uint32_t *d_crc, hipStream_t stream)
+hipError_t launch_deflate_finish(const uint8_t *d_slots, const ZChunkInfo *d_info, const ZSegment *d_segs, uint32_t nseg, uint32_t chunks,
+                                 uint32_t pieces, uint32_t header, unsigned long long *d_offsets, unsigned long long *d_totals, uint8_t *d_dst,
+                                 bool framed, uint32_t *d_crc, hipStream_t stream)
 {
-    if (nseg == 0 || chunks == 0 || pieces == 0 || reinterpret_cast<uintptr_t>(d_dst) % kSegAlign) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(deflate_scan_seg_kernel, dim3(nseg), dim3(1024), 0, stream, d_info, d_segs, d_offsets, d_totals);
+    // (framed: word stores and the CRC's word loads at every segment's multiple of kSegAlign; unframed: compact_chunk looks at the pointer)
+    if (nseg == 0 || chunks == 0 || pieces == 0 || (framed && reinterpret_cast<uintptr_t>(d_dst) % kSegAlign) || (d_crc && !framed)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(deflate_scan_kernel, dim3(nseg), dim3(1024), 0, stream, d_info, d_segs, d_offsets, d_totals);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(deflate_compact_seg_kernel, dim3(chunks), dim3(256), 0, stream, d_slots, d_info, d_offsets, d_segs, nseg, header, d_dst);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(deflate_crc_seg_kernel, dim3((pieces + 63) / 64), dim3(64), 0, stream, d_dst, d_segs, nseg, d_totals, d_crc);
+    hipLaunchKernelGGL(deflate_compact_kernel, dim3(chunks), dim3(256), 0, stream, d_slots, d_info, d_offsets, d_segs, nseg, header, d_dst, framed);
+    if ((e = hipGetLastError()) != hipSuccess || !d_crc) return e;
+    hipLaunchKernelGGL(deflate_crc_kernel, dim3((pieces + 63) / 64), dim3(64), 0, stream, d_dst, d_segs, nseg, d_totals, d_crc);
     return hipGetLastError();
 }
 

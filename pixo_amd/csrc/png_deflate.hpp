@@ -1,5 +1,6 @@
-// png_deflate.hpp — host-callable launchers of the device DEFLATE (png_deflate.hip): bytes in HBM -> a zlib stream in
-// HBM, optionally laid out as the bodies of 256 KiB IDAT chunks with room for their frames, and the CRC-32 of its pieces.
+// png_deflate.hpp — host-callable launchers of the device DEFLATE (png_deflate.hip): one or more runs of bytes in HBM -> a
+// zlib stream each in HBM, optionally laid out as the bodies of 256 KiB IDAT chunks with room for their frames, and the
+// CRC-32 of their pieces.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -37,37 +38,28 @@ inline uint64_t z_chunks(uint64_t len) { return (len + kZChunk - 1) / kZChunk; }
 // preceded by 8 bytes (length, type) and followed by 4 (CRC).
 inline uint64_t z_framed_size(uint64_t stream_len) { return stream_len + 12 * ((stream_len + kIdatBytes - 1) / kIdatBytes); }
 
-// One workgroup per chunk: match finding, greedy parse, Huffman codes, the smallest of stored / fixed / dynamic into the
-// chunk's slot; then the exclusive scan of the block lengths.  d_tok: z_chunks * kZTokStride u32; d_slots: z_chunks *
-// kZSlot bytes; d_info: z_chunks entries; d_offsets: z_chunks + 1 u64 (the last: the sum of all block bytes).
-// hint_bpp / hint_row: distances tried at every position besides 1 and the hash table's (0 or out of range: not tried).
-// effort 0: the table's latest occurrence, greedy parse (d_prev is not read).  effort 1: hash chains of kZEffortProbes entries
-// linked in sub-steps of kZEffortSubstep, one-step lazy parse; d_prev: z_chunks * kZPrevStride u16.
-hipError_t launch_deflate_chunks(const void *d_data, uint64_t len, uint32_t hint_bpp, uint32_t hint_row, uint32_t effort, uint32_t *d_tok,
-                                 uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, unsigned long long *d_offsets, hipStream_t stream);
-// The 2 header bytes, the blocks at their final offsets and the 4 checksum bytes into d_dst.
-hipError_t launch_deflate_compact(const uint8_t *d_slots, const ZChunkInfo *d_info, const unsigned long long *d_offsets,
-                                  uint64_t chunks, uint32_t header, uint32_t adler, uint8_t *d_dst, bool framed, hipStream_t stream);
-// zlib.crc32 of every kCrcPiece bytes of a framed stream of stream_len bytes.  A piece is read a word at a time from
-// d_dst + 8 + 12 * (IDAT chunks in front) + a multiple of kCrcPiece: d_dst must be 4-byte aligned, or the launch is refused.
-// It is: a framed stream is only ever written to the context's own buffer, a caller's d_out gets the unframed one.
-static_assert(kCrcPiece % 4 == 0 && kIdatBytes % kCrcPiece == 0, "a CRC piece starts on a word of the framed stream and lies inside one IDAT chunk");
-hipError_t launch_deflate_crc(const uint8_t *d_dst, uint64_t stream_len, uint32_t *d_crc, hipStream_t stream);
-
-// ---- batches: nseg streams (segments, png_deflate_math.h ZSegment) in one launch each ---------------------------------
+// A launch works on nseg streams (segments, png_deflate_math.h ZSegment) at once; a single stream is a table of one.
 // d_segs: the table of nseg + 1 entries that seg_layout filled in, in device memory; d_data / d_dst: what the segments' src
-// / dst count from.  The scratch is indexed by global chunk as above (`chunks` = d_segs[nseg].first_chunk of them).
+// / dst count from.  The scratch is indexed by global chunk (`chunks` = d_segs[nseg].first_chunk of them): d_tok: chunks *
+// kZTokStride u32; d_slots: chunks * kZSlot bytes; d_info: chunks entries.
 static_assert(pixo_pngz::kSegChunk == kZChunk && pixo_pngz::kSegIdat == kIdatBytes && pixo_pngz::kSegPiece == kCrcPiece, "one set of sizes");
 static_assert(sizeof(pixo_pngz::ZSegment) == 48, "the table's layout is the same on both sides");
-// Every chunk of every segment into its slot: one workgroup per chunk, no chunk looks in front of its segment's first byte.
-hipError_t launch_deflate_segments(const void *d_data, const pixo_pngz::ZSegment *d_segs, uint32_t nseg, uint32_t chunks, uint32_t effort,
-                                   uint32_t *d_tok, uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, hipStream_t stream);
+static_assert(kCrcPiece % 4 == 0 && kIdatBytes % kCrcPiece == 0, "a CRC piece starts on a word of the framed stream and lies inside one IDAT chunk");
+// One workgroup per chunk of every segment: match finding, parse, Huffman codes, the smallest of stored / fixed / dynamic into
+// the chunk's slot; no chunk looks in front of its segment's first byte.  The segment's hint_bpp / hint_row: distances tried
+// at every position besides 1 and the hash table's (0 or out of range: not tried).
+// effort 0: the table's latest occurrence, greedy parse (d_prev is not read).  effort 1: hash chains of kZEffortProbes entries
+// linked in sub-steps of kZEffortSubstep, one-step lazy parse; d_prev: chunks * kZPrevStride u16.
+hipError_t launch_deflate(const void *d_data, const pixo_pngz::ZSegment *d_segs, uint32_t nseg, uint32_t chunks, uint32_t effort, uint32_t *d_tok,
+                          uint16_t *d_prev, uint8_t *d_slots, ZChunkInfo *d_info, hipStream_t stream);
 // Scan (d_offsets: `chunks` u64, restarting at every segment; d_totals: nseg u64, each segment's block bytes), compaction
-// (every segment's header, blocks and d_segs[s].adler as IDAT bodies at d_dst + dst; d_dst 16-byte aligned) and the CRC-32
-// of every 4 KiB piece (d_crc: `pieces` = d_segs[nseg].first_piece words; segment s's values start at first_piece, those
-// behind its stream's end are not written).  d_segs[s].adler must be final by now.
-hipError_t launch_deflate_segments_finish(const uint8_t *d_slots, const ZChunkInfo *d_info, const pixo_pngz::ZSegment *d_segs, uint32_t nseg,
-                                          uint32_t chunks, uint32_t pieces, uint32_t header, unsigned long long *d_offsets,
-                                          unsigned long long *d_totals, uint8_t *d_dst, uint32_t *d_crc, hipStream_t stream);
+// (every segment's header, blocks and d_segs[s].adler at d_dst + dst) and, where d_crc is given, the CRC-32 of every 4 KiB
+// piece (d_crc: `pieces` = d_segs[nseg].first_piece words; segment s's values start at first_piece, those behind its
+// stream's end are not written).  framed: the streams as IDAT bodies with room for their frames, d_dst 16-byte aligned (the
+// launch is refused otherwise); unframed: the bare stream at any address, bytes where words would not be aligned, no CRC.
+// d_segs[s].adler must be final by now.
+hipError_t launch_deflate_finish(const uint8_t *d_slots, const ZChunkInfo *d_info, const pixo_pngz::ZSegment *d_segs, uint32_t nseg, uint32_t chunks,
+                                 uint32_t pieces, uint32_t header, unsigned long long *d_offsets, unsigned long long *d_totals, uint8_t *d_dst,
+                                 bool framed, uint32_t *d_crc, hipStream_t stream);
 
 } // namespace pixo_dev

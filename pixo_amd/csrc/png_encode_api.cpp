@@ -2,7 +2,8 @@
 // compressed where it lies (png_deflate.hip), its blocks are compacted into the bodies of 256 KiB IDAT chunks, the chunks'
 // CRC-32 come from the device in 4 KiB pieces, and only the finished file crosses to the host.  The chunks around IDAT are
 // the reference's byte for byte (src/png/mod.rs:513-630); the IDAT body is this library's own DEFLATE.
-// The batch entries run the same stages over N equal images at once, every image a segment (png_deflate_math.h ZSegment).
+// There is one tail (tail_begin, tail_finish, tail_deliver) over a table of segments (png_deflate_math.h ZSegment): a single
+// file and a bare zlib stream are a table of one, the batch entries run N equal images through it at once.
 #include "capi_internal.hpp"
 #include "png_deflate.hpp"
 #include "png_filter.hpp"
@@ -37,53 +38,6 @@ uint32_t adler_of_chunks(const pixo_dev::ZChunkInfo *info, uint64_t chunks, uint
         s1 = (s1 + info[c].sum_a % M) % M;
     }
     return static_cast<uint32_t>((s2 << 16) | s1);
-}
-
-// One run of the device DEFLATE: len > 0 bytes at d_data on the context's device -> their zlib stream.
-struct ZlibJob {
-    const void *d_data;
-    size_t len;
-    uint8_t level;                   // the header's FLEVEL only
-    uint32_t hint_bpp, hint_row;     // distances the match search tries besides 1 and its hash table's (0: none)
-    void *d_dst = nullptr;           // where the stream goes (null: c.z_stream)
-    const uint32_t *adler = nullptr; // the checksum when the caller has it already (only the total comes down then)
-    bool framed = false;             // as IDAT bodies (z_framed_size) in c.z_stream; their pieces' CRC-32 are then on the way into c.h_zinfo
-    uint32_t effort = 0;             // 0: the table's latest occurrence, greedy; 1: hash chains and a lazy parse (PIXO_PNG_EFFORT_HIGH)
-};
-int zlib_on_device(Context &c, const ZlibJob &j, uint64_t *stream_len)
-{
-    const uint64_t chunks = pixo_dev::z_chunks(j.len), bound = stored_bound(j.len);
-    const size_t info_bytes = chunks * sizeof(pixo_dev::ZChunkInfo), off_bytes = (chunks + 1) * sizeof(unsigned long long);
-    const size_t crc_bytes = j.framed ? static_cast<size_t>((bound + pixo_dev::kCrcPiece - 1) / pixo_dev::kCrcPiece) * 4 : 0;
-    int rc;
-    if ((rc = c.z_tok.reserve(chunks * pixo_dev::kZTokStride * sizeof(uint32_t))) || (rc = c.z_slots.reserve(chunks * pixo_dev::kZSlot)) ||
-        (rc = c.z_info.reserve(info_bytes + off_bytes)) || (rc = c.h_zinfo.reserve(std::max(info_bytes + off_bytes, crc_bytes))))
-        return rc;
-    if (!j.d_dst && (rc = c.z_stream.reserve(pixo_dev::z_framed_size(bound) + 16))) return rc;
-    if (j.framed && (rc = c.z_crc.reserve(crc_bytes))) return rc;
-    if (j.effort && (rc = c.z_prev.reserve(chunks * pixo_dev::kZPrevStride * sizeof(uint16_t)))) return rc;
-    auto *d_info = c.z_info.as<pixo_dev::ZChunkInfo>();
-    auto *d_off = reinterpret_cast<unsigned long long *>(c.z_info.as<uint8_t>() + info_bytes);
-    HIP_TRY(pixo_dev::launch_deflate_chunks(j.d_data, j.len, j.hint_bpp, j.hint_row, j.effort, c.z_tok.as<uint32_t>(), j.effort ? c.z_prev.as<uint16_t>() : nullptr, c.z_slots.as<uint8_t>(), d_info, d_off,
-                                            c.stream));
-    // The blocks' total, the last word of z_info, comes down: alone when the checksum is known, behind all the checksum is made from otherwise
-    const size_t all = info_bytes + off_bytes, down = j.adler ? sizeof(unsigned long long) : all;
-    HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, c.z_info.as<uint8_t>() + all - down, down, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    const unsigned long long blocks = *reinterpret_cast<const unsigned long long *>(c.h_zinfo.as<uint8_t>() + down - sizeof(unsigned long long));
-    const uint32_t adler = j.adler ? *j.adler : adler_of_chunks(c.h_zinfo.as<pixo_dev::ZChunkInfo>(), chunks, j.len);
-    *stream_len = 2 + blocks + 4;
-    if (*stream_len > bound) return fail(PIXO_ERR_COMPRESSION, "Compression error: device DEFLATE exceeded the stored bound");
-    uint8_t head[2];
-    zlib_header(j.level, head);
-    uint8_t *dst = j.d_dst ? static_cast<uint8_t *>(j.d_dst) : c.z_stream.as<uint8_t>();
-    HIP_TRY(pixo_dev::launch_deflate_compact(c.z_slots.as<uint8_t>(), d_info, d_off, chunks, head[0] | (uint32_t{head[1]} << 8), adler, dst, j.framed, c.stream));
-    if (j.framed) {
-        HIP_TRY(pixo_dev::launch_deflate_crc(dst, *stream_len, c.z_crc.as<uint32_t>(), c.stream));
-        const size_t pieces = static_cast<size_t>((*stream_len + pixo_dev::kCrcPiece - 1) / pixo_dev::kCrcPiece);
-        HIP_TRY(hipMemcpyAsync(c.h_zinfo.p, c.z_crc.p, pieces * 4, hipMemcpyDeviceToHost, c.stream));
-    }
-    return PIXO_OK;
 }
 
 int bad_effort(uint32_t effort) // an argument out of its enumeration, as for the resize algorithm
@@ -146,75 +100,20 @@ void frame_idats(uint8_t *idat, uint64_t stream_len, const uint32_t *piece_crc)
     std::memcpy(idat + pixo_dev::z_framed_size(stream_len), iend.data(), 12);
 }
 
-// A prepared stream of `len` bytes in c.p_out -> the finished file in a block the caller owns: DEFLATE, copy, frame, deliver.
-int png_finish(Context &c, const pixo_png_options &o, const pixo_png_layout &layout, uint32_t trns_len, size_t len, uint32_t adler,
-               const PngFilterView &view, uint8_t **out, size_t *out_len)
-{
-    ZlibJob job{c.p_out.p, len, o.compression_level, view.bpp, view.row};
-    job.adler = &adler;
-    job.framed = true;
-    job.effort = (o.flags & PIXO_PNG_EFFORT_HIGH) ? 1 : 0;
-    uint64_t stream_len = 0;
-    int rc = zlib_on_device(c, job, &stream_len);
-    if (rc) return rc;
-
-    const std::vector<uint8_t> head = png_head(o.width, o.height, layout, trns_len);
-    const size_t framed = static_cast<size_t>(pixo_dev::z_framed_size(stream_len)), file_len = head.size() + framed + 12;
-    if ((rc = c.h_file.reserve(file_len))) return rc;
-    uint8_t *file = c.h_file.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(file + head.size(), c.z_stream.p, framed, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream)); // (the pieces' CRC-32 have arrived as well)
-    std::memcpy(file, head.data(), head.size());
-    frame_idats(file + head.size(), stream_len, c.h_zinfo.as<uint32_t>());
-    return deliver(file, file_len, out, out_len);
-}
-
-// Pixels on the context's device -> the finished file: prepare, then png_finish.
-int png_file(Context &c, const void *d_px, const pixo_png_options &o, uint8_t **out, size_t *out_len)
-{
-    int rc = c.p_out.reserve(static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) * bytes_per_pixel(o.color_type) + 1));
-    if (rc) return rc;
-    pixo_png_layout layout;
-    size_t len = 0;
-    uint32_t adler = 0;
-    PngFilterView view;
-    if ((rc = png_prepare_on_device(c, d_px, o, c.p_out.p, &layout, &len, &adler, &view))) return rc;
-    return png_finish(c, o, layout, layout.palette_len, len, adler, view, out, out_len);
-}
-
-// ... with quantisation (mod.rs:469-511): the gate declines -> png_file; otherwise the indices as an 8-bit, one-byte-per-pixel
-// image through the same filter, DEFLATE, CRC and chunk path (encode_indexed_into, :1814-1886).
-int png_file_lossy(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization &q, uint8_t **out, size_t *out_len)
-{
-    bool applied = false;
-    pixo_png_layout layout;
-    uint32_t trns_len = 0;
-    int rc = png_quantize_on_device(c, d_px, o, q, &applied, &layout, &trns_len);
-    if (rc) return rc;
-    if (!applied) return png_file(c, d_px, o, out, out_len);
-    uint8_t strategy = o.filter_strategy; // :1866-1874: palette-aware filtering
-    if (strategy == PIXO_PNG_ADAPTIVE || strategy == PIXO_PNG_ADAPTIVE_FAST || strategy == PIXO_PNG_MINSUM || strategy == PIXO_PNG_BIGRAMS) strategy = PIXO_PNG_NONE;
-    int run = 0;
-    bool seq = false;
-    const size_t len = static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) + 1);
-    if ((rc = png_plan(o.width, o.height, static_cast<uint64_t>(o.width) * o.height, 1, strategy, o.flags, &run, &seq)) || (rc = c.p_out.reserve(len))) return rc;
-    uint32_t adler = 0;
-    if ((rc = png_filter_on_device(c, c.q_index.p, o.width, o.height, 1, run, seq, c.p_out.p, &adler))) return rc;
-    return png_finish(c, o, layout, trns_len, len, adler, PngFilterView{1, o.width + 1}, out, out_len);
-}
-
-// ---- batches: N equal images, one pass of filters, DEFLATE and CRC (DESIGN.md §4.6c, "segments") ------------------------
-// One image's prepared stream in c.p_out, and what its file needs around the IDAT chunks.
+// ---- the tail: prepared streams (segments) -> their zlib streams in one pass of DEFLATE, scan, compaction and CRC ----------
+// Every entry ends here: a single file or a bare zlib stream is a table of one segment, a batch one of N.
+// One prepared stream, and what its file needs around the IDAT chunks.
 struct PngSegment {
-    size_t src = 0, len = 0; // its first byte counted from c.p_out.p, its bytes
-    PngFilterView view{1, 0};
+    size_t src = 0, len = 0; // its first byte counted from the tail's d_data, its bytes
+    PngFilterView view{1, 0}; // distances the match search tries besides 1 and its hash table's (0: none)
     uint32_t adler = 0;
     pixo_png_layout layout;
     uint32_t trns_len = 0;
 };
-// Where a batch's files go: blocks the caller owns (files), or back to back into an arena in host memory (offsets).
+// Where the files go: blocks the caller owns (files), or back to back into an arena in host memory (offsets).
 struct BatchSink {
     uint8_t **files = nullptr;
+    bool staged = false; // blocks: none from the pinned pool, every file through the context's pinned file buffer into a fresh malloc block (the single entries)
     uint8_t *arena = nullptr;
     size_t cap = 0;
     size_t *offsets = nullptr, *lens = nullptr;
@@ -228,23 +127,28 @@ int wait_for(Context &c, BatchSink &sink)
     HIP_TRY(hipStreamSynchronize(c.stream));
     return PIXO_OK;
 }
+uint32_t png_effort(const pixo_png_options &o) { return (o.flags & PIXO_PNG_EFFORT_HIGH) ? 1 : 0; }
 
-// The batched tail of one sub-batch: the segment table, the scratch, the launches.  Host side of the table, the segments'
-// totals and the pieces' CRC-32: c.h_zinfo, in that order.
+// One run of the tail: the segment table, the scratch, the launches.  Host side, in c.h_zinfo: the table, then what comes
+// down — the segments' totals and the pieces' CRC-32 of framed streams, the chunks' records of a bare one.
 struct BatchTail {
+    const void *d_data = nullptr; // what the segments' src count from (set by the caller)
+    void *d_dst = nullptr;        // where the streams go (null: c.z_stream)
+    bool framed = true;           // as IDAT bodies (z_framed_size) with their pieces' CRC-32; false: the bare zlib stream of one segment, at any address
     uint32_t nseg = 0, chunks = 0, pieces = 0, header = 0;
-    size_t table_bytes = 0, info_bytes = 0, off_bytes = 0, totals_bytes = 0;
+    size_t table_bytes = 0, info_bytes = 0, totals_bytes = 0;
     ZSegment *h_table = nullptr;
     ZSegment *d_table = nullptr;
-    unsigned long long *d_off = nullptr, *d_totals = nullptr;
-    const unsigned long long *h_totals = nullptr;
-    const uint32_t *h_crc = nullptr;
+    unsigned long long *d_off = nullptr, *d_totals = nullptr; // (the totals in front of the CRC values in c.z_crc: one copy brings both)
+    uint8_t *h_down = nullptr;
+    const unsigned long long *h_totals() const { return reinterpret_cast<const unsigned long long *>(h_down); }
+    const uint32_t *h_crc() const { return reinterpret_cast<const uint32_t *>(h_down + totals_bytes); }
 };
 // Reserves everything, uploads the table and launches the DEFLATE of every chunk of every segment.  The Adler-32 of the
-// segments need not be known yet: the compaction reads them (tail_finish).
-int tail_begin(Context &c, const std::vector<PngSegment> &segs, const pixo_png_options &o, BatchTail &t)
+// segments need not be known yet: the compaction reads them (tail_finish).  level: the header's FLEVEL only; effort 0: the
+// table's latest occurrence, greedy; 1: hash chains and a lazy parse (PIXO_PNG_EFFORT_HIGH).
+int tail_begin(Context &c, const std::vector<PngSegment> &segs, uint8_t level, uint32_t effort, BatchTail &t)
 {
-    const uint32_t effort = (o.flags & PIXO_PNG_EFFORT_HIGH) ? 1 : 0;
     t.nseg = static_cast<uint32_t>(segs.size());
     std::vector<ZSegment> table(t.nseg + 1);
     for (uint32_t i = 0; i < t.nseg; ++i) table[i] = ZSegment{segs[i].src, segs[i].len, 0, 0, 0, segs[i].view.bpp, segs[i].view.row, segs[i].adler, 0};
@@ -253,65 +157,64 @@ int tail_begin(Context &c, const std::vector<PngSegment> &segs, const pixo_png_o
     t.pieces = table[t.nseg].first_piece;
     t.table_bytes = table.size() * sizeof(ZSegment);
     t.info_bytes = t.chunks * sizeof(pixo_dev::ZChunkInfo);
-    t.off_bytes = t.chunks * sizeof(unsigned long long);
     t.totals_bytes = t.nseg * sizeof(unsigned long long);
+    const size_t off_bytes = t.chunks * sizeof(unsigned long long), crc_bytes = t.framed ? static_cast<size_t>(t.pieces) * 4 : 0;
     int rc;
     if ((rc = c.z_tok.reserve(static_cast<size_t>(t.chunks) * pixo_dev::kZTokStride * sizeof(uint32_t))) ||
-        (rc = c.z_slots.reserve(static_cast<size_t>(t.chunks) * pixo_dev::kZSlot)) ||
-        (rc = c.z_info.reserve(t.info_bytes + t.off_bytes + t.totals_bytes + t.table_bytes)) ||
-        (rc = c.h_zinfo.reserve(t.table_bytes + t.totals_bytes + static_cast<size_t>(t.pieces) * 4)) ||
-        (rc = c.z_stream.reserve(static_cast<size_t>(table[t.nseg].dst) + 16)) || (rc = c.z_crc.reserve(static_cast<size_t>(t.pieces) * 4)))
+        (rc = c.z_slots.reserve(static_cast<size_t>(t.chunks) * pixo_dev::kZSlot)) || (rc = c.z_info.reserve(t.info_bytes + off_bytes + t.table_bytes)) ||
+        (rc = c.h_zinfo.reserve(t.table_bytes + std::max(t.totals_bytes + crc_bytes, t.info_bytes))) || (rc = c.z_crc.reserve(t.totals_bytes + crc_bytes)))
         return rc;
+    if (!t.d_dst && (rc = c.z_stream.reserve(static_cast<size_t>(table[t.nseg].dst) + 16))) return rc;
     if (effort && (rc = c.z_prev.reserve(static_cast<size_t>(t.chunks) * pixo_dev::kZPrevStride * sizeof(uint16_t)))) return rc;
     uint8_t *d = c.z_info.as<uint8_t>(), *h = c.h_zinfo.as<uint8_t>();
     t.d_off = reinterpret_cast<unsigned long long *>(d + t.info_bytes);
-    t.d_totals = reinterpret_cast<unsigned long long *>(d + t.info_bytes + t.off_bytes);
-    t.d_table = reinterpret_cast<ZSegment *>(d + t.info_bytes + t.off_bytes + t.totals_bytes);
+    t.d_table = reinterpret_cast<ZSegment *>(d + t.info_bytes + off_bytes);
+    t.d_totals = c.z_crc.as<unsigned long long>();
     t.h_table = reinterpret_cast<ZSegment *>(h);
-    t.h_totals = reinterpret_cast<const unsigned long long *>(h + t.table_bytes);
-    t.h_crc = reinterpret_cast<const uint32_t *>(h + t.table_bytes + t.totals_bytes);
+    t.h_down = h + t.table_bytes;
     std::memcpy(t.h_table, table.data(), t.table_bytes);
     uint8_t head[2];
-    zlib_header(o.compression_level, head);
+    zlib_header(level, head);
     t.header = head[0] | (uint32_t{head[1]} << 8);
     HIP_TRY(hipMemcpyAsync(t.d_table, t.h_table, t.table_bytes, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(pixo_dev::launch_deflate_segments(c.p_out.p, t.d_table, t.nseg, t.chunks, effort, c.z_tok.as<uint32_t>(),
-                                              effort ? c.z_prev.as<uint16_t>() : nullptr, c.z_slots.as<uint8_t>(), c.z_info.as<pixo_dev::ZChunkInfo>(), c.stream));
+    HIP_TRY(pixo_dev::launch_deflate(t.d_data, t.d_table, t.nseg, t.chunks, effort, c.z_tok.as<uint32_t>(), effort ? c.z_prev.as<uint16_t>() : nullptr,
+                                     c.z_slots.as<uint8_t>(), c.z_info.as<pixo_dev::ZChunkInfo>(), c.stream));
     return PIXO_OK;
 }
-// Scan, compaction and CRC over all segments; their totals and piece values come down together.  adlers_late: the segments'
-// checksums became known after tail_begin (the stream has been synchronised since): the table goes up once more.
-int tail_finish(Context &c, const std::vector<PngSegment> &segs, BatchTail &t, bool adlers_late, BatchSink &sink)
+// Scan, compaction and CRC over all segments; the totals and piece values of framed streams are on their way down behind
+// them.  adlers_late: the segments' checksums became known after tail_begin (the stream has been synchronised since): the
+// table goes up once more.
+int tail_finish(Context &c, const std::vector<PngSegment> &segs, BatchTail &t, bool adlers_late)
 {
     if (adlers_late) {
         for (uint32_t i = 0; i < t.nseg; ++i) t.h_table[i].adler = segs[i].adler;
         HIP_TRY(hipMemcpyAsync(t.d_table, t.h_table, t.table_bytes, hipMemcpyHostToDevice, c.stream));
     }
-    HIP_TRY(pixo_dev::launch_deflate_segments_finish(c.z_slots.as<uint8_t>(), c.z_info.as<pixo_dev::ZChunkInfo>(), t.d_table, t.nseg, t.chunks, t.pieces,
-                                                     t.header, t.d_off, t.d_totals, c.z_stream.as<uint8_t>(), c.z_crc.as<uint32_t>(), c.stream));
-    HIP_TRY(hipMemcpyAsync(c.h_zinfo.as<uint8_t>() + t.table_bytes, t.d_totals, t.totals_bytes, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipMemcpyAsync(c.h_zinfo.as<uint8_t>() + t.table_bytes + t.totals_bytes, c.z_crc.p, static_cast<size_t>(t.pieces) * 4, hipMemcpyDeviceToHost, c.stream));
-    return wait_for(c, sink);
+    uint32_t *d_crc = t.framed ? reinterpret_cast<uint32_t *>(c.z_crc.as<uint8_t>() + t.totals_bytes) : nullptr;
+    HIP_TRY(pixo_dev::launch_deflate_finish(c.z_slots.as<uint8_t>(), c.z_info.as<pixo_dev::ZChunkInfo>(), t.d_table, t.nseg, t.chunks, t.pieces, t.header, t.d_off,
+                                            t.d_totals, t.d_dst ? static_cast<uint8_t *>(t.d_dst) : c.z_stream.as<uint8_t>(), t.framed, d_crc, c.stream));
+    if (t.framed) HIP_TRY(hipMemcpyAsync(t.h_down, c.z_crc.p, t.totals_bytes + static_cast<size_t>(t.pieces) * 4, hipMemcpyDeviceToHost, c.stream));
+    return PIXO_OK;
 }
-// The framed streams behind their heads, in the caller's blocks or at their arena offsets; frames and IEND by the host.
-// first: the sub-batch's first image in the batch.
+// Copy, frame, deliver: the framed streams behind their heads, in the caller's blocks or at their arena offsets; frames and
+// IEND by the host.  first: the segments' first image in the sink.
 int tail_deliver(Context &c, const std::vector<PngSegment> &segs, const BatchTail &t, const pixo_png_options &o, uint32_t first, BatchSink &sink)
 {
     struct File { std::vector<uint8_t> head; uint64_t stream_len = 0; size_t framed = 0, len = 0; uint8_t *at = nullptr; bool staged = false; };
     std::vector<File> f(t.nseg);
     for (uint32_t i = 0; i < t.nseg; ++i) {
-        f[i].stream_len = 2 + t.h_totals[i] + 4;
+        f[i].stream_len = 2 + t.h_totals()[i] + 4;
         if (f[i].stream_len > stored_bound(segs[i].len)) return fail(PIXO_ERR_COMPRESSION, "Compression error: device DEFLATE exceeded the stored bound");
         f[i].head = png_head(o.width, o.height, segs[i].layout, segs[i].trns_len);
         f[i].framed = static_cast<size_t>(pixo_dev::z_framed_size(f[i].stream_len));
         f[i].len = f[i].head.size() + f[i].framed + 12;
         sink.lens[first + i] = f[i].len;
     }
-    // Blocks: from the pinned pool, the copies go straight into them.  Arena: straight into a pinned one.  Otherwise (the pool
-    // is exhausted, the arena is pageable) through the context's pinned file buffer.
+    // Blocks: from the pinned pool, the copies go straight into them.  Arena: straight into a pinned one.  Otherwise (the sink
+    // asks for it, the pool is exhausted, the arena is pageable) through the context's pinned file buffer.
     size_t stage = 0;
     if (sink.files) {
-        bool pooled = true;
+        bool pooled = !sink.staged;
         for (uint32_t i = 0; i < t.nseg && pooled; ++i)
             if (!(sink.files[first + i] = pool_take(f[i].len))) pooled = false;
         for (uint32_t i = 0; i < t.nseg; ++i) {
@@ -349,10 +252,10 @@ int tail_deliver(Context &c, const std::vector<PngSegment> &segs, const BatchTai
         const hipError_t idle = hipStreamSynchronize(c.stream);
         if (e == hipSuccess) e = idle;
     }
-    if (e != hipSuccess) return hip_fail(e, "device-to-host copy of the PNG batch files");
+    if (e != hipSuccess) return hip_fail(e, "device-to-host copy of the PNG files");
     for (uint32_t i = 0; i < t.nseg; ++i) {
         if (!f[i].at) continue;
-        frame_idats(f[i].at + f[i].head.size(), f[i].stream_len, t.h_crc + t.h_table[i].first_piece);
+        frame_idats(f[i].at + f[i].head.size(), f[i].stream_len, t.h_crc() + t.h_table[i].first_piece);
         if (!f[i].staged) continue;
         if (sink.files) {
             size_t n = 0;
@@ -364,30 +267,86 @@ int tail_deliver(Context &c, const std::vector<PngSegment> &segs, const BatchTai
     return PIXO_OK;
 }
 
-// One image of a batch the image-by-image way in: its prepared stream at c.p_out + seg.src, by the single entries' own sequence.
+// One image's prepared stream at c.p_out + seg.src: reduced and filtered, or with q (mod.rs:469-511) and where its gate
+// applies the indices as an 8-bit, one-byte-per-pixel image through the same filters (encode_indexed_into, :1814-1886).
+// c.p_out is reserved here for a stream that ends where this one does: a batch has reserved all its images' before the
+// first, so nothing moves under the streams in front.
 int png_segment_of_image(Context &c, const void *d_img, const pixo_png_options &o, const pixo_png_quantization *q, PngSegment &seg)
 {
-    uint8_t *dst = c.p_out.as<uint8_t>() + seg.src;
     int rc;
-    if (q) { // png_file_lossy
+    if (q) {
         bool applied = false;
         if ((rc = png_quantize_on_device(c, d_img, o, *q, &applied, &seg.layout, &seg.trns_len))) return rc;
         if (applied) {
-            uint8_t strategy = o.filter_strategy;
+            uint8_t strategy = o.filter_strategy; // :1866-1874: palette-aware filtering
             if (strategy == PIXO_PNG_ADAPTIVE || strategy == PIXO_PNG_ADAPTIVE_FAST || strategy == PIXO_PNG_MINSUM || strategy == PIXO_PNG_BIGRAMS) strategy = PIXO_PNG_NONE;
             int run = 0;
             bool seq = false;
-            if ((rc = png_plan(o.width, o.height, static_cast<uint64_t>(o.width) * o.height, 1, strategy, o.flags, &run, &seq))) return rc;
             seg.len = static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) + 1);
             seg.view = PngFilterView{1, o.width + 1};
-            return png_filter_on_device(c, c.q_index.p, o.width, o.height, 1, run, seq, dst, &seg.adler);
+            if ((rc = png_plan(o.width, o.height, static_cast<uint64_t>(o.width) * o.height, 1, strategy, o.flags, &run, &seq)) || (rc = c.p_out.reserve(seg.src + seg.len)))
+                return rc;
+            return png_filter_on_device(c, c.q_index.p, o.width, o.height, 1, run, seq, c.p_out.as<uint8_t>() + seg.src, &seg.adler);
         }
     }
-    if ((rc = png_prepare_on_device(c, d_img, o, dst, &seg.layout, &seg.len, &seg.adler, &seg.view))) return rc;
+    if ((rc = c.p_out.reserve(seg.src + static_cast<size_t>(o.height) * (static_cast<size_t>(o.width) * bytes_per_pixel(o.color_type) + 1)))) return rc;
+    if ((rc = png_prepare_on_device(c, d_img, o, c.p_out.as<uint8_t>() + seg.src, &seg.layout, &seg.len, &seg.adler, &seg.view))) return rc;
     seg.trns_len = seg.layout.palette_len;
     return PIXO_OK;
 }
 
+// Pixels on the context's device -> the finished file in a block the caller owns: one segment through the tail, delivered
+// through the context's pinned file buffer.  The host waits twice behind the prepare stage's own: for the total, for the file.
+int png_file(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization *q, uint8_t **out, size_t *out_len)
+{
+    std::vector<PngSegment> seg(1);
+    int rc = png_segment_of_image(c, d_px, o, q, seg[0]);
+    if (rc) return rc;
+    uint8_t *file = nullptr;
+    size_t file_len = 0;
+    BatchSink sink;
+    sink.files = &file;
+    sink.lens = &file_len;
+    sink.staged = true;
+    BatchTail tail;
+    tail.d_data = c.p_out.p;
+    if ((rc = tail_begin(c, seg, o.compression_level, png_effort(o), tail)) || (rc = tail_finish(c, seg, tail, false)) || (rc = wait_for(c, sink)) ||
+        (rc = tail_deliver(c, seg, tail, o, 0, sink)))
+        return rc;
+    if (debug().trace) std::fprintf(stderr, "[pixo_hip] png file: %u chunk(s), host waits %u (behind the image's own)\n", tail.chunks, sink.waits);
+    *out = file;
+    *out_len = file_len;
+    return PIXO_OK;
+}
+
+// len > 0 bytes at d_data on the context's device -> their bare zlib stream at d_dst (null: c.z_stream): one unframed segment
+// through the tail.  The checksum is not known up front: the chunks' records come down behind the DEFLATE, the host joins
+// their sums (and adds up the blocks' bytes: the stream's length), and the table goes up again with it.  One wait here;
+// the launches of tail_finish are in flight on return.
+int zlib_stream(Context &c, const void *d_data, size_t len, uint8_t level, uint32_t hint_bpp, uint32_t hint_row, uint32_t effort, void *d_dst,
+                BatchSink &sink, uint64_t *stream_len)
+{
+    std::vector<PngSegment> seg(1);
+    seg[0].len = len;
+    seg[0].view = PngFilterView{hint_bpp, hint_row};
+    BatchTail tail;
+    tail.d_data = d_data;
+    tail.d_dst = d_dst;
+    tail.framed = false;
+    int rc = tail_begin(c, seg, level, effort, tail);
+    if (rc) return rc;
+    const auto *info = reinterpret_cast<const pixo_dev::ZChunkInfo *>(tail.h_down);
+    HIP_TRY(hipMemcpyAsync(tail.h_down, c.z_info.p, tail.info_bytes, hipMemcpyDeviceToHost, c.stream));
+    if ((rc = wait_for(c, sink))) return rc;
+    seg[0].adler = adler_of_chunks(info, tail.chunks, len);
+    uint64_t blocks = 0;
+    for (uint32_t k = 0; k < tail.chunks; ++k) blocks += info[k].bytes;
+    *stream_len = 2 + blocks + 4;
+    if (*stream_len > stored_bound(len)) return fail(PIXO_ERR_COMPRESSION, "Compression error: device DEFLATE exceeded the stored bound");
+    return tail_finish(c, seg, tail, true);
+}
+
+// ---- batches: N equal images, one pass of filters, DEFLATE and CRC (DESIGN.md §4.6c, "segments") ------------------------
 // `batch` images back to back at d_px -> their files into the sink.  Sub-batches run one after the other on the context.  A
 // sub-batch holds at most 64 MiB of prepared stream AND at most kBatchChunks chunks, and always at least one image: the
 // scratch is per CHUNK, not per byte — kZTokStride * 4 + kZSlot = 327,696 bytes for every chunk however short (524,304 with
@@ -415,6 +374,7 @@ int png_batch(Context &c, const void *d_px, const pixo_png_options &o, const pix
         if ((rc = c.p_out.reserve(full * nb))) return rc;
         std::vector<PngSegment> segs(nb);
         BatchTail tail;
+        tail.d_data = c.p_out.p;
         Stopwatch watch; // (debug switch trace: wall time between the host's waits)
         for (uint32_t i = 0; i < nb; ++i) segs[i].src = full * i;
         if (filter_batch) {
@@ -428,7 +388,7 @@ int png_batch(Context &c, const void *d_px, const pixo_png_options &o, const pix
                 sg.view = PngFilterView{bpp, o.width * bpp + 1};
             }
             // filters, row sums on their way down, DEFLATE behind them: one wait for all three, then the checksums on the host
-            if ((rc = png_filter_batch_begin(c, d_first, o.width, o.height, nb, bpp, run, c.p_out.p)) || (rc = tail_begin(c, segs, o, tail)) ||
+            if ((rc = png_filter_batch_begin(c, d_first, o.width, o.height, nb, bpp, run, c.p_out.p)) || (rc = tail_begin(c, segs, o.compression_level, png_effort(o), tail)) ||
                 (rc = wait_for(c, sink)))
                 return rc;
             for (uint32_t i = 0; i < nb; ++i) segs[i].adler = png_filter_batch_adler(c, o.width, o.height, bpp, i);
@@ -437,9 +397,9 @@ int png_batch(Context &c, const void *d_px, const pixo_png_options &o, const pix
             for (uint32_t i = 0; i < nb; ++i)
                 if ((rc = png_segment_of_image(c, d_first + px_bytes * i, o, q, segs[i]))) return rc;
             watch.lap("png batch: images prepared");
-            if ((rc = tail_begin(c, segs, o, tail))) return rc;
+            if ((rc = tail_begin(c, segs, o.compression_level, png_effort(o), tail))) return rc;
         }
-        if ((rc = tail_finish(c, segs, tail, filter_batch, sink))) return rc;
+        if ((rc = tail_finish(c, segs, tail, filter_batch)) || (rc = wait_for(c, sink))) return rc;
         watch.lap(filter_batch ? "png batch: scan, compact, CRC" : "png batch: DEFLATE to CRC");
         if ((rc = tail_deliver(c, segs, tail, o, first, sink))) return rc;
         watch.lap("png batch: copies, frames");
@@ -518,11 +478,11 @@ int pixo_hip_zlib_compress_effort(const uint8_t *data, size_t len, uint8_t level
     int rc = upload(c, c.p_in, data, len);
     if (rc) return rc;
     uint64_t n = 0;
-    ZlibJob job{c.p_in.p, len, level, hint_bpp, hint_row};
-    job.effort = effort;
-    if ((rc = zlib_on_device(c, job, &n)) || (rc = c.h_file.reserve(n))) return rc;
+    BatchSink sink; // (the host waits twice: for the chunks' records, for the stream)
+    if ((rc = zlib_stream(c, c.p_in.p, len, level, hint_bpp, hint_row, effort, nullptr, sink, &n)) || (rc = c.h_file.reserve(n))) return rc;
     HIP_TRY(hipMemcpyAsync(c.h_file.p, c.z_stream.p, n, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
+    if ((rc = wait_for(c, sink))) return rc;
+    if (debug().trace) std::fprintf(stderr, "[pixo_hip] zlib: host waits %u\n", sink.waits);
     return deliver(c.h_file.as<uint8_t>(), n, out, out_len);
 }
 
@@ -553,10 +513,9 @@ int pixo_hip_zlib_compress_effort_device(const void *d_data, size_t len, uint8_t
     }
     PIXO_REQUIRE(d_data);
     uint64_t n = 0;
-    ZlibJob job{d_data, len, level, hint_bpp, hint_row, d_out};
-    job.effort = effort;
-    if ((rc = zlib_on_device(*c, job, &n))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    BatchSink sink; // (the host waits twice: for the chunks' records, for the stream)
+    if ((rc = zlib_stream(*c, d_data, len, level, hint_bpp, hint_row, effort, d_out, sink, &n)) || (rc = wait_for(*c, sink))) return rc;
+    if (debug().trace) std::fprintf(stderr, "[pixo_hip] zlib to the device: host waits %u\n", sink.waits);
     *out_len = n;
     return PIXO_OK;
 }
@@ -576,7 +535,7 @@ int pixo_hip_png_encode(const uint8_t *data, size_t data_len, const pixo_png_opt
     PIXO_REQUIRE(out_len);
     PIXO_THREAD_CONTEXT(c);
     if ((rc = upload(c, c.p_in, data, data_len))) return rc;
-    return png_file(c, c.p_in.p, *options, out, out_len);
+    return png_file(c, c.p_in.p, *options, nullptr, out, out_len);
 }
 
 int pixo_hip_png_encode_device(const void *d_pixels, const pixo_png_options *options, uint8_t **out, size_t *out_len)
@@ -588,7 +547,7 @@ int pixo_hip_png_encode_device(const void *d_pixels, const pixo_png_options *opt
     PIXO_REQUIRE(out_len);
     Context *c = nullptr;
     if ((rc = context_on_current_device(&c))) return rc;
-    return png_file(*c, d_pixels, *options, out, out_len);
+    return png_file(*c, d_pixels, *options, nullptr, out, out_len);
 }
 
 int pixo_hip_png_encode_lossy(const uint8_t *data, size_t data_len, const pixo_png_options *options, const pixo_png_quantization *quantization,
@@ -602,7 +561,7 @@ int pixo_hip_png_encode_lossy(const uint8_t *data, size_t data_len, const pixo_p
     PIXO_REQUIRE(out_len);
     PIXO_THREAD_CONTEXT(c);
     if ((rc = upload(c, c.p_in, data, data_len))) return rc;
-    return png_file_lossy(c, c.p_in.p, *options, *quantization, out, out_len);
+    return png_file(c, c.p_in.p, *options, quantization, out, out_len);
 }
 
 int pixo_hip_png_encode_lossy_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization, uint8_t **out,
@@ -616,7 +575,7 @@ int pixo_hip_png_encode_lossy_device(const void *d_pixels, const pixo_png_option
     PIXO_REQUIRE(out_len);
     Context *c = nullptr;
     if ((rc = context_on_current_device(&c))) return rc;
-    return png_file_lossy(*c, d_pixels, *options, *quantization, out, out_len);
+    return png_file(*c, d_pixels, *options, quantization, out, out_len);
 }
 
 int pixo_hip_png_encode_batch_device(const void *d_pixels, const pixo_png_options *options, const pixo_png_quantization *quantization, uint32_t batch,

@@ -1,7 +1,10 @@
-"""PNG batch entries on the device: `batch` equally sized images in one pass of filters, DEFLATE and CRC.  The oracle
-throughout is the single-image entry, called on each image separately in the same process: file i of a batch is its file
-byte for byte.  Where fixtures exist (tests/golden/png_files.json, made by the reference's own wasm build) the files are
-also held against them.
+"""PNG batch entries on the device: `batch` equally sized images in one pass of filters, DEFLATE and CRC.  Throughout, file i
+of a batch is held against the single-image entry's file for the same image, called separately in the same process: byte for
+byte.  The single entry runs the same DEFLATE tail with a table of one segment, so that equality shows that segments do not
+disturb each other (no match, offset, checksum or CRC piece crosses two images), not that the tail is right.  What pins the
+bytes themselves is independent of both: the fixtures (tests/golden/png_files.json, made by the reference's own wasm build),
+held against the files here where they exist, and tests/golden/png_own_bytes.json (tests/test_gpu_png_own_bytes.py), the
+digests of every entry's output recorded while single and batch entries were separate code.
 
 The fixture options carry NO_RAYON (the wasm build's semantics, which the stored streams were made with).  With it preset
 0's AdaptiveFast is the sequential form, which prepares image by image: those groups set PNG_BATCH only.  The two preset-0

@@ -113,7 +113,7 @@ def test_device_entry_gives_the_same_tokens(name):
 
 
 def encode_hints(layout):
-    """The hints png.encode gives its compressor (png_encode_api.cpp, png_file): the bytes of a pixel — 1 where samples are
+    """The hints png.encode gives its compressor (png_encode_api.cpp, the view png_segment_of_image leaves in its segment): the bytes of a pixel — 1 where samples are
     packed below 8 bits or are palette indices — and the bytes of a row with its filter byte, row_bytes + 1."""
     bytewise = layout.bit_depth < 8 or layout.color_type_byte == 3
     return (1 if bytewise else layout.bytes_per_pixel), layout.row_bytes + 1

@@ -5,7 +5,7 @@
 
 Shapes: 64 x 256^2 RGB, 1024 x 64^2 RGB, 64 x 1920x1080 RGB; preset 0 on each, preset 1 as well on the 256^2 shape; content:
 photo-like (`synth.scene`) and noise.  `png.encode_batch_device` against a loop of `png.encode_device` over the same
-images in HBM — the loop runs code the batch entries leave alone.  Batch and loop alternate, every shape is warmed up
+images in HBM — both end in the same DEFLATE tail, the loop with a table of one segment per call.  Batch and loop alternate, every shape is warmed up
 first.  Written: host wall time around the call (median [min .. max] over the repeats), files per second, the spread, and
 for the batch the wall time between the host's waits as the library's `trace` switch prints it (one more call per row, its
 stderr captured; these are host times around device work, not device events).  Where the batch does not win, the row says so.

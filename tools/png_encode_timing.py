@@ -11,7 +11,8 @@ behind SIZE_BOUNDS in tests/test_gpu_png_encode.py and tests/test_gpu_png_deflat
 
 timing: 4096 x 4096 RGBA and RGB on gradient, photo-like and noise content, preset 0.  Device events around repeated
 calls (median [min .. max]): the whole `encode_device` call, `prepare_device` alone, the device zlib stage alone
-(`zlib_compress_device` on the prepared stream: chunk kernel + scan + compaction and the one host decision between them),
+(`zlib_compress_device` on the prepared stream: one unframed segment through the tail — chunk kernel, the checksum joined
+on the host from the chunks' records, scan + compaction),
 and beside them what a caller did before this path existed: `prepare_device`, the stream copied to the host,
 `zlib.compress(stream, 1)` on one core.  Every device row is given at both efforts, the high one also as a ratio to the
 default of the same call.  Behind them, each in a fresh child process per library (PIXO_HIP_LIB):

@@ -31,6 +31,21 @@ def main():
     d_z = torch.empty(cap, dtype=torch.uint8, device=dev); torch.cuda.synchronize()
     out["6MiB_zlib_compress_device"] = median_us(lambda: png.zlib_compress_device(d, n, d_z, cap, bpp=4, row=4 * w + 1), 5, 60)
     del d, d_out, d_z
+    # small calls, where a fixed cost per call of the DEFLATE tail shows: whole files of 64x64 and 256x256 RGB at preset 0, 4 KiB of zlib
+    for side in (64, 256):
+        d_s = torch.from_numpy(synth.scene(side, side, 31)).to(dev)
+        os_ = png.PngOptions.builder(side, side).color_type(ColorType.Rgb).preset(0).build(); torch.cuda.synchronize()
+        out["%dx%d_png_encode_device" % (side, side)] = median_us(lambda: png.encode_device(d_s, os_), 50, 1000)
+    d_4k = torch.from_numpy(synth.scene(64, 64, 31)[:4096].copy()).to(dev)
+    d_z = torch.empty(png.stored_bound(4096), dtype=torch.uint8, device=dev); torch.cuda.synchronize()
+    out["4KiB_zlib_compress_device"] = median_us(lambda: png.zlib_compress_device(d_4k, 4096, d_z, d_z.numel()), 50, 1000)
+    # a batch: the 64 x 256x256 photo row of png_batch_timing.py, preset 0
+    import numpy as np
+    from png_batch_timing import images
+    d_all = torch.from_numpy(np.concatenate(images("photo", 64, 256, 256))).to(dev)
+    ob = png.PngOptions.builder(256, 256).color_type(ColorType.Rgb).preset(0).build(); torch.cuda.synchronize()
+    out["64x256x256_png_encode_batch_device"] = median_us(lambda: png.encode_batch_device(d_all, ob, 64), 3, 30)
+    del d_s, d_4k, d_z, d_all
     # a small image: the fixed cost per call of the row filters
     sw, sh = 200, 150
     small = synth.rgba_noise_alpha1(sw, sh, 3)
