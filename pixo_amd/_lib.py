@@ -6,7 +6,7 @@ points fails loudly.
 import ctypes as C
 import os
 
-from .error import from_status
+from .error import BufferTooSmall, from_status
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIXO_HIP_LIB lets kernel A/B experiments (tools/ab_build.sh) point at another build of the
@@ -55,28 +55,109 @@ class PngQuantizationC(C.Structure):
     _fields_ = [("mode", C.c_uint8), ("dithering", C.c_uint8), ("max_colors", C.c_uint16)]
 
 
-# every symbol include/pixo_hip.h declares
-SYMBOLS = [
-    "pixo_jpeg_options_from_preset", "pixo_hip_jpeg_encode", "pixo_hip_jpeg_encode_into",
-    "pixo_hip_encode_jpeg", "pixo_hip_coeff_geometry", "pixo_hip_jpeg_coeffs",
-    "pixo_hip_jpeg_coeffs_device", "pixo_hip_jpeg_coeffs_integer", "pixo_hip_jpeg_coeffs_integer_device", "pixo_hip_jpeg_entropy_encode", "pixo_hip_jpeg_entropy_encode_device",
-    "pixo_hip_jpeg_encode_device", "pixo_hip_jpeg_encode_device_into", "pixo_hip_jpeg_encode_batch_device", "pixo_hip_jpeg_encode_batch_device_into", "pixo_hip_debug_lookback_fallbacks", "pixo_hip_debug_routes", "pixo_hip_debug_dispatch_gate", "pixo_hip_debug_stream_copy", "pixo_hip_debug_stream_io", "pixo_hip_debug_engine_clock", "pixo_hip_debug_scan_device_async", "pixo_hip_debug_scan_device_async_batch", "pixo_hip_png_filter", "pixo_hip_png_filter_device", "pixo_hip_png_filter_async",
-    "pixo_hip_png_adler32_from_row_sums", "pixo_hip_png_options_from_preset", "pixo_hip_png_prepare", "pixo_hip_png_prepare_device",
-    "pixo_hip_png_palette_order", "pixo_hip_zlib_compress", "pixo_hip_zlib_compress_device", "pixo_hip_zlib_compress_effort", "pixo_hip_zlib_compress_effort_device",
-    "pixo_hip_png_deflate_effort_params", "pixo_hip_png_encode",
-    "pixo_hip_png_encode_device", "pixo_hip_png_quantize", "pixo_hip_png_quantize_device", "pixo_hip_png_encode_lossy",
-    "pixo_hip_png_encode_lossy_device", "pixo_hip_png_encode_batch_device", "pixo_hip_png_encode_batch_device_into", "pixo_hip_png_encode_batch",
-    "pixo_hip_debug_png_dither_stats", "pixo_hip_png_median_cut", "pixo_hip_resize", "pixo_hip_resize_into", "pixo_hip_resize_device", "pixo_hip_resize_image",
-    "pixo_hip_resize_contributions", "pixo_hip_png_decode", "pixo_hip_png_decode_info", "pixo_hip_png_decode_device", "pixo_hip_zlib_inflate",
-    "pixo_hip_png_unfilter_pass_rows", "pixo_hip_debug_png_decode_timed", "pixo_hip_band",
-    "pixo_hip_band_encoder_create", "pixo_hip_band_encoder_destroy", "pixo_hip_band_encoder_rows",
-    "pixo_hip_band_encoder_coeffs", "pixo_hip_band_encoder_count", "pixo_hip_band_encoder_lengths",
-    "pixo_hip_band_encoder_pack", "pixo_hip_band_encoder_pack_device", "pixo_hip_band_encoder_copy_body",
-    "pixo_hip_jpeg_splice", "pixo_hip_jpeg_splice_layout", "pixo_hip_jpeg_splice_finish", "pixo_hip_jpeg_band_count_host",
-    "pixo_hip_jpeg_band_bits_host", "pixo_hip_jpeg_band_piece_host", "pixo_hip_jpeg_encode_multi", "pixo_hip_jpeg_encode_batch_multi",
-    "pixo_hip_device_count", "pixo_hip_set_device", "pixo_hip_set_producer_stream", "pixo_hip_get_producer_stream", "pixo_hip_debug_configure", "pixo_hip_trim", "pixo_hip_free", "pixo_hip_copy_file",
-    "pixo_hip_last_error", "pixo_hip_version",
-]
+def _sig(*argtypes, ret=C.c_int, optional=False):
+    """One row of SIGNATURES.  No argtypes: left unset (the entry takes none, or ctypes' defaults serve).  optional: absent
+    from the older builds that A/B timing loads through PIXO_HIP_LIB (tools/ab/)."""
+    return (list(argtypes) or None, ret, optional)
+
+
+_vp, _sz, _u8, _u32, _u64, _int, _dbl = C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint64, C.c_int, C.c_double
+_szp, _u8p, _u32p, _u64p, _i16p = C.POINTER(_sz), C.POINTER(_u8), C.POINTER(_u32), C.POINTER(_u64), C.POINTER(C.c_int16)
+_u8pp, _optp, _roptp = C.POINTER(_u8p), C.POINTER(JpegOptionsC), C.POINTER(ResizeOptionsC)
+_poptp, _playp, _qoptp = C.POINTER(PngOptionsC), C.POINTER(PngLayoutC), C.POINTER(PngQuantizationC)
+_coeffs = (_vp, _u32, _u32, _u8, _u8, _u8, _vp, _sz, _vp, _vp, _sz)
+
+# every symbol include/pixo_hip.h declares: name -> (argtypes, restype, optional).  `load()` applies it; a new entry is declared
+# there and here (tests/test_cabi_cpu.py holds the two against each other).
+SIGNATURES = {
+    "pixo_jpeg_options_from_preset": _sig(_optp, _u32, _u32, _u8, _u8, ret=None),
+    "pixo_hip_jpeg_encode": _sig(_vp, _sz, _optp, _u8pp, _szp),
+    "pixo_hip_jpeg_encode_into": _sig(_vp, _sz, _vp, _sz, _optp, _szp),
+    "pixo_hip_encode_jpeg": _sig(_vp, _sz, _u32, _u32, _u8, _u8, _u8, _int, _u8pp, _szp),
+    "pixo_hip_coeff_geometry": _sig(_u32, _u32, _u8, _u8, _szp, _szp),
+    "pixo_hip_jpeg_coeffs": _sig(*_coeffs),
+    "pixo_hip_jpeg_coeffs_device": _sig(_vp, _u32, _u32, _u8, _u8, _u8, _u32, _vp, _vp, _vp, _vp),
+    "pixo_hip_jpeg_coeffs_integer": _sig(*_coeffs),
+    "pixo_hip_jpeg_coeffs_integer_device": _sig(_vp, _u32, _u32, _u8, _u8, _u8, _vp, _vp, _vp, _vp),
+    "pixo_hip_jpeg_entropy_encode": _sig(_vp, _vp, _vp, _optp, _u8pp, _szp),
+    "pixo_hip_jpeg_entropy_encode_device": _sig(_vp, _vp, _vp, _optp, _u8pp, _szp),
+    "pixo_hip_jpeg_encode_device": _sig(_vp, _optp, _u8pp, _szp),
+    "pixo_hip_jpeg_encode_device_into": _sig(_vp, _optp, _vp, _sz, _szp),
+    "pixo_hip_jpeg_encode_batch_device": _sig(_vp, _optp, _u32, _u8pp, _szp),
+    "pixo_hip_jpeg_encode_batch_device_into": _sig(_vp, _optp, _u32, _vp, _sz, _szp, _szp),
+    "pixo_hip_debug_lookback_fallbacks": _sig(ret=_u64),
+    "pixo_hip_debug_routes": _sig(_int, ret=_u64, optional=True),
+    "pixo_hip_debug_dispatch_gate": _sig(_u64p, _u64p, optional=True),
+    "pixo_hip_debug_stream_copy": _sig(_vp, _vp, _sz, _vp),
+    "pixo_hip_debug_stream_io": _sig(_vp, _vp, _u32, _u32, _u32, _vp, optional=True),
+    "pixo_hip_debug_engine_clock": _sig(_vp, C.POINTER(_dbl), optional=True),
+    "pixo_hip_debug_scan_device_async": _sig(_vp, _optp, _vp, C.POINTER(_int)),
+    "pixo_hip_debug_scan_device_async_batch": _sig(_vp, _optp, _u32, _vp, C.POINTER(_int), optional=True),
+    "pixo_hip_png_filter": _sig(_vp, _sz, _u32, _u32, _u32, _u8, _u32, _vp, _sz, _u32p),
+    "pixo_hip_png_filter_device": _sig(_vp, _u32, _u32, _u32, _u8, _u32, _vp, _u32p),
+    "pixo_hip_png_filter_async": _sig(_vp, _u32, _u32, _u32, _u8, _u32, _vp, _vp, _vp, _vp),
+    "pixo_hip_png_adler32_from_row_sums": _sig(_vp, _u32, _u32, _u32, ret=_u32),
+    "pixo_hip_png_options_from_preset": _sig(_poptp, _u32, _u32, _u8, ret=None),
+    "pixo_hip_png_prepare": _sig(_vp, _sz, _poptp, _vp, _sz, _szp, _playp, _u32p),
+    "pixo_hip_png_prepare_device": _sig(_vp, _poptp, _vp, _playp, _szp, _u32p),
+    "pixo_hip_png_palette_order": _sig(_vp, _vp, _u32, _vp),
+    "pixo_hip_zlib_compress": _sig(_vp, _sz, _u8, _u32, _u32, _u8pp, _szp),
+    "pixo_hip_zlib_compress_device": _sig(_vp, _sz, _u8, _u32, _u32, _vp, _sz, _szp),
+    "pixo_hip_zlib_compress_effort": _sig(_vp, _sz, _u8, _u32, _u32, _u32, _u8pp, _szp, optional=True),
+    "pixo_hip_zlib_compress_effort_device": _sig(_vp, _sz, _u8, _u32, _u32, _u32, _vp, _sz, _szp, optional=True),
+    "pixo_hip_png_deflate_effort_params": _sig(_u32p, _u32p, ret=None, optional=True),
+    "pixo_hip_png_encode": _sig(_vp, _sz, _poptp, _u8pp, _szp),
+    "pixo_hip_png_encode_device": _sig(_vp, _poptp, _u8pp, _szp),
+    "pixo_hip_png_quantize": _sig(_vp, _sz, _poptp, _qoptp, _vp, _sz, _vp, _u32p, _u32p, _u8p),
+    "pixo_hip_png_quantize_device": _sig(_vp, _poptp, _qoptp, _vp, _vp, _u32p, _u32p, _u8p),
+    "pixo_hip_png_encode_lossy": _sig(_vp, _sz, _poptp, _qoptp, _u8pp, _szp),
+    "pixo_hip_png_encode_lossy_device": _sig(_vp, _poptp, _qoptp, _u8pp, _szp),
+    "pixo_hip_png_encode_batch_device": _sig(_vp, _poptp, _qoptp, _u32, _u8pp, _szp, optional=True),
+    "pixo_hip_png_encode_batch_device_into": _sig(_vp, _poptp, _qoptp, _u32, _vp, _sz, _szp, _szp, optional=True),
+    "pixo_hip_png_encode_batch": _sig(_vp, _sz, _poptp, _qoptp, _u32, _u8pp, _szp, optional=True),
+    "pixo_hip_debug_png_dither_stats": _sig(_u64p, _u64p, _u64p),
+    "pixo_hip_png_median_cut": _sig(_vp, _vp, _u32, _u32, _vp, _u32p),
+    "pixo_hip_resize": _sig(_vp, _sz, _roptp, _u8pp, _szp),
+    "pixo_hip_resize_into": _sig(_vp, _sz, _vp, _sz, _roptp, _szp),
+    "pixo_hip_resize_device": _sig(_vp, _roptp, _vp, _vp),
+    "pixo_hip_resize_image": _sig(_vp, _sz, _u32, _u32, _u32, _u32, _u8, _u8, _u8pp, _szp),
+    "pixo_hip_resize_contributions": _sig(_u32, _u32, _vp, _vp, _vp, _sz, _szp),
+    "pixo_hip_png_decode": _sig(_vp, _sz, _u8pp, _szp, _u32p, _u32p, _u8p),
+    "pixo_hip_png_decode_info": _sig(_vp, _sz, _u32p, _u32p, _u8p),
+    "pixo_hip_png_decode_device": _sig(_vp, _sz, _vp, _sz, _u32p, _u32p, _u8p, _vp),
+    "pixo_hip_zlib_inflate": _sig(_vp, _sz, _vp, _sz),
+    "pixo_hip_png_unfilter_pass_rows": _sig(ret=_u32),
+    "pixo_hip_debug_png_decode_timed": _sig(_vp, _sz, C.POINTER(_dbl), _u64p),
+    "pixo_hip_band": _sig(_u32, _u32, _u8, _u8, _u32, _u32, _u32p, _u32p, _szp, _szp, _szp, _szp),
+    "pixo_hip_band_encoder_create": _sig(_optp, _u32, _u32, _int, C.POINTER(_vp)),
+    "pixo_hip_band_encoder_destroy": _sig(_vp, ret=None),
+    "pixo_hip_band_encoder_rows": _sig(_vp, _u32p, _u32p),
+    "pixo_hip_band_encoder_coeffs": _sig(_vp, _vp, _int, _i16p),
+    "pixo_hip_band_encoder_count": _sig(_vp, _i16p, _u64p),
+    "pixo_hip_band_encoder_lengths": _sig(_vp, _i16p, _u64p, _u64p),
+    "pixo_hip_band_encoder_pack": _sig(_vp, _u64, _u8pp, _szp),
+    "pixo_hip_band_encoder_pack_device": _sig(_vp, _u64, _vp, C.POINTER(_vp), _szp),
+    "pixo_hip_band_encoder_copy_body": _sig(_vp, _vp),
+    "pixo_hip_jpeg_splice": _sig(_optp, _u64p, C.POINTER(_vp), _szp, _u32, _u8pp, _szp),
+    "pixo_hip_jpeg_splice_layout": _sig(_optp, _u64p, _vp, _u32, _szp, _szp),
+    "pixo_hip_jpeg_splice_finish": _sig(_optp, _u64p, _vp, _u32, _vp, _sz),
+    "pixo_hip_jpeg_band_count_host": _sig(_vp, _vp, _vp, _optp, _u32, _i16p, _u64p),
+    "pixo_hip_jpeg_band_bits_host": _sig(_vp, _vp, _vp, _optp, _u32, _i16p, _u64p, _u64p),
+    "pixo_hip_jpeg_band_piece_host": _sig(_vp, _vp, _vp, _optp, _u32, _i16p, _u64p, _u64, _u8pp, _szp),
+    "pixo_hip_jpeg_encode_multi": _sig(_vp, _sz, _optp, C.POINTER(_int), _u32, _u8pp, _szp),
+    "pixo_hip_jpeg_encode_batch_multi": _sig(_vp, _optp, _u32, C.POINTER(_int), _u32, _vp, _sz, _szp, _szp),
+    "pixo_hip_device_count": _sig(),
+    "pixo_hip_set_device": _sig(_int),
+    "pixo_hip_set_producer_stream": _sig(_vp),
+    "pixo_hip_get_producer_stream": _sig(ret=_vp),
+    "pixo_hip_debug_configure": _sig(C.c_char_p),
+    "pixo_hip_trim": _sig(),
+    "pixo_hip_free": _sig(_vp, ret=None),
+    "pixo_hip_copy_file": _sig(_vp, _vp, _sz, ret=None),
+    "pixo_hip_last_error": _sig(ret=C.c_char_p),
+    "pixo_hip_version": _sig(ret=C.c_char_p),
+}
+SYMBOLS = list(SIGNATURES)
 
 _lib = None
 
@@ -109,129 +190,13 @@ def load():
             "There is no CPU fallback." % LIB_PATH)
     _preload_process_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    u8pp, szp = C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)
-    optp = C.POINTER(JpegOptionsC)
-    L.pixo_jpeg_options_from_preset.argtypes = [optp, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8]
-    L.pixo_jpeg_options_from_preset.restype = None
-    L.pixo_hip_jpeg_encode.argtypes = [C.c_void_p, C.c_size_t, optp, u8pp, szp]
-    L.pixo_hip_jpeg_encode_into.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, optp, szp]
-    L.pixo_hip_encode_jpeg.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint8,
-                                       C.c_uint8, C.c_uint8, C.c_int, u8pp, szp]
-    L.pixo_hip_coeff_geometry.argtypes = [C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, szp, szp]
-    L.pixo_hip_jpeg_coeffs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
-                                       C.c_uint8, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                       C.c_size_t]
-    L.pixo_hip_jpeg_coeffs_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint8,
-                                              C.c_uint8, C.c_uint8, C.c_uint32, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pixo_hip_jpeg_coeffs_integer.argtypes = L.pixo_hip_jpeg_coeffs.argtypes
-    L.pixo_hip_jpeg_coeffs_integer_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint8,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pixo_hip_jpeg_entropy_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, optp, u8pp, szp]
-    L.pixo_hip_jpeg_entropy_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, optp, u8pp, szp]
-    L.pixo_hip_jpeg_encode_device.argtypes = [C.c_void_p, optp, u8pp, szp]
-    L.pixo_hip_jpeg_encode_device_into.argtypes = [C.c_void_p, optp, C.c_void_p, C.c_size_t, szp]
-    L.pixo_hip_jpeg_encode_batch_device.argtypes = [C.c_void_p, optp, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
-    L.pixo_hip_jpeg_encode_batch_device_into.argtypes = [C.c_void_p, optp, C.c_uint32, C.c_void_p, C.c_size_t, szp, szp]
-    L.pixo_hip_debug_lookback_fallbacks.restype = C.c_uint64
-    if hasattr(L, "pixo_hip_debug_routes"):  # (absent from A/B builds of older trees)
-        L.pixo_hip_debug_routes.argtypes = [C.c_int]
-        L.pixo_hip_debug_routes.restype = C.c_uint64
-    if hasattr(L, "pixo_hip_debug_dispatch_gate"):  # (absent from A/B builds of older trees: tools/ab/)
-        L.pixo_hip_debug_dispatch_gate.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    L.pixo_hip_debug_stream_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    if hasattr(L, "pixo_hip_debug_engine_clock"):
-        L.pixo_hip_debug_engine_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    if hasattr(L, "pixo_hip_debug_stream_io"):
-        L.pixo_hip_debug_stream_io.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.pixo_hip_debug_scan_device_async.argtypes = [C.c_void_p, optp, C.c_void_p, C.POINTER(C.c_int)]
-    if hasattr(L, "pixo_hip_debug_scan_device_async_batch"):  # (absent from older builds dlopen'ed for A/B timing: PIXO_HIP_LIB)
-        L.pixo_hip_debug_scan_device_async_batch.argtypes = [C.c_void_p, optp, C.c_uint32, C.c_void_p, C.POINTER(C.c_int)]
-    L.pixo_hip_png_filter.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
-                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
-    L.pixo_hip_png_filter_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pixo_hip_png_adler32_from_row_sums.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
-    L.pixo_hip_png_adler32_from_row_sums.restype = C.c_uint32
-    L.pixo_hip_png_filter_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint32,
-                                             C.c_void_p, C.POINTER(C.c_uint32)]
-    poptp, playp = C.POINTER(PngOptionsC), C.POINTER(PngLayoutC)
-    L.pixo_hip_png_options_from_preset.argtypes = [poptp, C.c_uint32, C.c_uint32, C.c_uint8]
-    L.pixo_hip_png_options_from_preset.restype = None
-    L.pixo_hip_png_prepare.argtypes = [C.c_void_p, C.c_size_t, poptp, C.c_void_p, C.c_size_t, szp, playp, C.POINTER(C.c_uint32)]
-    L.pixo_hip_png_prepare_device.argtypes = [C.c_void_p, poptp, C.c_void_p, playp, szp, C.POINTER(C.c_uint32)]
-    L.pixo_hip_png_palette_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    L.pixo_hip_zlib_compress.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, u8pp, szp]
-    L.pixo_hip_zlib_compress_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, szp]
-    if hasattr(L, "pixo_hip_zlib_compress_effort"):  # (absent from A/B builds of older trees: tools/ab/)
-        L.pixo_hip_zlib_compress_effort.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_uint32, u8pp, szp]
-        L.pixo_hip_zlib_compress_effort_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint8, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, szp]
-        L.pixo_hip_png_deflate_effort_params.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.pixo_hip_png_deflate_effort_params.restype = None
-    L.pixo_hip_png_encode.argtypes = [C.c_void_p, C.c_size_t, poptp, u8pp, szp]
-    L.pixo_hip_png_encode_device.argtypes = [C.c_void_p, poptp, u8pp, szp]
-    qoptp, u32p = C.POINTER(PngQuantizationC), C.POINTER(C.c_uint32)
-    L.pixo_hip_png_quantize.argtypes = [C.c_void_p, C.c_size_t, poptp, qoptp, C.c_void_p, C.c_size_t, C.c_void_p, u32p, u32p, C.POINTER(C.c_uint8)]
-    L.pixo_hip_png_quantize_device.argtypes = [C.c_void_p, poptp, qoptp, C.c_void_p, C.c_void_p, u32p, u32p, C.POINTER(C.c_uint8)]
-    L.pixo_hip_png_encode_lossy.argtypes = [C.c_void_p, C.c_size_t, poptp, qoptp, u8pp, szp]
-    L.pixo_hip_png_encode_lossy_device.argtypes = [C.c_void_p, poptp, qoptp, u8pp, szp]
-    if hasattr(L, "pixo_hip_png_encode_batch_device"):  # (absent from A/B builds of older trees: tools/ab/)
-        L.pixo_hip_png_encode_batch_device.argtypes = [C.c_void_p, poptp, qoptp, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), szp]
-        L.pixo_hip_png_encode_batch_device_into.argtypes = [C.c_void_p, poptp, qoptp, C.c_uint32, C.c_void_p, C.c_size_t, szp, szp]
-        L.pixo_hip_png_encode_batch.argtypes = [C.c_void_p, C.c_size_t, poptp, qoptp, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), szp]
-    L.pixo_hip_debug_png_dither_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
-    L.pixo_hip_png_median_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, u32p]
-    roptp = C.POINTER(ResizeOptionsC)
-    L.pixo_hip_resize.argtypes = [C.c_void_p, C.c_size_t, roptp, u8pp, szp]
-    L.pixo_hip_resize_into.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, roptp, szp]
-    L.pixo_hip_resize_device.argtypes = [C.c_void_p, roptp, C.c_void_p, C.c_void_p]
-    L.pixo_hip_resize_image.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8,
-                                        u8pp, szp]
-    L.pixo_hip_resize_contributions.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, szp]
-    u8p = C.POINTER(C.c_uint8)
-    L.pixo_hip_png_decode.argtypes = [C.c_void_p, C.c_size_t, u8pp, szp, u32p, u32p, u8p]
-    L.pixo_hip_png_decode_info.argtypes = [C.c_void_p, C.c_size_t, u32p, u32p, u8p]
-    L.pixo_hip_png_decode_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, u32p, u32p, u8p, C.c_void_p]
-    L.pixo_hip_zlib_inflate.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
-    L.pixo_hip_png_unfilter_pass_rows.restype = C.c_uint32
-    L.pixo_hip_debug_png_decode_timed.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-    L.pixo_hip_band.argtypes = [C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint32, C.c_uint32,
-                                C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), szp, szp, szp, szp]
-    i16p, u64p = C.POINTER(C.c_int16), C.POINTER(C.c_uint64)
-    L.pixo_hip_band_encoder_create.argtypes = [optp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
-    L.pixo_hip_band_encoder_destroy.argtypes = [C.c_void_p]
-    L.pixo_hip_band_encoder_destroy.restype = None
-    L.pixo_hip_band_encoder_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.pixo_hip_band_encoder_coeffs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, i16p]
-    L.pixo_hip_band_encoder_count.argtypes = [C.c_void_p, i16p, u64p]
-    L.pixo_hip_band_encoder_lengths.argtypes = [C.c_void_p, i16p, u64p, u64p]
-    L.pixo_hip_band_encoder_pack.argtypes = [C.c_void_p, C.c_uint64, u8pp, szp]
-    L.pixo_hip_band_encoder_pack_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p), szp]
-    L.pixo_hip_band_encoder_copy_body.argtypes = [C.c_void_p, C.c_void_p]
-    L.pixo_hip_jpeg_splice_layout.argtypes = [optp, u64p, C.c_void_p, C.c_uint32, szp, szp]
-    L.pixo_hip_jpeg_splice_finish.argtypes = [optp, u64p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
-    L.pixo_hip_jpeg_splice.argtypes = [optp, u64p, C.POINTER(C.c_void_p), szp, C.c_uint32, u8pp, szp]
-    L.pixo_hip_jpeg_band_count_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, optp, C.c_uint32, i16p, u64p]
-    L.pixo_hip_jpeg_band_bits_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, optp, C.c_uint32, i16p, u64p, u64p]
-    L.pixo_hip_jpeg_band_piece_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, optp, C.c_uint32, i16p, u64p, C.c_uint64,
-                                                u8pp, szp]
-    L.pixo_hip_jpeg_encode_multi.argtypes = [C.c_void_p, C.c_size_t, optp, C.POINTER(C.c_int), C.c_uint32, u8pp, szp]
-    L.pixo_hip_jpeg_encode_batch_multi.argtypes = [C.c_void_p, optp, C.c_uint32, C.POINTER(C.c_int), C.c_uint32, C.c_void_p, C.c_size_t, szp, szp]
-    L.pixo_hip_set_producer_stream.argtypes = [C.c_void_p]
-    L.pixo_hip_get_producer_stream.restype = C.c_void_p
-    L.pixo_hip_debug_configure.argtypes = [C.c_char_p]
-    L.pixo_hip_device_count.restype = C.c_int
-    L.pixo_hip_set_device.argtypes = [C.c_int]
-    L.pixo_hip_free.argtypes = [C.c_void_p]
-    L.pixo_hip_free.restype = None
-    L.pixo_hip_copy_file.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.pixo_hip_copy_file.restype = None
-    L.pixo_hip_last_error.restype = C.c_char_p
-    L.pixo_hip_version.restype = C.c_char_p
-    for name in ("pixo_hip_jpeg_encode", "pixo_hip_jpeg_encode_into", "pixo_hip_encode_jpeg",
-                 "pixo_hip_coeff_geometry", "pixo_hip_jpeg_coeffs", "pixo_hip_jpeg_coeffs_device",
-                 "pixo_hip_jpeg_entropy_encode", "pixo_hip_band", "pixo_hip_set_device"):
-        getattr(L, name).restype = C.c_int
+    for name, (argtypes, restype, optional) in SIGNATURES.items():
+        if optional and not hasattr(L, name):
+            continue
+        fn = getattr(L, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = L
     return L
 
@@ -257,10 +222,24 @@ def ptr(x):
     return x.data_ptr() if hasattr(x, "data_ptr") else int(x)
 
 
-def check(rc):
-    """A status other than PIXO_OK raises the error it stands for (error.py), with the library's message."""
+def address(x):
+    """Where a buffer starts: a torch tensor, a numpy array, or the raw address itself."""
+    return x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data if hasattr(x, "ctypes") else int(x)
+
+
+def nbytes(x):
+    """The capacity in bytes of a torch tensor or a numpy array."""
+    return x.numel() * x.element_size() if hasattr(x, "numel") else x.nbytes
+
+
+def check(rc, needed=None):
+    """A status other than PIXO_OK raises the error it stands for (error.py), with the library's message; a BufferTooSmall
+    carries `needed`, when the caller has it, as `.needed`: the bytes a second attempt has to bring."""
     if rc:
-        raise from_status(rc, load().pixo_hip_last_error().decode())
+        e = from_status(rc, load().pixo_hip_last_error().decode())
+        if needed is not None and isinstance(e, BufferTooSmall):
+            e.needed = needed
+        raise e
 
 
 def take(L, p, n) -> bytes:
@@ -269,3 +248,29 @@ def take(L, p, n) -> bytes:
         return file_bytes(L, p, n.value)
     finally:
         L.pixo_hip_free(p)
+
+
+def take_files(L, files, lens, batch):
+    """The `batch` blocks a batch entry handed over, as a list of bytes; every block goes back to the library, also when
+    copying one of them raises."""
+    try:
+        return [file_bytes(L, files[i], lens[i]) for i in range(batch)]
+    finally:
+        for i in range(batch):
+            L.pixo_hip_free(files[i])
+
+
+def into_arena(entry, arena, batch):
+    """The tail of the batch entries that write their files back to back into the caller's arena: a torch CPU tensor, a numpy
+    array, or None for a size query.  `entry(address, capacity in bytes, offsets, lens)` makes the C call and returns its
+    status.  Returns (offsets, lens) — of a size query too; files that do not fit raise BufferTooSmall with `.needed`,
+    `.offsets` and `.lens`, which the library filled in all the same."""
+    offsets, lens = (C.c_size_t * batch)(), (C.c_size_t * batch)()
+    rc = entry(None, 0, offsets, lens) if arena is None else entry(address(arena), nbytes(arena), offsets, lens)
+    if not (rc == -9 and arena is None):  # (PIXO_ERR_BUFFER_TOO_SMALL is the answer to a size query)
+        try:
+            check(rc, needed=int(offsets[batch - 1] + lens[batch - 1]) if batch else 0)
+        except BufferTooSmall as e:
+            e.offsets, e.lens = list(offsets), list(lens)
+            raise
+    return list(offsets), list(lens)

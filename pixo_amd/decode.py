@@ -10,7 +10,6 @@ import numpy as np
 
 from . import _lib
 from .color import ColorType
-from .error import from_status
 
 
 @dataclass(frozen=True)
@@ -66,13 +65,9 @@ def decode_png_device(data, out=None, stream=None):
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
-    rc = L.pixo_hip_png_decode_device(f.ctypes.data, f.size, out.data_ptr(), out.numel(), C.byref(w), C.byref(h), C.byref(ct),
+    rc = L.pixo_hip_png_decode_device(f.ctypes.data, f.size, out.data_ptr(), _lib.nbytes(out), C.byref(w), C.byref(h), C.byref(ct),
                                       C.c_void_p(stream) if stream else None)
-    if rc:
-        e = from_status(rc, L.pixo_hip_last_error().decode())
-        if rc == -9:
-            e.needed = w.value * h.value * ColorType(ct.value).bytes_per_pixel()
-        raise e
+    _lib.check(rc, needed=w.value * h.value * ColorType(ct.value).bytes_per_pixel() if rc == -9 else None)
     color = ColorType(ct.value)
     n = w.value * h.value * color.bytes_per_pixel()
     return out.reshape(-1)[:n].view(h.value, w.value, color.bytes_per_pixel()), color

@@ -169,13 +169,8 @@ def encode_into_buffer(buffer: np.ndarray, data, options: JpegOptions) -> int:
         raise TypeError("buffer must be a contiguous uint8 array")
     n = C.c_size_t()
     oc = options._c()
-    rc = L.pixo_hip_jpeg_encode_into(buffer.ctypes.data, buffer.size, px.ctypes.data, px.size, C.byref(oc), C.byref(n))
-    if rc:
-        try:
-            _lib.check(rc)
-        except error.BufferTooSmall as e:
-            e.needed = n.value
-            raise
+    rc = L.pixo_hip_jpeg_encode_into(buffer.ctypes.data, buffer.nbytes, px.ctypes.data, px.size, C.byref(oc), C.byref(n))
+    _lib.check(rc, needed=n.value)
     return n.value
 
 
@@ -299,19 +294,10 @@ def encode_device_into(buffer, d_pixels, options: JpegOptions) -> int:
     file's length; raises `error.BufferTooSmall` (with `.needed`) when it does not fit — a pinned `buffer` may then have been
     written up to its capacity (small files are stored into pinned memory by the stuffing kernel itself), never beyond it."""
     L = _lib.load()
-    if hasattr(buffer, "data_ptr"):
-        ptr, cap = buffer.data_ptr(), buffer.numel() * buffer.element_size()
-    else:
-        ptr, cap = buffer.ctypes.data, buffer.nbytes
     n = C.c_size_t()
     oc = options._c()
-    rc = L.pixo_hip_jpeg_encode_device_into(_dev_ptr(d_pixels), C.byref(oc), ptr, cap, C.byref(n))
-    if rc:
-        try:
-            _lib.check(rc)
-        except error.BufferTooSmall as e:
-            e.needed = n.value
-            raise
+    rc = L.pixo_hip_jpeg_encode_device_into(_dev_ptr(d_pixels), C.byref(oc), _lib.address(buffer), _lib.nbytes(buffer), C.byref(n))
+    _lib.check(rc, needed=n.value)
     return n.value
 
 
@@ -324,11 +310,7 @@ def encode_batch_device(d_pixels, options: JpegOptions, batch: int):
     oc = options._c()
     rc = L.pixo_hip_jpeg_encode_batch_device(_dev_ptr(d_pixels), C.byref(oc), batch, files, lens)
     _lib.check(rc)
-    out = []
-    for i in range(batch):
-        out.append(_lib.file_bytes(L, files[i], lens[i]))
-        L.pixo_hip_free(files[i])
-    return out
+    return _lib.take_files(L, files, lens, batch)
 
 
 def encode_batch_device_raw(d_pixels, options: JpegOptions, batch: int):
@@ -352,28 +334,11 @@ def free_files(files, batch: int) -> None:
 def encode_batch_device_into(arena, d_pixels, options: JpegOptions, batch: int):
     """`pixo_hip_jpeg_encode_batch_device_into`: the `batch` files back to back in `arena` (a torch uint8 CPU tensor —
     ideally pinned —, a numpy uint8 array, or None for a size query), every file copied from the device straight to its
-    final place.  Returns (offsets, lens); raises BufferTooSmall (`.needed`) when the files do not fit."""
+    final place.  Returns (offsets, lens); raises BufferTooSmall (`.needed`, `.offsets`, `.lens`) when the files do not fit."""
     L = _lib.load()
-    offsets = (C.c_size_t * batch)()
-    lens = (C.c_size_t * batch)()
-    if arena is None:
-        ptr, cap = None, 0
-    elif hasattr(arena, "data_ptr"):
-        ptr, cap = arena.data_ptr(), arena.numel()
-    else:
-        ptr, cap = arena.ctypes.data, arena.size
     oc = options._c()
-    rc = L.pixo_hip_jpeg_encode_batch_device_into(_dev_ptr(d_pixels), C.byref(oc), batch, ptr, cap, offsets, lens)
-    if rc == -9 and arena is None:  # PIXO_ERR_BUFFER_TOO_SMALL: the answer to a size query
-        return list(offsets), list(lens)
-    if rc == -9:  # (offsets / lens were filled in: the size a second attempt needs)
-        try:
-            _lib.check(rc)
-        except error.BufferTooSmall as e:
-            e.needed = int(offsets[batch - 1] + lens[batch - 1]) if batch else 0
-            raise
-    _lib.check(rc)
-    return list(offsets), list(lens)
+    return _lib.into_arena(lambda ptr, cap, offsets, lens: L.pixo_hip_jpeg_encode_batch_device_into(
+        _dev_ptr(d_pixels), C.byref(oc), batch, ptr, cap, offsets, lens), arena, batch)
 
 
 def encode_batch_multi(arena, pixels, options: JpegOptions, batch: int, devices):
@@ -382,14 +347,6 @@ def encode_batch_multi(arena, pixels, options: JpegOptions, batch: int, devices)
     once), every GPU copying its files to their final place in `arena` (torch uint8 CPU tensor, ideally pinned, numpy uint8
     array, or None for a size query) over its own PCIe link.  Returns (offsets, lens); raises BufferTooSmall (`.needed`)."""
     L = _lib.load()
-    offsets = (C.c_size_t * batch)()
-    lens = (C.c_size_t * batch)()
-    if arena is None:
-        ptr, cap = None, 0
-    elif hasattr(arena, "data_ptr"):
-        ptr, cap = arena.data_ptr(), arena.numel()
-    else:
-        ptr, cap = arena.ctypes.data, arena.size
     # (the C entry takes no length: it reads batch * image_bytes from the pointer — whatever carries a size is checked here)
     bpp = {int(ColorType.Gray): 1, int(ColorType.Rgb): 3}.get(int(options.color_type))
     need = batch * options.width * options.height * bpp if bpp else None
@@ -409,17 +366,8 @@ def encode_batch_multi(arena, pixels, options: JpegOptions, batch: int, devices)
         raise error.CompressionError("Compression error: encode_batch_multi: no device listed")
     devs = (C.c_int * len(devices))(*[int(d) for d in devices])
     oc = options._c()
-    rc = L.pixo_hip_jpeg_encode_batch_multi(src, C.byref(oc), batch, devs, len(devices), ptr, cap, offsets, lens)
-    if rc == -9 and arena is None:  # PIXO_ERR_BUFFER_TOO_SMALL: the answer to a size query
-        return list(offsets), list(lens)
-    if rc == -9:
-        try:
-            _lib.check(rc)
-        except error.BufferTooSmall as e:
-            e.needed = int(offsets[batch - 1] + lens[batch - 1]) if batch else 0
-            raise
-    _lib.check(rc)
-    return list(offsets), list(lens)
+    return _lib.into_arena(lambda ptr, cap, offsets, lens: L.pixo_hip_jpeg_encode_batch_multi(
+        src, C.byref(oc), batch, devs, len(devices), ptr, cap, offsets, lens), arena, batch)
 
 
 def debug_stream_copy(d_in, d_out, nbytes, stream=0):
@@ -588,13 +536,7 @@ class BandEncoder:
     def copy_body(self, dst) -> None:
         """The packed body -> `dst`: a torch tensor (CPU, ideally pinned, or on the encoder's GPU), a numpy
         uint8 array, or a raw address."""
-        if hasattr(dst, "data_ptr"):
-            ptr = dst.data_ptr()
-        elif hasattr(dst, "ctypes"):
-            ptr = dst.ctypes.data
-        else:
-            ptr = int(dst)
-        rc = self._L.pixo_hip_band_encoder_copy_body(self._h, ptr)
+        rc = self._L.pixo_hip_band_encoder_copy_body(self._h, _lib.address(dst))
         _lib.check(rc)
 
     def pack(self, bit_offset: int) -> bytes:
@@ -685,10 +627,9 @@ def splice_finish(options: JpegOptions, headers, file, file_len, total_counts=No
     L = _lib.load()
     blob = np.frombuffer(b"".join(h[:16] for h in headers), np.uint8)
     tc = _counts(total_counts)
-    ptr = file.data_ptr() if hasattr(file, "data_ptr") else file.ctypes.data
     oc = options._c()
     rc = L.pixo_hip_jpeg_splice_finish(C.byref(oc), tc.ctypes.data_as(C.POINTER(C.c_uint64)) if tc is not None else None,
-                                       blob.ctypes.data, len(headers), ptr, file_len)
+                                       blob.ctypes.data, len(headers), _lib.address(file), file_len)
     _lib.check(rc)
 
 

@@ -349,14 +349,6 @@ def _check_batch_pixels(d_pixels, options, batch):
             raise ValueError("a batch of %d images of %dx%d needs %d bytes of pixels, the tensor holds %d" % (batch, options.width, options.height, need, have))
 
 
-def _take_files(L, files, lens, batch):
-    out = []
-    for i in range(batch):
-        out.append(_lib.file_bytes(L, files[i], lens[i]))
-        L.pixo_hip_free(files[i])
-    return out
-
-
 def encode_batch_device(d_pixels, options, batch):
     """`batch` equally sized images back to back in HBM (torch tensor / raw pointer) -> list of `batch` PNG files (bytes),
     each byte for byte what `encode_device` returns for its image.  `options.quantization`, when not Off, is passed on."""
@@ -364,35 +356,18 @@ def encode_batch_device(d_pixels, options, batch):
     _check_batch_pixels(d_pixels, options, batch)
     files, lens, o = (C.POINTER(C.c_uint8) * batch)(), (C.c_size_t * batch)(), options.to_c()
     _lib.check(L.pixo_hip_png_encode_batch_device(_lib.ptr(d_pixels), C.byref(o), _quant_arg(options), batch, files, lens))
-    return _take_files(L, files, lens, batch)
+    return _lib.take_files(L, files, lens, batch)
 
 
 def encode_batch_device_into(arena, d_pixels, options, batch):
     """The `batch` files back to back in `arena` (a torch uint8 CPU tensor, pinned or not, a numpy uint8 array, or None
     for a size query — which does the device work: a PNG's size is known only after compression).  Returns (offsets,
-    lens); raises BufferTooSmall (`.needed`) when the files do not fit."""
-    from . import error
+    lens); raises BufferTooSmall (`.needed`, `.offsets`, `.lens`) when the files do not fit."""
     L = _lib.load()
     _check_batch_pixels(d_pixels, options, batch)
-    offsets, lens, o = (C.c_size_t * batch)(), (C.c_size_t * batch)(), options.to_c()
-    if arena is None:
-        ptr, cap = None, 0
-    elif hasattr(arena, "data_ptr"):
-        ptr, cap = arena.data_ptr(), arena.numel()
-    else:
-        ptr, cap = arena.ctypes.data, arena.size
-    rc = L.pixo_hip_png_encode_batch_device_into(_lib.ptr(d_pixels), C.byref(o), _quant_arg(options), batch, ptr, cap, offsets, lens)
-    if rc == -9 and arena is None:  # PIXO_ERR_BUFFER_TOO_SMALL: the answer to a size query
-        return list(offsets), list(lens)
-    if rc == -9:
-        try:
-            _lib.check(rc)
-        except error.BufferTooSmall as e:
-            e.needed = int(offsets[batch - 1] + lens[batch - 1]) if batch else 0
-            e.offsets, e.lens = list(offsets), list(lens)
-            raise
-    _lib.check(rc)
-    return list(offsets), list(lens)
+    o, q = options.to_c(), _quant_arg(options)
+    return _lib.into_arena(lambda ptr, cap, offsets, lens: L.pixo_hip_png_encode_batch_device_into(
+        _lib.ptr(d_pixels), C.byref(o), q, batch, ptr, cap, offsets, lens), arena, batch)
 
 
 def encode_batch(data, options, batch):
@@ -401,7 +376,7 @@ def encode_batch(data, options, batch):
     px = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     files, lens, o = (C.POINTER(C.c_uint8) * batch)(), (C.c_size_t * batch)(), options.to_c()
     _lib.check(L.pixo_hip_png_encode_batch(px.ctypes.data, px.size, C.byref(o), _quant_arg(options), batch, files, lens))
-    return _take_files(L, files, lens, batch)
+    return _lib.take_files(L, files, lens, batch)
 
 
 # ---- lossy mode: palette quantisation and dithering on the device ------------------------------------------------------

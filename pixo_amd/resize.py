@@ -9,7 +9,6 @@ import numpy as np
 
 from . import _lib
 from .color import ColorType
-from .error import from_status
 
 MAX_DIMENSION = 1 << 24
 
@@ -91,11 +90,8 @@ def resize_into(output, data, options: ResizeOptions) -> int:
     assert output.dtype == np.uint8 and output.flags["C_CONTIGUOUS"] and output.flags["WRITEABLE"]
     n = C.c_size_t()
     o = options._c()
-    rc = L.pixo_hip_resize_into(output.ctypes.data, output.size, px.ctypes.data, px.size, C.byref(o), C.byref(n))
-    if rc:
-        e = from_status(rc, L.pixo_hip_last_error().decode())
-        e.needed = n.value
-        raise e
+    rc = L.pixo_hip_resize_into(output.ctypes.data, output.nbytes, px.ctypes.data, px.size, C.byref(o), C.byref(n))
+    _lib.check(rc, needed=n.value)
     return n.value
 
 

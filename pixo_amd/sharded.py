@@ -26,11 +26,13 @@ multi-GPU form, `encode_batch`: whole images travel from the source rank to the 
 xGMI link, all posted at once), every rank encodes its images (src/jpeg/mod.rs:88 per image), and the finished FILES
 travel to `dst` the same way — pixels out, files back, never a coefficient.
 """
+import ctypes as C
 import os
+import time
 
 import numpy as np
 
-from . import jpeg
+from . import _lib, error, jpeg
 
 
 def band_codable(options) -> bool:
@@ -45,7 +47,7 @@ def band_codable(options) -> bool:
 
 
 class _HostBand:
-    """Stand-in for `jpeg.BandEncoder` on a band's tuple in host memory (tests: gloo on CPU; also the twin
+    """`jpeg.BandEncoder` on a band's tuple in host memory, same interface (tests: gloo on CPU; also the twin
     the device coder is checked against)."""
 
     def __init__(self, options, parts, index, coeff_fn):
@@ -55,6 +57,8 @@ class _HostBand:
         self.rows = self.row_end - self.row_begin
         self.coeff_fn = coeff_fn
         self.y = self.cb = self.cr = np.zeros((0, 64), np.int16)
+        self._prev = self._counts = None  # what `lengths` was given: the pack step codes with the same
+        self._piece = bytes(16)
 
     def close(self):
         pass
@@ -75,14 +79,22 @@ class _HostBand:
         return jpeg.band_count_host(self.y, self.cb, self.cr, self.options, self.rows, prev_dc)
 
     def lengths(self, prev_dc, total_counts=None):
+        self._prev, self._counts = list(prev_dc), total_counts
         if self.rows == 0:
             return 0
         return jpeg.band_bits_host(self.y, self.cb, self.cr, self.options, self.rows, prev_dc, total_counts)
 
-    def pack(self, bit_offset):
-        if self.rows == 0:
-            return bytes(16)
-        return jpeg.band_piece_host(self.y, self.cb, self.cr, self.options, self.rows, self._prev, bit_offset, self._counts)
+    def pack_device(self, bit_offset):
+        """(16-byte piece header, length of the stuffed body); the body stays here until `copy_body`."""
+        if self._prev is None:
+            raise RuntimeError("band encoder: lengths(prev_dc, total_counts) comes before pack_device(bit_offset)")
+        if self.rows:
+            self._piece = jpeg.band_piece_host(self.y, self.cb, self.cr, self.options, self.rows, self._prev, bit_offset, self._counts)
+        return self._piece[:16], len(self._piece) - 16
+
+    def copy_body(self, dst):
+        """The packed body -> `dst`: a torch CPU tensor, a numpy uint8 array, or a raw address."""
+        C.memmove(_lib.address(dst), self._piece[16:], len(self._piece) - 16)
 
 
 def _wire(group, tdev):
@@ -115,16 +127,71 @@ def _all_gather_i64(values, group, device):
     return [o.cpu().tolist() for o in out]
 
 
-_pinned = {}  # grow-only pinned staging for the finished file on the destination rank
+_file_buffers = {}  # grow-only staging for the finished file on the destination rank
 
 
-def _pinned_file(n):
-    import torch
-    t = _pinned.get("file")
-    if t is None or t.numel() < n:
-        t = torch.empty(n + n // 4 + 4096, dtype=torch.uint8).pin_memory()
-        _pinned["file"] = t
-    return t
+class _Place:
+    """Where a rank's tensors live: on its GPU, or — when a test's host function stands in for the rank's encoder — in host
+    memory.  Everything that differs between the two is said here."""
+
+    def __init__(self, host, device=None):
+        import torch
+        self.on_gpu = not host
+        if self.on_gpu and device is None:
+            device = torch.cuda.current_device()
+        self.tdev = torch.device("cuda", device) if self.on_gpu else torch.device("cpu")
+
+    def file_buffer(self, n):
+        """A CPU uint8 tensor of at least n bytes for the finished file: pinned (`pin_memory()` needs a GPU), else plain."""
+        import torch
+        t = _file_buffers.get(self.on_gpu)
+        if t is None or t.numel() < n:
+            t = torch.empty(n + n // 4 + 4096, dtype=torch.uint8)
+            t = _file_buffers[self.on_gpu] = t.pin_memory() if self.on_gpu else t
+        return t
+
+    def synchronize(self):
+        if self.on_gpu:
+            import torch
+            torch.cuda.synchronize(self.tdev)
+
+    def after_torch(self, pixels=None):
+        """`with` this around the library's device-pointer calls: they are ordered after what torch enqueued on this device's
+        current stream (which wrote `pixels`, or what the wire delivered).  Nothing to order for host memory."""
+        import contextlib
+        import torch
+        if not self.on_gpu or (pixels is not None and not getattr(pixels, "is_cuda", False)):
+            return contextlib.nullcontext()
+        return jpeg.producer_stream(torch.cuda.current_stream(self.tdev).cuda_stream)
+
+    def to_host(self, whole, n, out):
+        """The first n bytes of `whole` in a CPU tensor: `out` if given, else the file buffer (or `whole` itself, already there)."""
+        if out is None and not self.on_gpu:
+            return whole
+        arena = out if out is not None else self.file_buffer(n)
+        arena[:n].copy_(whole[:n], non_blocking=True)
+        self.synchronize()
+        return arena
+
+
+class _Phases:
+    """The caller's `phases` dict: `lap(name)` adds the wall milliseconds since the previous lap to `phases[name]` and keeps
+    `total_ms` at the time since the start.  `sync`, when given, runs before the clock is read (the device at a step's boundary).
+    With `phases=None` a lap does nothing."""
+
+    def __init__(self, phases, sync=None):
+        self.phases, self.sync = phases, sync
+        self.start = self.last = time.perf_counter()
+
+    def lap(self, name):
+        if self.phases is None:
+            return
+        if self.sync is not None:
+            self.sync()
+        now = time.perf_counter()
+        self.phases[name] = self.phases.get(name, 0.0) + (now - self.last) * 1e3
+        self.phases["total_ms"] = (now - self.start) * 1e3
+        self.last = now
 
 
 class SharedFile:
@@ -146,13 +213,11 @@ class SharedFile:
 
     def __init__(self, name, size, create):
         from multiprocessing import shared_memory
-        import time
         total = size + self._HEADER
         try:
             self.shm = shared_memory.SharedMemory(name=name, create=create, size=total if create else 0)
         except FileExistsError:
             old = shared_memory.SharedMemory(name=name, create=False)
-            self._untrack(old)
             owner = None
             for _ in range(50):  # (a maker that has not written its header yet: up to half a second)
                 owner = self._read_header(old.buf)
@@ -161,13 +226,14 @@ class SharedFile:
                 time.sleep(0.01)
             mine = owner is not None and owner[0] == os.getpid() and owner[1] == self._start_time(os.getpid())
             if owner is not None and not mine and self._maybe_alive(owner):
+                self._untrack(old)
                 old.close()
                 raise FileExistsError("SharedFile %r is in use by live process %d: names must be unique per job" % (name, owner[0]))
-            old.close()
             try:
-                shared_memory.SharedMemory(name=name, create=False).unlink()  # (stale — its maker is gone — or this process's own: replaced)
+                old.unlink()  # (stale — its maker is gone — or this process's own: replaced; unlink() also untracks the handle)
             except FileNotFoundError:
-                pass
+                self._untrack(old)
+            old.close()
             self.shm = shared_memory.SharedMemory(name=name, create=True, size=total)
         if create:
             self._write_header(self.shm.buf)
@@ -267,14 +333,77 @@ def shared_file_bound(options) -> int:
     return 2048 + 416 * blocks
 
 
+def _too_small(message, needed):
+    e = error.BufferTooSmall(message)
+    e.needed = needed
+    return e
+
+
 def _check_shared(shared, file_len):
     """All ranks computed the same `file_len` from the gathered piece headers: all raise, nobody is left in a barrier."""
     if file_len > shared.size:
-        from . import error
-        e = error.BufferTooSmall("output buffer too small: the file needs %d bytes, the shared segment has %d"
-                                 % (file_len, shared.size))
-        e.needed = file_len
-        raise e
+        raise _too_small("output buffer too small: the file needs %d bytes, the shared segment has %d" % (file_len, shared.size), file_len)
+
+
+def _band_exchanges(enc, options, last, group, wire, timer):
+    """What the bands owe each other before one can be packed: boundary DCs, with optimised tables the summed symbol counts,
+    and the lengths in bits.  Returns (the DC predictors this band starts from, total counts or None, this band's bit offset)."""
+    import torch
+    import torch.distributed as dist
+    rank = dist.get_rank(group)
+    # exchange 1: boundary DCs (+ whether the band has rows)
+    got = _all_gather_i64([enc.row_end > enc.row_begin] + last, group, wire)
+    timer.lap("exchange_dc_ms")
+    prev = [0, 0, 0]
+    for r in range(rank):
+        if got[r][0]:
+            prev = got[r][1:4]
+    total_counts = None
+    if options.optimize_huffman:  # exchange 1b: symbol statistics, summed
+        t = torch.from_numpy(enc.count(prev).view(np.int64).copy()).to(wire)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        total_counts = t.cpu().numpy().view(np.uint64)
+    bits = enc.lengths(prev, total_counts)
+    timer.lap("lengths_ms")
+    # exchange 2: bits per band -> this band's bit offset
+    all_bits = [b[0] for b in _all_gather_i64([bits], group, wire)]
+    timer.lap("exchange_bits_ms")
+    return prev, total_counts, sum(all_bits[:rank])
+
+
+def _bodies_into_shared(enc, shared, offset, length, file_len, group):
+    """Delivery into the node's shared file: every rank copies its body to its final place, over its own GPU's PCIe link.
+    Returns the file's bytes (every rank has them mapped)."""
+    import torch.distributed as dist
+    _check_shared(shared, file_len)
+    arr = shared.array()
+    if length:
+        enc.copy_body(arr.ctypes.data + offset)
+    dist.barrier(group=group)
+    return arr
+
+
+def _bodies_gathered(enc, place, lens, body_off, file_len, out, dst, group, wire):
+    """Delivery by gather: the bodies travel to `dst` over xGMI (one gather of equal-sized buffers), then over dst's PCIe link
+    to their places in `out` or the file buffer.  Returns that CPU tensor on `dst`, None elsewhere."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    if world == 1:
+        file = out if out is not None else place.file_buffer(file_len)
+        enc.copy_body(file[body_off[0]:])  # device -> its final place in the (pinned) file
+        return file
+    send = torch.empty(max(max(lens), 1), dtype=torch.uint8, device=place.tdev)
+    enc.copy_body(send)
+    recv = _gather_bulk(send, dst, group, wire)
+    if recv is None:
+        return None
+    file = out if out is not None else place.file_buffer(file_len)
+    for k in range(world):
+        if lens[k]:
+            file[body_off[k]: body_off[k] + lens[k]].copy_(recv[k][: lens[k]], non_blocking=True)
+    place.synchronize()
+    return file
 
 
 def encode_banded(band_pixels, options, group=None, dst=0, device=None, coeff_fn=None, out=None, shared=None, phases=None):
@@ -295,135 +424,41 @@ def encode_banded(band_pixels, options, group=None, dst=0, device=None, coeff_fn
     `device`: HIP device index of this rank (default: torch's current device); `coeff_fn(band_pixels,
     band_options) -> (y, cb, cr)`: tests substitute a CPU function, which also routes the entropy stage
     through the host twins, so that the whole exchange runs on gloo without a GPU."""
-    import torch
+    import contextlib
     import torch.distributed as dist
 
     if not band_codable(options):
         raise ValueError("progressive scans and restart markers are not band-codable: use encode_gathered / "
                          "encode_gathered_device")
     rank, world = dist.get_rank(group), dist.get_world_size(group)
-    on_gpu = coeff_fn is None
-    prev_producer = None
-    if on_gpu:
-        if device is None:
-            device = torch.cuda.current_device()
-        enc = jpeg.BandEncoder(options, world, rank, device)
-        tdev = torch.device("cuda", device)
-        if hasattr(band_pixels, "is_cuda") and band_pixels.is_cuda:
-            # (per thread and sticky: the previous setting is put back when the call returns, see `finally`)
-            prev_producer = jpeg.get_producer_stream()
-            jpeg.set_producer_stream(torch.cuda.current_stream(tdev).cuda_stream)
-    else:
-        enc = _HostBand(options, world, rank, coeff_fn)
-        tdev = torch.device("cpu")
-    wire = _wire(group, tdev)
-    import time
-    t_start = t_lap = time.perf_counter()
-
-    def lap(name):
-        nonlocal t_lap
-        if phases is not None:
-            t1 = time.perf_counter()
-            phases[name] = phases.get(name, 0.0) + (t1 - t_lap) * 1e3
-            phases["total_ms"] = (t1 - t_start) * 1e3
-            t_lap = t1
-    try:
-        rows = enc.row_end - enc.row_begin
+    place = _Place(coeff_fn is not None, device)
+    enc = _HostBand(options, world, rank, coeff_fn) if coeff_fn is not None else jpeg.BandEncoder(options, world, rank, place.tdev.index)
+    wire = _wire(group, place.tdev)
+    timer = _Phases(phases)
+    with place.after_torch(band_pixels), contextlib.closing(enc):
         last = enc.coeffs(band_pixels)
-        lap("coeffs_ms")
-        # exchange 1: boundary DCs (+ whether the band has rows)
-        got = _all_gather_i64([rows > 0] + last, group, wire)
-        lap("exchange_dc_ms")
-        prev = [0, 0, 0]
-        for r in range(rank):
-            if got[r][0]:
-                prev = got[r][1:4]
-        total_counts = None
-        if options.optimize_huffman:  # exchange 1b: symbol statistics, summed
-            counts = enc.count(prev)
-            t = torch.from_numpy(counts.view(np.int64).copy()).to(wire)
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-            total_counts = t.cpu().numpy().view(np.uint64)
-        if not on_gpu:
-            enc._prev, enc._counts = prev, total_counts
-        bits = enc.lengths(prev, total_counts)
-        lap("lengths_ms")
-        # exchange 2: bits per band -> this band's bit offset
-        all_bits = [b[0] for b in _all_gather_i64([bits], group, wire)]
-        offset = sum(all_bits[:rank])
-        lap("exchange_bits_ms")
-        if not on_gpu and shared is not None:  # host twins through the shared file: header exchange, body at its final place
-            piece = enc.pack(offset)
-            words = np.frombuffer(piece[:16], np.int64)
-            all_hdr = [np.array(h, np.int64).tobytes() for h in _all_gather_i64([int(words[0]), int(words[1])], group, wire)]
-            file_len, body_off = jpeg.splice_layout(options, all_hdr, total_counts)
-            _check_shared(shared, file_len)
-            arr = shared.array()
-            body = np.frombuffer(piece, np.uint8)[16:]
-            arr[body_off[rank]: body_off[rank] + body.size] = body
-            dist.barrier(group=group)
-            if rank != dst:
-                return None
-            jpeg.splice_finish(options, all_hdr, arr, file_len, total_counts)
-            return file_len
-        if not on_gpu:  # host twins: whole pieces, gathered as objects
-            piece = enc.pack(offset)
-            pieces = [None] * world if rank == dst else None
-            dist.gather_object(piece, pieces, dst=dst, group=group)
-            if rank != dst:
-                return None
-            blob = jpeg.splice(options, pieces, total_counts)
-            if out is None:
-                return blob
-            out[: len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
-            return len(blob)
-        # device: the body stays in HBM; exchange 3 = the 16-byte piece headers -> the file's layout
-        hdr, n = enc.pack_device(offset)
-        lap("pack_ms")
+        timer.lap("coeffs_ms")
+        _, total_counts, offset = _band_exchanges(enc, options, last, group, wire, timer)
+        # the body stays where the encoder packed it; exchange 3 = the 16-byte piece headers -> the file's layout
+        hdr, _ = enc.pack_device(offset)
+        timer.lap("pack_ms")
         words = np.frombuffer(hdr, np.int64)
         all_hdr = [np.array(h, np.int64).tobytes() for h in _all_gather_i64([int(words[0]), int(words[1])], group, wire)]
         file_len, body_off = jpeg.splice_layout(options, all_hdr, total_counts)
         lens = [int(np.frombuffer(h, np.uint64)[1]) for h in all_hdr]
-        lap("exchange_hdr_ms")
+        timer.lap("exchange_hdr_ms")
         if shared is not None:
-            # every rank: device -> the body's final place in the node's shared file, over this GPU's own PCIe link
-            _check_shared(shared, file_len)
-            arr = shared.array()
-            if lens[rank]:
-                enc.copy_body(arr.ctypes.data + body_off[rank])
-            dist.barrier(group=group)
-            lap("bodies_ms")
-            if rank != dst:
-                return None
-            jpeg.splice_finish(options, all_hdr, arr, file_len, total_counts)
-            lap("splice_ms")
-            return file_len
-        if world == 1:
-            file = out if out is not None else _pinned_file(file_len)
-            enc.copy_body(file[body_off[0]:])  # device -> its final place in the (pinned) file
+            file = _bodies_into_shared(enc, shared, body_off[rank], lens[rank], file_len, group)
         else:
-            # the bodies travel to dst over xGMI (one gather of equal-sized buffers), then dst's PCIe link
-            send = torch.empty(max(max(lens), 1), dtype=torch.uint8, device=tdev)
-            enc.copy_body(send)
-            recv = _gather_bulk(send, dst, group, wire)
-            if rank != dst:
-                lap("bodies_ms")
-                return None
-            file = out if out is not None else _pinned_file(file_len)
-            for k in range(world):
-                if lens[k]:
-                    file[body_off[k]: body_off[k] + lens[k]].copy_(recv[k][: lens[k]], non_blocking=True)
-            torch.cuda.synchronize(tdev)
-        lap("bodies_ms")
+            file = _bodies_gathered(enc, place, lens, body_off, file_len, out, dst, group, wire)
+        timer.lap("bodies_ms")
+        if rank != dst:
+            return None
         jpeg.splice_finish(options, all_hdr, file, file_len, total_counts)
-        lap("splice_ms")
-        if out is not None:
+        timer.lap("splice_ms")
+        if shared is not None or out is not None:
             return file_len
         return file[:file_len].numpy().tobytes()
-    finally:
-        enc.close()
-        if prev_producer is not None:
-            jpeg.set_producer_stream(prev_producer)
 
 
 def encode_gathered(data, options, group=None, coeff_fn=None, dst=0):
@@ -564,6 +599,188 @@ def _p2p(ops, group=None):
     _p2p_wait(_p2p_post(ops, group))
 
 
+def _encode_into(arena, at, d_pixels, options, count, grow):
+    """`jpeg.encode_batch_device_into` behind `arena[:at]`.  When the files do not fit, `grow(bytes needed)` returns a larger arena
+    that kept `arena[:at]` — the lengths were filled in: the second attempt fits — or None: the arena is fixed, and the error the
+    caller's.  Returns (the arena used, offsets from `at`, lens)."""
+    while True:
+        try:
+            offsets, lens = jpeg.encode_batch_device_into(arena[at:], d_pixels, options, count)
+            return arena, [int(x) for x in offsets], [int(x) for x in lens]
+        except error.BufferTooSmall as e:
+            arena = grow(int(e.needed))
+            if arena is None:
+                raise
+
+
+def _batch_alone(batch_pixels, options, n, px, place, out, shared, timer):
+    """World of one: nothing to scatter or gather.  The files go straight from this GPU into the destination's host arena — the
+    caller's, or the node-shared segment (registered: the device-to-host copies land in it directly) — while the library overlaps
+    their way over PCIe with the kernels of the next sub-batch: no device arena, no second pass over the bytes."""
+    import torch
+    fixed = out is not None or shared is not None
+    if shared is not None:
+        arena = torch.from_numpy(shared.array())
+    else:
+        arena = out if out is not None else place.file_buffer(n * (px // 2 + 4096))
+    with place.after_torch():
+        arena, offsets, lens = _encode_into(arena, 0, batch_pixels.reshape(-1), options, n,
+                                            lambda needed: None if fixed else place.file_buffer(needed))
+    timer.lap("encode_ms")
+    return (None if shared is not None else arena), offsets, lens
+
+
+def _cut(a, b, nw):
+    """The parts of a share [a, b), in image indices: two with two waves and at least two images, else one."""
+    if nw == 1 or b - a < 2:
+        return [(a, b)]
+    m = (a + b + 1) // 2
+    return [(a, m), (m, b)]
+
+
+def _scatter_post(batch_pixels, parts, px, waves, src, group, place):
+    """Step 1 — posted, not waited for: `src` goes on to its own share while its sends are in flight; with two waves a receiver
+    encodes the first part of its share while the second part travels.  Returns (this rank's pixels, its parts, per part the
+    handle of its arrival — None: nothing travels —, src's handles of its sends)."""
+    import torch
+    import torch.distributed as dist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    nw = 2 if (waves == 2 and parts[-1][1] >= 2 * world) else 1
+    lo, hi = parts[rank]
+    my_parts = _cut(lo, hi, nw)
+    if rank != src:
+        mine = torch.empty((hi - lo) * px, dtype=torch.uint8, device=place.tdev)
+        gsrc = _global(group, src)
+        return mine, my_parts, [_p2p_post([("recv", mine[(a - lo) * px: (b - lo) * px], gsrc)], group) if b > a else None for (a, b) in my_parts], []
+    whole = batch_pixels.reshape(-1)
+    pending = []
+    for w in range(nw):
+        ops = []
+        for r, (a, b) in enumerate(parts):
+            pr = _cut(a, b, nw)
+            if r != src and w < len(pr) and pr[w][1] > pr[w][0]:
+                ops.append(("send", whole[pr[w][0] * px: pr[w][1] * px], _global(group, r)))
+        pending.append(_p2p_post(ops, group))
+    return whole[lo * px: hi * px], my_parts, [None] * len(my_parts), pending  # (its own images are where they are)
+
+
+def _device_part(run, at, d_pixels, options, count, spare):
+    """`count` images of this rank's share -> their files behind `run[:at]`, in an arena in ITS HBM.  Returns (the run — a larger
+    one, with `spare` bytes for the images still to come, if it had to grow — and the files' lengths)."""
+    import torch
+
+    def grow(needed):
+        grown = torch.empty(at + needed + spare, dtype=torch.uint8, device=run.device)
+        grown[:at].copy_(run[:at])
+        return grown
+    run, _, lens = _encode_into(run, at, d_pixels, options, count, grow)
+    return run, lens
+
+
+def _host_part(encode_fn):
+    """`_device_part` with a test's `encode_fn(images, options, count) -> list of bytes` in the device's place."""
+    def part(run, at, pixels, options, count, spare):
+        import torch
+        files = encode_fn(pixels.numpy(), options, count)
+        blob = np.frombuffer(b"".join(files), np.uint8).copy()
+        return torch.cat([run[:at], torch.from_numpy(blob)]), [len(f) for f in files]
+    return part
+
+
+def _encode_share(mine, my_parts, arrivals, options, px, place, encode_part, timer):
+    """Step 2: this rank's images part by part, as they arrive; the files stay, back to back, in the run the next step sends them
+    from.  A failure here must not leave the other ranks waiting in step 3: it is returned, and travels as a status word.
+    Returns (run, lens, failure)."""
+    import torch
+    lo, hi = my_parts[0][0], my_parts[-1][1]
+    reserve = px // 2 + 4096  # bytes per image the run starts with
+    lens, at = [], 0
+    try:
+        run = torch.empty((hi - lo) * reserve, dtype=torch.uint8, device=place.tdev)
+        with place.after_torch():  # the received pixels were written on torch's stream
+            for k, (a, b) in enumerate(my_parts):
+                _p2p_wait(arrivals[k])
+                timer.lap("scatter_wait_ms")
+                if b > a:
+                    run, part_lens = encode_part(run, at, mine[(a - lo) * px: (b - lo) * px], options, b - a, (hi - b) * reserve)
+                    lens += part_lens
+                    at += sum(part_lens)
+                    timer.lap("encode_ms")
+        return run, lens, None
+    except Exception as ex:  # noqa: BLE001 — reported to every rank in step 3
+        return None, [0] * (hi - lo), ex
+
+
+class _Files:
+    """Where every image's file and every rank's run of files lie in the arena, from the exchanged lengths."""
+
+    def __init__(self, all_lens, parts):
+        self.lens = [x for r, (a, b) in enumerate(parts) for x in all_lens[r][: b - a]]
+        self.offsets, self.total = [], 0
+        for x in self.lens:
+            self.offsets.append(self.total)
+            self.total += x
+        self.run_len = [sum(all_lens[r][: b - a]) for r, (a, b) in enumerate(parts)]
+        self.run_off = [self.offsets[a] if b > a else self.total for (a, b) in parts]
+
+
+def _exchange_sizes(lens, failure, parts, my_cap, group, wire, timer):
+    """Step 3: one all_gather of every rank's per-image lengths, padded to the longest share, behind a status word and `my_cap`
+    (dst's fixed capacity; -1: none).  A rank whose encode step failed makes every rank raise here: every rank knows, nobody posts
+    a send or a receive.  Returns (the files' layout, every rank's capacity word)."""
+    import torch.distributed as dist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    most = max(b - a for a, b in parts)
+    gathered = _all_gather_i64([0 if failure is None else -1, my_cap] + lens + [0] * (most - len(lens)), group, wire)
+    bad = [r for r in range(world) if gathered[r][0] != 0]
+    if bad:
+        if failure is not None:
+            raise failure
+        raise RuntimeError("encode_batch: the encode step failed on rank(s) %s of the group" % bad)
+    timer.lap("sizes_ms")
+    return _Files([g[2:] for g in gathered], parts), [g[1] for g in gathered]
+
+
+def _files_into_shared(run, files, shared, place, group, timer):
+    """Step 4 with a shared arena: every rank writes its own run at its final offset, over its own link."""
+    import torch
+    import torch.distributed as dist
+    rank = dist.get_rank(group)
+    _check_shared(shared, files.total)  # (every rank computed the same total: all raise, nobody is left in the barrier)
+    off, length = files.run_off[rank], files.run_len[rank]
+    if length:
+        # (device -> the mapping: a DMA when the segment is registered, staged otherwise)
+        torch.from_numpy(shared.array()[off: off + length]).copy_(run[:length])
+        place.synchronize()
+    dist.barrier(group=group)
+    timer.lap("copy_ms")
+
+
+def _files_gathered(run, files, dst_cap, place, out, dst, group, timer):
+    """Step 4 by gather: every rank sends its run to `dst`, which receives each at its final offset of ONE arena where its own
+    run lies, and brings that arena to the host once.  dst's output too small: every rank knows (its capacity travelled with the
+    sizes) and raises the same error before a byte moves.  Returns the CPU arena on `dst`, None elsewhere."""
+    import torch
+    import torch.distributed as dist
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    if 0 <= dst_cap < files.total:
+        raise _too_small("output buffer too small: need %d bytes" % files.total, files.total)
+    if rank != dst:
+        if files.run_len[rank]:
+            _p2p([("send", run[: files.run_len[rank]], _global(group, dst))], group)
+        timer.lap("gather_ms")
+        return None
+    whole = torch.empty(max(files.total, 1), dtype=torch.uint8, device=place.tdev)
+    place_of = [whole[o: o + n] for o, n in zip(files.run_off, files.run_len)]
+    if files.run_len[rank]:
+        place_of[rank].copy_(run[: files.run_len[rank]])
+    _p2p([("recv", place_of[r], _global(group, r)) for r in range(world) if r != dst and files.run_len[r]], group)
+    timer.lap("gather_ms")
+    arena = place.to_host(whole, files.total, out)
+    timer.lap("copy_ms")
+    return arena
+
+
 def encode_batch(batch_pixels, options, n, group=None, src=0, dst=0, device=None, encode_fn=None, out=None, shared=None, waves=1, phases=None):
     """Collective over `group`: `n` equally sized images (described by `options`) lie back to back on rank `src` — a torch
     uint8 tensor on its GPU (other ranks pass None) — and come back as `n` JFIF files on rank `dst`, each byte-identical to
@@ -598,204 +815,29 @@ def encode_batch(batch_pixels, options, n, group=None, src=0, dst=0, device=None
 
     `encode_fn(images, options, count) -> list of bytes` replaces step 2 for tests without a GPU (gloo, CPU tensors: the
     scatter, the size exchange and the gather are the same calls)."""
-    import torch
     import torch.distributed as dist
 
     rank, world = dist.get_rank(group), dist.get_world_size(group)
-    on_gpu = encode_fn is None
-    bpp = 1 if int(options.color_type) == 0 else 3
-    px = options.width * options.height * bpp
+    px = options.width * options.height * (1 if int(options.color_type) == 0 else 3)
+    if rank == src and (batch_pixels is None or batch_pixels.numel() != n * px):
+        raise ValueError("encode_batch: rank src passes the %d images back to back (%d bytes)" % (n, n * px))
+    place = _Place(encode_fn is not None, device)
+    encode_part = _host_part(encode_fn) if encode_fn is not None else _device_part
+    timer = _Phases(phases, place.synchronize)
+    if world == 1 and encode_fn is None:
+        return _batch_alone(batch_pixels, options, n, px, place, out, shared, timer)
     parts = batch_partition(n, world)
-    lo, hi = parts[rank]
-    cnt = hi - lo
-    if on_gpu:
-        if device is None:
-            device = torch.cuda.current_device()
-        tdev = torch.device("cuda", device)
-    else:
-        tdev = torch.device("cpu")
-    gsrc, gdst = _global(group, src), _global(group, dst)
-
-    import time
-    t_start = time.perf_counter()
-
-    def lap(name, t0):
-        if phases is None:
-            return time.perf_counter()
-        if on_gpu:
-            torch.cuda.synchronize(tdev)
-        t1 = time.perf_counter()
-        phases[name] = phases.get(name, 0.0) + (t1 - t0) * 1e3
-        return t1
-
-    if world == 1 and on_gpu:
-        # nothing to scatter or gather: the files go straight from this GPU into the destination's host arena — the caller's,
-        # or the node-shared segment (registered: the device-to-host copies land in it directly) — while the library overlaps
-        # their way over PCIe with the kernels of the next sub-batch: no device arena, no second pass over the bytes
-        if batch_pixels is None or batch_pixels.numel() != n * px:
-            raise ValueError("encode_batch: rank src passes the %d images back to back (%d bytes)" % (n, n * px))
-        prev = jpeg.get_producer_stream()
-        jpeg.set_producer_stream(torch.cuda.current_stream(tdev).cuda_stream)
-        try:
-            if shared is not None:
-                arena = torch.from_numpy(shared.array())
-            else:
-                arena = out if out is not None else _pinned_file(n * (px // 2 + 4096))
-            while True:
-                try:
-                    offsets, lens = jpeg.encode_batch_device_into(arena, batch_pixels.reshape(-1), options, n)
-                    lap("encode_ms", t_start)
-                    if phases is not None:
-                        phases["total_ms"] = (time.perf_counter() - t_start) * 1e3
-                    return (None if shared is not None else arena), [int(x) for x in offsets], [int(x) for x in lens]
-                except jpeg.error.BufferTooSmall as e:
-                    if out is not None or shared is not None:
-                        raise
-                    arena = _pinned_file(int(e.needed))
-        finally:
-            jpeg.set_producer_stream(prev)
-
-    # 1. scatter — posted, not waited for: `src` goes on to its own share while its sends are in flight; with two waves a
-    # receiver encodes the first part of its share while the second part travels
-    nw = 2 if (waves == 2 and n >= 2 * world) else 1
-
-    def cut(a, b):  # the parts of a share, in image indices
-        if nw == 1 or b - a < 2:
-            return [(a, b)]
-        m = (a + b + 1) // 2
-        return [(a, m), (m, b)]
-    my_parts = cut(lo, hi)
-    pending = []
-    if rank == src:
-        if batch_pixels is None or batch_pixels.numel() != n * px:
-            raise ValueError("encode_batch: rank src passes the %d images back to back (%d bytes)" % (n, n * px))
-        whole = batch_pixels.reshape(-1)
-        mine = whole[lo * px: hi * px]
-        for w in range(nw):
-            ops = []
-            for r, (a, b) in enumerate(parts):
-                pr = cut(a, b)
-                if r != src and w < len(pr) and pr[w][1] > pr[w][0]:
-                    ops.append(("send", whole[pr[w][0] * px: pr[w][1] * px], _global(group, r)))
-            pending.append(_p2p_post(ops, group))
-        arrivals = [None] * len(my_parts)  # (its own images are where they are)
-    else:
-        mine = torch.empty(cnt * px, dtype=torch.uint8, device=tdev)
-        arrivals = [_p2p_post([("recv", mine[(a - lo) * px: (b - lo) * px], gsrc)], group) if b > a else None for (a, b) in my_parts]
-    t_lap = lap("scatter_post_ms", t_start)
-
-    # 2. encode this rank's images part by part; the files stay, back to back, where the next step sends them from.  A
-    # failure here must not leave the other ranks waiting in step 3: it travels as a status word.
-    lens, failure = [], None
-    run = torch.empty(0, dtype=torch.uint8, device=tdev)
-    try:
-        if not on_gpu:
-            files = []
-            for k, (a, b) in enumerate(my_parts):
-                _p2p_wait(arrivals[k])
-                t_lap = lap("scatter_wait_ms", t_lap)
-                if b > a:
-                    files += encode_fn(mine[(a - lo) * px: (b - lo) * px].numpy(), options, b - a)
-                t_lap = lap("encode_ms", t_lap)
-            lens = [len(f) for f in files]
-            if cnt and sum(lens):
-                run = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8)
-        elif cnt:
-            cap = cnt * (px // 2 + 4096)
-            prev = jpeg.get_producer_stream()
-            jpeg.set_producer_stream(torch.cuda.current_stream(tdev).cuda_stream)  # the received pixels were written on torch's stream
-            try:
-                run = torch.empty(cap, dtype=torch.uint8, device=tdev)
-                at_run = 0
-                for k, (a, b) in enumerate(my_parts):
-                    _p2p_wait(arrivals[k])
-                    t_lap = lap("scatter_wait_ms", t_lap)
-                    if b <= a:
-                        continue
-                    while True:
-                        try:
-                            _, part_lens = jpeg.encode_batch_device_into(run[at_run:], mine[(a - lo) * px: (b - lo) * px], options, b - a)
-                            break
-                        except jpeg.error.BufferTooSmall as e:  # (the lengths were filled in: the second attempt fits)
-                            grown = torch.empty(at_run + int(e.needed) + (hi - b) * (px // 2 + 4096), dtype=torch.uint8, device=tdev)
-                            grown[:at_run].copy_(run[:at_run])
-                            run = grown
-                    lens += [int(x) for x in part_lens]
-                    at_run += sum(int(x) for x in part_lens)
-                    t_lap = lap("encode_ms", t_lap)
-            finally:
-                jpeg.set_producer_stream(prev)
-    except Exception as ex:  # noqa: BLE001 — reported to every rank below
-        failure = ex
-        lens = [0] * cnt
+    mine, my_parts, arrivals, pending = _scatter_post(batch_pixels, parts, px, waves, src, group, place)
+    timer.lap("scatter_post_ms")
+    run, lens, failure = _encode_share(mine, my_parts, arrivals, options, px, place, encode_part, timer)
     for h in pending:  # (src: its sends have long left; they must have before the tensors they read are released)
         _p2p_wait(h)
-    t_lap = lap("scatter_wait_ms", t_lap)
-
-    # 3. sizes: every rank's per-image lengths, padded to the longest share
-    most = max(b - a for a, b in parts)
+    timer.lap("scatter_wait_ms")
     my_cap = int(out.numel()) if (out is not None and rank == dst and shared is None) else -1  # (dst's fixed output, if any)
-    gathered = _all_gather_i64([0 if failure is None else -1, my_cap] + lens + [0] * (most - cnt), group, _wire(group, tdev))
-    bad = [r for r in range(world) if gathered[r][0] != 0]
-    if bad:  # every rank knows: nobody posts a send or a receive, everybody raises
-        if failure is not None:
-            raise failure
-        raise RuntimeError("encode_batch: the encode step failed on rank(s) %s of the group" % bad)
-    all_lens = [g[2:] for g in gathered]
-    dst_cap = gathered[dst][1]
-    t_lap = lap("sizes_ms", t_lap)
-    lens_all = [x for r, (a, b) in enumerate(parts) for x in all_lens[r][: b - a]]
-    offsets, at = [], 0
-    for x in lens_all:
-        offsets.append(at)
-        at += x
-    run_len = [sum(all_lens[r][: b - a]) for r, (a, b) in enumerate(parts)]
-    run_off = [offsets[a] if b > a else at for (a, b) in parts]
-
-    # 4. (shared arena) every rank writes its own run at its final offset, over its own link
+    files, caps = _exchange_sizes(lens, failure, parts, my_cap, group, _wire(group, place.tdev), timer)
     if shared is not None:
-        _check_shared(shared, at)  # (every rank computed the same total: all raise, nobody is left in the barrier)
-        if run_len[rank]:
-            dest = torch.from_numpy(shared.array()[run_off[rank]: run_off[rank] + run_len[rank]])
-            dest.copy_(run[: run_len[rank]])  # (device -> the mapping: a DMA when the segment is registered, staged otherwise)
-            if on_gpu:
-                torch.cuda.synchronize(tdev)
-        dist.barrier(group=group)
-        lap("copy_ms", t_lap)
-        if phases is not None:
-            phases["total_ms"] = (time.perf_counter() - t_start) * 1e3
-        return (None, offsets, lens_all) if rank == dst else None
-    # 4. gather the files on dst, every run straight to its final offset.  dst's output too small: every rank knows (its
-    # capacity travelled with the sizes) and raises the same error before a byte moves.
-    if 0 <= dst_cap < at:
-        from . import error
-        e = error.BufferTooSmall("output buffer too small: need %d bytes" % at)
-        e.needed = at
-        raise e
-    if rank != dst:
-        if run_len[rank]:
-            _p2p([("send", run[: run_len[rank]], gdst)], group)
-        lap("gather_ms", t_lap)
-        if phases is not None:
-            phases["total_ms"] = (time.perf_counter() - t_start) * 1e3
-        return None
-    whole = torch.empty(max(at, 1), dtype=torch.uint8, device=tdev)
-    if run_len[rank]:
-        whole[run_off[rank]: run_off[rank] + run_len[rank]].copy_(run[: run_len[rank]])
-    _p2p([("recv", whole[run_off[r]: run_off[r] + run_len[r]], _global(group, r)) for r in range(world) if r != dst and run_len[r]], group)
-    if not on_gpu:
-        arena = whole if out is None else out
-        if out is not None:
-            out[:at].copy_(whole[:at])
-        lap("gather_ms", t_lap)
-        if phases is not None:
-            phases["total_ms"] = (time.perf_counter() - t_start) * 1e3
-        return arena, offsets, lens_all
-    t_lap = lap("gather_ms", t_lap)
-    arena = out if out is not None else _pinned_file(at)
-    arena[:at].copy_(whole[:at], non_blocking=True)
-    torch.cuda.synchronize(tdev)
-    lap("copy_ms", t_lap)
-    if phases is not None:
-        phases["total_ms"] = (time.perf_counter() - t_start) * 1e3
-    return arena, offsets, lens_all
+        _files_into_shared(run, files, shared, place, group, timer)
+        arena = None
+    else:
+        arena = _files_gathered(run, files, caps[dst], place, out, dst, group, timer)
+    return (arena, files.offsets, files.lens) if rank == dst else None

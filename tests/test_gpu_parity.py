@@ -326,7 +326,7 @@ def test_batch_into_one_arena_every_file_at_its_final_place(shape):
     o = _opts(w, h, ct, ss, 80)
     offs, lens = jpeg.encode_batch_device_into(None, d_px, o, n)  # size query
     assert lens == [len(f) for f in want] and offs == [sum(lens[:i]) for i in range(n)]
-    total = sum(lens)
+    total, query = sum(lens), (offs, lens)
     for arena in (torch.full((total + 64,), 0x5A, dtype=torch.uint8).pin_memory(), torch.full((total,), 0x5A, dtype=torch.uint8),
                   np.full(total + 7, 0x5A, np.uint8)):
         offs, lens = jpeg.encode_batch_device_into(arena, d_px, o, n)
@@ -335,8 +335,9 @@ def test_batch_into_one_arena_every_file_at_its_final_place(shape):
             assert raw[offs[i]: offs[i] + lens[i]].tobytes() == want[i], i
         assert bool((raw[total:] == 0x5A).all())
     small = torch.zeros(total - 1, dtype=torch.uint8).pin_memory()
-    with pytest.raises(error.Error, match="need %d bytes" % total):
+    with pytest.raises(error.Error, match="need %d bytes" % total) as e:
         jpeg.encode_batch_device_into(small, d_px, o, n)
+    assert (e.value.offsets, e.value.lens, e.value.needed) == query + (total,)  # (the error carries the size query's answer)
     # per-image option sets go one by one, into the same layout
     o2 = _opts(w, h, ct, ss, 80, optimize_huffman=True)
     want2 = [O.encode(im, O.make_options(w, h, ct, 80, ss, optimize_huffman=True)) for im in imgs]

@@ -48,7 +48,8 @@ def _worker_banded(rank, world, port, w, h, ct, ss, q, ret, flags=None):
     import oracle_lib as O
     import synth
     from pixo_amd import jpeg, sharded
-    flags = flags or {}
+    flags = dict(flags or {})
+    into_out, with_phases = flags.pop("_out", False), flags.pop("_phases", False)  # (test controls, not encoder options)
     px = synth.noise_gray(w, h, 77) if ct == 0 else synth.noise(w, h, 77)
     bpp = 1 if ct == 0 else 3
 
@@ -58,9 +59,23 @@ def _worker_banded(rank, world, port, w, h, ct, ss, q, ret, flags=None):
     o = _options(w, h, ct, ss, q, flags)
     b = jpeg.band(w, h, ct, ss, world, rank)
     mine = px[b["row_begin"] * w * bpp: b["row_end"] * w * bpp]  # a rank holds only its own rows
-    got = sharded.encode_banded(mine, o, coeff_fn=cpu_coeffs)
+    want = O.encode(px, O.make_options(w, h, ct, q, ss, **flags))
+    if into_out:  # the file lands in the caller's CPU tensor on rank 0, which gets its length
+        import torch
+        out = torch.full((len(want) + 64,), 0xAB, dtype=torch.uint8) if rank == 0 else None
+        got = sharded.encode_banded(mine, o, coeff_fn=cpu_coeffs, out=out)
+        if rank == 0:
+            assert got == len(want) and bool((out[got:] == 0xAB).all())
+            got = out[:got].numpy().tobytes()
+    elif with_phases:  # the host twins go through every step of the one flow, and every rank's dict says so
+        phases = {}
+        got = sharded.encode_banded(mine, o, coeff_fn=cpu_coeffs, phases=phases)
+        assert {"coeffs_ms", "lengths_ms", "pack_ms", "exchange_hdr_ms", "total_ms"} <= set(phases), sorted(phases)
+        assert ("splice_ms" in phases) == (rank == 0), sorted(phases)
+    else:
+        got = sharded.encode_banded(mine, o, coeff_fn=cpu_coeffs)
     if rank == 0:
-        ret.put(got == O.encode(px, O.make_options(w, h, ct, q, ss, **flags)))
+        ret.put(got == want)
     else:
         assert got is None
     dist.barrier()
@@ -105,6 +120,57 @@ def _worker_banded_flags(rank, world, port, flags, ret):
 def test_three_rank_uneven_bands(flags):
     """13 MCU rows over 3 ranks (5 + 4 + 4); with optimised tables the ranks also sum their symbol counts."""
     assert _run(_worker_banded_flags, 3, (flags,)) is True
+
+
+def _worker_banded_case_flags(rank, world, port, case, flags, ret):
+    _worker_banded(rank, world, port, *case, ret, flags)
+
+
+@pytest.mark.parametrize("case", [(40, 16, 2, 1, 80), (100, 75, 2, 0, 60)])
+def test_two_rank_file_lands_in_the_callers_tensor(case):
+    """`out=<CPU uint8 tensor>`: the file's length on rank 0, None on rank 1, the oracle's bytes in out[:n] and nothing behind
+    them.  (40x16 4:2:0: rank 1's band is empty.)"""
+    assert _run(_worker_banded_case_flags, 2, (case, {"_out": True})) is True
+
+
+def test_two_rank_host_twins_record_every_step():
+    """The host twins run the device flow: pack, header exchange and splice are recorded like the steps before them."""
+    assert _run(_worker_banded_case_flags, 2, ((100, 75, 2, 0, 60), {"_phases": True})) is True
+
+
+def test_host_twin_packs_and_copies_what_band_piece_host_makes():
+    """`_HostBand` alone, the middle band of three: pack_device + copy_body = header ‖ body of `jpeg.band_piece_host`'s piece,
+    into a numpy array and to a raw address; pack_device before lengths says so."""
+    import ctypes
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import numpy as np
+    import oracle_lib as O
+    import synth
+    from pixo_amd import jpeg, sharded
+    w, h, ct, ss, q = 100, 75, 2, 0, 60
+    o = _options(w, h, ct, ss, q, {})
+    px = synth.noise(w, h, 77)
+
+    def twin():
+        t = sharded._HostBand(o, 3, 1, lambda sub, bo: O.coeffs(sub, bo.width, bo.height, ct, ss, bo.quality))
+        t.coeffs(px[t.row_begin * w * 3: t.row_end * w * 3])
+        return t
+    with pytest.raises(RuntimeError, match="lengths"):
+        twin().pack_device(0)
+    t = twin()
+    prev, bit_offset = [5, -3, 7], 13
+    assert t.lengths(prev) == jpeg.band_bits_host(t.y, t.cb, t.cr, o, t.rows, prev)
+    want = jpeg.band_piece_host(t.y, t.cb, t.cr, o, t.rows, prev, bit_offset)
+    hdr, n = t.pack_device(bit_offset)
+    assert len(hdr) == 16 and n == len(want) - 16 and n > 0
+    arr = np.full(n + 8, 0xAB, np.uint8)
+    t.copy_body(arr)
+    assert hdr + arr[:n].tobytes() == want and (arr[n:] == 0xAB).all()
+    raw = ctypes.create_string_buffer(b"\xab" * (n + 8), n + 8)
+    t.copy_body(ctypes.addressof(raw))
+    assert hdr + raw.raw[:n] == want and raw.raw[n:] == b"\xab" * 8
+    t.close()
 
 
 def _worker_banded_shared(rank, world, port, w, h, ct, ss, q, flags, ret):
