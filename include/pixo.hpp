@@ -18,6 +18,7 @@
 //   pixo::resize::ResizeOptions + builder resize.rs:65  pixo::resize::ResizeOptions / ResizeOptionsBuilder
 //   pixo::resize::resize / resize_into resize.rs:165    pixo::resize::resize / resize_into
 //   (wasm) resizeImage                 wasm.rs:183      pixo::resize_image
+//   (a loop over pixo::resize::resize)                  pixo::resize::resize_batch / resize_batch_device
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -386,6 +387,30 @@ inline void resize_device(const void *d_src, const ResizeOptions &options, void 
     const pixo_resize_options c = options.c();
     const int rc = pixo_hip_resize_device(d_src, &c, d_dst, stream);
     if (rc != PIXO_OK) throw Error::from_status(rc);
+}
+// Batches: N sources of individual sizes -> N images of one size, back to back (contract: pixo_hip.h).  Device pixels,
+// enqueued on `stream`: image i lands at d_dst + i * dst_width * dst_height * bytes_per_pixel(color_type)
+inline void resize_batch_device(const std::vector<pixo_resize_source> &sources, uint32_t dst_width, uint32_t dst_height, ColorType color_type,
+                                ResizeAlgorithm algorithm, void *d_dst, void *stream = nullptr)
+{
+    const int rc = pixo_hip_resize_batch_device(sources.data(), (uint32_t)sources.size(), dst_width, dst_height, (uint8_t)color_type,
+                                                (uint8_t)algorithm, d_dst, stream);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+}
+// ... host pixels -> the images in one vector, image after image
+[[nodiscard]] inline std::vector<uint8_t> resize_batch(const std::vector<pixo_resize_source> &sources, uint32_t dst_width, uint32_t dst_height,
+                                                       ColorType color_type, ResizeAlgorithm algorithm)
+{
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    const int rc = pixo_hip_resize_batch(sources.data(), (uint32_t)sources.size(), dst_width, dst_height, (uint8_t)color_type, (uint8_t)algorithm,
+                                         &block, &n);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    struct Block { // (released also when the copy below throws)
+        uint8_t *p;
+        ~Block() { pixo_hip_free(p); }
+    } held{block};
+    return std::vector<uint8_t>(block, block + n);
 }
 } // namespace resize
 

@@ -469,6 +469,45 @@ int pixo_hip_resize_image(const uint8_t *data, size_t data_len, uint32_t src_wid
 int pixo_hip_resize_contributions(uint32_t src, uint32_t dst, uint32_t *starts, uint32_t *counts,
                                   float *weights, size_t capacity, size_t *total);
 
+/* ---- resize batches: N sources of individual sizes -> N images of ONE size, back to back ---- */
+
+/* One source of a batch: width * height * bytes-per-pixel bytes at `pixels`. */
+typedef struct pixo_resize_source {
+    const void *pixels;
+    uint32_t width, height;
+} pixo_resize_source; /* 16 bytes */
+
+/* The stage in front of the batch encoders (pixo_hip_jpeg_encode_batch_device*, pixo_hip_png_encode_batch_device*), which
+ * read `batch` equally sized images back to back: `sources` is a HOST array of `batch` (1..65535) entries whose `pixels` are
+ * DEVICE pointers of the current HIP device; image i is written at d_dst + i * dst_width * dst_height * bytes-per-pixel with no
+ * padding (image starts are not dword aligned in general), byte for byte what pixo_hip_resize_device writes for source i.  One
+ * launch for nearest and bilinear, two for Lanczos3, whatever `batch` is: every image's workgroups read its own description.
+ * Images of one width share a horizontal Lanczos3 table, images of one height a vertical one; tables and descriptions go to the
+ * device in one copy.  Lanczos3 batches whose intermediates (source height rows of dst_width, padded to 16 bytes) exceed 256 MiB
+ * run as sub-batches, one behind the other on `stream`.
+ * Enqueue only, ordered like pixo_hip_resize_device (behind the producer stream's work); the one host wait is for the
+ * calling thread's previous batch, whose tables are about to be replaced.  `sources` may be released when the call returns.
+ * Checks, all before anything is enqueued (no GPU needed for a refusal): `sources`; batch (PIXO_ERR_COMPRESSION, "batch must be
+ * 1..65535"); then for i = 0, 1, ... pixo_hip_resize's checks on (source i, destination, color_type, algorithm) — the first
+ * failure returns that entry's status and its message with " (image i)" appended (a block of images beyond 2^62 bytes:
+ * PIXO_ERR_COMPRESSION); then every `pixels`; then d_dst. */
+int pixo_hip_resize_batch_device(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height,
+                                 uint8_t color_type, uint8_t algorithm, void *d_dst, void *stream);
+
+/* Same with HOST pixels: `pixels` are host pointers; *out receives one block of batch * dst_width * dst_height *
+ * bytes-per-pixel bytes (*out_len), image after image, released with pixo_hip_free.  Returns when the block is complete. */
+int pixo_hip_resize_batch(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height,
+                          uint8_t color_type, uint8_t algorithm, uint8_t **out, size_t *out_len);
+
+/* Tests: what the batch entries would decide for these sizes, computed on the HOST, no GPU needed (`pixels` is ignored; the
+ * checks are the batch entries').  Sub-batch k is images sub_first[k] .. sub_first[k + 1] (sub_first has room for batch + 1
+ * entries, *sub_count + 1 are written); mid_at[i] is image i's byte offset in its sub-batch's Lanczos3 intermediate; use_lds[i]
+ * whether its horizontal pass stages source rows in LDS; *axis_tables how many distinct axis tables are built.  Nearest and
+ * bilinear: one sub-batch, no tables. */
+int pixo_hip_debug_resize_batch_plan(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height,
+                                     uint8_t color_type, uint8_t algorithm, uint32_t *sub_first, uint32_t *sub_count,
+                                     uint64_t *mid_at, uint8_t *use_lds, uint32_t *axis_tables);
+
 /* ---- multi-GPU band sharding -------------------------------------- */
 
 /* Splits the image into `parts` contiguous MCU-row bands; band `index` covers pixel

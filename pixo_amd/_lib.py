@@ -32,6 +32,11 @@ class ResizeOptionsC(C.Structure):
     ]
 
 
+class ResizeSourceC(C.Structure):
+    """pixo_resize_source (include/pixo_hip.h): one source of a resize batch"""
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
 class PngOptionsC(C.Structure):
     """pixo_png_options (include/pixo_hip.h)"""
     _fields_ = [
@@ -65,6 +70,7 @@ _vp, _sz, _u8, _u32, _u64, _int, _dbl = C.c_void_p, C.c_size_t, C.c_uint8, C.c_u
 _szp, _u8p, _u32p, _u64p, _i16p = C.POINTER(_sz), C.POINTER(_u8), C.POINTER(_u32), C.POINTER(_u64), C.POINTER(C.c_int16)
 _u8pp, _optp, _roptp = C.POINTER(_u8p), C.POINTER(JpegOptionsC), C.POINTER(ResizeOptionsC)
 _poptp, _playp, _qoptp = C.POINTER(PngOptionsC), C.POINTER(PngLayoutC), C.POINTER(PngQuantizationC)
+_rsrcp = C.POINTER(ResizeSourceC)
 _coeffs = (_vp, _u32, _u32, _u8, _u8, _u8, _vp, _sz, _vp, _vp, _sz)
 
 # every symbol include/pixo_hip.h declares: name -> (argtypes, restype, optional).  `load()` applies it; a new entry is declared
@@ -122,6 +128,9 @@ SIGNATURES = {
     "pixo_hip_resize_device": _sig(_vp, _roptp, _vp, _vp),
     "pixo_hip_resize_image": _sig(_vp, _sz, _u32, _u32, _u32, _u32, _u8, _u8, _u8pp, _szp),
     "pixo_hip_resize_contributions": _sig(_u32, _u32, _vp, _vp, _vp, _sz, _szp),
+    "pixo_hip_resize_batch_device": _sig(_rsrcp, _u32, _u32, _u32, _u8, _u8, _vp, _vp, optional=True),
+    "pixo_hip_resize_batch": _sig(_rsrcp, _u32, _u32, _u32, _u8, _u8, _u8pp, _szp, optional=True),
+    "pixo_hip_debug_resize_batch_plan": _sig(_rsrcp, _u32, _u32, _u32, _u8, _u8, _u32p, _u32p, _u64p, _u8p, _u32p, optional=True),
     "pixo_hip_png_decode": _sig(_vp, _sz, _u8pp, _szp, _u32p, _u32p, _u8p),
     "pixo_hip_png_decode_info": _sig(_vp, _sz, _u32p, _u32p, _u8p),
     "pixo_hip_png_decode_device": _sig(_vp, _sz, _vp, _sz, _u32p, _u32p, _u8p, _vp),

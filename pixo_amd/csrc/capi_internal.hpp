@@ -16,7 +16,7 @@
 //   png_encode_api.cpp  the extern "C" zlib / PNG whole-file entry points: prepare, the DEFLATE tail over a segment table (png_deflate.hip), file head and IDAT frames;
 //                    the PNG batch entries: segments, sub-batches, the batched tail
 //   png_quantize_api.cpp  PNG lossy mode: gate, histogram and median cut on the host, the kernels of png_quantize.hip, the extern "C" quantize entries
-//   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables
+//   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables; the resize batch entries: plan, sub-batches
 //   png_decode_api.cpp  the extern "C" PNG decode entry points: chunk walk and checks, the host inflate (png_inflate.cpp), the runs of rows,
 //                    the launches of png_unfilter.hip
 #pragma once
@@ -104,6 +104,8 @@ inline int bad_length(size_t expected, size_t got)
 //   png_batch_bytes=n  a sub-batch of pixo_hip_png_encode_batch* holds at most n bytes of prepared stream (and at least one image)
 //                      instead of 64 MiB: tests reach a sub-batch boundary with small images (the limit of 1024 chunks a sub-batch,
 //                      which bounds the scratch, stays)
+//   resize_batch_bytes=n  a sub-batch of pixo_hip_resize_batch* holds at most n bytes of Lanczos3 intermediate (and at least one
+//                      image) instead of 256 MiB: tests reach a sub-batch boundary with small images
 //   no_bands_upload    host pixels are uploaded in one copy instead of MCU-row bands pipelined with the kernels
 //   plain_host         no host-memory policy (for embedders that own theirs): pixo_hip_free returns every block to malloc at once
 //                      (no blocks kept for the next large file), fresh blocks are plain malloc, no madvise(MADV_HUGEPAGE) on the
@@ -125,6 +127,7 @@ struct DebugSwitches {
     uint32_t spin_budget = 1u << 20;
     uint32_t batch_parts = 0; // (measurements) sub-batches of pixo_hip_jpeg_encode_batch_device_into, 0 = the library's choice
     uint64_t png_batch_bytes = 0; // bytes of prepared stream a sub-batch of the PNG batch entries holds at most, 0 = 64 MiB
+    uint64_t resize_batch_bytes = 0; // bytes of Lanczos3 intermediate a sub-batch of the resize batch entries holds at most, 0 = 256 MiB
 };
 const DebugSwitches &debug();
 
@@ -266,6 +269,12 @@ struct Context {
     uint32_t r_max_span = 0;                            // ... the widest source span of one horizontal tile
     size_t r_v_at = 0;                                  // ... where the vertical axis starts in r_tables
     hipEvent_t r_done = nullptr;                        // the last Lanczos3 job (it reads r_tables, writes r_mid) has run
+    // resize batches (resize_api.cpp): buffers of their own, so that the single entry's cached tables stay what r_dims says
+    Buf rb_in{Buf::Mem::Device, Buf::Grow::Exact}, rb_out{Buf::Mem::Device, Buf::Grow::Exact}; // host entry: every source up, the block of images down
+    Buf rb_mid;                                          // Lanczos3: the intermediates of one sub-batch, image after image
+    Buf rb_tables;                                       // the axis tables of a call, behind them its ResizeBatchItem per image
+    Buf rb_stage{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here on the host, uploaded from here in one copy
+    hipEvent_t rb_done = nullptr;                        // the last batch job (it reads rb_tables, writes rb_mid) has run
     // PNG decode (png_decode_api.cpp, png_unfilter.hip)
     Buf u_inflated{Buf::Mem::Pinned, Buf::Grow::Exact};  // the inflated stream: the host inflate writes it, the upload reads it
     Buf u_stream{Buf::Mem::Device, Buf::Grow::Exact};    // ... on the device

@@ -83,6 +83,7 @@ DebugSwitches parse_switches(const char *e)
         else if (name == "copy_threads") v.copy_threads = static_cast<unsigned>(num < 1 ? 1 : (num > 64 ? 64 : num));
         else if (name == "batch_parts" && num > 0) v.batch_parts = static_cast<uint32_t>(num);
         else if (name == "png_batch_bytes" && num > 0) v.png_batch_bytes = static_cast<uint64_t>(num);
+        else if (name == "resize_batch_bytes" && num > 0) v.resize_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "spin_budget" && !val.empty()) v.spin_budget = static_cast<uint32_t>(num < 0 ? 0 : num);
         else if (name == "piece_schedule") {
             std::vector<uint32_t> w;
@@ -158,7 +159,7 @@ template <class F> void each_buf(Context &c, F &&f)
                    &c.q_work, &c.h_qwork, &c.q_index, &c.q_rows, &c.z_tok, &c.z_slots, &c.z_prev, &c.z_info, &c.z_stream, &c.z_crc, &c.h_zinfo,
                    &c.k_samples, &c.h_ksamples, &c.k_work, &c.h_kwork, &c.k_lut, &c.k_carry,
                    &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank, &c.h_file, &c.r_in, &c.r_out, &c.r_mid, &c.r_tables,
-                   &c.r_stage, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables};
+                   &c.r_stage, &c.rb_in, &c.rb_out, &c.rb_mid, &c.rb_tables, &c.rb_stage, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables};
     for (Buf *b : bufs) f(*b);
 }
 } // namespace
@@ -204,6 +205,8 @@ void Context::release()
     stats_done = side_ready = nullptr;
     if (r_done) (void)hipEventDestroy(r_done);
     r_done = nullptr;
+    if (rb_done) (void)hipEventDestroy(rb_done);
+    rb_done = nullptr;
     if (u_done) (void)hipEventDestroy(u_done);
     u_done = nullptr;
     stream = nullptr; ready = false;

@@ -11,6 +11,10 @@
 //   resize_lanczos_v_kernel  a thread owns four adjacent BYTES of an output row (the vertical pass treats every byte column
 //                            alike, whatever the pixel size): per tap the workgroup reads consecutive aligned dwords of one
 //                            intermediate row (rows padded to 16 bytes), the tap's weight is uniform over the workgroup.
+//
+// Each of the three is a __device__ body with two __global__ entries: the single one (one image, its shape in the kernel
+// arguments) and the batch one (blockIdx.z is the image: every workgroup reads its image's ResizeBatchItem, then walks the
+// same body).  N sources of individual sizes go to N images of ONE destination size, written back to back.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -19,7 +23,7 @@
 
 namespace {
 
-constexpr int kSegBytes = 8192; // LDS bytes per staged source row segment (four rows per workgroup: 32 KiB)
+constexpr int kSegBytes = pixo_dev::kResizeSegBytes; // LDS bytes per staged source row segment (four rows per workgroup: 32 KiB)
 
 // ---- nearest / bilinear -----------------------------------------------------------------------------------------------------
 template <int BPP> __device__ __forceinline__ void store_group(uint8_t *p, const uint8_t (&o)[4 * BPP], uint32_t pixels)
@@ -34,8 +38,8 @@ template <int BPP> __device__ __forceinline__ void store_group(uint8_t *p, const
 }
 
 template <int BPP, int ALGO>
-__global__ __launch_bounds__(256) void resize_point_kernel(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ dst,
-                                                           uint32_t dw, uint32_t dh)
+__device__ __forceinline__ void resize_point_body(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ dst, uint32_t dw,
+                                                  uint32_t dh)
 {
     const size_t gx = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (gx * 4 >= dw) return;
@@ -74,6 +78,21 @@ __global__ __launch_bounds__(256) void resize_point_kernel(const uint8_t *__rest
         store_group<BPP>(dst + (y * dw + x_first) * BPP, o, pixels);
     }
 }
+template <int BPP, int ALGO>
+__global__ __launch_bounds__(256) void resize_point_kernel(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ dst,
+                                                           uint32_t dw, uint32_t dh)
+{
+    resize_point_body<BPP, ALGO>(src, sw, sh, dst, dw, dh);
+}
+// Image blockIdx.z of a batch: its own source and column terms, its place in the block of outputs.  (An image of 4 * k + 1 .. 3
+// bytes puts the next one off a dword: store_group looks at the address.)
+template <int BPP, int ALGO>
+__global__ __launch_bounds__(256) void resize_point_batch_kernel(const pixo_dev::ResizeBatchItem *__restrict__ items, uint8_t *__restrict__ dst,
+                                                                 uint32_t dw, uint32_t dh)
+{
+    const pixo_dev::ResizeBatchItem it = items[blockIdx.z];
+    resize_point_body<BPP, ALGO>(it.src, it.sw, it.sh, dst + (size_t)blockIdx.z * dw * dh * BPP, dw, dh);
+}
 
 // ---- Lanczos3, horizontal ------------------------------------------------------------------------------------------------------
 // Stages bytes [first, first + n) of the image into seg, keeping their alignment: seg[shift + i] = img[first + i] with
@@ -99,8 +118,8 @@ __device__ __forceinline__ uint32_t stage_segment(const uint8_t *img, size_t img
 }
 
 template <int BPP>
-__global__ __launch_bounds__(256) void resize_lanczos_h_kernel(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ mid,
-                                                               size_t mid_stride, uint32_t dw, pixo_dev::ResizeAxisTable t, int use_lds)
+__device__ __forceinline__ void resize_lanczos_h_body(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ mid,
+                                                      size_t mid_stride, uint32_t dw, pixo_dev::ResizeAxisTable t, int use_lds)
 {
     __shared__ __attribute__((aligned(16))) uint8_t seg[4][kSegBytes];
     const size_t d = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -151,10 +170,35 @@ __global__ __launch_bounds__(256) void resize_lanczos_h_kernel(const uint8_t *__
             for (int c = 0; c < BPP; ++c) out[c] = rz_to_u8(acc[c]);
     }
 }
+template <int BPP>
+__global__ __launch_bounds__(256) void resize_lanczos_h_kernel(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ mid,
+                                                               size_t mid_stride, uint32_t dw, pixo_dev::ResizeAxisTable t, int use_lds)
+{
+    resize_lanczos_h_body<BPP>(src, sw, sh, mid, mid_stride, dw, t, use_lds);
+}
+// One axis of the batch's tables (ResizeAxisTable's layout at a byte offset of the block)
+__device__ __forceinline__ pixo_dev::ResizeAxisTable batch_axis(const uint8_t *tables, uint64_t at, uint32_t dst)
+{
+    pixo_dev::ResizeAxisTable t;
+    t.start = reinterpret_cast<const uint32_t *>(tables + at);
+    t.off = t.start + dst;
+    t.w = reinterpret_cast<const float *>(t.off + dst + 1);
+    return t;
+}
+// Image blockIdx.z of a sub-batch.  grid.y is sized for the tallest source: the body's row loop starts at blockIdx.y * 4, so a
+// workgroup beyond its image's rows runs no round of it and meets no barrier; the loop's bounds are uniform over a workgroup.
+template <int BPP>
+__global__ __launch_bounds__(256) void resize_lanczos_h_batch_kernel(const pixo_dev::ResizeBatchItem *__restrict__ items,
+                                                                     const uint8_t *__restrict__ tables, uint8_t *__restrict__ mid, size_t mid_stride,
+                                                                     uint32_t dw)
+{
+    const pixo_dev::ResizeBatchItem it = items[blockIdx.z];
+    resize_lanczos_h_body<BPP>(it.src, it.sw, it.sh, mid + it.mid_at, mid_stride, dw, batch_axis(tables, it.h_at, dw), (int)it.use_lds);
+}
 
 // ---- Lanczos3, vertical ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void resize_lanczos_v_kernel(const uint8_t *__restrict__ mid, size_t mid_stride, uint8_t *__restrict__ dst,
-                                                               size_t row_bytes, uint32_t dh, pixo_dev::ResizeAxisTable t)
+__device__ __forceinline__ void resize_lanczos_v_body(const uint8_t *__restrict__ mid, size_t mid_stride, uint8_t *__restrict__ dst, size_t row_bytes,
+                                                      uint32_t dh, pixo_dev::ResizeAxisTable t)
 {
     const size_t b = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (b >= row_bytes) return;
@@ -178,6 +222,19 @@ __global__ __launch_bounds__(256) void resize_lanczos_v_kernel(const uint8_t *__
         else
             for (uint32_t k = 0; k < n; ++k) out[k] = o[k];
     }
+}
+__global__ __launch_bounds__(256) void resize_lanczos_v_kernel(const uint8_t *__restrict__ mid, size_t mid_stride, uint8_t *__restrict__ dst,
+                                                               size_t row_bytes, uint32_t dh, pixo_dev::ResizeAxisTable t)
+{
+    resize_lanczos_v_body(mid, mid_stride, dst, row_bytes, dh, t);
+}
+// Image blockIdx.z of a sub-batch: its vertical table, its rows of the intermediate (mid_at is a multiple of 16: rows are padded)
+__global__ __launch_bounds__(256) void resize_lanczos_v_batch_kernel(const pixo_dev::ResizeBatchItem *__restrict__ items,
+                                                                     const uint8_t *__restrict__ tables, const uint8_t *__restrict__ mid,
+                                                                     size_t mid_stride, uint8_t *__restrict__ dst, size_t row_bytes, uint32_t dh)
+{
+    const pixo_dev::ResizeBatchItem it = items[blockIdx.z];
+    resize_lanczos_v_body(mid + it.mid_at, mid_stride, dst + (size_t)blockIdx.z * row_bytes * dh, row_bytes, dh, batch_axis(tables, it.v_at, dh));
 }
 
 uint32_t rows_grid(uint32_t rows, uint32_t per_block) // grid.y: the kernels stride over what does not fit
@@ -221,7 +278,7 @@ hipError_t launch_resize_lanczos_h(const uint8_t *d_src, uint32_t sw, uint32_t s
     if (bpp < 1 || bpp > 4) return hipErrorInvalidValue;
     static_assert(kResizeHTile == 64, "a wavefront per tile");
     // the staged segment keeps the source's alignment (up to 3 bytes in front) and is stored in whole dwords
-    const int use_lds = static_cast<size_t>(max_span) * bpp + 8 <= static_cast<size_t>(kSegBytes);
+    const int use_lds = resize_h_uses_lds(max_span, bpp);
     const size_t stride = resize_mid_stride(dw, bpp);
     const dim3 grid((dw + 63) / 64, rows_grid(sh, 4)), block(64, 4);
 #define PIXO_RZ_H(B) hipLaunchKernelGGL((resize_lanczos_h_kernel<B>), grid, block, 0, stream, d_src, sw, sh, d_mid, stride, dw, t, use_lds)
@@ -242,6 +299,59 @@ hipError_t launch_resize_lanczos_v(const uint8_t *d_mid, uint32_t sh, uint8_t *d
     const size_t row_bytes = static_cast<size_t>(dw) * bpp;
     const dim3 grid(static_cast<unsigned>((row_bytes + 1023) / 1024), rows_grid(dh, 1)), block(256);
     hipLaunchKernelGGL(resize_lanczos_v_kernel, grid, block, 0, stream, d_mid, resize_mid_stride(dw, bpp), d_dst, row_bytes, dh, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_point_batch(const ResizeBatchItem *d_items, uint32_t n, uint8_t *d_dst, uint32_t dw, uint32_t dh, uint32_t bpp,
+                                     int algorithm, hipStream_t stream)
+{
+    if (bpp < 1 || bpp > 4 || n < 1 || n > 65535 || (algorithm != RZ_NEAREST && algorithm != RZ_BILINEAR)) return hipErrorInvalidValue;
+    const dim3 grid((dw + 255) / 256, rows_grid(dh, 4), n), block(64, 4);
+#define PIXO_RZ_POINT(B, A) hipLaunchKernelGGL((resize_point_batch_kernel<B, A>), grid, block, 0, stream, d_items, d_dst, dw, dh)
+    if (algorithm == RZ_NEAREST) {
+        switch (bpp) {
+        case 1: PIXO_RZ_POINT(1, RZ_NEAREST); break;
+        case 2: PIXO_RZ_POINT(2, RZ_NEAREST); break;
+        case 3: PIXO_RZ_POINT(3, RZ_NEAREST); break;
+        default: PIXO_RZ_POINT(4, RZ_NEAREST); break;
+        }
+    } else {
+        switch (bpp) {
+        case 1: PIXO_RZ_POINT(1, RZ_BILINEAR); break;
+        case 2: PIXO_RZ_POINT(2, RZ_BILINEAR); break;
+        case 3: PIXO_RZ_POINT(3, RZ_BILINEAR); break;
+        default: PIXO_RZ_POINT(4, RZ_BILINEAR); break;
+        }
+    }
+#undef PIXO_RZ_POINT
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_lanczos_h_batch(const ResizeBatchItem *d_items, uint32_t n, uint32_t max_sh, const uint8_t *d_tables, uint8_t *d_mid,
+                                         uint32_t dw, uint32_t bpp, hipStream_t stream)
+{
+    if (bpp < 1 || bpp > 4 || n < 1 || n > 65535) return hipErrorInvalidValue;
+    const size_t stride = resize_mid_stride(dw, bpp);
+    const dim3 grid((dw + 63) / 64, rows_grid(max_sh, 4), n), block(64, 4);
+#define PIXO_RZ_H(B) hipLaunchKernelGGL((resize_lanczos_h_batch_kernel<B>), grid, block, 0, stream, d_items, d_tables, d_mid, stride, dw)
+    switch (bpp) {
+    case 1: PIXO_RZ_H(1); break;
+    case 2: PIXO_RZ_H(2); break;
+    case 3: PIXO_RZ_H(3); break;
+    default: PIXO_RZ_H(4); break;
+    }
+#undef PIXO_RZ_H
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_lanczos_v_batch(const ResizeBatchItem *d_items, uint32_t n, const uint8_t *d_tables, const uint8_t *d_mid, uint8_t *d_dst,
+                                         uint32_t dw, uint32_t dh, uint32_t bpp, hipStream_t stream)
+{
+    if (n < 1 || n > 65535) return hipErrorInvalidValue;
+    const size_t row_bytes = static_cast<size_t>(dw) * bpp;
+    const dim3 grid(static_cast<unsigned>((row_bytes + 1023) / 1024), rows_grid(dh, 1), n), block(256);
+    hipLaunchKernelGGL(resize_lanczos_v_batch_kernel, grid, block, 0, stream, d_items, d_tables, d_mid, resize_mid_stride(dw, bpp), d_dst, row_bytes,
+                       dh);
     return hipGetLastError();
 }
 

@@ -30,5 +30,30 @@ hipError_t launch_resize_lanczos_h(const uint8_t *d_src, uint32_t sw, uint32_t s
 // ... vertical pass: d_mid -> d_dst [dh][dw][bpp]
 hipError_t launch_resize_lanczos_v(const uint8_t *d_mid, uint32_t sh, uint8_t *d_dst, uint32_t dw, uint32_t dh, uint32_t bpp,
                                    ResizeAxisTable t, hipStream_t stream);
+// The horizontal kernel's LDS segment per source row, and whether a tile of `max_span` source pixels is staged in it: the
+// staged segment keeps the source's alignment (up to 3 bytes in front) and is stored in whole dwords
+constexpr uint32_t kResizeSegBytes = 8192;
+inline bool resize_h_uses_lds(uint32_t max_span, uint32_t bpp) { return static_cast<size_t>(max_span) * bpp + 8 <= size_t{kResizeSegBytes}; }
+
+// ---- batches: n sources of individual sizes -> n images of one destination size, back to back at d_dst ---------------------
+// What a workgroup of a batch kernel reads about its image (blockIdx.z).  The tables of all axes lie in one block: an axis
+// with destination size n at byte offset `at` (a multiple of 16) is start[n], off[n + 1], w[...] as in ResizeAxisTable.
+struct ResizeBatchItem {
+    const uint8_t *src;  // [sh][sw][bpp]
+    uint64_t mid_at;     // Lanczos3: where the image's sh rows of the intermediate start (bytes, a multiple of 16)
+    uint64_t h_at, v_at; // ... its horizontal (sw -> dw) and vertical (sh -> dh) axis in the block of tables
+    uint32_t sw, sh;
+    uint32_t use_lds;    // ... the horizontal pass stages this image's tiles in LDS
+    uint32_t reserved;
+};
+static_assert(sizeof(ResizeBatchItem) == 48, "uploaded as it is");
+// grid.z = n <= 65535 images; d_items and d_tables are device memory.  Image i is written at d_dst + i * dw * dh * bpp.
+hipError_t launch_resize_point_batch(const ResizeBatchItem *d_items, uint32_t n, uint8_t *d_dst, uint32_t dw, uint32_t dh, uint32_t bpp,
+                                     int algorithm, hipStream_t stream);
+// max_sh: the tallest source among the n (sizes grid.y; workgroups beyond a shorter image's rows leave at once)
+hipError_t launch_resize_lanczos_h_batch(const ResizeBatchItem *d_items, uint32_t n, uint32_t max_sh, const uint8_t *d_tables, uint8_t *d_mid,
+                                         uint32_t dw, uint32_t bpp, hipStream_t stream);
+hipError_t launch_resize_lanczos_v_batch(const ResizeBatchItem *d_items, uint32_t n, const uint8_t *d_tables, const uint8_t *d_mid, uint8_t *d_dst,
+                                         uint32_t dw, uint32_t dh, uint32_t bpp, hipStream_t stream);
 
 } // namespace pixo_dev

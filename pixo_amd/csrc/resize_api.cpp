@@ -1,11 +1,13 @@
 // resize_api.cpp — the extern "C" resize entry points (pixo::resize, reference src/resize.rs): argument checks in the
 // reference's order, the Lanczos3 contribution tables (built on the host once per call from resize_math.h, uploaded through
-// the context's pinned staging), the launches of resize.hip.
+// the context's pinned staging), the launches of resize.hip.  The batch entries: the plan (tables shared between images of
+// one size, sub-batches that bound the intermediate), one upload of tables and items, one launch per pass and sub-batch.
 #include "capi_internal.hpp"
 #include "resize.hpp"
 #include "resize_math.h"
 
 #include <algorithm>
+#include <map>
 #include <vector>
 
 using namespace pixo_capi;
@@ -36,15 +38,29 @@ int resize_plan(const pixo_resize_options *o, bool device, size_t data_len, size
 }
 
 // ---- contribution tables ----------------------------------------------------------------------------------------------------
-size_t axis_weights(uint32_t src, uint32_t dst)
+// The number of weights of an axis and what fill_axis will return for it, without computing a weight (the batch plan: whether
+// a tile fits the LDS segment)
+void axis_measure(uint32_t src, uint32_t dst, size_t *total, uint32_t *max_span)
 {
     const rz_axis a = rz_axis_of(src, dst);
-    size_t total = 0;
+    uint32_t span = 0, tile_lo = 0;
+    size_t at = 0;
     for (uint32_t d = 0; d < dst; ++d) {
         uint32_t s, e;
         rz_taps(a, src, d, &s, &e);
-        total += e > s ? e - s : 0;
+        if (e < s) e = s;
+        at += e - s;
+        if (d % pixo_dev::kResizeHTile == 0) tile_lo = s;
+        span = std::max(span, e - tile_lo);
     }
+    *total = at;
+    *max_span = span;
+}
+size_t axis_weights(uint32_t src, uint32_t dst)
+{
+    size_t total = 0;
+    uint32_t span = 0;
+    axis_measure(src, dst, &total, &span);
     return total;
 }
 // One axis as the kernels read it: start[dst], off[dst + 1] (u32), w[total] (f32); `total` from axis_weights
@@ -140,9 +156,232 @@ int resize_host(const uint8_t *data, size_t in_bytes, const pixo_resize_options 
     return PIXO_OK;
 }
 
+// ---- batches: n sources of individual sizes -> n images of one destination size --------------------------------------------
+constexpr uint64_t kResizeBatchMidBytes = uint64_t{256} << 20; // Lanczos3 intermediate one sub-batch holds at most (debug switch resize_batch_bytes)
+constexpr size_t kResizeBatchTableThreads = 8;                 // host threads that build a call's axis tables, at most ...
+constexpr size_t kResizeBatchTableShare = size_t{128} << 10;   // ... one per this many bytes of tables (small batches: the calling thread alone)
+
+// What the driver decided for a batch, before anything touches a device (also: pixo_hip_debug_resize_batch_plan).
+struct BatchAxis {
+    uint32_t src, dst;
+    uint32_t max_span; // of a horizontal axis: the widest source span of one tile
+    size_t at, bytes;  // its table in the block of tables
+};
+struct BatchPlan {
+    std::vector<uint32_t> sub_first;      // sub-batch k is images [sub_first[k], sub_first[k + 1])
+    std::vector<uint64_t> mid_at;         // per image: its rows' offset in the intermediate of its sub-batch
+    std::vector<uint8_t> use_lds;         // per image: the horizontal pass stages in LDS
+    std::vector<uint32_t> h_axis, v_axis; // per image: its axes in `axes`
+    std::vector<BatchAxis> axes;          // one per distinct source width and per distinct source height (the destination is the batch's)
+    size_t table_bytes = 0;               // all tables, each 16-byte aligned
+    uint64_t mid_bytes = 0;               // the largest sub-batch's intermediate
+};
+
+// The sources have passed resize_plan's checks.  No HIP in here.
+int resize_batch_plan(const pixo_resize_source *src, uint32_t batch, uint32_t dw, uint32_t dh, uint32_t bpp, uint8_t algorithm, BatchPlan &p)
+{
+    p.mid_at.assign(batch, 0);
+    p.use_lds.assign(batch, 0);
+    p.sub_first.assign(1, 0u);
+    if (algorithm != PIXO_RESIZE_LANCZOS3) { // no tables, no intermediate: never cut
+        p.sub_first.push_back(batch);
+        return PIXO_OK;
+    }
+    p.h_axis.assign(batch, 0);
+    p.v_axis.assign(batch, 0);
+    // one table per distinct (src, dst) pair per axis
+    std::map<uint32_t, uint32_t> h_of, v_of;
+    const auto axis_of = [&](std::map<uint32_t, uint32_t> &seen, uint32_t s, uint32_t d, uint32_t *index) -> int {
+        const auto found = seen.find(s);
+        if (found != seen.end()) { *index = found->second; return PIXO_OK; }
+        size_t total = 0;
+        uint32_t span = 0;
+        axis_measure(s, d, &total, &span);
+        if (total > 0xFFFFFFFFull) return fail(PIXO_ERR_COMPRESSION, "Compression error: contribution table too large");
+        BatchAxis a{s, d, span, p.table_bytes, axis_table_bytes(d, total)};
+        p.table_bytes += a.bytes;
+        *index = seen[s] = static_cast<uint32_t>(p.axes.size());
+        p.axes.push_back(a);
+        return PIXO_OK;
+    };
+    const uint64_t limit = debug().resize_batch_bytes ? debug().resize_batch_bytes : kResizeBatchMidBytes;
+    const uint64_t stride = pixo_dev::resize_mid_stride(dw, bpp);
+    uint64_t held = 0; // the current sub-batch's intermediate so far
+    for (uint32_t i = 0; i < batch; ++i) {
+        int rc;
+        if ((rc = axis_of(h_of, src[i].width, dw, &p.h_axis[i])) || (rc = axis_of(v_of, src[i].height, dh, &p.v_axis[i]))) return rc;
+        p.use_lds[i] = pixo_dev::resize_h_uses_lds(p.axes[p.h_axis[i]].max_span, bpp);
+        const uint64_t rows = stride * src[i].height; // (at most 2^26 * 2^24)
+        if (i > p.sub_first.back() && held + rows > limit) { // every sub-batch holds at least one image
+            p.sub_first.push_back(i);
+            held = 0;
+        }
+        p.mid_at[i] = held;
+        held += rows;
+        p.mid_bytes = std::max(p.mid_bytes, held);
+    }
+    p.sub_first.push_back(batch);
+    return PIXO_OK;
+}
+
+// The checks of the batch entries up to the sources' own (the entries' pointers come behind them): sources, batch, then
+// resize_plan's on (source i, destination) for i = 0, 1, ... with the single entry's status and its message + " (image i)".
+int resize_batch_checks(const pixo_resize_source *sources, uint32_t batch, uint32_t dw, uint32_t dh, uint8_t color_type, uint8_t algorithm,
+                        size_t *out_bytes)
+{
+    PIXO_REQUIRE(sources);
+    int rc = batch_in_range(batch);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < batch; ++i) {
+        pixo_resize_options o;
+        o.src_width = sources[i].width; o.src_height = sources[i].height;
+        o.dst_width = dw; o.dst_height = dh;
+        o.color_type = color_type; o.algorithm = algorithm;
+        size_t in_bytes = 0;
+        if ((rc = resize_plan(&o, true, 0, &in_bytes, out_bytes))) return fail(rc, t_error + " (image " + std::to_string(i) + ")");
+    }
+    if (*out_bytes > (size_t{1} << 62) / batch) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large");
+    return PIXO_OK;
+}
+int resize_batch_pixels_given(const pixo_resize_source *sources, uint32_t batch)
+{
+    for (uint32_t i = 0; i < batch; ++i)
+        if (!sources[i].pixels) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'pixels' (image " + std::to_string(i) + ")");
+    return PIXO_OK;
+}
+
+// Enqueues one batch on `s`: sources[i].pixels (device pointers) -> d_dst + i * out_bytes.  The tables and the items go up in one
+// copy; the sub-batches follow each other on `s`, so the intermediate is reused in stream order.
+int resize_batch_on_device(Context &c, const pixo_resize_source *sources, uint32_t batch, uint32_t dw, uint32_t dh, uint8_t color_type,
+                           uint8_t algorithm, uint8_t *d_dst, hipStream_t s)
+{
+    const uint32_t bpp = bytes_per_pixel(color_type);
+    const size_t out_bytes = static_cast<size_t>(dw) * dh * bpp;
+    BatchPlan p;
+    int rc = resize_batch_plan(sources, batch, dw, dh, bpp, algorithm, p);
+    if (rc) return rc;
+    const bool lanczos = algorithm == PIXO_RESIZE_LANCZOS3;
+    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
+    note_route((lanczos ? route::RESIZE_LANCZOS3 : algorithm == PIXO_RESIZE_NEAREST ? route::RESIZE_NEAREST : route::RESIZE_BILINEAR) |
+               route::RESIZE_BATCH | (subs > 1 ? route::SUB_BATCHES : 0));
+    if (!c.rb_done) HIP_TRY(hipEventCreateWithFlags(&c.rb_done, hipEventDisableTiming));
+    // the batch before may still be reading the tables and the items, and the staging may still be on its way: all of them are
+    // about to change.  The call's only host wait.
+    HIP_TRY(hipEventSynchronize(c.rb_done));
+    // everything is reserved before any address is handed out (a growing reserve frees first: a device-wide wait)
+    const size_t up_bytes = p.table_bytes + static_cast<size_t>(batch) * sizeof(pixo_dev::ResizeBatchItem);
+    if ((rc = c.rb_stage.reserve(up_bytes)) || (rc = c.rb_tables.reserve(up_bytes)) || (rc = c.rb_mid.reserve(p.mid_bytes))) return rc;
+    uint8_t *stage = c.rb_stage.as<uint8_t>();
+    // the weights are host work (a sine in f64 each) and the axes are independent: a ragged batch, with up to two tables per
+    // image, builds them on several threads (64 x 1080p -> 320x180 of individual sizes: 7.4 ms on one)
+    const unsigned builders = static_cast<unsigned>(std::min<size_t>({kResizeBatchTableThreads, p.axes.size(), p.table_bytes / kResizeBatchTableShare + 1}));
+    run_on_threads(builders, [&](unsigned k) {
+        for (size_t a = k; a < p.axes.size(); a += std::max(builders, 1u)) (void)fill_axis(p.axes[a].src, p.axes[a].dst, stage + p.axes[a].at);
+    });
+    pixo_dev::ResizeBatchItem *items = reinterpret_cast<pixo_dev::ResizeBatchItem *>(stage + p.table_bytes); // (table_bytes is a multiple of 16)
+    for (uint32_t i = 0; i < batch; ++i) {
+        pixo_dev::ResizeBatchItem &it = items[i];
+        it.src = static_cast<const uint8_t *>(sources[i].pixels);
+        it.mid_at = p.mid_at[i];
+        it.h_at = lanczos ? p.axes[p.h_axis[i]].at : 0;
+        it.v_at = lanczos ? p.axes[p.v_axis[i]].at : 0;
+        it.sw = sources[i].width; it.sh = sources[i].height;
+        it.use_lds = p.use_lds[i];
+        it.reserved = 0;
+    }
+    HIP_TRY(hipMemcpyAsync(c.rb_tables.p, stage, up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c.rb_done, s)); // (until the job's own record: the upload)
+    const uint8_t *d_tables = c.rb_tables.as<uint8_t>();
+    const pixo_dev::ResizeBatchItem *d_items = reinterpret_cast<const pixo_dev::ResizeBatchItem *>(d_tables + p.table_bytes);
+    for (uint32_t k = 0; k < subs; ++k) {
+        const uint32_t first = p.sub_first[k], n = p.sub_first[k + 1] - first;
+        uint8_t *out = d_dst + static_cast<size_t>(first) * out_bytes;
+        if (!lanczos) {
+            HIP_TRY(pixo_dev::launch_resize_point_batch(d_items + first, n, out, dw, dh, bpp, algorithm, s));
+            continue;
+        }
+        uint32_t max_sh = 0;
+        for (uint32_t i = first; i < first + n; ++i) max_sh = std::max(max_sh, sources[i].height);
+        HIP_TRY(pixo_dev::launch_resize_lanczos_h_batch(d_items + first, n, max_sh, d_tables, c.rb_mid.as<uint8_t>(), dw, bpp, s));
+        HIP_TRY(pixo_dev::launch_resize_lanczos_v_batch(d_items + first, n, d_tables, c.rb_mid.as<uint8_t>(), out, dw, dh, bpp, s));
+    }
+    HIP_TRY(hipEventRecord(c.rb_done, s));
+    return PIXO_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int pixo_hip_resize_batch_device(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height, uint8_t color_type,
+                                 uint8_t algorithm, void *d_dst, void *stream)
+{
+    size_t out_bytes = 0;
+    int rc = resize_batch_checks(sources, batch, dst_width, dst_height, color_type, algorithm, &out_bytes);
+    if (rc || (rc = resize_batch_pixels_given(sources, batch))) return rc;
+    PIXO_REQUIRE(d_dst);
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    return resize_batch_on_device(*c, sources, batch, dst_width, dst_height, color_type, algorithm, static_cast<uint8_t *>(d_dst), s);
+}
+
+int pixo_hip_resize_batch(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height, uint8_t color_type,
+                          uint8_t algorithm, uint8_t **out, size_t *out_len)
+{
+    size_t out_bytes = 0;
+    int rc = resize_batch_checks(sources, batch, dst_width, dst_height, color_type, algorithm, &out_bytes);
+    if (rc || (rc = resize_batch_pixels_given(sources, batch))) return rc;
+    PIXO_REQUIRE(out);
+    PIXO_REQUIRE(out_len);
+    const size_t bpp = bytes_per_pixel(color_type), all_out = out_bytes * batch;
+    std::vector<pixo_resize_source> on_device(sources, sources + batch);
+    std::vector<size_t> at(batch + 1, 0); // every source starts at a multiple of 16 in rb_in
+    for (uint32_t i = 0; i < batch; ++i) at[i + 1] = at[i] + ((static_cast<size_t>(sources[i].width) * sources[i].height * bpp + 15) & ~size_t{15});
+    PIXO_THREAD_CONTEXT(c);
+    if ((rc = c.rb_in.reserve(at[batch])) || (rc = reserve16(c.rb_out, all_out))) return rc;
+    for (uint32_t i = 0; i < batch; ++i) {
+        on_device[i].pixels = c.rb_in.as<uint8_t>() + at[i];
+        HIP_TRY(hipMemcpyAsync(c.rb_in.as<uint8_t>() + at[i], sources[i].pixels, static_cast<size_t>(sources[i].width) * sources[i].height * bpp,
+                               hipMemcpyHostToDevice, c.stream));
+    }
+    uint8_t *block = alloc_file(all_out);
+    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    rc = resize_batch_on_device(c, on_device.data(), batch, dst_width, dst_height, color_type, algorithm, c.rb_out.as<uint8_t>(), c.stream);
+    if (!rc) {
+        const hipError_t e = hipMemcpyAsync(block, c.rb_out.p, all_out, hipMemcpyDeviceToHost, c.stream);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    }
+    const hipError_t e = hipStreamSynchronize(c.stream); // (also after a failure: the uploads read the caller's pixels)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (rc) { free_file(block); return rc; }
+    *out = block;
+    *out_len = all_out;
+    return PIXO_OK;
+}
+
+int pixo_hip_debug_resize_batch_plan(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height, uint8_t color_type,
+                                     uint8_t algorithm, uint32_t *sub_first, uint32_t *sub_count, uint64_t *mid_at, uint8_t *use_lds,
+                                     uint32_t *axis_tables)
+{
+    size_t out_bytes = 0;
+    int rc = resize_batch_checks(sources, batch, dst_width, dst_height, color_type, algorithm, &out_bytes);
+    if (rc) return rc;
+    PIXO_REQUIRE(sub_first);
+    PIXO_REQUIRE(sub_count);
+    PIXO_REQUIRE(mid_at);
+    PIXO_REQUIRE(use_lds);
+    PIXO_REQUIRE(axis_tables);
+    BatchPlan p;
+    if ((rc = resize_batch_plan(sources, batch, dst_width, dst_height, bytes_per_pixel(color_type), algorithm, p))) return rc;
+    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
+    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    std::copy(p.mid_at.begin(), p.mid_at.end(), mid_at);
+    std::copy(p.use_lds.begin(), p.use_lds.end(), use_lds);
+    *axis_tables = static_cast<uint32_t>(p.axes.size());
+    return PIXO_OK;
+}
 
 int pixo_hip_resize_into(uint8_t *output, size_t capacity, const uint8_t *data, size_t data_len, const pixo_resize_options *options,
                          size_t *out_len)

@@ -13,8 +13,8 @@ from .color import ColorType
 MAX_DIMENSION = 1 << 24
 
 # this module's bits of the route record (pixo_hip_debug_routes; pixo_amd/csrc/routes.hpp)
-ROUTES = {"RESIZE_NEAREST": 36, "RESIZE_BILINEAR": 37, "RESIZE_LANCZOS3": 38}
-ROUTE_RESIZE_NEAREST, ROUTE_RESIZE_BILINEAR, ROUTE_RESIZE_LANCZOS3 = (1 << b for b in ROUTES.values())
+ROUTES = {"RESIZE_NEAREST": 36, "RESIZE_BILINEAR": 37, "RESIZE_LANCZOS3": 38, "RESIZE_BATCH": 41}
+ROUTE_RESIZE_NEAREST, ROUTE_RESIZE_BILINEAR, ROUTE_RESIZE_LANCZOS3, ROUTE_RESIZE_BATCH = (1 << b for b in ROUTES.values())
 
 
 class ResizeAlgorithm(enum.IntEnum):
@@ -103,6 +103,70 @@ def resize_device(d_src, options: ResizeOptions, d_dst, stream=0) -> None:
     o = options._c()
     rc = L.pixo_hip_resize_device(_lib.ptr(d_src), C.byref(o), _lib.ptr(d_dst), C.c_void_p(stream) if stream else None)
     _lib.check(rc)
+
+
+def _bpp(color_type) -> int:
+    """Bytes per pixel; 0 for a code that is no colour type (the library refuses it with its own message: no size to check)"""
+    return int(color_type) + 1 if 0 <= int(color_type) <= 3 else 0
+
+
+def _sources_c(sources, bpp, address):
+    """(pixels, width, height) triples as the C array; whatever carries a size (tensor, array) must hold width * height * bpp bytes
+    (the C entries take no length)."""
+    arr = (_lib.ResizeSourceC * max(len(sources), 1))()
+    for i, (px, w, h) in enumerate(sources):
+        if bpp and (hasattr(px, "numel") or hasattr(px, "nbytes")):
+            need, have = w * h * bpp, _lib.nbytes(px)
+            if have != need:
+                raise ValueError("source %d of %dx%d needs %d bytes of pixels, it holds %d" % (i, w, h, need, have))
+        arr[i] = _lib.ResizeSourceC(address(px), w, h)
+    return arr
+
+
+def resize_batch_device(sources, dst_width, dst_height, color_type, algorithm, d_dst, stream=0) -> None:
+    """`sources`: a list of (tensor_or_pointer, width, height) in HBM, each of its own size -> len(sources) images of
+    dst_width x dst_height back to back at d_dst, image i byte for byte what `resize_device` writes for source i: the layout
+    `jpeg.encode_batch_device` and `png.encode_batch_device` read.  One launch per pass whatever the number of images.
+    Enqueue only, ordered like `resize_device`."""
+    L = _lib.load()
+    bpp = _bpp(color_type)
+    arr = _sources_c(sources, bpp, _lib.ptr)
+    if bpp and hasattr(d_dst, "numel"):
+        need, have = len(sources) * dst_width * dst_height * bpp, _lib.nbytes(d_dst)
+        if have != need:
+            raise ValueError("a batch of %d images of %dx%d needs %d bytes of output, the tensor holds %d" % (len(sources), dst_width, dst_height, need, have))
+    rc = L.pixo_hip_resize_batch_device(arr, len(sources), dst_width, dst_height, int(color_type), int(algorithm), _lib.ptr(d_dst),
+                                        C.c_void_p(stream) if stream else None)
+    _lib.check(rc)
+
+
+def resize_batch(sources, dst_width, dst_height, color_type, algorithm) -> list:
+    """Host pixels: a list of (pixels, width, height) -> a list of bytes, image i what `resize` makes of source i."""
+    L = _lib.load()
+    bpp = _bpp(color_type)
+    held = [(_flat(px), w, h) for px, w, h in sources]
+    arr = _sources_c(held, bpp, _lib.address)
+    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    rc = L.pixo_hip_resize_batch(arr, len(held), dst_width, dst_height, int(color_type), int(algorithm), C.byref(out), C.byref(n))
+    _lib.check(rc)
+    block, each = _lib.take(L, out, n), dst_width * dst_height * bpp
+    return [block[i * each:(i + 1) * each] for i in range(len(held))]
+
+
+def resize_batch_plan(sizes, dst_width, dst_height, color_type, algorithm) -> dict:
+    """What the batch entries decide for sources of these (width, height), computed on the host (no GPU): `sub_first` (where
+    each sub-batch starts, and the batch's end), `mid_at` (each image's offset in its sub-batch's Lanczos3 intermediate),
+    `use_lds` (its horizontal pass stages in LDS) and `axis_tables` (distinct axis tables built)."""
+    L = _lib.load()
+    n = len(sizes)
+    arr = (_lib.ResizeSourceC * max(n, 1))(*[_lib.ResizeSourceC(None, w, h) for w, h in sizes])
+    sub_first, mid_at, use_lds = (C.c_uint32 * (n + 1))(), (C.c_uint64 * max(n, 1))(), (C.c_uint8 * max(n, 1))()
+    subs, tables = C.c_uint32(), C.c_uint32()
+    rc = L.pixo_hip_debug_resize_batch_plan(arr, n, dst_width, dst_height, int(color_type), int(algorithm), sub_first, C.byref(subs),
+                                            mid_at, use_lds, C.byref(tables))
+    _lib.check(rc)
+    return dict(sub_first=list(sub_first[:subs.value + 1]), mid_at=list(mid_at[:n]), use_lds=[bool(v) for v in use_lds[:n]],
+                axis_tables=tables.value)
 
 
 def resize_image(data, src_width, src_height, dst_width, dst_height, color_type: int, algorithm: int) -> bytes:
