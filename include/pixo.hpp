@@ -19,6 +19,7 @@
 //   pixo::resize::resize / resize_into resize.rs:165    pixo::resize::resize / resize_into
 //   (wasm) resizeImage                 wasm.rs:183      pixo::resize_image
 //   (a loop over pixo::resize::resize)                  pixo::resize::resize_batch / resize_batch_device
+//   (a loop over pixo::decode::decode_png)              pixo::decode::decode_png_batch
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -437,6 +438,27 @@ struct PngImage {
     return im;
 }
 [[nodiscard]] inline PngImage decode_png(const std::vector<uint8_t> &data) { return decode_png(data.data(), data.size()); }
+// Batches: N files -> N images, image i what decode_png makes of file i (contract: pixo_hip.h).  one_thread: the inflates
+// run on the calling thread instead of the library's small pool
+[[nodiscard]] inline std::vector<PngImage> decode_png_batch(const std::vector<pixo_png_file> &files, bool one_thread = false)
+{
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    std::vector<pixo_png_image> images(files.size() ? files.size() : 1);
+    const int rc = pixo_hip_png_decode_batch(files.data(), (uint32_t)files.size(), one_thread ? PIXO_DECODE_ONE_THREAD : 0u, &block, &n, images.data());
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    struct Block { // (released also when a copy below throws)
+        uint8_t *p;
+        ~Block() { pixo_hip_free(p); }
+    } held{block};
+    std::vector<PngImage> out(files.size());
+    for (size_t i = 0; i < files.size(); ++i) {
+        const pixo_png_image &im = images[i];
+        out[i].width = im.width; out[i].height = im.height; out[i].color_type = static_cast<ColorType>(im.color_type);
+        out[i].pixels.assign(block + im.offset, block + im.offset + (size_t)im.width * im.height * (im.color_type + 1u));
+    }
+    return out;
+}
 } // namespace decode
 
 // The reference's flat wasm export `resizeImage` (src/wasm.rs:183-201), same seven arguments.

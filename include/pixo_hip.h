@@ -653,6 +653,59 @@ uint32_t pixo_hip_png_unfilter_pass_rows(void);
  * [2] workgroups launched.  The pixels are released again. */
 int pixo_hip_debug_png_decode_timed(const uint8_t *file, size_t len, double ms[7], uint64_t counts[3]);
 
+/* ---- PNG decode batches: N files -> N images back to back in DEVICE memory, one launch per pass ---- */
+
+/* One file of a batch, in host memory. */
+typedef struct pixo_png_file {
+    const uint8_t *data;
+    size_t len;
+} pixo_png_file; /* 16 bytes */
+/* One image of the block a batch decodes into: width * height * bytes-per-pixel bytes at `offset`, of the colour type
+ * pixo_hip_png_decode reports for that file (no image is converted to another's).  offset[0] = 0, offset[i + 1] = offset[i] +
+ * image i's bytes rounded up to 16; the bytes between two images are never written.  `reserved` is written as zeros.  An array of
+ * pixo_resize_source can point straight at d_pixels + offset. */
+typedef struct pixo_png_image {
+    uint64_t offset;
+    uint32_t width, height;
+    uint8_t color_type;
+    uint8_t reserved[7];
+} pixo_png_image; /* 24 bytes */
+#define PIXO_DECODE_ONE_THREAD 1u /* flags bit 0: the inflates run on the calling thread (for callers that run a pool of their own) */
+
+/* The layout alone: `images` (batch entries) and *total (the end of the last image, not rounded) from the walks of the files — no
+ * inflate, no GPU.  What a caller of pixo_hip_png_decode_batch_device allocates from. */
+int pixo_hip_png_decode_batch_info(const pixo_png_file *files, uint32_t batch, pixo_png_image *images, size_t *total);
+/* `batch` (1..65535) files -> their pixels at d_pixels + images[i].offset, image i byte for byte what pixo_hip_png_decode returns
+ * for file i.  The streams are inflated on up to 8 host threads (the caller among them, never more than files) into one pinned
+ * staging buffer and go up in one copy, all tables in a second; then one reconstruction launch per distinct filter unit (at most
+ * 6) and one conversion launch per kernel form (at most 3), whatever `batch` is.  Batches whose device staging (inflated streams
+ * + reconstructed rows) exceeds 512 MiB run as sub-batches, one behind the other on `stream`.  Enqueue only, ordered like
+ * pixo_hip_png_decode_device; the one host wait is for the calling thread's previous decode job.  d_pixels may have any alignment.
+ * Checks, all before anything is enqueued.  Phase 1, no GPU and no inflate: `files`; batch (PIXO_ERR_COMPRESSION, "batch must be
+ * 1..65535"); the trailing out-pointers; then for i = 0, 1, ... files[i].data and the walk of file i — the first failure returns
+ * that file's status and its message with " (image i)" appended, `images` untouched; a block of pixels beyond 2^62 bytes
+ * (PIXO_ERR_COMPRESSION); then `images` is filled; capacity below the total: PIXO_ERR_BUFFER_TOO_SMALL with the total in the
+ * message; then d_pixels.  Phase 2, what only the inflated streams show (whatever inflate raises, Adler-32, size, a filter byte
+ * above 4, a palette file without PLTE): every file is inflated, the failing file with the lowest index decides, " (image i)"
+ * appended, whatever the thread count. */
+int pixo_hip_png_decode_batch_device(const pixo_png_file *files, uint32_t batch, uint32_t flags, void *d_pixels, size_t capacity,
+                                     pixo_png_image *images, void *stream);
+/* The same with the block in HOST memory: *out receives *out_len = total bytes laid out as `images` says (the gaps hold
+ * nothing of meaning), released with pixo_hip_free.  Returns when the block is complete. */
+int pixo_hip_png_decode_batch(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len,
+                              pixo_png_image *images);
+/* Tests: what the batch entries decide, computed on the HOST (phase 1, the inflates into ordinary memory, the plan), no GPU
+ * needed; refusals as the decode entries', phase 2 included.  Sub-batch k is images sub_first[k] .. sub_first[k + 1] (room for
+ * batch + 1 entries, *sub_count + 1 are written); runs_per_image[i]: workgroups that reconstruct image i; the launch counts are
+ * summed over the sub-batches (conversion forms as for a 16-byte aligned d_pixels); *threads: host threads that inflated. */
+int pixo_hip_debug_png_decode_batch_plan(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint32_t *sub_first,
+                                         uint32_t *sub_count, uint64_t *runs_per_image, uint32_t *unfilter_launches,
+                                         uint32_t *convert_launches, uint32_t *threads);
+/* MEASUREMENT only (tools/png_decode_batch_timing.py): pixo_hip_png_decode_batch with its legs timed — ms[0] the inflates and
+ * the runs of rows (host clock), [1] uploads, [2] reconstruction launches, [3] conversion launches (HIP events, summed over the
+ * sub-batches), [4] the whole call.  The block is released again. */
+int pixo_hip_debug_png_decode_batch_timed(const pixo_png_file *files, uint32_t batch, uint32_t flags, double ms[5]);
+
 /* ---- runtime ----------------------------------------------------------------------- */
 
 int pixo_hip_device_count(void);            /* 0 when no GPU / no driver              */

@@ -37,6 +37,16 @@ class ResizeSourceC(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class PngFileC(C.Structure):
+    """pixo_png_file (include/pixo_hip.h): one file of a decode batch"""
+    _fields_ = [("data", C.c_void_p), ("len", C.c_size_t)]
+
+
+class PngImageC(C.Structure):
+    """pixo_png_image (include/pixo_hip.h): one image of the block a decode batch writes"""
+    _fields_ = [("offset", C.c_uint64), ("width", C.c_uint32), ("height", C.c_uint32), ("color_type", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
 class PngOptionsC(C.Structure):
     """pixo_png_options (include/pixo_hip.h)"""
     _fields_ = [
@@ -71,6 +81,7 @@ _szp, _u8p, _u32p, _u64p, _i16p = C.POINTER(_sz), C.POINTER(_u8), C.POINTER(_u32
 _u8pp, _optp, _roptp = C.POINTER(_u8p), C.POINTER(JpegOptionsC), C.POINTER(ResizeOptionsC)
 _poptp, _playp, _qoptp = C.POINTER(PngOptionsC), C.POINTER(PngLayoutC), C.POINTER(PngQuantizationC)
 _rsrcp = C.POINTER(ResizeSourceC)
+_pfilep, _pimgp = C.POINTER(PngFileC), C.POINTER(PngImageC)
 _coeffs = (_vp, _u32, _u32, _u8, _u8, _u8, _vp, _sz, _vp, _vp, _sz)
 
 # every symbol include/pixo_hip.h declares: name -> (argtypes, restype, optional).  `load()` applies it; a new entry is declared
@@ -137,6 +148,11 @@ SIGNATURES = {
     "pixo_hip_zlib_inflate": _sig(_vp, _sz, _vp, _sz),
     "pixo_hip_png_unfilter_pass_rows": _sig(ret=_u32),
     "pixo_hip_debug_png_decode_timed": _sig(_vp, _sz, C.POINTER(_dbl), _u64p),
+    "pixo_hip_png_decode_batch_info": _sig(_pfilep, _u32, _pimgp, _szp, optional=True),
+    "pixo_hip_png_decode_batch_device": _sig(_pfilep, _u32, _u32, _vp, _sz, _pimgp, _vp, optional=True),
+    "pixo_hip_png_decode_batch": _sig(_pfilep, _u32, _u32, _u8pp, _szp, _pimgp, optional=True),
+    "pixo_hip_debug_png_decode_batch_plan": _sig(_pfilep, _u32, _u32, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p, optional=True),
+    "pixo_hip_debug_png_decode_batch_timed": _sig(_pfilep, _u32, _u32, C.POINTER(_dbl), optional=True),
     "pixo_hip_band": _sig(_u32, _u32, _u8, _u8, _u32, _u32, _u32p, _u32p, _szp, _szp, _szp, _szp),
     "pixo_hip_band_encoder_create": _sig(_optp, _u32, _u32, _int, C.POINTER(_vp)),
     "pixo_hip_band_encoder_destroy": _sig(_vp, ret=None),

@@ -18,7 +18,7 @@
 //   png_quantize_api.cpp  PNG lossy mode: gate, histogram and median cut on the host, the kernels of png_quantize.hip, the extern "C" quantize entries
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables; the resize batch entries: plan, sub-batches
 //   png_decode_api.cpp  the extern "C" PNG decode entry points: chunk walk and checks, the host inflate (png_inflate.cpp), the runs of rows,
-//                    the launches of png_unfilter.hip
+//                    the launches of png_unfilter.hip; the decode batch entries: two-phase checks, the inflate pool, plan, sub-batches
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -106,6 +106,8 @@ inline int bad_length(size_t expected, size_t got)
 //                      which bounds the scratch, stays)
 //   resize_batch_bytes=n  a sub-batch of pixo_hip_resize_batch* holds at most n bytes of Lanczos3 intermediate (and at least one
 //                      image) instead of 256 MiB: tests reach a sub-batch boundary with small images
+//   decode_batch_bytes=n  a sub-batch of pixo_hip_png_decode_batch* holds at most n bytes of device staging (inflated streams +
+//                      reconstructed rows; at least one image) instead of 512 MiB: tests reach a sub-batch boundary with small images
 //   no_bands_upload    host pixels are uploaded in one copy instead of MCU-row bands pipelined with the kernels
 //   plain_host         no host-memory policy (for embedders that own theirs): pixo_hip_free returns every block to malloc at once
 //                      (no blocks kept for the next large file), fresh blocks are plain malloc, no madvise(MADV_HUGEPAGE) on the
@@ -128,6 +130,7 @@ struct DebugSwitches {
     uint32_t batch_parts = 0; // (measurements) sub-batches of pixo_hip_jpeg_encode_batch_device_into, 0 = the library's choice
     uint64_t png_batch_bytes = 0; // bytes of prepared stream a sub-batch of the PNG batch entries holds at most, 0 = 64 MiB
     uint64_t resize_batch_bytes = 0; // bytes of Lanczos3 intermediate a sub-batch of the resize batch entries holds at most, 0 = 256 MiB
+    uint64_t decode_batch_bytes = 0; // bytes of device staging a sub-batch of the PNG decode batch entries holds at most, 0 = 512 MiB
 };
 const DebugSwitches &debug();
 
@@ -276,11 +279,11 @@ struct Context {
     Buf rb_stage{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here on the host, uploaded from here in one copy
     hipEvent_t rb_done = nullptr;                        // the last batch job (it reads rb_tables, writes rb_mid) has run
     // PNG decode (png_decode_api.cpp, png_unfilter.hip)
-    Buf u_inflated{Buf::Mem::Pinned, Buf::Grow::Exact};  // the inflated stream: the host inflate writes it, the upload reads it
+    Buf u_inflated{Buf::Mem::Pinned, Buf::Grow::Exact};  // the inflated stream (a batch: all its streams): the host inflate writes it, the upload reads it
     Buf u_stream{Buf::Mem::Device, Buf::Grow::Exact};    // ... on the device
     Buf u_rows{Buf::Mem::Device, Buf::Grow::Exact};      // the reconstructed rows, 16-byte pitched
     Buf u_out{Buf::Mem::Device, Buf::Grow::Exact};       // host entry: the pixels before they go down
-    Buf u_tables{Buf::Mem::Device, Buf::Grow::Exact};    // the palette table (256 words), behind it the runs of rows
+    Buf u_tables{Buf::Mem::Device, Buf::Grow::Exact};    // the palette table (256 words), behind it the runs of rows (a batch: descriptions, runs, block tables, palettes)
     Buf h_utables{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here, uploaded from here
     hipEvent_t u_done = nullptr;                         // the last decode job (it reads all of the above) has run
 

@@ -1,6 +1,8 @@
 // png_decode_api.cpp — the extern "C" PNG decode entry points (pixo::decode::decode_png, reference src/decode/png.rs:101-291):
 // the chunk walk and its checks in the reference's order and words, the host inflate (png_inflate.cpp) into pinned memory, the
-// runs of rows that do not read the row above, and the launches of png_unfilter.hip.
+// runs of rows that do not read the row above, and the launches of png_unfilter.hip.  The batch entries (N files -> N images
+// back to back in device memory): two phases of checks, the inflates on a small pool of host threads, the plan of sub-batches
+// and launches, one upload of streams and one of tables.
 //
 // The order in which a faulty file is refused: signature; per chunk in file order "truncated PNG chunk", its CRC-32, then its
 // own length / field checks; then missing IEND, missing IHDR, zero dimension, dimension above 2^24, compression method, filter
@@ -12,6 +14,7 @@
 #include "png_unfilter.hpp"
 
 #include <algorithm>
+#include <atomic>
 
 using namespace pixo_capi;
 using namespace pixo_pngu;
@@ -301,9 +304,387 @@ int decode_to_block(const uint8_t *file, size_t len, uint8_t **pixels, size_t *p
     return PIXO_OK;
 }
 
+// ---- batches: N files -> N images back to back in HBM, one launch per pass and sub-batch (DESIGN.md §4.6e "Batches") ---------
+constexpr uint64_t kDecodeBatchBytes = uint64_t{512} << 20; // device staging (streams + reconstructed rows) one sub-batch holds at most
+                                                            // (debug switch decode_batch_bytes)
+constexpr uint32_t kDecodeBatchThreads = 8;                 // host threads that inflate a batch, the caller among them, at most
+constexpr uint32_t kFilterUnits[6] = {1, 2, 3, 4, 6, 8};
+
+inline uint64_t round16(uint64_t n) { return (n + 15) & ~uint64_t{15}; }
+
+struct BatchFile {
+    PngFile f;
+    uint64_t row = 0, pitch = 0, expected = 0;
+    uint64_t in_at = 0; // where its stream starts in the batch's staging (a multiple of 16)
+    // phase 2, filled by whichever thread inflated the file
+    pixo_inflate::Kind kind = pixo_inflate::OK;
+    std::string msg;
+    Runs runs;
+};
+struct DecodeBatch {
+    std::vector<BatchFile> files;
+    std::vector<pixo_png_image> images;
+    uint64_t total = 0, staging = 0; // bytes of pixels (the end of the last image); bytes of all streams
+    uint32_t threads = 1;
+    double inflate_ms = 0;
+};
+
+// Phase 1 behind `files` and `batch`: per file its `data`, then the walk; the block's layout.  No HIP, no inflate.
+int batch_walk(const pixo_png_file *files, uint32_t batch, bool join, DecodeBatch &b)
+{
+    b.files.resize(batch);
+    b.images.resize(batch);
+    for (uint32_t i = 0; i < batch; ++i) {
+        const std::string where = " (image " + std::to_string(i) + ")";
+        if (!files[i].data) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'data'" + where);
+        const int rc = png_walk(files[i].data, files[i].len, join, b.files[i].f);
+        if (rc) return fail(rc, t_error + where);
+    }
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        BatchFile &x = b.files[i];
+        x.row = x.f.row_bytes();
+        x.pitch = pixo_dev::unfilter_pitch(x.row);
+        x.expected = static_cast<uint64_t>(x.f.height) * (x.row + 1);
+        x.in_at = b.staging;
+        b.staging += round16(x.expected);
+        const uint64_t end = at + x.f.pixel_bytes(); // (an image is at most 2^50 bytes: no wrap below the limit)
+        if (end > (uint64_t{1} << 62)) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large");
+        pixo_png_image &im = b.images[i];
+        std::memset(&im, 0, sizeof im);
+        im.offset = at; im.width = x.f.width; im.height = x.f.height; im.color_type = x.f.out_color_type();
+        b.total = end;
+        at = round16(end);
+    }
+    return PIXO_OK;
+}
+
+// Phase 2: every stream inflated to stage + in_at and cut into runs, on up to kDecodeBatchThreads threads which hand back
+// (kind, message) — fail() is the calling thread's; the failing file with the lowest index decides, whoever inflated it.
+int batch_inflate(DecodeBatch &b, uint8_t *stage, uint32_t flags)
+{
+    const uint32_t batch = static_cast<uint32_t>(b.files.size());
+    b.threads = (flags & PIXO_DECODE_ONE_THREAD) ? 1u : std::min(batch, kDecodeBatchThreads);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::atomic<uint32_t> next{0};
+    run_on_threads(b.threads, [&](unsigned) {
+        for (uint32_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < batch;) {
+            BatchFile &x = b.files[i];
+            x.kind = pixo_inflate::inflate_zlib(x.f.idat, x.f.idat_len, stage + x.in_at, x.expected, &x.msg);
+            if (x.kind != pixo_inflate::OK) continue;
+            uint32_t bad_row = 0;
+            x.runs = find_runs(stage + x.in_at, x.f.height, x.row, &bad_row);
+            if (bad_row < x.f.height) {
+                x.kind = pixo_inflate::INVALID;
+                x.msg = "invalid filter type: " + std::to_string(stage[x.in_at + static_cast<uint64_t>(bad_row) * (x.row + 1)]);
+            } else if (x.f.color_type == CT_INDEXED && !x.f.has_plte) {
+                x.kind = pixo_inflate::INVALID;
+                x.msg = "missing PLTE chunk";
+            }
+        }
+    });
+    b.inflate_ms = ms_since(t0);
+    for (uint32_t i = 0; i < batch; ++i)
+        if (const int rc = inflate_status(b.files[i].kind, b.files[i].msg)) return fail(rc, t_error + " (image " + std::to_string(i) + ")");
+    return PIXO_OK;
+}
+
+// What the driver decided, before anything touches a device (also: pixo_hip_debug_png_decode_batch_plan)
+struct DecodeBatchPlan {
+    std::vector<uint32_t> sub_first;        // sub-batch k is images [sub_first[k], sub_first[k + 1])
+    std::vector<uint64_t> rows_at;          // per image: its rows' offset in its sub-batch's rows buffer
+    std::vector<uint32_t> kernel;           // per image: the convert kernel form (pixo_dev::ConvertKernel)
+    uint64_t stream_bytes = 0, rows_bytes = 0; // the largest sub-batch's
+    struct Unfilter { uint32_t sub, unit; uint64_t first_run, n_runs; };
+    struct Convert { uint32_t sub, kernel; uint64_t first, n, max_items; };
+    std::vector<Unfilter> unfilter;         // the launches in stream order within their sub-batch ...
+    std::vector<Convert> convert;
+    std::vector<pixo_dev::UnfilterBatchRun> runs; // ... and the tables they read: runs by (sub-batch, filter unit),
+    std::vector<uint32_t> list;                   //     block tables by (sub-batch, kernel form)
+};
+// d_pixels: the address the offsets count from (the plan entry: 0, any 16-byte aligned block)
+void decode_batch_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodeBatchPlan &p)
+{
+    const uint32_t batch = static_cast<uint32_t>(b.files.size());
+    const uint64_t limit = debug().decode_batch_bytes ? debug().decode_batch_bytes : kDecodeBatchBytes;
+    p.rows_at.assign(batch, 0);
+    p.kernel.assign(batch, 0);
+    p.sub_first.assign(1, 0);
+    uint64_t held = 0, rows = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        const BatchFile &x = b.files[i];
+        const uint64_t mine = x.f.height * x.pitch, need = round16(x.expected) + mine;
+        if (i > p.sub_first.back() && held + need > limit) { // every sub-batch holds at least one image
+            p.sub_first.push_back(i);
+            held = rows = 0;
+        }
+        p.rows_at[i] = rows;
+        rows += mine;
+        held += need;
+        p.rows_bytes = std::max(p.rows_bytes, rows);
+        p.stream_bytes = std::max(p.stream_bytes, x.in_at + round16(x.expected) - b.files[p.sub_first.back()].in_at);
+        p.kernel[i] = pixo_dev::convert_kernel_of(convert_of(x.f.color_type, x.f.depth), static_cast<uint64_t>(x.f.width) * bytes_per_pixel(x.f.out_color_type()),
+                                                  d_pixels + static_cast<uintptr_t>(b.images[i].offset));
+    }
+    p.sub_first.push_back(batch);
+    for (uint32_t k = 0; k + 1 < p.sub_first.size(); ++k) {
+        const uint32_t first = p.sub_first[k], end = p.sub_first[k + 1];
+        for (const uint32_t unit : kFilterUnits) {
+            const uint64_t run0 = p.runs.size();
+            for (uint32_t i = first; i < end; ++i) {
+                if (filter_unit(b.files[i].f.color_type, b.files[i].f.depth) != unit) continue;
+                const std::vector<uint32_t> &pairs = b.files[i].runs.pairs;
+                for (size_t r = 0; r + 1 < pairs.size(); r += 2) p.runs.push_back({i, pairs[r], pairs[r + 1], 0});
+            }
+            if (p.runs.size() > run0) p.unfilter.push_back({k, unit, run0, p.runs.size() - run0});
+        }
+        for (uint32_t form = 0; form < pixo_dev::CONVERT_KERNELS; ++form) {
+            const uint64_t at = p.list.size();
+            uint64_t max_items = 0;
+            for (uint32_t i = first; i < end; ++i) {
+                if (p.kernel[i] != form) continue;
+                const PngFile &f = b.files[i].f;
+                const uint64_t bytes = f.pixel_bytes();
+                max_items = std::max<uint64_t>(max_items, form == pixo_dev::CONVERT_KERNEL_COPY16 ? bytes / 16
+                                                        : form == pixo_dev::CONVERT_KERNEL_BYTES ? (bytes + 3) / 4 : static_cast<uint64_t>(f.width) * f.height);
+                p.list.push_back(i);
+            }
+            if (p.list.size() > at) p.convert.push_back({k, form, at, p.list.size() - at, max_items});
+        }
+    }
+}
+
+struct BatchLegs { // timed: events around the device legs of every sub-batch
+    std::vector<hipEvent_t> e;
+    ~BatchLegs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    int mark(hipStream_t s)
+    {
+        hipEvent_t x = nullptr;
+        HIP_TRY(hipEventCreate(&x));
+        e.push_back(x);
+        HIP_TRY(hipEventRecord(x, s));
+        return PIXO_OK;
+    }
+};
+
+// Everything behind phase 1: waits for this thread's previous decode job (the call's one host wait), inflates into the pinned
+// staging, checks what only the streams show, then enqueues on `s`: all tables in one copy; per sub-batch its streams in one
+// copy, one unfilter launch per filter unit, one convert launch per kernel form.  Nothing is enqueued after a refusal.
+int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs = nullptr)
+{
+    const uint32_t batch = static_cast<uint32_t>(b.files.size());
+    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(c.u_done)); // the job before may still be reading the pinned buffers this one is about to write
+    int rc;
+    if ((rc = c.u_inflated.reserve(b.staging))) return rc;
+    if ((rc = batch_inflate(b, c.u_inflated.as<uint8_t>(), flags))) return rc;
+    DecodeBatchPlan p;
+    decode_batch_plan(b, reinterpret_cast<uintptr_t>(d_pixels), p);
+    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
+    note_route(route::PNG_DECODE_BATCH | (subs > 1 ? route::SUB_BATCHES : 0));
+
+    // the tables: descriptions, runs, block tables, a palette table per palette image; every section starts at a multiple of 16
+    uint32_t palettes = 0;
+    for (const BatchFile &x : b.files) palettes += x.f.color_type == CT_INDEXED;
+    const size_t images_bytes = static_cast<size_t>(batch) * sizeof(pixo_dev::UnfilterBatchImage), runs_at = images_bytes;
+    const size_t list_at = runs_at + p.runs.size() * sizeof(pixo_dev::UnfilterBatchRun);
+    const size_t tables_at = round16(list_at + p.list.size() * sizeof(uint32_t));
+    const size_t up_bytes = tables_at + std::max<size_t>(palettes, 1) * 256 * sizeof(uint32_t);
+    // everything is reserved before any address is handed out
+    if ((rc = c.u_stream.reserve(p.stream_bytes + pixo_dev::kUnfilterPiece)) || (rc = c.u_rows.reserve(p.rows_bytes)) ||
+        (rc = c.h_utables.reserve(up_bytes)) || (rc = c.u_tables.reserve(up_bytes)))
+        return rc;
+    uint8_t *stage = c.h_utables.as<uint8_t>();
+    pixo_dev::UnfilterBatchImage *images = reinterpret_cast<pixo_dev::UnfilterBatchImage *>(stage);
+    uint32_t *palette = reinterpret_cast<uint32_t *>(stage + tables_at);
+    uint32_t table_at = 0, sub = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        const BatchFile &x = b.files[i];
+        while (i >= p.sub_first[sub + 1]) ++sub;
+        pixo_dev::UnfilterBatchImage &im = images[i];
+        std::memset(&im, 0, sizeof im);
+        im.stream_at = x.in_at - b.files[p.sub_first[sub]].in_at;
+        im.rows_at = p.rows_at[i];
+        im.row_bytes = x.row; im.pitch = x.pitch;
+        im.out_at = b.images[i].offset;
+        im.width = x.f.width; im.height = x.f.height;
+        im.form = convert_of(x.f.color_type, x.f.depth); im.depth = x.f.depth; im.out_bpp = bytes_per_pixel(x.f.out_color_type());
+        im.aligned4 = (reinterpret_cast<uintptr_t>(d_pixels) + b.images[i].offset) % 4 == 0;
+        if (x.f.color_type != CT_INDEXED) continue;
+        im.table_at = table_at;
+        const bool rgba = x.f.out_color_type() == PIXO_RGBA;
+        for (uint32_t k = 0; k < 256; ++k) palette[table_at + k] = palette_rgba(x.f.plte, x.f.plte_entries, x.f.trns, rgba ? x.f.trns_len : 0, k);
+        table_at += 256;
+    }
+    if (!p.runs.empty()) std::memcpy(stage + runs_at, p.runs.data(), p.runs.size() * sizeof(pixo_dev::UnfilterBatchRun));
+    if (!p.list.empty()) std::memcpy(stage + list_at, p.list.data(), p.list.size() * sizeof(uint32_t));
+
+    const uint8_t *d_tables = c.u_tables.as<uint8_t>();
+    const pixo_dev::UnfilterBatchImage *d_images = reinterpret_cast<const pixo_dev::UnfilterBatchImage *>(d_tables);
+    HIP_TRY(hipMemcpyAsync(c.u_tables.p, stage, up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c.u_done, s)); // (until the job's own record: whatever has been enqueued when a later step fails)
+    size_t iu = 0, iv = 0;
+    for (uint32_t k = 0; k < subs; ++k) {
+        const uint64_t from = b.files[p.sub_first[k]].in_at;
+        const uint64_t bytes = (p.sub_first[k + 1] < batch ? b.files[p.sub_first[k + 1]].in_at : b.staging) - from;
+        if (legs && (rc = legs->mark(s))) return rc;
+        HIP_TRY(hipMemcpyAsync(c.u_stream.p, c.u_inflated.as<uint8_t>() + from, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(c.u_done, s));
+        if (legs && (rc = legs->mark(s))) return rc;
+        for (; iu < p.unfilter.size() && p.unfilter[iu].sub == k; ++iu) {
+            pixo_dev::UnfilterBatchArgs u;
+            u.stream = c.u_stream.as<uint8_t>(); u.rows = c.u_rows.as<uint8_t>(); u.images = d_images;
+            u.runs = reinterpret_cast<const pixo_dev::UnfilterBatchRun *>(d_tables + runs_at) + p.unfilter[iu].first_run;
+            u.n_runs = static_cast<uint32_t>(p.unfilter[iu].n_runs); u.bpp = p.unfilter[iu].unit;
+            HIP_TRY(pixo_dev::launch_png_unfilter_batch(u, s));
+        }
+        if (legs && (rc = legs->mark(s))) return rc;
+        for (; iv < p.convert.size() && p.convert[iv].sub == k; ++iv) {
+            pixo_dev::UnconvertBatchArgs v;
+            v.rows = c.u_rows.as<uint8_t>(); v.out = d_pixels; v.images = d_images;
+            v.list = reinterpret_cast<const uint32_t *>(d_tables + list_at) + p.convert[iv].first;
+            v.n = static_cast<uint32_t>(p.convert[iv].n); v.kernel = p.convert[iv].kernel;
+            v.tables = reinterpret_cast<const uint32_t *>(d_tables + tables_at); v.max_items = p.convert[iv].max_items;
+            HIP_TRY(pixo_dev::launch_png_convert_batch(v, s));
+        }
+        if (legs && (rc = legs->mark(s))) return rc;
+        HIP_TRY(hipEventRecord(c.u_done, s));
+    }
+    return PIXO_OK;
+}
+
+// The batch entries' first two checks
+int batch_head(const pixo_png_file *files, uint32_t batch)
+{
+    PIXO_REQUIRE(files);
+    return batch_in_range(batch);
+}
+void report(const DecodeBatch &b, pixo_png_image *images) { std::copy(b.images.begin(), b.images.end(), images); }
+
+// Host files -> one block of the pinned pool the caller owns
+int decode_batch_to_block(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len, pixo_png_image *images, double *legs_ms)
+{
+    DecodeBatch b;
+    int rc = batch_walk(files, batch, true, b);
+    if (rc) return rc;
+    report(b, images);
+    PIXO_THREAD_CONTEXT(c);
+    const size_t n = static_cast<size_t>(b.total);
+    if ((rc = reserve16(c.u_out, n))) return rc;
+    BatchLegs legs;
+    if ((rc = decode_batch_on_device(c, b, flags, c.u_out.as<uint8_t>(), c.stream, legs_ms ? &legs : nullptr))) return rc;
+    uint8_t *block = pool_take(n);
+    if (!block) block = alloc_file(n);
+    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    hipError_t e = hipMemcpyAsync(block, c.u_out.p, n, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { free_file(block); return hip_fail(e, "png decode batch"); }
+    if (legs_ms) {
+        legs_ms[0] = b.inflate_ms;
+        legs_ms[1] = legs_ms[2] = legs_ms[3] = 0;
+        for (size_t k = 0; k + 3 < legs.e.size(); k += 4)
+            for (int i = 0; i < 3; ++i) {
+                float ms = 0;
+                e = hipEventElapsedTime(&ms, legs.e[k + i], legs.e[k + i + 1]);
+                if (e != hipSuccess) { free_file(block); return hip_fail(e, "hipEventElapsedTime"); }
+                legs_ms[1 + i] += ms;
+            }
+    }
+    *out = block;
+    *out_len = n;
+    return PIXO_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int pixo_hip_png_decode_batch_info(const pixo_png_file *files, uint32_t batch, pixo_png_image *images, size_t *total)
+{
+    int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(images);
+    PIXO_REQUIRE(total);
+    DecodeBatch b;
+    if ((rc = batch_walk(files, batch, false, b))) return rc;
+    report(b, images);
+    *total = static_cast<size_t>(b.total);
+    return PIXO_OK;
+}
+
+int pixo_hip_png_decode_batch_device(const pixo_png_file *files, uint32_t batch, uint32_t flags, void *d_pixels, size_t capacity,
+                                     pixo_png_image *images, void *stream)
+{
+    CallerStorageScope storage(d_pixels != nullptr && capacity != 0);
+    int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(images);
+    DecodeBatch b;
+    if ((rc = batch_walk(files, batch, true, b))) return rc;
+    report(b, images);
+    if (capacity < b.total) return too_small(static_cast<size_t>(b.total));
+    PIXO_REQUIRE(d_pixels);
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    return decode_batch_on_device(*c, b, flags, static_cast<uint8_t *>(d_pixels), s);
+}
+
+int pixo_hip_png_decode_batch(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len, pixo_png_image *images)
+{
+    const int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(out);
+    PIXO_REQUIRE(out_len);
+    PIXO_REQUIRE(images);
+    return decode_batch_to_block(files, batch, flags, out, out_len, images, nullptr);
+}
+
+int pixo_hip_debug_png_decode_batch_plan(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint32_t *sub_first, uint32_t *sub_count,
+                                         uint64_t *runs_per_image, uint32_t *unfilter_launches, uint32_t *convert_launches, uint32_t *threads)
+{
+    int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(sub_first);
+    PIXO_REQUIRE(sub_count);
+    PIXO_REQUIRE(runs_per_image);
+    PIXO_REQUIRE(unfilter_launches);
+    PIXO_REQUIRE(convert_launches);
+    PIXO_REQUIRE(threads);
+    DecodeBatch b;
+    if ((rc = batch_walk(files, batch, true, b))) return rc;
+    uint8_t *stage = static_cast<uint8_t *>(std::malloc(std::max<size_t>(static_cast<size_t>(b.staging), 1)));
+    if (!stage) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    rc = batch_inflate(b, stage, flags);
+    std::free(stage);
+    if (rc) return rc;
+    DecodeBatchPlan p;
+    decode_batch_plan(b, 0, p);
+    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
+    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    for (uint32_t i = 0; i < batch; ++i) runs_per_image[i] = b.files[i].runs.pairs.size() / 2;
+    *unfilter_launches = static_cast<uint32_t>(p.unfilter.size());
+    *convert_launches = static_cast<uint32_t>(p.convert.size());
+    *threads = b.threads;
+    return PIXO_OK;
+}
+
+int pixo_hip_debug_png_decode_batch_timed(const pixo_png_file *files, uint32_t batch, uint32_t flags, double ms[5])
+{
+    const int rc0 = batch_head(files, batch);
+    if (rc0) return rc0;
+    PIXO_REQUIRE(ms);
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    std::vector<pixo_png_image> images(batch);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = decode_batch_to_block(files, batch, flags, &block, &n, images.data(), ms);
+    if (rc) return rc;
+    ms[4] = ms_since(t0);
+    free_file(block);
+    return PIXO_OK;
+}
 
 int pixo_hip_png_decode(const uint8_t *file, size_t len, uint8_t **pixels, size_t *pixels_len, uint32_t *width, uint32_t *height, uint8_t *color_type)
 {

@@ -35,7 +35,7 @@ enum : uint64_t {
     TRELLIS_GROUP = 1ull << 23,    // ... eight lanes per block
     BATCH_FUSED = 1ull << 24,      // a batch through the fused kernel, every image a segment
     BATCH_TWO_KERNEL = 1ull << 25, // a batch through coefficient kernel + entropy stage
-    SUB_BATCHES = 1ull << 26,      // a batch in several sub-batches over two contexts (resize batches: one after the other on one stream)
+    SUB_BATCHES = 1ull << 26,      // a batch in several sub-batches over two contexts (resize and decode batches: one after the other on one stream)
     BANDS_MULTI = 1ull << 27,      // one image in bands over several devices (pixo_hip_jpeg_encode_multi)
     PNG_REGS = 1ull << 28,         // PNG filter kernel: adaptive strategies with the row in the registers of 256 threads
     PNG_GENERAL = 1ull << 29,      // ... the general form (fixed filters, or rows too long for registers)
@@ -51,6 +51,7 @@ enum : uint64_t {
     PNG_BATCH = 1ull << 39,        // PNG batch entries: one DEFLATE, scan, compaction and CRC launch over all images of a sub-batch
     PNG_BATCH_FILTER = 1ull << 40, // ... and one filter launch over all their rows in front of it
     RESIZE_BATCH = 1ull << 41,     // resize batch entries: one launch per pass over all images of a sub-batch (beside the algorithm's bit)
+    PNG_DECODE_BATCH = 1ull << 42, // PNG decode batch entries: one unfilter launch per filter unit and one convert launch per kernel form a sub-batch
 };
 }
 

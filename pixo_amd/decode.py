@@ -73,6 +73,85 @@ def decode_png_device(data, out=None, stream=None):
     return out.reshape(-1)[:n].view(h.value, w.value, color.bytes_per_pixel()), color
 
 
+# ---- batches: N files -> N images back to back in device memory, one launch per pass (include/pixo_hip.h) ----------------------
+ROUTES = {"PNG_DECODE_BATCH": 42}  # the route record's bit of the batch entries (csrc/routes.hpp; read with jpeg.routes)
+ROUTE_PNG_DECODE_BATCH = 1 << ROUTES["PNG_DECODE_BATCH"]
+ONE_THREAD = 1  # PIXO_DECODE_ONE_THREAD
+
+
+def _files_c(files):
+    """The files as the C array, and the arrays that keep their bytes alive"""
+    held = [_file(f) for f in files]
+    arr = (_lib.PngFileC * max(len(held), 1))()
+    for i, f in enumerate(held):
+        arr[i] = _lib.PngFileC(f.ctypes.data, f.size)
+    return arr, held
+
+
+def _bytes_of(im) -> int:
+    return im.width * im.height * ColorType(im.color_type).bytes_per_pixel()
+
+
+def decode_png_batch_info(files):
+    """([(width, height, ColorType, offset)], total) of the block decode_png_batch_device writes: image i at `offset`, every
+    offset a multiple of 16, `total` the end of the last image.  The walks and their checks only — no inflate, no GPU."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    images, total = (_lib.PngImageC * max(len(held), 1))(), C.c_size_t()
+    _lib.check(L.pixo_hip_png_decode_batch_info(arr, len(held), images, C.byref(total)))
+    return [(im.width, im.height, ColorType(im.color_type), im.offset) for im in images[:len(held)]], total.value
+
+
+def decode_png_batch(files, one_thread=False) -> list:
+    """PNG files (bytes) -> [PngImage] with host pixels, image i what decode_png makes of file i.  The inflates run on up to 8
+    host threads unless `one_thread`."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    images = (_lib.PngImageC * max(len(held), 1))()
+    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    _lib.check(L.pixo_hip_png_decode_batch(arr, len(held), ONE_THREAD if one_thread else 0, C.byref(out), C.byref(n), images))
+    block = _lib.take(L, out, n)
+    return [PngImage(im.width, im.height, block[im.offset:im.offset + _bytes_of(im)], ColorType(im.color_type)) for im in images[:len(held)]]
+
+
+def decode_png_batch_device(files, out=None, stream=None, one_thread=False) -> list:
+    """PNG files (host bytes) -> [(uint8 tensor view (height, width, channels), ColorType)], views into ONE uint8 device
+    tensor: `out` (contiguous, any alignment; the bytes between two images are left as they are), or one allocated from
+    decode_png_batch_info.  Enqueue only, ordered like decode_png_device; BufferTooSmall carries the total in `.needed`.  The
+    views are what resize.resize_batch_device takes as sources (grouped by colour type)."""
+    import torch
+    L = _lib.load()
+    arr, held = _files_c(files)
+    images = (_lib.PngImageC * max(len(held), 1))()
+    if out is None:
+        out = torch.empty(max(decode_png_batch_info(held)[1], 1), dtype=torch.uint8, device="cuda")
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    rc = L.pixo_hip_png_decode_batch_device(arr, len(held), ONE_THREAD if one_thread else 0, out.data_ptr(), _lib.nbytes(out), images,
+                                            C.c_void_p(stream) if stream else None)
+    last = images[len(held) - 1] if held else None
+    _lib.check(rc, needed=last.offset + _bytes_of(last) if rc == -9 else None)
+    flat = out.reshape(-1)
+    return [(flat[im.offset:im.offset + _bytes_of(im)].view(im.height, im.width, ColorType(im.color_type).bytes_per_pixel()), ColorType(im.color_type))
+            for im in images[:len(held)]]
+
+
+def decode_png_batch_plan(files, one_thread=False) -> dict:
+    """What the batch entries decide for these files, computed on the host (no GPU): `sub_first` (where each sub-batch starts,
+    and the batch's end), `runs` (workgroups that reconstruct each image), `unfilter_launches` and `convert_launches` (summed
+    over the sub-batches) and `threads` (host threads that inflated).  Refuses as the decode entries do."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    n = len(held)
+    sub_first, runs = (C.c_uint32 * (n + 1))(), (C.c_uint64 * max(n, 1))()
+    subs, unfilter, convert, threads = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _lib.check(L.pixo_hip_debug_png_decode_batch_plan(arr, n, ONE_THREAD if one_thread else 0, sub_first, C.byref(subs), runs, C.byref(unfilter),
+                                                      C.byref(convert), C.byref(threads)))
+    return dict(sub_first=list(sub_first[:subs.value + 1]), runs=list(runs[:n]), unfilter_launches=unfilter.value,
+                convert_launches=convert.value, threads=threads.value)
+
+
 def inflate_zlib(data, expected: int) -> bytes:
     """The host inflate alone (inflate.rs:294-352 with Some(expected)); no GPU."""
     L = _lib.load()

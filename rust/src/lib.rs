@@ -98,6 +98,17 @@ const PIXO_ERR_BUFFER_TOO_SMALL: c_int = -9;
 /// denser effort (hash chains, one-step lazy parse); `effort = 1` of the two zlib entries below is the same finder.
 pub const PNG_EFFORT_HIGH: u32 = 2;
 
+/// `pixo_png_file` (include/pixo_hip.h): one file of a decode batch
+#[repr(C)]
+struct CPngFile { data: *const u8, len: usize }
+/// `pixo_png_image` (include/pixo_hip.h): one image of the block a decode batch writes
+#[repr(C)]
+#[derive(Clone, Copy)]
+#[allow(dead_code)]
+struct CPngImage { offset: u64, width: u32, height: u32, color_type: u8, reserved: [u8; 7] }
+/// `PIXO_DECODE_ONE_THREAD`: the bit of a decode batch's `flags` that keeps the inflates on the calling thread
+pub const DECODE_ONE_THREAD: u32 = 1;
+
 extern "C" {
     // include/pixo_hip.h
     fn pixo_hip_jpeg_encode_into(output: *mut u8, capacity: usize, data: *const u8, len: usize, opts: *const COptions,
@@ -124,6 +135,8 @@ extern "C" {
                              color_type: u8, algorithm: u8, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     fn pixo_hip_png_decode(file: *const u8, len: usize, pixels: *mut *mut u8, pixels_len: *mut usize, width: *mut u32, height: *mut u32,
                            color_type: *mut u8) -> c_int;
+    fn pixo_hip_png_decode_batch(files: *const CPngFile, batch: u32, flags: u32, out: *mut *mut u8, out_len: *mut usize,
+                                 images: *mut CPngImage) -> c_int;
     fn pixo_hip_free(p: *mut u8);
     fn pixo_hip_copy_file(dst: *mut u8, src: *const u8, n: usize);
     fn pixo_hip_last_error() -> *const c_char;
@@ -408,34 +421,66 @@ pub mod decode {
         pub color_type: ColorType,
     }
 
+    /// The library's status and message turned back into the variant (a batch's message ends in " (image i)": it stays in the
+    /// text of the two string variants)
+    fn error_of(rc: c_int) -> Error {
+        let msg = last_error();
+        match rc {
+            -10 => Error::InvalidDecode(msg.trim_start_matches("Decode error: ").to_string()),
+            -11 => Error::UnsupportedDecode(msg.trim_start_matches("Unsupported: ").to_string()),
+            // the two variants with fields: the dimensions are the text's "WxH"
+            -1 | -4 => {
+                let dims = msg.split(|c: char| !(c.is_ascii_digit() || c == 'x')).find(|t| t.contains('x') && t.len() > 2).unwrap_or("0x0");
+                let mut it = dims.split('x').map(|v| v.parse::<u32>().unwrap_or(0));
+                let (w, h) = (it.next().unwrap_or(0), it.next().unwrap_or(0));
+                if rc == -1 { Error::InvalidDimensions { width: w, height: h } } else { Error::ImageTooLarge { width: w, height: h, max: 1 << 24 } }
+            }
+            _ => Error::CompressionError(msg.trim_start_matches("Compression error: ").to_string()),
+        }
+    }
+    fn color_type_of(ct: u8) -> ColorType {
+        match ct { 0 => ColorType::Gray, 1 => ColorType::GrayAlpha, 2 => ColorType::Rgb, _ => ColorType::Rgba }
+    }
+
+    /// A loop over `decode_png` in one call (`pixo_hip_png_decode_batch`): the inflates run on a small pool of host threads
+    /// (`one_thread`: on the calling thread), the files' streams go to the device in one copy and every pass is one launch for
+    /// all of them.  Image i is what `decode_png(files[i])` returns, in its own colour type; the first file the walk refuses,
+    /// or else the lowest-indexed file whose stream is faulty, decides the error, its index in the message.
+    pub fn decode_png_batch(files: &[&[u8]], one_thread: bool) -> Result<Vec<PngImage>> {
+        let c_files: Vec<CPngFile> = files.iter().map(|f| CPngFile { data: f.as_ptr(), len: f.len() }).collect();
+        let mut images = vec![CPngImage { offset: 0, width: 0, height: 0, color_type: 0, reserved: [0; 7] }; files.len().max(1)];
+        let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
+        let flags = if one_thread { DECODE_ONE_THREAD } else { 0 };
+        let list = if files.is_empty() { std::ptr::null() } else { c_files.as_ptr() };
+        let rc = unsafe { pixo_hip_png_decode_batch(list, files.len() as u32, flags, &mut p, &mut n, images.as_mut_ptr()) };
+        if rc != 0 { return Err(error_of(rc)); }
+        let mut out = Vec::with_capacity(files.len());
+        for im in &images[..files.len()] {
+            let bytes = im.width as usize * im.height as usize * (im.color_type as usize + 1);
+            let mut pixels = Vec::<u8>::with_capacity(bytes);
+            unsafe {
+                pixo_hip_copy_file(pixels.as_mut_ptr(), p.add(im.offset as usize), bytes);
+                pixels.set_len(bytes);
+            }
+            out.push(PngImage { width: im.width, height: im.height, pixels, color_type: color_type_of(im.color_type) });
+        }
+        unsafe { pixo_hip_free(p) };
+        Ok(out)
+    }
+
     /// `pixo::decode::decode_png(data)` (`src/decode/png.rs:101`)
     pub fn decode_png(data: &[u8]) -> Result<PngImage> {
         let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
         let (mut width, mut height, mut ct) = (0u32, 0u32, 0u8);
         let rc = unsafe { pixo_hip_png_decode(data.as_ptr(), data.len(), &mut p, &mut n, &mut width, &mut height, &mut ct) };
-        if rc != 0 {
-            let msg = last_error();
-            return Err(match rc {
-                -10 => Error::InvalidDecode(msg.trim_start_matches("Decode error: ").to_string()),
-                -11 => Error::UnsupportedDecode(msg.trim_start_matches("Unsupported: ").to_string()),
-                // the two variants with fields: the dimensions are the text's "WxH"
-                -1 | -4 => {
-                    let dims = msg.split(|c: char| !(c.is_ascii_digit() || c == 'x')).find(|t| t.contains('x') && t.len() > 2).unwrap_or("0x0");
-                    let mut it = dims.split('x').map(|v| v.parse::<u32>().unwrap_or(0));
-                    let (w, h) = (it.next().unwrap_or(0), it.next().unwrap_or(0));
-                    if rc == -1 { Error::InvalidDimensions { width: w, height: h } } else { Error::ImageTooLarge { width: w, height: h, max: 1 << 24 } }
-                }
-                _ => Error::CompressionError(msg.trim_start_matches("Compression error: ").to_string()),
-            });
-        }
+        if rc != 0 { return Err(error_of(rc)); }
         let mut pixels = Vec::<u8>::with_capacity(n);
         unsafe {
             pixo_hip_copy_file(pixels.as_mut_ptr(), p, n);
             pixels.set_len(n);
             pixo_hip_free(p);
         }
-        let color_type = match ct { 0 => ColorType::Gray, 1 => ColorType::GrayAlpha, 2 => ColorType::Rgb, _ => ColorType::Rgba };
-        Ok(PngImage { width, height, pixels, color_type })
+        Ok(PngImage { width, height, pixels, color_type: color_type_of(ct) })
     }
 }
 
