@@ -439,13 +439,16 @@ struct PngImage {
 }
 [[nodiscard]] inline PngImage decode_png(const std::vector<uint8_t> &data) { return decode_png(data.data(), data.size()); }
 // Batches: N files -> N images, image i what decode_png makes of file i (contract: pixo_hip.h).  one_thread: the inflates
-// run on the calling thread instead of the library's small pool
-[[nodiscard]] inline std::vector<PngImage> decode_png_batch(const std::vector<pixo_png_file> &files, bool one_thread = false)
+// run on the calling thread instead of the library's small pool.  device_inflate (opt-in): the inflates run on the device, one
+// wavefront per stream (PIXO_DECODE_DEVICE_INFLATE); the host inflates again only what the device does not vouch for
+[[nodiscard]] inline std::vector<PngImage> decode_png_batch(const std::vector<pixo_png_file> &files, bool one_thread = false,
+                                                            bool device_inflate = false)
 {
     uint8_t *block = nullptr;
     size_t n = 0;
     std::vector<pixo_png_image> images(files.size() ? files.size() : 1);
-    const int rc = pixo_hip_png_decode_batch(files.data(), (uint32_t)files.size(), one_thread ? PIXO_DECODE_ONE_THREAD : 0u, &block, &n, images.data());
+    const uint32_t flags = (one_thread ? PIXO_DECODE_ONE_THREAD : 0u) | (device_inflate ? PIXO_DECODE_DEVICE_INFLATE : 0u);
+    const int rc = pixo_hip_png_decode_batch(files.data(), (uint32_t)files.size(), flags, &block, &n, images.data());
     if (rc != PIXO_OK) throw Error::from_status(rc);
     struct Block { // (released also when a copy below throws)
         uint8_t *p;

@@ -671,6 +671,18 @@ typedef struct pixo_png_image {
     uint8_t reserved[7];
 } pixo_png_image; /* 24 bytes */
 #define PIXO_DECODE_ONE_THREAD 1u /* flags bit 0: the inflates run on the calling thread (for callers that run a pool of their own) */
+/* flags bit 1 (opt-in; the batch entries only): the streams are inflated ON THE DEVICE, one wavefront per stream, all streams of
+ * a sub-batch in one launch (png_inflate.hip).  The compressed streams go up instead of the inflated ones; per sub-batch one
+ * inflate launch, one launch that gathers the filter bytes, one small copy of status records and filter bytes down, and one
+ * host wait for it.  The host then decides in index order: a stream whose device verdict is not OK, or whose Adler-32 differs
+ * from the last four bytes of its IDAT data, is inflated again by the host inflate, whose result is the truth — its error is
+ * returned as without the flag, its bytes replace the stream on the device.  Image i stays byte for byte what
+ * pixo_hip_png_decode returns for file i.  What changes in the contract, under this flag only: phase 1 and the zlib header
+ * checks (the 6-byte minimum, method, header checksum, preset dictionary) are still made before anything is enqueued, but the
+ * other phase-2 refusals come AFTER the inflate launch of their sub-batch, and with several sub-batches after earlier
+ * sub-batches' images were written: d_pixels is unspecified after a refusal.  The calls wait on the host once per sub-batch.
+ * At most 11 launches a sub-batch.  The single-file entries never inflate on the device: one stream is one wavefront. */
+#define PIXO_DECODE_DEVICE_INFLATE 2u
 
 /* The layout alone: `images` (batch entries) and *total (the end of the last image, not rounded) from the walks of the files — no
  * inflate, no GPU.  What a caller of pixo_hip_png_decode_batch_device allocates from. */
@@ -701,6 +713,23 @@ int pixo_hip_png_decode_batch(const pixo_png_file *files, uint32_t batch, uint32
 int pixo_hip_debug_png_decode_batch_plan(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint32_t *sub_first,
                                          uint32_t *sub_count, uint64_t *runs_per_image, uint32_t *unfilter_launches,
                                          uint32_t *convert_launches, uint32_t *threads);
+/* The boundaries of the device inflate (png_inflate_math.h; tests place their cases by them): tokens a step holds at most; bytes
+ * of the LDS ring (DEFLATE's window); the distance beyond which a match closes its step; bytes of a stored block copied at a time. */
+uint32_t pixo_hip_png_inflate_step_tokens(void);
+uint32_t pixo_hip_png_inflate_window_bytes(void);
+uint32_t pixo_hip_png_inflate_far_distance(void);
+uint32_t pixo_hip_png_inflate_stored_chunk(void);
+/* Tests and measurements: the inflate kernel alone over `n` (1..65535) zlib streams of any origin in host memory (pixo_png_file:
+ * data, len >= 6; the two header bytes and the four checksum bytes are skipped, not checked).  `out` is a host block of
+ * max(out_at[i] + expected[i]) bytes that the caller has filled: the whole block is uploaded, stream i is inflated on the device
+ * into [out_at[i], out_at[i] + expected[i]) of it, and the block is downloaded again, so that every byte outside the regions —
+ * and inside them behind produced[i] — can be checked for being untouched.  The raw device results, no host inflate behind them:
+ * verdict[i] 0 OK (the final block ended at exactly expected[i] bytes), 1 FAILED, 2 NEEDS_HOST (an over-subscribed code set);
+ * produced[i] bytes of region i are inflated bytes whatever the verdict, adler[i] is their Adler-32.  *kernel_ms: the inflate
+ * launch's device time by HIP events. */
+int pixo_hip_debug_zlib_inflate_batch_device(const pixo_png_file *streams, uint32_t n, const uint64_t *expected, uint8_t *out,
+                                             const uint64_t *out_at, uint32_t *verdict, uint64_t *produced, uint32_t *adler,
+                                             double *kernel_ms);
 /* MEASUREMENT only (tools/png_decode_batch_timing.py): pixo_hip_png_decode_batch with its legs timed — ms[0] the inflates and
  * the runs of rows (host clock), [1] uploads, [2] reconstruction launches, [3] conversion launches (HIP events, summed over the
  * sub-batches), [4] the whole call.  The block is released again. */

@@ -153,6 +153,11 @@ SIGNATURES = {
     "pixo_hip_png_decode_batch": _sig(_pfilep, _u32, _u32, _u8pp, _szp, _pimgp, optional=True),
     "pixo_hip_debug_png_decode_batch_plan": _sig(_pfilep, _u32, _u32, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p, optional=True),
     "pixo_hip_debug_png_decode_batch_timed": _sig(_pfilep, _u32, _u32, C.POINTER(_dbl), optional=True),
+    "pixo_hip_png_inflate_step_tokens": _sig(ret=_u32, optional=True),
+    "pixo_hip_png_inflate_window_bytes": _sig(ret=_u32, optional=True),
+    "pixo_hip_png_inflate_far_distance": _sig(ret=_u32, optional=True),
+    "pixo_hip_png_inflate_stored_chunk": _sig(ret=_u32, optional=True),
+    "pixo_hip_debug_zlib_inflate_batch_device": _sig(_pfilep, _u32, _u64p, _vp, _u64p, _u32p, _u64p, _u32p, C.POINTER(_dbl), optional=True),
     "pixo_hip_band": _sig(_u32, _u32, _u8, _u8, _u32, _u32, _u32p, _u32p, _szp, _szp, _szp, _szp),
     "pixo_hip_band_encoder_create": _sig(_optp, _u32, _u32, _int, C.POINTER(_vp)),
     "pixo_hip_band_encoder_destroy": _sig(_vp, ret=None),

@@ -285,6 +285,13 @@ struct Context {
     Buf u_out{Buf::Mem::Device, Buf::Grow::Exact};       // host entry: the pixels before they go down
     Buf u_tables{Buf::Mem::Device, Buf::Grow::Exact};    // the palette table (256 words), behind it the runs of rows (a batch: descriptions, runs, block tables, palettes)
     Buf h_utables{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here, uploaded from here
+    // ... batches with PIXO_DECODE_DEVICE_INFLATE (png_inflate.hip): per sub-batch
+    Buf h_zin{Buf::Mem::Pinned, Buf::Grow::Headroom};    // the stream and gather descriptions, behind them the compressed streams, each padded
+    Buf u_zin{Buf::Mem::Device, Buf::Grow::Exact};       // ... on the device
+    Buf u_zout{Buf::Mem::Device, Buf::Grow::Exact};      // the status record of every stream, behind them every image's filter bytes
+    Buf h_zout{Buf::Mem::Pinned, Buf::Grow::Headroom};   // ... copied to the host
+    Buf h_uruns{Buf::Mem::Pinned, Buf::Grow::Headroom};  // a sub-batch's runs of rows, which are known only behind its inflate
+    Buf u_runs{Buf::Mem::Device, Buf::Grow::Exact};      // ... on the device
     hipEvent_t u_done = nullptr;                         // the last decode job (it reads all of the above) has run
 
     // Small results for the host, one field per purpose: pinned, allocated once with the stream (ensure).

@@ -160,7 +160,8 @@ template <class F> void each_buf(Context &c, F &&f)
                    &c.q_work, &c.h_qwork, &c.q_index, &c.q_rows, &c.z_tok, &c.z_slots, &c.z_prev, &c.z_info, &c.z_stream, &c.z_crc, &c.h_zinfo,
                    &c.k_samples, &c.h_ksamples, &c.k_work, &c.h_kwork, &c.k_lut, &c.k_carry,
                    &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank, &c.h_file, &c.r_in, &c.r_out, &c.r_mid, &c.r_tables,
-                   &c.r_stage, &c.rb_in, &c.rb_out, &c.rb_mid, &c.rb_tables, &c.rb_stage, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables};
+                   &c.r_stage, &c.rb_in, &c.rb_out, &c.rb_mid, &c.rb_tables, &c.rb_stage, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables,
+                   &c.h_zin, &c.u_zin, &c.u_zout, &c.h_zout, &c.h_uruns, &c.u_runs};
     for (Buf *b : bufs) f(*b);
 }
 } // namespace

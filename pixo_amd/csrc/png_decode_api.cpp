@@ -2,15 +2,20 @@
 // the chunk walk and its checks in the reference's order and words, the host inflate (png_inflate.cpp) into pinned memory, the
 // runs of rows that do not read the row above, and the launches of png_unfilter.hip.  The batch entries (N files -> N images
 // back to back in device memory): two phases of checks, the inflates on a small pool of host threads, the plan of sub-batches
-// and launches, one upload of streams and one of tables.
+// and launches, one upload of streams and one of tables.  With PIXO_DECODE_DEVICE_INFLATE the batch entries inflate on the device
+// (png_inflate.hip): the compressed streams go up, the host reads each stream's status and filter bytes and inflates again only
+// what the device did not vouch for.
 //
 // The order in which a faulty file is refused: signature; per chunk in file order "truncated PNG chunk", its CRC-32, then its
 // own length / field checks; then missing IEND, missing IHDR, zero dimension, dimension above 2^24, compression method, filter
 // method, interlace (Unsupported), bit depth against colour type, no IDAT, whatever inflate raises, Adler-32, size, the first
-// row in row order with a filter byte above 4, a palette image without PLTE.  All of it is known on the host before a kernel starts.
+// row in row order with a filter byte above 4, a palette image without PLTE.  All of it is known on the host before a kernel starts
+// — except under PIXO_DECODE_DEVICE_INFLATE, where what follows the zlib header checks is known only behind the inflate launch of
+// the file's sub-batch: d_pixels is unspecified after such a refusal (status, message and index are the same).
 #include "capi_internal.hpp"
 #include "png_deflate_math.h"
 #include "png_inflate.hpp"
+#include "png_inflate_dev.hpp"
 #include "png_unfilter.hpp"
 
 #include <algorithm>
@@ -169,14 +174,15 @@ struct Runs {
     std::vector<uint32_t> pairs; // (first row, rows)
     uint64_t segments = 0, longest_segment = 0;
 };
+// filters: row y's filter byte at filters[y * stride] (a stream: row_bytes + 1; the gathered bytes of the device inflate: 1).
 // *bad_row: the first row whose filter byte is above 4 (height: none)
-Runs find_runs(const uint8_t *stream, uint32_t height, uint64_t row_bytes, uint32_t *bad_row)
+Runs find_runs(const uint8_t *filters, uint32_t height, uint64_t stride, uint32_t *bad_row)
 {
     Runs r;
     *bad_row = height;
     uint32_t run_at = 0, seg_at = 0;
     for (uint32_t y = 0; y < height; ++y) {
-        const uint8_t ft = stream[static_cast<size_t>(y) * (row_bytes + 1)];
+        const uint8_t ft = filters[static_cast<size_t>(y) * stride];
         if (ft > FILTER_PAETH) { *bad_row = y; return r; }
         if (y > 0 && ft <= FILTER_SUB) {
             ++r.segments;
@@ -228,7 +234,7 @@ int decode_on_device(Context &c, const PngFile &f, uint8_t *d_out, hipStream_t s
     t_stats.inflate_ms = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
     uint32_t bad_row = 0;
-    const Runs runs = find_runs(stream, f.height, row, &bad_row);
+    const Runs runs = find_runs(stream, f.height, row + 1, &bad_row);
     if (bad_row < f.height) return invalid("invalid filter type: " + std::to_string(stream[static_cast<size_t>(bad_row) * (row + 1)]));
     if (f.color_type == CT_INDEXED && !f.has_plte) return invalid("missing PLTE chunk");
     t_stats.runs_ms = ms_since(t0);
@@ -373,7 +379,7 @@ int batch_inflate(DecodeBatch &b, uint8_t *stage, uint32_t flags)
             x.kind = pixo_inflate::inflate_zlib(x.f.idat, x.f.idat_len, stage + x.in_at, x.expected, &x.msg);
             if (x.kind != pixo_inflate::OK) continue;
             uint32_t bad_row = 0;
-            x.runs = find_runs(stage + x.in_at, x.f.height, x.row, &bad_row);
+            x.runs = find_runs(stage + x.in_at, x.f.height, x.row + 1, &bad_row);
             if (bad_row < x.f.height) {
                 x.kind = pixo_inflate::INVALID;
                 x.msg = "invalid filter type: " + std::to_string(stage[x.in_at + static_cast<uint64_t>(bad_row) * (x.row + 1)]);
@@ -467,23 +473,15 @@ struct BatchLegs { // timed: events around the device legs of every sub-batch
     }
 };
 
-// Everything behind phase 1: waits for this thread's previous decode job (the call's one host wait), inflates into the pinned
-// staging, checks what only the streams show, then enqueues on `s`: all tables in one copy; per sub-batch its streams in one
-// copy, one unfilter launch per filter unit, one convert launch per kernel form.  Nothing is enqueued after a refusal.
-int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs = nullptr)
+// The tables of a batch in the pinned staging: descriptions, runs, block tables, a palette table per palette image; every section
+// starts at a multiple of 16.  Reserves every buffer the launches of a batch use: nothing has been handed out yet.
+struct BatchTables {
+    size_t runs_at = 0, list_at = 0, tables_at = 0, up_bytes = 0;
+};
+int batch_tables(Context &c, const DecodeBatch &b, const DecodeBatchPlan &p, const uint8_t *d_pixels, BatchTables &t)
 {
     const uint32_t batch = static_cast<uint32_t>(b.files.size());
-    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
-    HIP_TRY(hipEventSynchronize(c.u_done)); // the job before may still be reading the pinned buffers this one is about to write
     int rc;
-    if ((rc = c.u_inflated.reserve(b.staging))) return rc;
-    if ((rc = batch_inflate(b, c.u_inflated.as<uint8_t>(), flags))) return rc;
-    DecodeBatchPlan p;
-    decode_batch_plan(b, reinterpret_cast<uintptr_t>(d_pixels), p);
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
-    note_route(route::PNG_DECODE_BATCH | (subs > 1 ? route::SUB_BATCHES : 0));
-
-    // the tables: descriptions, runs, block tables, a palette table per palette image; every section starts at a multiple of 16
     uint32_t palettes = 0;
     for (const BatchFile &x : b.files) palettes += x.f.color_type == CT_INDEXED;
     const size_t images_bytes = static_cast<size_t>(batch) * sizeof(pixo_dev::UnfilterBatchImage), runs_at = images_bytes;
@@ -518,6 +516,45 @@ int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *
     }
     if (!p.runs.empty()) std::memcpy(stage + runs_at, p.runs.data(), p.runs.size() * sizeof(pixo_dev::UnfilterBatchRun));
     if (!p.list.empty()) std::memcpy(stage + list_at, p.list.data(), p.list.size() * sizeof(uint32_t));
+    t.runs_at = runs_at; t.list_at = list_at; t.tables_at = tables_at; t.up_bytes = up_bytes;
+    return PIXO_OK;
+}
+// One conversion launch of the plan
+int launch_convert(Context &c, const DecodeBatchPlan::Convert &cv, const BatchTables &t, uint8_t *d_pixels, hipStream_t s)
+{
+    const uint8_t *d_tables = c.u_tables.as<uint8_t>();
+    pixo_dev::UnconvertBatchArgs v;
+    v.rows = c.u_rows.as<uint8_t>(); v.out = d_pixels; v.images = reinterpret_cast<const pixo_dev::UnfilterBatchImage *>(d_tables);
+    v.list = reinterpret_cast<const uint32_t *>(d_tables + t.list_at) + cv.first;
+    v.n = static_cast<uint32_t>(cv.n); v.kernel = cv.kernel;
+    v.tables = reinterpret_cast<const uint32_t *>(d_tables + t.tables_at); v.max_items = cv.max_items;
+    HIP_TRY(pixo_dev::launch_png_convert_batch(v, s));
+    return PIXO_OK;
+}
+
+int decode_batch_device_inflate(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs);
+
+// Everything behind phase 1: waits for this thread's previous decode job (the call's one host wait), inflates into the pinned
+// staging, checks what only the streams show, then enqueues on `s`: all tables in one copy; per sub-batch its streams in one
+// copy, one unfilter launch per filter unit, one convert launch per kernel form.  Nothing is enqueued after a refusal.
+int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs = nullptr)
+{
+    const uint32_t batch = static_cast<uint32_t>(b.files.size());
+    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(c.u_done)); // the job before may still be reading the pinned buffers this one is about to write
+    if (flags & PIXO_DECODE_DEVICE_INFLATE) return decode_batch_device_inflate(c, b, flags, d_pixels, s, legs);
+    int rc;
+    if ((rc = c.u_inflated.reserve(b.staging))) return rc;
+    if ((rc = batch_inflate(b, c.u_inflated.as<uint8_t>(), flags))) return rc;
+    DecodeBatchPlan p;
+    decode_batch_plan(b, reinterpret_cast<uintptr_t>(d_pixels), p);
+    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
+    note_route(route::PNG_DECODE_BATCH | (subs > 1 ? route::SUB_BATCHES : 0));
+
+    BatchTables t;
+    if ((rc = batch_tables(c, b, p, d_pixels, t))) return rc;
+    const size_t runs_at = t.runs_at, up_bytes = t.up_bytes;
+    uint8_t *stage = c.h_utables.as<uint8_t>();
 
     const uint8_t *d_tables = c.u_tables.as<uint8_t>();
     const pixo_dev::UnfilterBatchImage *d_images = reinterpret_cast<const pixo_dev::UnfilterBatchImage *>(d_tables);
@@ -539,17 +576,248 @@ int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *
             HIP_TRY(pixo_dev::launch_png_unfilter_batch(u, s));
         }
         if (legs && (rc = legs->mark(s))) return rc;
-        for (; iv < p.convert.size() && p.convert[iv].sub == k; ++iv) {
-            pixo_dev::UnconvertBatchArgs v;
-            v.rows = c.u_rows.as<uint8_t>(); v.out = d_pixels; v.images = d_images;
-            v.list = reinterpret_cast<const uint32_t *>(d_tables + list_at) + p.convert[iv].first;
-            v.n = static_cast<uint32_t>(p.convert[iv].n); v.kernel = p.convert[iv].kernel;
-            v.tables = reinterpret_cast<const uint32_t *>(d_tables + tables_at); v.max_items = p.convert[iv].max_items;
-            HIP_TRY(pixo_dev::launch_png_convert_batch(v, s));
-        }
+        for (; iv < p.convert.size() && p.convert[iv].sub == k; ++iv)
+            if ((rc = launch_convert(c, p.convert[iv], t, d_pixels, s))) return rc;
         if (legs && (rc = legs->mark(s))) return rc;
         HIP_TRY(hipEventRecord(c.u_done, s));
     }
+    return PIXO_OK;
+}
+
+// ---- PIXO_DECODE_DEVICE_INFLATE ------------------------------------------------------------------------------------------------
+// The zlib header checks of inflate_zlib (the 6-byte minimum, method, header checksum, preset dictionary): what the kernel never sees
+bool zlib_head_sound(const PngFile &f)
+{
+    if (f.idat_len < 6) return false;
+    const uint8_t cmf = f.idat[0], flg = f.idat[1];
+    return (cmf & 0x0F) == 8 && ((static_cast<unsigned>(cmf) << 8) | flg) % 31 == 0 && !(flg & 0x20);
+}
+// Before a device is touched: a file whose zlib header is unsound makes the call end as it does without the flag — the host
+// inflates into ordinary memory and the failing file with the lowest index decides, this one or one in front of it.
+int batch_zlib_heads(DecodeBatch &b, uint32_t flags)
+{
+    bool sound = true;
+    for (const BatchFile &x : b.files) sound = sound && zlib_head_sound(x.f);
+    if (sound) return PIXO_OK;
+    uint8_t *stage = static_cast<uint8_t *>(std::malloc(std::max<size_t>(static_cast<size_t>(b.staging), 1)));
+    if (!stage) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    const int rc = batch_inflate(b, stage, flags);
+    std::free(stage);
+    return rc ? rc : invalid("invalid zlib stream"); // (never: the host inflate makes the same header checks)
+}
+
+// A sub-batch's compressed streams in the pinned staging as the kernel wants them: every stream's DEFLATE bytes start at a
+// multiple of 16 and are followed by at least 16 zero bytes.
+inline uint64_t inflate_input_bytes(const PngFile &f) { return round16(f.idat_len - 6) + pixo_dev::kInflateInputAlign; }
+
+// The batch job with the inflates on the device.  Per sub-batch: descriptions and compressed streams up in one copy, the inflate
+// launch, the gather of the filter bytes, status records and filter bytes down in one copy, ONE host wait; then the host decides
+// in index order (a stream the device does not vouch for is inflated again here: the host's result is the truth), the runs of
+// rows go up, and the unfilter and convert launches follow as without the flag.  The wait for sub-batch k's records also covers
+// everything enqueued before it, so the pinned staging (h_zin, h_uruns, u_inflated) is free to be rewritten for sub-batch k.
+int decode_batch_device_inflate(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs)
+{
+    using pixo_dev::FilterGatherImage;
+    using pixo_dev::InflateStatus;
+    using pixo_dev::InflateStream;
+    int rc;
+    DecodeBatchPlan p; // (no runs are known yet: the cuts, the rows' places and the conversion launches do not need them)
+    decode_batch_plan(b, reinterpret_cast<uintptr_t>(d_pixels), p);
+    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
+    note_route(route::PNG_DECODE_BATCH | route::PNG_INFLATE_DEVICE | (subs > 1 ? route::SUB_BATCHES : 0));
+    BatchTables t;
+    if ((rc = batch_tables(c, b, p, d_pixels, t))) return rc;
+    // the largest sub-batch's staging: descriptions + padded inputs; records + filter bytes; runs (a run but the last has pass_rows rows)
+    size_t zin_bytes = 0, zout_bytes = 0, runs_bytes = 0;
+    for (uint32_t k = 0; k < subs; ++k) {
+        size_t in = 0, rows = 0, runs = 0;
+        for (uint32_t i = p.sub_first[k]; i < p.sub_first[k + 1]; ++i) {
+            in += inflate_input_bytes(b.files[i].f);
+            rows += b.files[i].f.height;
+            runs += b.files[i].f.height / pixo_dev::kUnfilterPassRows + 1;
+        }
+        const size_t m = p.sub_first[k + 1] - p.sub_first[k];
+        zin_bytes = std::max(zin_bytes, m * (sizeof(InflateStream) + sizeof(FilterGatherImage)) + in);
+        zout_bytes = std::max(zout_bytes, m * sizeof(InflateStatus) + rows);
+        runs_bytes = std::max(runs_bytes, runs * sizeof(pixo_dev::UnfilterBatchRun));
+    }
+    if ((rc = c.h_zin.reserve(zin_bytes)) || (rc = c.u_zin.reserve(zin_bytes)) || (rc = c.u_zout.reserve(zout_bytes)) ||
+        (rc = c.h_zout.reserve(zout_bytes)) || (rc = c.h_uruns.reserve(runs_bytes)) || (rc = c.u_runs.reserve(runs_bytes)))
+        return rc;
+
+    const uint8_t *d_tables = c.u_tables.as<uint8_t>();
+    const pixo_dev::UnfilterBatchImage *h_images = c.h_utables.as<pixo_dev::UnfilterBatchImage>();
+    HIP_TRY(hipMemcpyAsync(c.u_tables.p, c.h_utables.p, t.up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c.u_done, s));
+    b.threads = 1;
+    size_t iv = 0;
+    for (uint32_t k = 0; k < subs; ++k) {
+        const uint32_t first = p.sub_first[k], end = p.sub_first[k + 1], m = end - first;
+        const auto t0 = std::chrono::steady_clock::now();
+        uint8_t *zin = c.h_zin.as<uint8_t>();
+        InflateStream *streams = reinterpret_cast<InflateStream *>(zin);
+        FilterGatherImage *gather = reinterpret_cast<FilterGatherImage *>(zin + m * sizeof(InflateStream));
+        const size_t input_at = m * (sizeof(InflateStream) + sizeof(FilterGatherImage));
+        uint64_t in_at = 0, filters_at = 0;
+        uint32_t max_height = 0;
+        for (uint32_t i = first; i < end; ++i) {
+            const BatchFile &x = b.files[i];
+            const uint64_t in_len = x.f.idat_len - 6, padded = inflate_input_bytes(x.f);
+            streams[i - first] = {in_at, in_len, h_images[i].stream_at, x.expected};
+            gather[i - first] = {h_images[i].stream_at, x.row + 1, filters_at, x.f.height, 0};
+            std::memcpy(zin + input_at + in_at, x.f.idat + 2, in_len);
+            std::memset(zin + input_at + in_at + in_len, 0, padded - in_len);
+            in_at += padded;
+            filters_at += x.f.height;
+            max_height = std::max(max_height, x.f.height);
+        }
+        if (legs && (rc = legs->mark(s))) return rc;
+        HIP_TRY(hipMemcpyAsync(c.u_zin.p, zin, input_at + in_at, hipMemcpyHostToDevice, s));
+        pixo_dev::InflateArgs ia;
+        ia.input = c.u_zin.as<uint8_t>() + input_at; ia.out = c.u_stream.as<uint8_t>();
+        ia.streams = c.u_zin.as<InflateStream>(); ia.status = c.u_zout.as<InflateStatus>(); ia.n = m;
+        HIP_TRY(pixo_dev::launch_png_inflate(ia, s));
+        pixo_dev::FilterGatherArgs ga;
+        ga.stream = c.u_stream.as<uint8_t>(); ga.filters = c.u_zout.as<uint8_t>() + m * sizeof(InflateStatus);
+        ga.images = reinterpret_cast<const FilterGatherImage *>(c.u_zin.as<uint8_t>() + m * sizeof(InflateStream)); ga.n = m; ga.max_height = max_height;
+        HIP_TRY(pixo_dev::launch_png_filter_gather(ga, s));
+        HIP_TRY(hipMemcpyAsync(c.h_zout.p, c.u_zout.p, m * sizeof(InflateStatus) + filters_at, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(c.u_done, s));
+        HIP_TRY(hipEventSynchronize(c.u_done)); // the sub-batch's one host wait
+        const InflateStatus *status = c.h_zout.as<InflateStatus>();
+        const uint8_t *filters = c.h_zout.as<uint8_t>() + m * sizeof(InflateStatus);
+
+        // what the device does not vouch for is inflated again by the host, on the pool (or on the caller)
+        std::vector<uint32_t> suspect;
+        std::vector<uint64_t> redo_at;
+        uint64_t redo_bytes = 0;
+        for (uint32_t i = first; i < end; ++i) {
+            const PngFile &f = b.files[i].f;
+            if (status[i - first].verdict == pixo_pngi::OK && status[i - first].adler == be32(f.idat + f.idat_len - 4)) continue;
+            suspect.push_back(i);
+            redo_at.push_back(redo_bytes);
+            redo_bytes += round16(b.files[i].expected);
+        }
+        if (!suspect.empty()) {
+            if ((rc = c.u_inflated.reserve(redo_bytes))) return rc;
+            const uint32_t threads = (flags & PIXO_DECODE_ONE_THREAD) ? 1u : std::min<uint32_t>(static_cast<uint32_t>(suspect.size()), kDecodeBatchThreads);
+            b.threads = std::max(b.threads, threads);
+            std::atomic<uint32_t> next{0};
+            run_on_threads(threads, [&](unsigned) {
+                for (uint32_t j; (j = next.fetch_add(1, std::memory_order_relaxed)) < suspect.size();) {
+                    BatchFile &x = b.files[suspect[j]];
+                    x.kind = pixo_inflate::inflate_zlib(x.f.idat, x.f.idat_len, c.u_inflated.as<uint8_t>() + redo_at[j], x.expected, &x.msg);
+                }
+            });
+        }
+        // ... and then, in index order, the checks in the order they have without the flag
+        uint64_t at = 0;
+        for (uint32_t i = first, j = 0; i < end; at += b.files[i].f.height, ++i) {
+            BatchFile &x = b.files[i];
+            const std::string where = " (image " + std::to_string(i) + ")";
+            const uint8_t *bytes = filters + at;
+            uint64_t stride = 1;
+            if (j < suspect.size() && suspect[j] == i) {
+                if ((rc = inflate_status(x.kind, x.msg))) return fail(rc, t_error + where);
+                bytes = c.u_inflated.as<uint8_t>() + redo_at[j];
+                stride = x.row + 1;
+                HIP_TRY(hipMemcpyAsync(c.u_stream.as<uint8_t>() + h_images[i].stream_at, bytes, x.expected, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipEventRecord(c.u_done, s));
+                note_route(route::PNG_INFLATE_HOST_REDO);
+                ++j;
+            }
+            uint32_t bad_row = 0;
+            x.runs = find_runs(bytes, x.f.height, stride, &bad_row);
+            if (bad_row < x.f.height) return fail(invalid("invalid filter type: " + std::to_string(bytes[bad_row * stride])), t_error + where);
+            if (x.f.color_type == CT_INDEXED && !x.f.has_plte) return fail(invalid("missing PLTE chunk"), t_error + where);
+        }
+        // the runs of this sub-batch by filter unit, as decode_batch_plan lays them out
+        pixo_dev::UnfilterBatchRun *runs = c.h_uruns.as<pixo_dev::UnfilterBatchRun>();
+        struct Launch { uint32_t unit; size_t first_run, n_runs; };
+        std::vector<Launch> launches;
+        size_t n_runs = 0;
+        for (const uint32_t unit : kFilterUnits) {
+            const size_t run0 = n_runs;
+            for (uint32_t i = first; i < end; ++i) {
+                if (filter_unit(b.files[i].f.color_type, b.files[i].f.depth) != unit) continue;
+                const std::vector<uint32_t> &pairs = b.files[i].runs.pairs;
+                for (size_t r = 0; r + 1 < pairs.size(); r += 2) runs[n_runs++] = {i, pairs[r], pairs[r + 1], 0};
+            }
+            if (n_runs > run0) launches.push_back({unit, run0, n_runs - run0});
+        }
+        b.inflate_ms += ms_since(t0);
+        HIP_TRY(hipMemcpyAsync(c.u_runs.p, runs, n_runs * sizeof(pixo_dev::UnfilterBatchRun), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(c.u_done, s));
+        if (legs && (rc = legs->mark(s))) return rc;
+        for (const Launch &l : launches) {
+            pixo_dev::UnfilterBatchArgs u;
+            u.stream = c.u_stream.as<uint8_t>(); u.rows = c.u_rows.as<uint8_t>();
+            u.images = reinterpret_cast<const pixo_dev::UnfilterBatchImage *>(d_tables);
+            u.runs = c.u_runs.as<pixo_dev::UnfilterBatchRun>() + l.first_run;
+            u.n_runs = static_cast<uint32_t>(l.n_runs); u.bpp = l.unit;
+            HIP_TRY(pixo_dev::launch_png_unfilter_batch(u, s));
+        }
+        if (legs && (rc = legs->mark(s))) return rc;
+        for (; iv < p.convert.size() && p.convert[iv].sub == k; ++iv)
+            if ((rc = launch_convert(c, p.convert[iv], t, d_pixels, s))) return rc;
+        if (legs && (rc = legs->mark(s))) return rc;
+        HIP_TRY(hipEventRecord(c.u_done, s));
+    }
+    return PIXO_OK;
+}
+
+// The inflate kernel alone (pixo_hip_debug_zlib_inflate_batch_device)
+int inflate_batch_debug(Context &c, const pixo_png_file *streams, uint32_t n, const uint64_t *expected, uint8_t *out, const uint64_t *out_at,
+                        uint32_t *verdict, uint64_t *produced, uint32_t *adler, double *kernel_ms)
+{
+    using pixo_dev::InflateStatus;
+    using pixo_dev::InflateStream;
+    int rc;
+    uint64_t block = 0, in_bytes = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const std::string where = " (image " + std::to_string(i) + ")";
+        if (!streams[i].data) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'data'" + where);
+        if (streams[i].len < 6) return fail(invalid("zlib stream too short"), t_error + where);
+        if (out_at[i] > (uint64_t{1} << 40) || expected[i] > (uint64_t{1} << 40)) return fail(PIXO_ERR_COMPRESSION, "Compression error: region too large" + where);
+        block = std::max(block, out_at[i] + expected[i]);
+        in_bytes += round16(streams[i].len - 6) + pixo_dev::kInflateInputAlign;
+    }
+    if (block) PIXO_REQUIRE(out);
+    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(c.u_done));
+    const size_t input_at = static_cast<size_t>(n) * sizeof(InflateStream), status_bytes = static_cast<size_t>(n) * sizeof(InflateStatus);
+    if ((rc = c.h_zin.reserve(input_at + in_bytes)) || (rc = c.u_zin.reserve(input_at + in_bytes)) || (rc = c.u_zout.reserve(status_bytes)) ||
+        (rc = c.h_zout.reserve(status_bytes)) || (rc = c.u_stream.reserve(block + pixo_dev::kUnfilterPiece)))
+        return rc;
+    uint8_t *zin = c.h_zin.as<uint8_t>();
+    uint64_t in_at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t in_len = streams[i].len - 6, padded = round16(in_len) + pixo_dev::kInflateInputAlign;
+        reinterpret_cast<InflateStream *>(zin)[i] = {in_at, in_len, out_at[i], expected[i]};
+        std::memcpy(zin + input_at + in_at, streams[i].data + 2, in_len);
+        std::memset(zin + input_at + in_at + in_len, 0, padded - in_len);
+        in_at += padded;
+    }
+    hipStream_t s = c.stream;
+    Legs timed;
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreate(&timed.e[i]));
+    HIP_TRY(hipMemcpyAsync(c.u_zin.p, zin, input_at + in_at, hipMemcpyHostToDevice, s));
+    if (block) HIP_TRY(hipMemcpyAsync(c.u_stream.p, out, block, hipMemcpyHostToDevice, s));
+    pixo_dev::InflateArgs ia;
+    ia.input = c.u_zin.as<uint8_t>() + input_at; ia.out = c.u_stream.as<uint8_t>();
+    ia.streams = c.u_zin.as<InflateStream>(); ia.status = c.u_zout.as<InflateStatus>(); ia.n = n;
+    HIP_TRY(hipEventRecord(timed.e[0], s));
+    HIP_TRY(pixo_dev::launch_png_inflate(ia, s));
+    HIP_TRY(hipEventRecord(timed.e[1], s));
+    HIP_TRY(hipMemcpyAsync(c.h_zout.p, c.u_zout.p, status_bytes, hipMemcpyDeviceToHost, s));
+    if (block) HIP_TRY(hipMemcpyAsync(out, c.u_stream.p, block, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(c.u_done, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, timed.e[0], timed.e[1]));
+    *kernel_ms = ms;
+    const InflateStatus *status = c.h_zout.as<InflateStatus>();
+    for (uint32_t i = 0; i < n; ++i) { verdict[i] = status[i].verdict; produced[i] = status[i].produced; adler[i] = status[i].adler; }
     return PIXO_OK;
 }
 
@@ -568,6 +836,7 @@ int decode_batch_to_block(const pixo_png_file *files, uint32_t batch, uint32_t f
     int rc = batch_walk(files, batch, true, b);
     if (rc) return rc;
     report(b, images);
+    if ((flags & PIXO_DECODE_DEVICE_INFLATE) && (rc = batch_zlib_heads(b, flags))) return rc;
     PIXO_THREAD_CONTEXT(c);
     const size_t n = static_cast<size_t>(b.total);
     if ((rc = reserve16(c.u_out, n))) return rc;
@@ -624,6 +893,7 @@ int pixo_hip_png_decode_batch_device(const pixo_png_file *files, uint32_t batch,
     report(b, images);
     if (capacity < b.total) return too_small(static_cast<size_t>(b.total));
     PIXO_REQUIRE(d_pixels);
+    if ((flags & PIXO_DECODE_DEVICE_INFLATE) && (rc = batch_zlib_heads(b, flags))) return rc;
     Context *c = nullptr;
     if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -740,6 +1010,26 @@ int pixo_hip_zlib_inflate(const uint8_t *data, size_t len, uint8_t *out, size_t 
 }
 
 uint32_t pixo_hip_png_unfilter_pass_rows(void) { return pixo_dev::kUnfilterPassRows; }
+uint32_t pixo_hip_png_inflate_step_tokens(void) { return pixo_pngi::kStepTokens; }
+uint32_t pixo_hip_png_inflate_window_bytes(void) { return pixo_pngi::kWindowBytes; }
+uint32_t pixo_hip_png_inflate_far_distance(void) { return pixo_pngi::kFarDistance; }
+uint32_t pixo_hip_png_inflate_stored_chunk(void) { return pixo_pngi::kStoredChunk; }
+
+int pixo_hip_debug_zlib_inflate_batch_device(const pixo_png_file *streams, uint32_t n, const uint64_t *expected, uint8_t *out, const uint64_t *out_at,
+                                             uint32_t *verdict, uint64_t *produced, uint32_t *adler, double *kernel_ms)
+{
+    PIXO_REQUIRE(streams);
+    const int rc = batch_in_range(n);
+    if (rc) return rc;
+    PIXO_REQUIRE(expected);
+    PIXO_REQUIRE(out_at);
+    PIXO_REQUIRE(verdict);
+    PIXO_REQUIRE(produced);
+    PIXO_REQUIRE(adler);
+    PIXO_REQUIRE(kernel_ms);
+    PIXO_THREAD_CONTEXT(c);
+    return inflate_batch_debug(c, streams, n, expected, out, out_at, verdict, produced, adler, kernel_ms);
+}
 
 int pixo_hip_debug_png_decode_timed(const uint8_t *file, size_t len, double ms[7], uint64_t counts[3])
 {

@@ -52,6 +52,8 @@ enum : uint64_t {
     PNG_BATCH_FILTER = 1ull << 40, // ... and one filter launch over all their rows in front of it
     RESIZE_BATCH = 1ull << 41,     // resize batch entries: one launch per pass over all images of a sub-batch (beside the algorithm's bit)
     PNG_DECODE_BATCH = 1ull << 42, // PNG decode batch entries: one unfilter launch per filter unit and one convert launch per kernel form a sub-batch
+    PNG_INFLATE_DEVICE = 1ull << 43, // ... with PIXO_DECODE_DEVICE_INFLATE: the streams of a sub-batch inflated in one launch (png_inflate.hip)
+    PNG_INFLATE_HOST_REDO = 1ull << 44, // ... a stream the device did not vouch for was inflated again by the host, whose bytes replaced it
 };
 }
 

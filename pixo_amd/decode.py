@@ -1,6 +1,7 @@
 """`pixo::decode` on the MI355X (reference src/decode/png.rs): a PNG file -> 8-bit pixels.  The chunk walk, its checks and the
 inflate run on the host, in the reference's order and with its messages; row reconstruction and the conversion to pixels run
-on the device.  Mirrors `PngImage` and `decode_png`; `decode_png_info` and `decode_png_device` are what a caller needs to keep
+on the device — and, for the batch entries with `device_inflate=True`, the inflate too (one wavefront per stream; the single entries
+keep the host inflate: one stream is one wavefront).  Mirrors `PngImage` and `decode_png`; `decode_png_info` and `decode_png_device` are what a caller needs to keep
 the pixels in device memory for `resize.resize_device`, `jpeg.encode_device` and `png.encode_device`.  JPEG decode is not
 provided.  No CPU fallback."""
 import ctypes as C
@@ -77,6 +78,14 @@ def decode_png_device(data, out=None, stream=None):
 ROUTES = {"PNG_DECODE_BATCH": 42}  # the route record's bit of the batch entries (csrc/routes.hpp; read with jpeg.routes)
 ROUTE_PNG_DECODE_BATCH = 1 << ROUTES["PNG_DECODE_BATCH"]
 ONE_THREAD = 1  # PIXO_DECODE_ONE_THREAD
+DEVICE_INFLATE = 2  # PIXO_DECODE_DEVICE_INFLATE: the batch entries inflate on the device (opt-in)
+# ... and the bits of that path (a dict of its own: ROUTES above is the complete list of the batch entries' own bit)
+INFLATE_ROUTES = {"PNG_INFLATE_DEVICE": 43, "PNG_INFLATE_HOST_REDO": 44}
+INFLATE_OK, INFLATE_FAILED, INFLATE_NEEDS_HOST = 0, 1, 2  # the device verdicts (png_inflate_math.h)
+
+
+def _flags(one_thread, device_inflate) -> int:
+    return (ONE_THREAD if one_thread else 0) | (DEVICE_INFLATE if device_inflate else 0)
 
 
 def _files_c(files):
@@ -102,23 +111,25 @@ def decode_png_batch_info(files):
     return [(im.width, im.height, ColorType(im.color_type), im.offset) for im in images[:len(held)]], total.value
 
 
-def decode_png_batch(files, one_thread=False) -> list:
+def decode_png_batch(files, one_thread=False, device_inflate=False) -> list:
     """PNG files (bytes) -> [PngImage] with host pixels, image i what decode_png makes of file i.  The inflates run on up to 8
-    host threads unless `one_thread`."""
+    host threads unless `one_thread` — or, with `device_inflate`, on the device, all streams of a sub-batch in one launch; the host
+    then inflates again only the streams the device did not vouch for (on those threads).  The images are the same bytes."""
     L = _lib.load()
     arr, held = _files_c(files)
     images = (_lib.PngImageC * max(len(held), 1))()
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
-    _lib.check(L.pixo_hip_png_decode_batch(arr, len(held), ONE_THREAD if one_thread else 0, C.byref(out), C.byref(n), images))
+    _lib.check(L.pixo_hip_png_decode_batch(arr, len(held), _flags(one_thread, device_inflate), C.byref(out), C.byref(n), images))
     block = _lib.take(L, out, n)
     return [PngImage(im.width, im.height, block[im.offset:im.offset + _bytes_of(im)], ColorType(im.color_type)) for im in images[:len(held)]]
 
 
-def decode_png_batch_device(files, out=None, stream=None, one_thread=False) -> list:
+def decode_png_batch_device(files, out=None, stream=None, one_thread=False, device_inflate=False) -> list:
     """PNG files (host bytes) -> [(uint8 tensor view (height, width, channels), ColorType)], views into ONE uint8 device
     tensor: `out` (contiguous, any alignment; the bytes between two images are left as they are), or one allocated from
     decode_png_batch_info.  Enqueue only, ordered like decode_png_device; BufferTooSmall carries the total in `.needed`.  The
-    views are what resize.resize_batch_device takes as sources (grouped by colour type)."""
+    views are what resize.resize_batch_device takes as sources (grouped by colour type).  `device_inflate`: as decode_png_batch;
+    the call then waits on the host once per sub-batch, and after a refusal that only the inflated streams show `out` is unspecified."""
     import torch
     L = _lib.load()
     arr, held = _files_c(files)
@@ -128,7 +139,7 @@ def decode_png_batch_device(files, out=None, stream=None, one_thread=False) -> l
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
-    rc = L.pixo_hip_png_decode_batch_device(arr, len(held), ONE_THREAD if one_thread else 0, out.data_ptr(), _lib.nbytes(out), images,
+    rc = L.pixo_hip_png_decode_batch_device(arr, len(held), _flags(one_thread, device_inflate), out.data_ptr(), _lib.nbytes(out), images,
                                             C.c_void_p(stream) if stream else None)
     last = images[len(held) - 1] if held else None
     _lib.check(rc, needed=last.offset + _bytes_of(last) if rc == -9 else None)
@@ -159,3 +170,38 @@ def inflate_zlib(data, expected: int) -> bytes:
     out = np.empty(max(expected, 1), np.uint8)
     _lib.check(L.pixo_hip_zlib_inflate(f.ctypes.data if f.size else out.ctypes.data, f.size, out.ctypes.data, expected))
     return out[:expected].tobytes()
+
+
+def inflate_step_tokens() -> int:
+    """Tokens a step of the device inflate holds at most (png_inflate_math.h kStepTokens)."""
+    return int(_lib.load().pixo_hip_png_inflate_step_tokens())
+
+
+def inflate_window_bytes() -> int:
+    """Bytes of the device inflate's LDS ring (kWindowBytes)."""
+    return int(_lib.load().pixo_hip_png_inflate_window_bytes())
+
+
+def inflate_far_distance() -> int:
+    """A match further back than this closes its step (kFarDistance)."""
+    return int(_lib.load().pixo_hip_png_inflate_far_distance())
+
+
+def inflate_stored_chunk() -> int:
+    """Bytes of a stored block the device inflate copies at a time (kStoredChunk)."""
+    return int(_lib.load().pixo_hip_png_inflate_stored_chunk())
+
+
+def inflate_zlib_batch_debug(streams, expected, out, out_at):
+    """The inflate kernel alone (pixo_hip_debug_zlib_inflate_batch_device): zlib streams (bytes, of any origin) inflated on the
+    device into `out` — a uint8 numpy array the caller has filled, at least max(out_at[i] + expected[i]) bytes, uploaded whole and
+    downloaded again — stream i into [out_at[i], out_at[i] + expected[i]).  No host inflate behind it.  Returns
+    (verdicts, produced, adlers, kernel_ms)."""
+    L = _lib.load()
+    arr, held = _files_c(streams)
+    n = len(held)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= max([a + e for a, e in zip(out_at, expected)] + [0])
+    exp, at = (C.c_uint64 * max(n, 1))(*expected), (C.c_uint64 * max(n, 1))(*out_at)
+    verdict, produced, adler, ms = (C.c_uint32 * max(n, 1))(), (C.c_uint64 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), C.c_double()
+    _lib.check(L.pixo_hip_debug_zlib_inflate_batch_device(arr, n, exp, out.ctypes.data, at, verdict, produced, adler, C.byref(ms)))
+    return list(verdict[:n]), list(produced[:n]), list(adler[:n]), ms.value

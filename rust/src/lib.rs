@@ -108,6 +108,9 @@ struct CPngFile { data: *const u8, len: usize }
 struct CPngImage { offset: u64, width: u32, height: u32, color_type: u8, reserved: [u8; 7] }
 /// `PIXO_DECODE_ONE_THREAD`: the bit of a decode batch's `flags` that keeps the inflates on the calling thread
 pub const DECODE_ONE_THREAD: u32 = 1;
+/// `PIXO_DECODE_DEVICE_INFLATE`: the bit that makes a decode batch inflate on the device, one wavefront per stream (opt-in;
+/// the host inflates again only the streams the device does not vouch for; the images are the same bytes)
+pub const DECODE_DEVICE_INFLATE: u32 = 2;
 
 extern "C" {
     // include/pixo_hip.h
@@ -447,10 +450,14 @@ pub mod decode {
     /// all of them.  Image i is what `decode_png(files[i])` returns, in its own colour type; the first file the walk refuses,
     /// or else the lowest-indexed file whose stream is faulty, decides the error, its index in the message.
     pub fn decode_png_batch(files: &[&[u8]], one_thread: bool) -> Result<Vec<PngImage>> {
+        decode_png_batch_flags(files, if one_thread { DECODE_ONE_THREAD } else { 0 })
+    }
+
+    /// `decode_png_batch` with the batch's `flags` spelled out: `DECODE_ONE_THREAD`, `DECODE_DEVICE_INFLATE`, or both.
+    pub fn decode_png_batch_flags(files: &[&[u8]], flags: u32) -> Result<Vec<PngImage>> {
         let c_files: Vec<CPngFile> = files.iter().map(|f| CPngFile { data: f.as_ptr(), len: f.len() }).collect();
         let mut images = vec![CPngImage { offset: 0, width: 0, height: 0, color_type: 0, reserved: [0; 7] }; files.len().max(1)];
         let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
-        let flags = if one_thread { DECODE_ONE_THREAD } else { 0 };
         let list = if files.is_empty() { std::ptr::null() } else { c_files.as_ptr() };
         let rc = unsafe { pixo_hip_png_decode_batch(list, files.len() as u32, flags, &mut p, &mut n, images.as_mut_ptr()) };
         if rc != 0 { return Err(error_of(rc)); }

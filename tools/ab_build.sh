@@ -27,7 +27,7 @@ ALL="$(sed -n 's/^KERNELS *= *//p' Makefile) $(sed -n 's/^HOST *= *//p' Makefile
 PRELOAD="-mllvm -amdgpu-kernarg-preload-count=14"
 preload() { { [ $1 = jpeg_kernels.hip ] || [ $1 = jpeg_pixels_code.hip ]; } && echo "$PRELOAD" || true; }
 for f in $ALL; do
-  o=$OBJ/${f%.*}.o
+  o=$OBJ/$f.o   # (the whole name: png_inflate.hip and png_inflate.cpp share a stem)
   if [ ! -f $o ] || [ $f -nt $o ] || [ -n "$(find . ../../include -name '*.h*' -newer $o | head -1)" ]; then /opt/rocm/bin/hipcc $FLAGS $(preload $f) -c $f -o $o & fi
 done
 wait
@@ -37,9 +37,9 @@ while [ $# -ge 2 ]; do
     case " $SRC " in
       *" $f "*)
         case "$2" in *NO_PRELOAD*) P="";; *) P="$(preload $f)";; esac
-        /opt/rocm/bin/hipcc $FLAGS $P $2 -c $f -o $OBJ/${f%.*}_$1.o
-        OBJS="$OBJS $OBJ/${f%.*}_$1.o";;
-      *) OBJS="$OBJS $OBJ/${f%.*}.o";;
+        /opt/rocm/bin/hipcc $FLAGS $P $2 -c $f -o $OBJ/${f}_$1.o
+        OBJS="$OBJS $OBJ/${f}_$1.o";;
+      *) OBJS="$OBJS $OBJ/$f.o";;
     esac
   done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../../tools/ab/ab_$1.so $OBJS
