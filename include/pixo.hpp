@@ -20,6 +20,7 @@
 //   (wasm) resizeImage                 wasm.rs:183      pixo::resize_image
 //   (a loop over pixo::resize::resize)                  pixo::resize::resize_batch / resize_batch_device
 //   (a loop over pixo::decode::decode_png)              pixo::decode::decode_png_batch
+//   (a loop over pixo::png::encode, one size each)      pixo::png::encode_images
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -314,6 +315,29 @@ struct Prepared {
 [[nodiscard]] inline std::vector<std::vector<uint8_t>> encode_batch(const std::vector<uint8_t> &data, const PngOptions &options, uint32_t batch)
 {
     return encode_batch(data.data(), data.size(), options, batch);
+}
+// Images of individual sizes and colour types anywhere in `block` (what decode::decode_png_batch works from: image i at
+// images[i].offset) -> their files, file i byte for byte what `encode` makes of image i with `options` at its width, height
+// and colour type; the options' own are not read (contract: pixo_hip.h).  `quantization` is passed on when it is not Off.
+[[nodiscard]] inline std::vector<std::vector<uint8_t>> encode_images(const uint8_t *block, size_t len, const std::vector<pixo_png_image> &images,
+                                                                     const PngOptions &options)
+{
+    const pixo_png_options c = options.to_c();
+    const pixo_png_quantization q = options.quantization.to_c();
+    const uint32_t batch = static_cast<uint32_t>(images.size() > 0xFFFFFFFFull ? 0xFFFFFFFFull : images.size());
+    std::vector<uint8_t *> files(batch ? batch : 1, nullptr);
+    std::vector<size_t> lens(batch ? batch : 1, 0);
+    const pixo_png_image none{}; // (no images: the batch check answers, not the null check in front of it)
+    const int rc = pixo_hip_png_encode_images(block, len, images.empty() ? &none : images.data(), batch, &c, options.quantization.mode == QuantizationMode::Off ? nullptr : &q,
+                                              files.data(), lens.data());
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    struct Blocks { // (released also when a copy below throws)
+        std::vector<uint8_t *> &files;
+        ~Blocks() { for (uint8_t *f : files) pixo_hip_free(f); }
+    } blocks{files};
+    std::vector<std::vector<uint8_t>> out(batch);
+    for (uint32_t i = 0; i < batch; ++i) out[i].assign(files[i], files[i] + lens[i]);
+    return out;
 }
 } // namespace png
 

@@ -735,6 +735,48 @@ int pixo_hip_debug_zlib_inflate_batch_device(const pixo_png_file *streams, uint3
  * sub-batches), [4] the whole call.  The block is released again. */
 int pixo_hip_debug_png_decode_batch_timed(const pixo_png_file *files, uint32_t batch, uint32_t flags, double ms[5]);
 
+/* ---- PNG encode of images of individual sizes and colour types, anywhere in one block ---- */
+
+/* `batch` images anywhere in one block in HBM on the current HIP device: image i is images[i].width x images[i].height pixels
+ * of images[i].color_type at d_pixels + images[i].offset (any alignment, gaps and overlaps allowed, `reserved` not read) —
+ * what pixo_hip_png_decode_batch_device fills in.  `options` is a template: its width, height and color_type are NOT read;
+ * `quantization` may be NULL (lossless).  File i is byte for byte what pixo_hip_png_encode_device —
+ * pixo_hip_png_encode_lossy_device when `quantization` is given — returns for image i alone, called with `options` after image
+ * i's width, height and colour type are written into it: every strategy, preset, flag and colour type.
+ * Sub-batches as pixo_hip_png_encode_batch_device (at most 64 MiB of unreduced stream and 1024 chunks, greedy in index order,
+ * at least one image); the DEFLATE, its scan, the compaction and the CRC-32 run as one launch each over all images of a
+ * sub-batch.  The way in is each image's own: with quantisation, optimize_alpha, reduce_color_type and reduce_palette off
+ * and the image's AdaptiveFast not the sequential form (its own height decides), its rows are filtered in a launch shared with
+ * all images of its class — bytes per pixel, rows and first byte multiples of 4 or not, the filter kernel's form for its row
+ * length and resolved strategy, rows that fit the LDS stage or not — so the number of filter launches follows the classes
+ * present, not `batch`; every other image is prepared by itself, with its own host round trips.
+ * files[i] / lens[i] receive `batch` files, each a block the caller releases with pixo_hip_free; after a failure no block
+ * stays allocated.  Checks, all before the thread's context is touched, in this order: null options; an unknown
+ * options->filter_strategy; null d_pixels; null images; batch in 1..65535; `quantization` (when given) as
+ * pixo_hip_png_encode_lossy_device checks it; null files, null lens; then for i = 0, 1, ... image i: a zero side, a side above
+ * 2^24, a colour type above 3 (statuses and messages of pixo_hip_png_encode_device's checks), offset + the image's bytes
+ * beyond 2^62 (PIXO_ERR_COMPRESSION) — each with " (image i)" appended. */
+int pixo_hip_png_encode_images_device(const void *d_pixels, const pixo_png_image *images, uint32_t batch, const pixo_png_options *options,
+                                      const pixo_png_quantization *quantization, uint8_t **files, size_t *lens);
+/* The same, the files back to back in `arena` in host memory: sink semantics and the size query exactly as
+ * pixo_hip_png_encode_batch_device_into (offsets / lens filled in also with PIXO_ERR_BUFFER_TOO_SMALL; a device arena is
+ * refused).  Checks as above with `offsets` in the place of `files`. */
+int pixo_hip_png_encode_images_device_into(const void *d_pixels, const pixo_png_image *images, uint32_t batch, const pixo_png_options *options,
+                                           const pixo_png_quantization *quantization, uint8_t *arena, size_t capacity, size_t *offsets,
+                                           size_t *lens);
+/* ... and for a block in host memory (what pixo_hip_png_decode_batch returns): the checks above with `data` for d_pixels, then
+ * data_len below the furthest image's end: PIXO_ERR_INVALID_DATA_LENGTH, "expected <that end> bytes, got <data_len>". */
+int pixo_hip_png_encode_images(const uint8_t *data, size_t data_len, const pixo_png_image *images, uint32_t batch,
+                               const pixo_png_options *options, const pixo_png_quantization *quantization, uint8_t **files, size_t *lens);
+/* Tests: what the entries above decide, no GPU needed.  alignment (0..15): d_pixels modulo 16.  Sub-batch k is images
+ * sub_first[k] .. sub_first[k + 1] (room for batch + 1 entries, *sub_count + 1 are written); way_in[i]: 1 when image i's rows go
+ * through a shared filter launch, 0 when it is prepared by itself; run_strategy[i]: the strategy png_plan resolves for the
+ * unreduced image i; *filter_launches: shared filter launches summed over the sub-batches.  Checks as the entries' (no
+ * pixels; alignment behind `quantization`; the five out-pointers in the place of files and lens). */
+int pixo_hip_debug_png_encode_images_plan(const pixo_png_image *images, uint32_t batch, const pixo_png_options *options,
+                                          const pixo_png_quantization *quantization, uint32_t alignment, uint32_t *sub_first,
+                                          uint32_t *sub_count, uint8_t *way_in, uint8_t *run_strategy, uint32_t *filter_launches);
+
 /* ---- runtime ----------------------------------------------------------------------- */
 
 int pixo_hip_device_count(void);            /* 0 when no GPU / no driver              */

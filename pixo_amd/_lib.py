@@ -153,7 +153,11 @@ SIGNATURES = {
     "pixo_hip_png_decode_batch": _sig(_pfilep, _u32, _u32, _u8pp, _szp, _pimgp, optional=True),
     "pixo_hip_debug_png_decode_batch_plan": _sig(_pfilep, _u32, _u32, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p, optional=True),
     "pixo_hip_debug_png_decode_batch_timed": _sig(_pfilep, _u32, _u32, C.POINTER(_dbl), optional=True),
-    "pixo_hip_png_inflate_step_tokens": _sig(ret=_u32, optional=True),
+    "pixo_hip_png_encode_images_device": _sig(_vp, _pimgp, _u32, _poptp, _qoptp, _u8pp, _szp, optional=True),
+    "pixo_hip_png_encode_images_device_into": _sig(_vp, _pimgp, _u32, _poptp, _qoptp, _vp, _sz, _szp, _szp, optional=True),
+    "pixo_hip_png_encode_images": _sig(_vp, _sz, _pimgp, _u32, _poptp, _qoptp, _u8pp, _szp, optional=True),
+    "pixo_hip_debug_png_encode_images_plan": _sig(_pimgp, _u32, _poptp, _qoptp, _u32, _u32p, _u32p, _u8p, _u8p, _u32p, optional=True),
+    "pixo_hip_png_inflate_step_tokens":_sig(ret=_u32, optional=True),
     "pixo_hip_png_inflate_window_bytes": _sig(ret=_u32, optional=True),
     "pixo_hip_png_inflate_far_distance": _sig(ret=_u32, optional=True),
     "pixo_hip_png_inflate_stored_chunk": _sig(ret=_u32, optional=True),

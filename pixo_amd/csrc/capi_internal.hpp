@@ -40,6 +40,7 @@
 #include "jpeg_scan_block.h" // (the table form of the flat walk: built on the host, see upload_scan_tables)
 #include "baseline_plan.hpp"
 #include "routes.hpp"
+#include "png_images_math.h"
 
 namespace pixo_capi {
 
@@ -239,6 +240,7 @@ struct Context {
     uint32_t batch_per_block = 0;  // ... of the last batch (1 + bytes per block; 0: none yet): whether sub-batches pay, jpeg_api.cpp
     Buf p_in, p_out, p_sums, p_scratch; // PNG filter stage
     Buf h_sums{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... p_sums copied to the host
+    Buf p_images, h_images{Buf::Mem::Pinned, Buf::Grow::Exact}; // the records of a ragged filter launch (png_images_math.h) and what they go up from
     // PNG reductions (png_reduce_api.cpp)
     Buf q_work{Buf::Mem::Device, Buf::Grow::Exact};  // one PngWork: analysis, key lookup table, index map, histogram, pair counts
     Buf h_qwork{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... its host side: results come down into it, tables go up from it
@@ -600,12 +602,20 @@ int png_filter_on_device(Context &c, const void *d_in, uint32_t width, uint32_t 
 // `batch` equal images back to back at d_in in one launch, their streams back to back at d_out; the row sums are on their way
 // to the host when this returns.  Once the stream has been synchronised, png_filter_batch_adler combines image i's.
 int png_filter_batch_begin(Context &c, const void *d_in, uint32_t width, uint32_t height, uint32_t batch, uint32_t bpp, int run, void *d_out);
-uint32_t png_filter_batch_adler(const Context &c, uint32_t width, uint32_t height, uint32_t bpp, uint32_t image);
+// ... the Adler-32 of one image from its own rows' sums: `height` rows of row_bytes + 1 stream bytes, the first row's sums at
+// index sums_at of the sums that came down (equal images: image * height)
+uint32_t png_filter_batch_adler(const Context &c, uint64_t sums_at, uint32_t height, uint64_t row_bytes);
+// Images of individual sizes (png_images_math.h): the items' records go up in one copy, one launch per class of images
+// present, all row sums on their way down in one copy; item k's sums start at the heights in front of it summed.  Nothing is
+// waited for.  *launches: how many filter launches were made.
+int png_filter_images_begin(Context &c, const void *d_in, const std::vector<pixo_png_images::Item> &items, void *d_out, uint32_t *launches);
 
 // ---- PNG prepare (png_reduce_api.cpp) --------------------------------------------------------------------------------
 // The prepare and whole-file entries' checks in the reference's order; with_data: the host pixels' length too (one that passes IS the input size)
 // images: the data are those of a batch of so many equal images back to back
 int png_check_options(const pixo_png_options *o, bool with_data = false, size_t data_len = 0, uint32_t images = 1);
+// ... its first three: a zero side, a side above the reference's limit, a colour type that is none of the four
+int png_check_image(uint32_t width, uint32_t height, uint8_t color_type);
 // How the filters saw the rows (packed and palette rows: as one-byte pixels): what a match search behind them is told.
 struct PngFilterView { uint32_t bpp, row; }; // bytes per filter pixel, bytes per filtered row
 // d_px: width * height * bpp bytes on the context's device; reductions + filters, the stream is left in d_out

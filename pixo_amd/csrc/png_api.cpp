@@ -72,9 +72,34 @@ int pixo_capi::png_filter_batch_begin(Context &c, const void *d_in, uint32_t wid
     HIP_TRY(hipMemcpyAsync(c.h_sums.p, c.p_sums.p, static_cast<size_t>(rows) * 16, hipMemcpyDeviceToHost, c.stream));
     return PIXO_OK;
 }
-uint32_t pixo_capi::png_filter_batch_adler(const Context &c, uint32_t width, uint32_t height, uint32_t bpp, uint32_t image)
+uint32_t pixo_capi::png_filter_batch_adler(const Context &c, uint64_t sums_at, uint32_t height, uint64_t row_bytes)
 {
-    return combine_adler(c.h_sums.as<unsigned long long>() + 2 * static_cast<size_t>(image) * height, height, static_cast<uint64_t>(width) * bpp + 1);
+    return combine_adler(c.h_sums.as<unsigned long long>() + 2 * static_cast<size_t>(sums_at), height, row_bytes + 1);
+}
+
+// The ragged form (png_encode_api.cpp png_images): the records of all classes in one upload, one launch per class, the sums
+// of all rows in one copy down.  The pinned table is written only after the stream has drained what read it last: every
+// caller has waited for its previous sub-batch's files by then.
+int pixo_capi::png_filter_images_begin(Context &c, const void *d_in, const std::vector<pixo_png_images::Item> &items, void *d_out, uint32_t *launches)
+{
+    namespace im = pixo_png_images;
+    std::vector<im::Record> table;
+    std::vector<im::Launch> plan;
+    std::vector<uint32_t> record_item;
+    uint64_t rows = 0;
+    for (const im::Item &it : items) rows += it.height;
+    if (items.empty() || rows > 0x7FFFFFFFull || !im::build_table(items, reinterpret_cast<uintptr_t>(d_in), table, plan, record_item))
+        return hip_fail(hipErrorInvalidValue, "rows of a PNG batch");
+    const size_t bytes = table.size() * sizeof(im::Record);
+    int rc;
+    if ((rc = reserve_sums(c, static_cast<uint32_t>(rows))) || (rc = c.p_images.reserve(bytes)) || (rc = c.h_images.reserve(bytes))) return rc;
+    std::memcpy(c.h_images.p, table.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(c.p_images.p, c.h_images.p, bytes, hipMemcpyHostToDevice, c.stream));
+    for (const im::Launch &l : plan)
+        HIP_TRY(pixo_dev::launch_png_filter_images(d_in, d_out, c.p_sums.as<unsigned long long>(), c.p_images.as<im::Record>() + l.first_record, l, c.stream));
+    HIP_TRY(hipMemcpyAsync(c.h_sums.p, c.p_sums.p, static_cast<size_t>(rows) * 16, hipMemcpyDeviceToHost, c.stream));
+    *launches = static_cast<uint32_t>(plan.size());
+    return PIXO_OK;
 }
 
 namespace {

@@ -3,7 +3,8 @@
 // CRC-32 come from the device in 4 KiB pieces, and only the finished file crosses to the host.  The chunks around IDAT are
 // the reference's byte for byte (src/png/mod.rs:513-630); the IDAT body is this library's own DEFLATE.
 // There is one tail (tail_begin, tail_finish, tail_deliver) over a table of segments (png_deflate_math.h ZSegment): a single
-// file and a bare zlib stream are a table of one, the batch entries run N equal images through it at once.
+// file and a bare zlib stream are a table of one, the batch entries run N equal images through it at once, the images
+// entries N images of individual sizes and colour types.
 #include "capi_internal.hpp"
 #include "png_deflate.hpp"
 #include "png_filter.hpp"
@@ -109,6 +110,7 @@ struct PngSegment {
     uint32_t adler = 0;
     pixo_png_layout layout;
     uint32_t trns_len = 0;
+    uint32_t width = 0, height = 0; // the image's, for its IHDR
 };
 // Where the files go: blocks the caller owns (files), or back to back into an arena in host memory (offsets).
 struct BatchSink {
@@ -198,14 +200,14 @@ int tail_finish(Context &c, const std::vector<PngSegment> &segs, BatchTail &t, b
 }
 // Copy, frame, deliver: the framed streams behind their heads, in the caller's blocks or at their arena offsets; frames and
 // IEND by the host.  first: the segments' first image in the sink.
-int tail_deliver(Context &c, const std::vector<PngSegment> &segs, const BatchTail &t, const pixo_png_options &o, uint32_t first, BatchSink &sink)
+int tail_deliver(Context &c, const std::vector<PngSegment> &segs, const BatchTail &t, uint32_t first, BatchSink &sink)
 {
     struct File { std::vector<uint8_t> head; uint64_t stream_len = 0; size_t framed = 0, len = 0; uint8_t *at = nullptr; bool staged = false; };
     std::vector<File> f(t.nseg);
     for (uint32_t i = 0; i < t.nseg; ++i) {
         f[i].stream_len = 2 + t.h_totals()[i] + 4;
         if (f[i].stream_len > stored_bound(segs[i].len)) return fail(PIXO_ERR_COMPRESSION, "Compression error: device DEFLATE exceeded the stored bound");
-        f[i].head = png_head(o.width, o.height, segs[i].layout, segs[i].trns_len);
+        f[i].head = png_head(segs[i].width, segs[i].height, segs[i].layout, segs[i].trns_len);
         f[i].framed = static_cast<size_t>(pixo_dev::z_framed_size(f[i].stream_len));
         f[i].len = f[i].head.size() + f[i].framed + 12;
         sink.lens[first + i] = f[i].len;
@@ -300,6 +302,8 @@ int png_segment_of_image(Context &c, const void *d_img, const pixo_png_options &
 int png_file(Context &c, const void *d_px, const pixo_png_options &o, const pixo_png_quantization *q, uint8_t **out, size_t *out_len)
 {
     std::vector<PngSegment> seg(1);
+    seg[0].width = o.width;
+    seg[0].height = o.height;
     int rc = png_segment_of_image(c, d_px, o, q, seg[0]);
     if (rc) return rc;
     uint8_t *file = nullptr;
@@ -311,7 +315,7 @@ int png_file(Context &c, const void *d_px, const pixo_png_options &o, const pixo
     BatchTail tail;
     tail.d_data = c.p_out.p;
     if ((rc = tail_begin(c, seg, o.compression_level, png_effort(o), tail)) || (rc = tail_finish(c, seg, tail, false)) || (rc = wait_for(c, sink)) ||
-        (rc = tail_deliver(c, seg, tail, o, 0, sink)))
+        (rc = tail_deliver(c, seg, tail, 0, sink)))
         return rc;
     if (debug().trace) std::fprintf(stderr, "[pixo_hip] png file: %u chunk(s), host waits %u (behind the image's own)\n", tail.chunks, sink.waits);
     *out = file;
@@ -376,7 +380,7 @@ int png_batch(Context &c, const void *d_px, const pixo_png_options &o, const pix
         BatchTail tail;
         tail.d_data = c.p_out.p;
         Stopwatch watch; // (debug switch trace: wall time between the host's waits)
-        for (uint32_t i = 0; i < nb; ++i) segs[i].src = full * i;
+        for (uint32_t i = 0; i < nb; ++i) { segs[i].src = full * i; segs[i].width = o.width; segs[i].height = o.height; }
         if (filter_batch) {
             for (PngSegment &sg : segs) {
                 std::memset(&sg.layout, 0, sizeof(sg.layout));
@@ -391,7 +395,7 @@ int png_batch(Context &c, const void *d_px, const pixo_png_options &o, const pix
             if ((rc = png_filter_batch_begin(c, d_first, o.width, o.height, nb, bpp, run, c.p_out.p)) || (rc = tail_begin(c, segs, o.compression_level, png_effort(o), tail)) ||
                 (rc = wait_for(c, sink)))
                 return rc;
-            for (uint32_t i = 0; i < nb; ++i) segs[i].adler = png_filter_batch_adler(c, o.width, o.height, bpp, i);
+            for (uint32_t i = 0; i < nb; ++i) segs[i].adler = png_filter_batch_adler(c, static_cast<uint64_t>(i) * o.height, o.height, static_cast<uint64_t>(o.width) * bpp);
             watch.lap("png batch: filters, DEFLATE");
         } else {
             for (uint32_t i = 0; i < nb; ++i)
@@ -401,7 +405,7 @@ int png_batch(Context &c, const void *d_px, const pixo_png_options &o, const pix
         }
         if ((rc = tail_finish(c, segs, tail, filter_batch)) || (rc = wait_for(c, sink))) return rc;
         watch.lap(filter_batch ? "png batch: scan, compact, CRC" : "png batch: DEFLATE to CRC");
-        if ((rc = tail_deliver(c, segs, tail, o, first, sink))) return rc;
+        if ((rc = tail_deliver(c, segs, tail, first, sink))) return rc;
         watch.lap("png batch: copies, frames");
         if (debug().trace)
             std::fprintf(stderr, "[pixo_hip] png batch: sub-batch %u, %u image(s), %u chunk(s), %s way in, host waits %u%s\n", part, nb, tail.chunks,
@@ -450,6 +454,194 @@ int png_batch_checks(const void *pixels, uint32_t batch, const pixo_png_quantiza
     if (into) { const void *offsets = files_or_offsets; PIXO_REQUIRE(offsets); }
     else { const void *files = files_or_offsets; PIXO_REQUIRE(files); }
     PIXO_REQUIRE(lens);
+    return PIXO_OK;
+}
+
+// ---- images of individual sizes and colour types in one block ("Images of individual sizes") ----------
+// What the driver decides about a batch before anything touches a device (also: pixo_hip_debug_png_encode_images_plan).
+struct ImagesPlan {
+    struct Image {
+        pixo_png_options o; // the template with the image's width, height and colour type written into it
+        uint32_t bpp = 0;
+        size_t full = 0;    // h * (w * bpp + 1): its unreduced stream, what its segment is given
+        int run = 0;        // what png_plan resolves for the unreduced image
+        bool batched = false; // the batched way in: a ragged filter launch; otherwise png_segment_of_image
+    };
+    std::vector<Image> image;
+    std::vector<uint32_t> sub_first; // sub-batch k: images sub_first[k] .. sub_first[k + 1]
+};
+// Sub-batches: greedy in index order under 64 MiB of unreduced stream (debug switch png_batch_bytes) and kBatchChunks chunks,
+// at least one image each.  The way in is the image's own: png_plan with ITS area and height (an area of at most 4096 pixels
+// turns the adaptive strategies into Sub, a height of at most 32 makes AdaptiveFast the sequential form).
+int plan_images(const pixo_png_image *images, uint32_t batch, const pixo_png_options &o, const pixo_png_quantization *q, ImagesPlan &p)
+{
+    const uint64_t limit = debug().png_batch_bytes ? debug().png_batch_bytes : (uint64_t{64} << 20);
+    p.image.resize(batch);
+    p.sub_first.assign(1, 0);
+    uint64_t bytes = 0, chunks = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        ImagesPlan::Image &x = p.image[i];
+        x.o = o;
+        x.o.width = images[i].width;
+        x.o.height = images[i].height;
+        x.o.color_type = images[i].color_type;
+        x.bpp = bytes_per_pixel(x.o.color_type);
+        x.full = static_cast<size_t>(x.o.height) * (static_cast<size_t>(x.o.width) * x.bpp + 1);
+        bool seq = false;
+        if (const int rc = png_plan(x.o.width, x.o.height, static_cast<uint64_t>(x.o.width) * x.o.height, x.bpp, o.filter_strategy, o.flags, &x.run, &seq)) return rc;
+        x.batched = !q && !o.optimize_alpha && !o.reduce_color_type && !o.reduce_palette && !seq;
+        const uint64_t c = seg_chunks(x.full);
+        if (i > p.sub_first.back() && (bytes + x.full > limit || chunks + c > kBatchChunks)) {
+            p.sub_first.push_back(i);
+            bytes = chunks = 0;
+        }
+        bytes += x.full;
+        chunks += c;
+    }
+    p.sub_first.push_back(batch);
+    return PIXO_OK;
+}
+// The items of a sub-batch's ragged launches: its batched images in index order, stream i at segment i's place.
+std::vector<pixo_png_images::Item> items_of(const ImagesPlan &p, const pixo_png_image *images, uint32_t first, uint32_t end)
+{
+    std::vector<pixo_png_images::Item> items;
+    size_t at = 0;
+    for (uint32_t i = first; i < end; at += p.image[i].full, ++i) {
+        const ImagesPlan::Image &x = p.image[i];
+        if (x.batched) items.push_back({i - first, images[i].offset, at, x.o.width * x.bpp, x.o.height, x.bpp, x.run});
+    }
+    return items;
+}
+
+// The images at d_px + images[i].offset -> their files into the sink.  Sub-batches run one after the other on the context.
+// In a sub-batch the image-by-image segments are prepared first (each waits for the host on its own: reductions, the
+// quantiser, the sequential AdaptiveFast's checksum), then the ragged filter launches of the others are enqueued, then ONE
+// tail runs over all segments: the DEFLATE of the prepared images is already behind the filters when the host waits for the
+// row sums.  (The other order — launches first — would let every image-by-image wait drain the filter launches too, and
+// both use the context's row sums.)
+int png_images(Context &c, const void *d_px, const pixo_png_image *images, const pixo_png_options &o, const pixo_png_quantization *q, uint32_t batch,
+               BatchSink &sink)
+{
+    ImagesPlan p;
+    int rc = plan_images(images, batch, o, q, p);
+    if (rc) return rc;
+    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size()) - 1;
+    note_route(route::PNG_IMAGES | (subs > 1 ? route::SUB_BATCHES : 0));
+    for (uint32_t part = 0; part < subs; ++part) {
+        const uint32_t first = p.sub_first[part], end = p.sub_first[part + 1], nb = end - first, waits0 = sink.waits;
+        std::vector<PngSegment> segs(nb);
+        size_t total = 0;
+        for (uint32_t i = 0; i < nb; ++i) {
+            segs[i].src = total;
+            segs[i].width = p.image[first + i].o.width;
+            segs[i].height = p.image[first + i].o.height;
+            total += p.image[first + i].full;
+        }
+        if ((rc = c.p_out.reserve(total))) return rc;
+        BatchTail tail;
+        Stopwatch watch; // (debug switch trace: wall time between the host's waits)
+        for (uint32_t i = 0; i < nb; ++i) {
+            const ImagesPlan::Image &x = p.image[first + i];
+            if (!x.batched && (rc = png_segment_of_image(c, static_cast<const uint8_t *>(d_px) + images[first + i].offset, x.o, q, segs[i]))) return rc;
+        }
+        watch.lap("png images: images prepared");
+        tail.d_data = c.p_out.p; // (reserved for all streams before the first: nothing has moved)
+        const std::vector<pixo_png_images::Item> items = items_of(p, images, first, end);
+        uint32_t launches = 0;
+        if (!items.empty()) {
+            for (const pixo_png_images::Item &it : items) {
+                const ImagesPlan::Image &x = p.image[first + it.image];
+                PngSegment &sg = segs[it.image];
+                std::memset(&sg.layout, 0, sizeof(sg.layout));
+                sg.layout.color_type_byte = x.o.color_type == PIXO_GRAY ? 0 : x.o.color_type == PIXO_GRAY_ALPHA ? 4 : x.o.color_type == PIXO_RGB ? 2 : 6;
+                sg.layout.bit_depth = 8;
+                sg.layout.bytes_per_pixel = static_cast<uint8_t>(x.bpp);
+                sg.layout.row_bytes = it.row_bytes;
+                sg.len = x.full;
+                sg.view = PngFilterView{x.bpp, it.row_bytes + 1};
+            }
+            note_route(route::PNG_IMAGES_FILTER);
+            // filters, row sums on their way down, DEFLATE behind them: one wait for all three, then the checksums on the host
+            if ((rc = png_filter_images_begin(c, d_px, items, c.p_out.p, &launches)) || (rc = tail_begin(c, segs, o.compression_level, png_effort(o), tail)) ||
+                (rc = wait_for(c, sink)))
+                return rc;
+            uint64_t sums_at = 0;
+            for (const pixo_png_images::Item &it : items) {
+                segs[it.image].adler = png_filter_batch_adler(c, sums_at, it.height, it.row_bytes);
+                sums_at += it.height;
+            }
+            watch.lap("png images: filters, DEFLATE");
+        } else if ((rc = tail_begin(c, segs, o.compression_level, png_effort(o), tail))) {
+            return rc;
+        }
+        if ((rc = tail_finish(c, segs, tail, !items.empty())) || (rc = wait_for(c, sink))) return rc;
+        watch.lap("png images: scan, compact, CRC");
+        if ((rc = tail_deliver(c, segs, tail, first, sink))) return rc;
+        watch.lap("png images: copies, frames");
+        if (debug().trace)
+            std::fprintf(stderr, "[pixo_hip] png images: sub-batch %u, %u image(s), %u chunk(s), %zu batched in %u filter launch(es), host waits %u\n", part, nb,
+                         tail.chunks, items.size(), launches, sink.waits - waits0);
+    }
+    return PIXO_OK;
+}
+
+int png_images_blocks(Context &c, const void *d_px, const pixo_png_image *images, const pixo_png_options &o, const pixo_png_quantization *q, uint32_t batch,
+                      uint8_t **files, size_t *lens)
+{
+    for (uint32_t i = 0; i < batch; ++i) { files[i] = nullptr; lens[i] = 0; }
+    BatchSink sink;
+    sink.files = files;
+    sink.lens = lens;
+    const int rc = png_images(c, d_px, images, o, q, batch, sink);
+    if (rc) {
+        (void)hipStreamSynchronize(c.stream); // (no copy is in flight when the blocks go back)
+        for (uint32_t i = 0; i < batch; ++i) { free_file(files[i]); files[i] = nullptr; lens[i] = 0; }
+    }
+    return rc;
+}
+
+int png_images_into(Context &c, const void *d_px, const pixo_png_image *images, const pixo_png_options &o, const pixo_png_quantization *q, uint32_t batch,
+                    uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens)
+{
+    for (uint32_t i = 0; i < batch; ++i) { offsets[i] = 0; lens[i] = 0; }
+    BatchSink sink;
+    sink.arena = arena;
+    sink.cap = arena ? capacity : 0;
+    sink.offsets = offsets;
+    sink.lens = lens;
+    const hipMemoryType arena_type = arena ? pointer_info(arena).type : hipMemoryTypeUnregistered;
+    if (arena_type == hipMemoryTypeDevice) return hip_fail(hipErrorInvalidValue, "arena of a PNG batch in device memory (host memory only)");
+    sink.pinned = arena_type == hipMemoryTypeHost;
+    const int rc = png_images(c, d_px, images, o, q, batch, sink);
+    if (rc) return rc;
+    return arena && sink.at <= capacity ? PIXO_OK : too_small(sink.at);
+}
+
+// The checks the images entries share, in their order (include/pixo_hip.h): those in front of the out-pointers, then (behind
+// them) every image's own; *block_end: the furthest image's end.  with_pixels false: the plan entry, which takes none.
+int png_images_checks(const pixo_png_options *options, const void *pixels, bool with_pixels, const pixo_png_image *images, uint32_t batch,
+                      const pixo_png_quantization *quantization)
+{
+    PIXO_REQUIRE(options);
+    if (options->filter_strategy > PIXO_PNG_BIGRAMS) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown PNG filter strategy");
+    if (with_pixels) PIXO_REQUIRE(pixels);
+    PIXO_REQUIRE(images);
+    int rc = batch_in_range(batch);
+    if (rc || (quantization && (rc = png_check_quantization(quantization)))) return rc;
+    return PIXO_OK;
+}
+int png_images_check_each(const pixo_png_image *images, uint32_t batch, uint64_t *block_end)
+{
+    uint64_t furthest = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        const std::string where = " (image " + std::to_string(i) + ")";
+        const pixo_png_image &im = images[i];
+        if (const int rc = png_check_image(im.width, im.height, im.color_type)) return fail(rc, t_error + where);
+        const uint64_t bytes = static_cast<uint64_t>(im.width) * im.height * bytes_per_pixel(im.color_type), most = uint64_t{1} << 62; // (an image is at most 2^50 bytes)
+        if (im.offset > most || im.offset + bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch input too large" + where);
+        furthest = std::max(furthest, im.offset + bytes);
+    }
+    *block_end = furthest;
     return PIXO_OK;
 }
 
@@ -608,6 +800,82 @@ int pixo_hip_png_encode_batch(const uint8_t *data, size_t data_len, const pixo_p
     PIXO_THREAD_CONTEXT(c);
     if ((rc = upload(c, c.p_in, data, data_len))) return rc;
     return png_batch_blocks(c, c.p_in.p, *options, quantization, batch, files, lens);
+}
+
+int pixo_hip_png_encode_images_device(const void *d_pixels, const pixo_png_image *images, uint32_t batch, const pixo_png_options *options,
+                                      const pixo_png_quantization *quantization, uint8_t **files, size_t *lens)
+{
+    uint64_t end = 0;
+    int rc = png_images_checks(options, d_pixels, true, images, batch, quantization);
+    if (rc) return rc;
+    PIXO_REQUIRE(files);
+    PIXO_REQUIRE(lens);
+    if ((rc = png_images_check_each(images, batch, &end))) return rc;
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc;
+    return png_images_blocks(*c, d_pixels, images, *options, quantization, batch, files, lens);
+}
+
+int pixo_hip_png_encode_images_device_into(const void *d_pixels, const pixo_png_image *images, uint32_t batch, const pixo_png_options *options,
+                                           const pixo_png_quantization *quantization, uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens)
+{
+    CallerStorageScope storage(arena && capacity);
+    uint64_t end = 0;
+    int rc = png_images_checks(options, d_pixels, true, images, batch, quantization);
+    if (rc) return rc;
+    PIXO_REQUIRE(offsets);
+    PIXO_REQUIRE(lens);
+    if ((rc = png_images_check_each(images, batch, &end))) return rc;
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc;
+    return png_images_into(*c, d_pixels, images, *options, quantization, batch, arena, capacity, offsets, lens);
+}
+
+int pixo_hip_png_encode_images(const uint8_t *data, size_t data_len, const pixo_png_image *images, uint32_t batch, const pixo_png_options *options,
+                               const pixo_png_quantization *quantization, uint8_t **files, size_t *lens)
+{
+    uint64_t end = 0;
+    int rc = png_images_checks(options, data, true, images, batch, quantization);
+    if (rc) return rc;
+    PIXO_REQUIRE(files);
+    PIXO_REQUIRE(lens);
+    if ((rc = png_images_check_each(images, batch, &end))) return rc;
+    if (data_len < end) return bad_length(static_cast<size_t>(end), data_len);
+    PIXO_THREAD_CONTEXT(c);
+    if ((rc = upload(c, c.p_in, data, static_cast<size_t>(end)))) return rc;
+    return png_images_blocks(c, c.p_in.p, images, *options, quantization, batch, files, lens);
+}
+
+int pixo_hip_debug_png_encode_images_plan(const pixo_png_image *images, uint32_t batch, const pixo_png_options *options,
+                                          const pixo_png_quantization *quantization, uint32_t alignment, uint32_t *sub_first, uint32_t *sub_count,
+                                          uint8_t *way_in, uint8_t *run_strategy, uint32_t *filter_launches)
+{
+    uint64_t end = 0;
+    int rc = png_images_checks(options, nullptr, false, images, batch, quantization);
+    if (rc) return rc;
+    if (alignment > 15) return fail(PIXO_ERR_COMPRESSION, "Compression error: alignment must be 0..15");
+    PIXO_REQUIRE(sub_first);
+    PIXO_REQUIRE(sub_count);
+    PIXO_REQUIRE(way_in);
+    PIXO_REQUIRE(run_strategy);
+    PIXO_REQUIRE(filter_launches);
+    if ((rc = png_images_check_each(images, batch, &end))) return rc;
+    ImagesPlan p;
+    if ((rc = plan_images(images, batch, *options, quantization, p))) return rc;
+    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size()) - 1;
+    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
+    *sub_count = subs;
+    *filter_launches = 0;
+    for (uint32_t i = 0; i < batch; ++i) { way_in[i] = p.image[i].batched ? 1 : 0; run_strategy[i] = static_cast<uint8_t>(p.image[i].run); }
+    for (uint32_t k = 0; k < subs; ++k) {
+        std::vector<pixo_png_images::Record> table;
+        std::vector<pixo_png_images::Launch> launches;
+        std::vector<uint32_t> record_item;
+        if (!pixo_png_images::build_table(items_of(p, images, p.sub_first[k], p.sub_first[k + 1]), alignment, table, launches, record_item))
+            return hip_fail(hipErrorInvalidValue, "rows of a PNG batch");
+        *filter_launches += static_cast<uint32_t>(launches.size());
+    }
+    return PIXO_OK;
 }
 
 } // extern "C"

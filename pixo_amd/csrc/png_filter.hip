@@ -18,6 +18,7 @@
 #include "jpeg_kernels.hpp"
 #include "png_filter.hpp"
 #include "png_filter_math.h"
+#include "png_images_math.h"
 
 namespace pixo_dev {
 namespace {
@@ -134,6 +135,16 @@ struct Args {
     uint32_t bitmap_off;  // Bigrams: byte offset of the 8 KiB "pair seen" bitmap inside the dynamic LDS
     uint32_t late_half;   // the second thousand of a launch's workgroups starts late (a whole MI355X holds 2048 at once: launch_png_filter_rows)
 };
+// The ragged form's arguments: the launch's records (png_images_math.h) behind the single image's.  row_bytes, height,
+// strategy and first_row of Args are not read there; stage_bytes and bitmap_off are the launch class's.
+struct RaggedArgs : Args {
+    const pixo_png_images::Record *images;
+    uint32_t image_count;
+};
+// SINGLE: one image.  BATCH: equal images back to back.  RAGGED: images of individual sizes, one record each.
+enum { SINGLE = 0, BATCH = 1, RAGGED = 2 };
+template <int MODE> struct ArgsOf { using type = Args; };
+template <> struct ArgsOf<RAGGED> { using type = RaggedArgs; };
 
 // Pass 2 for filter F.  The output row starts at byte y * (n + 1) of the stream — a different
 // alignment for every row — so the filtered bytes are staged in LDS (filter byte at offset 15, row
@@ -203,12 +214,11 @@ template <int NT> __device__ __forceinline__ void flush_stage(const uint8_t *sta
 // alignment for every row — so the filtered bytes are staged in LDS and written out by flush_stage.
 // Rows too long for the LDS stage (a.stage_bytes == 0) store unaligned dwords directly.
 template <int BPP, bool FAST, int F, int NEED>
-__device__ __forceinline__ void write_row(const Args &a, uint32_t y, const uint8_t *row, const uint8_t *prev, int n,
+__device__ __forceinline__ void write_row(const Args &a, uint8_t *orow, const uint8_t *row, const uint8_t *prev, int n,
                                           unsigned long long &s1, unsigned long long &s2)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     const int ndw = (n + 3) / 4, per_iter = kThreads * 4;
-    uint8_t *orow = a.out + (size_t)y * (a.row_bytes + 1);
     const unsigned long long L = (unsigned long long)n + 1; // bytes of the output row; byte p has weight L - p
     const bool staged = a.stage_bytes != 0;
     if (threadIdx.x == 0) {
@@ -229,11 +239,10 @@ __device__ __forceinline__ void write_row(const Args &a, uint32_t y, const uint8
 // both work from those registers.
 constexpr int kRegIters = 4;
 template <int BPP, int F, int NT, int ITERS>
-__device__ __forceinline__ void stage_row_regs(const Args &a, uint32_t y, const Raw *raw, int n, unsigned long long *acc64, int tid)
+__device__ __forceinline__ void stage_row_regs(uint8_t *orow, const Raw *raw, int n, unsigned long long *acc64, int tid)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     const int ndw = (n + 3) / 4, per_iter = NT * 4; // (256 or 512 threads)
-    uint8_t *orow = a.out + (size_t)y * (a.row_bytes + 1);
     const uint32_t L = (uint32_t)n + 1;
     uint32_t s1 = 0, s2 = 0; // this thread's 64 bytes: s2 < 16 x 16385 x 1020 < 2^32
     if (tid == 0) { stage[15] = (uint8_t)F; s1 = (unsigned)F; s2 = L * (unsigned)F; }
@@ -256,11 +265,11 @@ __device__ __forceinline__ void stage_row_regs(const Args &a, uint32_t y, const 
     }
 }
 template <int BPP, int F, int NT, int ITERS>
-__device__ __forceinline__ void write_row_regs(const Args &a, uint32_t y, const Raw *raw, int n, unsigned long long *acc64, int tid)
+__device__ __forceinline__ void write_row_regs(uint8_t *orow, const Raw *raw, int n, unsigned long long *acc64, int tid)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
-    stage_row_regs<BPP, F, NT, ITERS>(a, y, raw, n, acc64, tid);
-    flush_stage<NT>(stage, a.out + (size_t)y * (a.row_bytes + 1), n, tid);
+    stage_row_regs<BPP, F, NT, ITERS>(orow, raw, n, acc64, tid);
+    flush_stage<NT>(stage, orow, n, tid);
 }
 
 // Bigrams (filter.rs:406-472, score_bigrams :635-649): the score of a candidate is the number of DISTINCT
@@ -312,8 +321,45 @@ enum { K_GENERAL = 0, K_REGS = 1, K_BIGRAMS = 2, K_REGS512 = 3 };
 // BATCH: the rows are those of several images of a.height rows each, back to back (launch_png_filter_batch): the first row
 // of EVERY image has no row above, and no row ever reads another image's.  Everything else — the XCD chunks, late_half, the
 // output and the sums at row y of the launch — is the single image's; the default keeps the single-image instantiations as they were.
-template <int BPP, bool FAST, int KIND, int ITERS = kRegIters, bool BATCH = false>
-__global__ __launch_bounds__(KIND == K_REGS512 ? 2 * kThreads : kThreads) void png_filter_kernel(const Args a)
+// RAGGED: the rows are those of images of individual row lengths and heights (launch_png_filter_images).  Row y of the launch
+// — still what the XCD chunks permute: they know nothing of images — belongs to the record found by a binary search over
+// first_row; row length, source, destination, strategy and the sums' index are that record's.  The search and the record are
+// uniform across the workgroup: scalar loads, the values stay in scalar registers.  stage_bytes, bitmap_off and late_half
+// stay the launch's (rows too long for the stage are launched apart).
+struct RowOf { // what a workgroup works on
+    const uint8_t *row, *prev;
+    uint8_t *orow;
+    size_t sums; // index of its sums in row_sums ([2] each)
+    int n, strategy;
+};
+template <int MODE> __device__ __forceinline__ RowOf row_of(const typename ArgsOf<MODE>::type &a, uint32_t y)
+{
+    RowOf r;
+    if constexpr (MODE == RAGGED) {
+        // (the table was uploaded before the launch and nothing writes it: read through the constant address space, the
+        // search and the record are scalar loads)
+        using ConstRecord = const __attribute__((address_space(4))) pixo_png_images::Record;
+        ConstRecord *table = (ConstRecord *)a.images;
+        ConstRecord *im = table + pixo_png_images::image_of_row(table, a.image_count, y);
+        const uint32_t line = y - im->first_row, row_bytes = im->row_bytes;
+        r.n = (int)row_bytes;
+        r.row = a.data + im->src + (size_t)line * row_bytes;
+        r.prev = line ? r.row - row_bytes : nullptr;
+        r.orow = a.out + im->dst + (size_t)line * ((size_t)row_bytes + 1);
+        r.sums = (size_t)im->sums_at + line;
+        r.strategy = im->strategy;
+    } else {
+        r.n = (int)a.row_bytes; // < 2^31 (checked by the launcher)
+        r.row = a.data + (size_t)y * a.row_bytes;
+        r.prev = (MODE == BATCH ? y % a.height : y) ? r.row - a.row_bytes : nullptr;
+        r.orow = a.out + (size_t)y * (a.row_bytes + 1);
+        r.sums = y;
+        r.strategy = a.forced ? *a.forced : a.strategy;
+    }
+    return r;
+}
+template <int BPP, bool FAST, int KIND, int ITERS = kRegIters, int MODE = SINGLE>
+__global__ __launch_bounds__(KIND == K_REGS512 ? 2 * kThreads : kThreads) void png_filter_kernel(const typename ArgsOf<MODE>::type a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ unsigned long long red[20];
@@ -331,13 +377,13 @@ __global__ __launch_bounds__(KIND == K_REGS512 ? 2 * kThreads : kThreads) void p
     // (two sleeps 41.6, four 43.0, graded quarters 41.6-44.5; profiles/r03_png_stagger_ab.txt).
     if (KIND == K_REGS && a.late_half && nb >= 2048u && (y >> 10) == 1u) __builtin_amdgcn_s_sleep(127);
     if (y < full) { const uint32_t xcd = y & 7u, i = y >> 3; y = (((i >> 5) * 8u + xcd) << 5) + (i & 31u); }
-    y += a.first_row;
-    const int n = (int)a.row_bytes; // < 2^31 (checked by the launcher)
-    const uint8_t *row = a.data + (size_t)y * a.row_bytes;
-    const uint8_t *prev = (BATCH ? y % a.height : y) ? row - a.row_bytes : nullptr;
+    if (MODE != RAGGED) y += a.first_row;
+    const RowOf w = row_of<MODE>(a, y);
+    const int n = w.n;
+    const uint8_t *row = w.row, *prev = w.prev;
     constexpr int NT = KIND == K_REGS512 ? 2 * kThreads : kThreads;
     const int ndw = (n + 3) / 4, per_iter = NT * 4;
-    int strategy = a.forced ? *a.forced : a.strategy;
+    int strategy = w.strategy;
 
     int f = strategy;
     if (KIND == K_BIGRAMS) {
@@ -398,13 +444,13 @@ __global__ __launch_bounds__(KIND == K_REGS512 ? 2 * kThreads : kThreads) void p
         f = decide<uint32_t>(strategy, tot, (uint32_t)n);
         if (a.winner0 && y == 0 && threadIdx.x == 0) *a.winner0 = f;
         switch (f) {
-        case F_NONE: write_row_regs<BPP, F_NONE, NT, ITERS>(a, y, raw, n, acc64, (int)threadIdx.x); break;
-        case F_SUB: write_row_regs<BPP, F_SUB, NT, ITERS>(a, y, raw, n, acc64, (int)threadIdx.x); break;
-        case F_UP: write_row_regs<BPP, F_UP, NT, ITERS>(a, y, raw, n, acc64, (int)threadIdx.x); break;
-        case F_AVG: write_row_regs<BPP, F_AVG, NT, ITERS>(a, y, raw, n, acc64, (int)threadIdx.x); break;
-        default: write_row_regs<BPP, F_PAETH, NT, ITERS>(a, y, raw, n, acc64, (int)threadIdx.x); break;
+        case F_NONE: write_row_regs<BPP, F_NONE, NT, ITERS>(w.orow, raw, n, acc64, (int)threadIdx.x); break;
+        case F_SUB: write_row_regs<BPP, F_SUB, NT, ITERS>(w.orow, raw, n, acc64, (int)threadIdx.x); break;
+        case F_UP: write_row_regs<BPP, F_UP, NT, ITERS>(w.orow, raw, n, acc64, (int)threadIdx.x); break;
+        case F_AVG: write_row_regs<BPP, F_AVG, NT, ITERS>(w.orow, raw, n, acc64, (int)threadIdx.x); break;
+        default: write_row_regs<BPP, F_PAETH, NT, ITERS>(w.orow, raw, n, acc64, (int)threadIdx.x); break;
         }
-        if (threadIdx.x == 0) { a.row_sums[2 * (size_t)y] = acc64[0]; a.row_sums[2 * (size_t)y + 1] = acc64[1]; }
+        if (threadIdx.x == 0) { a.row_sums[2 * w.sums] = acc64[0]; a.row_sums[2 * w.sums + 1] = acc64[1]; }
         return;
     } else if (strategy > PNG_S_PAETH) {
         // pass 1: scores of the candidates (AdaptiveFast never looks at None / Average)
@@ -431,14 +477,14 @@ __global__ __launch_bounds__(KIND == K_REGS512 ? 2 * kThreads : kThreads) void p
     // pass 2: the winning filter -> output row (filter byte + n bytes), Adler partial sums
     unsigned long long s1 = 0, s2 = 0;
     switch (f) { // uniform: one filter's code and loads per row
-    case F_NONE: write_row<BPP, FAST, F_NONE, 0>(a, y, row, prev, n, s1, s2); break;
-    case F_SUB: write_row<BPP, FAST, F_SUB, 1>(a, y, row, prev, n, s1, s2); break;
-    case F_UP: write_row<BPP, FAST, F_UP, 2>(a, y, row, prev, n, s1, s2); break;
-    case F_AVG: write_row<BPP, FAST, F_AVG, 3>(a, y, row, prev, n, s1, s2); break;
-    default: write_row<BPP, FAST, F_PAETH, 7>(a, y, row, prev, n, s1, s2); break;
+    case F_NONE: write_row<BPP, FAST, F_NONE, 0>(a, w.orow, row, prev, n, s1, s2); break;
+    case F_SUB: write_row<BPP, FAST, F_SUB, 1>(a, w.orow, row, prev, n, s1, s2); break;
+    case F_UP: write_row<BPP, FAST, F_UP, 2>(a, w.orow, row, prev, n, s1, s2); break;
+    case F_AVG: write_row<BPP, FAST, F_AVG, 3>(a, w.orow, row, prev, n, s1, s2); break;
+    default: write_row<BPP, FAST, F_PAETH, 7>(a, w.orow, row, prev, n, s1, s2); break;
     }
     const unsigned long long t1 = wg_sum(s1, red), t2 = wg_sum(s2, red);
-    if (threadIdx.x == 0) { a.row_sums[2 * (size_t)y] = t1; a.row_sums[2 * (size_t)y + 1] = t2; }
+    if (threadIdx.x == 0) { a.row_sums[2 * w.sums] = t1; a.row_sums[2 * w.sums + 1] = t2; }
 }
 
 // Bigrams with the row in registers (round 3; rows of at most kRegIters x 4 KiB, staged): the row and the row above are
@@ -486,8 +532,8 @@ __device__ __forceinline__ void bigram_candidate(const Raw *raw, int n, int ndw,
     if ((tid & 63) == 0) atomicAdd(count, c);
 }
 
-template <int BPP, bool FAST, bool BATCH = false>
-__global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const Args a)
+template <int BPP, bool FAST, int MODE = SINGLE>
+__global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const typename ArgsOf<MODE>::type a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t stage[];
     __shared__ unsigned long long acc64[2];
@@ -495,10 +541,10 @@ __global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const Args a
     const uint32_t nb = gridDim.x, full = nb & ~255u; // rows in chunks of 32 per XCD (png_filter_kernel)
     uint32_t y = blockIdx.x;
     if (y < full) { const uint32_t xcd = y & 7u, i = y >> 3; y = (((i >> 5) * 8u + xcd) << 5) + (i & 31u); }
-    y += a.first_row;
-    const int n = (int)a.row_bytes, ndw = (n + 3) / 4, tid = (int)threadIdx.x;
-    const uint8_t *row = a.data + (size_t)y * a.row_bytes;
-    const uint8_t *prev = (BATCH ? y % a.height : y) ? row - a.row_bytes : nullptr;
+    if (MODE != RAGGED) y += a.first_row;
+    const RowOf w = row_of<MODE>(a, y);
+    const int n = w.n, ndw = (n + 3) / 4, tid = (int)threadIdx.x;
+    const uint8_t *row = w.row, *prev = w.prev;
     uint32_t *bm0 = reinterpret_cast<uint32_t *>(stage + a.bitmap_off), *bm1 = bm0 + 2048, *xch = bm1 + 2048;
     if (tid < 5) cnt[tid] = 0;
     if (tid < 2) acc64[tid] = 0;
@@ -526,58 +572,71 @@ __global__ __launch_bounds__(kThreads) void png_bigrams_regs_kernel(const Args a
     for (int i = 0; i < 5; i++) tot[i] = cnt[i];
     const int f = decide_bigrams(tot);
     switch (f) {
-    case F_NONE: write_row_regs<BPP, F_NONE, kThreads, kRegIters>(a, y, raw, n, acc64, tid); break;
-    case F_SUB: write_row_regs<BPP, F_SUB, kThreads, kRegIters>(a, y, raw, n, acc64, tid); break;
-    case F_UP: write_row_regs<BPP, F_UP, kThreads, kRegIters>(a, y, raw, n, acc64, tid); break;
-    case F_AVG: write_row_regs<BPP, F_AVG, kThreads, kRegIters>(a, y, raw, n, acc64, tid); break;
-    default: write_row_regs<BPP, F_PAETH, kThreads, kRegIters>(a, y, raw, n, acc64, tid); break;
+    case F_NONE: write_row_regs<BPP, F_NONE, kThreads, kRegIters>(w.orow, raw, n, acc64, tid); break;
+    case F_SUB: write_row_regs<BPP, F_SUB, kThreads, kRegIters>(w.orow, raw, n, acc64, tid); break;
+    case F_UP: write_row_regs<BPP, F_UP, kThreads, kRegIters>(w.orow, raw, n, acc64, tid); break;
+    case F_AVG: write_row_regs<BPP, F_AVG, kThreads, kRegIters>(w.orow, raw, n, acc64, tid); break;
+    default: write_row_regs<BPP, F_PAETH, kThreads, kRegIters>(w.orow, raw, n, acc64, tid); break;
     }
-    if (tid == 0) { a.row_sums[2 * (size_t)y] = acc64[0]; a.row_sums[2 * (size_t)y + 1] = acc64[1]; }
+    if (tid == 0) { a.row_sums[2 * w.sums] = acc64[0]; a.row_sums[2 * w.sums + 1] = acc64[1]; }
 }
 
-template <int BPP, bool BATCH = false> hipError_t launch_bpp(const Args &a, uint32_t rows, bool fast, hipStream_t s)
+// One launch of the form `kind` (png_images_math.h KIND_*: the kernel's KIND, or the register form of Bigrams).
+template <int BPP, int MODE = SINGLE> hipError_t launch_kind(const typename ArgsOf<MODE>::type &a, int kind, uint32_t rows, bool fast, hipStream_t s)
 {
-    const uint64_t ndw = (a.row_bytes + 3) / 4;
     namespace r = pixo_capi::route;
-    if (a.strategy == PNG_S_BIGRAMS && a.stage_bytes != 0 && ndw <= (uint64_t)kRegIters * kThreads * 4) {
+    namespace im = pixo_png_images;
+    static_assert(im::KIND_GENERAL == K_GENERAL && im::KIND_REGS == K_REGS && im::KIND_BIGRAMS == K_BIGRAMS && im::KIND_REGS512 == K_REGS512, "one numbering");
+    if (kind == im::KIND_BIGRAMS_REGS) {
         pixo_capi::note_route(r::PNG_BIGRAMS_REGS);
         const uint32_t lds = a.stage_bytes + 2 * 8192u + 4u * (kRegIters * kThreads + 1); // stage | two bitmaps | exchange array
-        if (fast) hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, true, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
-        else hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, false, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
-    } else if (a.strategy == PNG_S_BIGRAMS) {
+        if (fast) hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, true, MODE>), dim3(rows), dim3(kThreads), lds, s, a);
+        else hipLaunchKernelGGL((png_bigrams_regs_kernel<BPP, false, MODE>), dim3(rows), dim3(kThreads), lds, s, a);
+    } else if (kind == im::KIND_BIGRAMS) {
         pixo_capi::note_route(r::PNG_BIGRAMS);
         const uint32_t lds = a.stage_bytes + 8192u;
-        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_BIGRAMS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
-        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_BIGRAMS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), lds, s, a);
-    } else if (a.strategy > PNG_S_PAETH && !a.forced && ndw <= (uint64_t)kRegIters * 2 * kThreads * 4 && a.stage_bytes != 0) {
-        // rows of up to 16 KiB: 256 threads hold them; up to 32 KiB: 512 threads
-        if (ndw <= (uint64_t)kRegIters * kThreads * 4) {
-            pixo_capi::note_route(r::PNG_REGS);
-            if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
-            else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
-        } else {
-            pixo_capi::note_route(r::PNG_REGS512);
-            if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS512, kRegIters, BATCH>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
-            else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS512, kRegIters, BATCH>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
-        }
+        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_BIGRAMS, kRegIters, MODE>), dim3(rows), dim3(kThreads), lds, s, a);
+        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_BIGRAMS, kRegIters, MODE>), dim3(rows), dim3(kThreads), lds, s, a);
+    } else if (kind == im::KIND_REGS) { // rows of up to 16 KiB: 256 threads hold them
+        pixo_capi::note_route(r::PNG_REGS);
+        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS, kRegIters, MODE>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS, kRegIters, MODE>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+    } else if (kind == im::KIND_REGS512) { // up to 32 KiB: 512 threads
+        pixo_capi::note_route(r::PNG_REGS512);
+        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_REGS512, kRegIters, MODE>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
+        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_REGS512, kRegIters, MODE>), dim3(rows), dim3(2 * kThreads), a.stage_bytes, s, a);
     } else {
         pixo_capi::note_route(r::PNG_GENERAL);
-        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_GENERAL, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
-        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_GENERAL, kRegIters, BATCH>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+        if (fast) hipLaunchKernelGGL((png_filter_kernel<BPP, true, K_GENERAL, kRegIters, MODE>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
+        else hipLaunchKernelGGL((png_filter_kernel<BPP, false, K_GENERAL, kRegIters, MODE>), dim3(rows), dim3(kThreads), a.stage_bytes, s, a);
     }
     return hipGetLastError();
+}
+
+// The form a launch of one row length takes (pixo_png_images::kind_of restates these conditions for the ragged form, whose
+// images are sorted into launches by them; tests/emu_png_images holds the two against each other).
+template <int BPP, int MODE = SINGLE> hipError_t launch_bpp(const Args &a, uint32_t rows, bool fast, hipStream_t s)
+{
+    const uint64_t ndw = (a.row_bytes + 3) / 4;
+    namespace im = pixo_png_images;
+    int kind = im::KIND_GENERAL;
+    if (a.strategy == PNG_S_BIGRAMS && a.stage_bytes != 0 && ndw <= (uint64_t)kRegIters * kThreads * 4) kind = im::KIND_BIGRAMS_REGS;
+    else if (a.strategy == PNG_S_BIGRAMS) kind = im::KIND_BIGRAMS;
+    else if (a.strategy > PNG_S_PAETH && !a.forced && ndw <= (uint64_t)kRegIters * 2 * kThreads * 4 && a.stage_bytes != 0)
+        kind = ndw <= (uint64_t)kRegIters * kThreads * 4 ? im::KIND_REGS : im::KIND_REGS512;
+    return launch_kind<BPP, MODE>(a, kind, rows, fast, s);
 }
 
 hipError_t launch_rows(const Args &a, uint32_t rows, uint32_t bpp, bool fast, hipStream_t s, bool batch = false)
 {
     if (batch) {
         switch (bpp) {
-        case 1: return launch_bpp<1, true>(a, rows, fast, s);
-        case 2: return launch_bpp<2, true>(a, rows, fast, s);
-        case 3: return launch_bpp<3, true>(a, rows, fast, s);
-        case 4: return launch_bpp<4, true>(a, rows, fast, s);
-        case 6: return launch_bpp<6, true>(a, rows, fast, s);
-        case 8: return launch_bpp<8, true>(a, rows, fast, s);
+        case 1: return launch_bpp<1, BATCH>(a, rows, fast, s);
+        case 2: return launch_bpp<2, BATCH>(a, rows, fast, s);
+        case 3: return launch_bpp<3, BATCH>(a, rows, fast, s);
+        case 4: return launch_bpp<4, BATCH>(a, rows, fast, s);
+        case 6: return launch_bpp<6, BATCH>(a, rows, fast, s);
+        case 8: return launch_bpp<8, BATCH>(a, rows, fast, s);
         default: return hipErrorInvalidValue;
         }
     }
@@ -662,6 +721,35 @@ hipError_t launch_png_filter_batch(const void *d_data, uint32_t width, uint32_t 
     // (an image's first byte is image_rows * row_bytes behind the one before: a multiple of 4 when row_bytes is)
     const bool fast = reinterpret_cast<uintptr_t>(d_data) % 4 == 0 && a.row_bytes % 4 == 0;
     return launch_rows(a, (uint32_t)rows, bpp, fast, stream, true);
+}
+
+// One launch class of images of individual sizes: l.count records at d_records (first_row 0 and ascending, l.rows rows in
+// all), every image's bytes at d_data + src, its stream at d_out + dst, its rows' sums from d_row_sums[2 * sums_at] on.
+// The dynamic LDS is sized for the class's longest row; a class is either staged or not (png_images_math.h class_of), so
+// stage_bytes == 0 still speaks for the whole launch.
+hipError_t launch_png_filter_images(const void *d_data, void *d_out, unsigned long long *d_row_sums, const pixo_png_images::Record *d_records,
+                                    const pixo_png_images::Launch &l, hipStream_t stream)
+{
+    if (l.count == 0 || l.rows == 0 || l.rows > 0x7FFFFFFFu || l.max_row_bytes >= 0x7FFFFFF0u) return hipErrorInvalidValue;
+    RaggedArgs a;
+    a.data = static_cast<const uint8_t *>(d_data);
+    a.out = static_cast<uint8_t *>(d_out);
+    a.row_sums = d_row_sums;
+    a.row_bytes = 0; a.height = 0; a.strategy = 0; a.first_row = 0; // (the records')
+    a.forced = nullptr; a.winner0 = nullptr;
+    a.stage_bytes = l.staged ? pixo_png_images::stage_bytes(l.max_row_bytes) : 0u;
+    if (l.staged != (a.stage_bytes != 0)) return hipErrorInvalidValue;
+    a.bitmap_off = a.stage_bytes;
+    a.late_half = (l.rows >= 2048u && whole_chip_device()) ? 1u : 0u;
+    a.images = d_records;
+    a.image_count = l.count;
+    switch (l.bpp) {
+    case 1: return launch_kind<1, RAGGED>(a, (int)l.kind, l.rows, l.fast, stream);
+    case 2: return launch_kind<2, RAGGED>(a, (int)l.kind, l.rows, l.fast, stream);
+    case 3: return launch_kind<3, RAGGED>(a, (int)l.kind, l.rows, l.fast, stream);
+    case 4: return launch_kind<4, RAGGED>(a, (int)l.kind, l.rows, l.fast, stream);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace pixo_dev

@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "png_images_math.h"
+
 namespace pixo_dev {
 
 // FilterStrategy in the reference's declaration order (src/png/mod.rs:345-364)
@@ -27,5 +29,12 @@ hipError_t launch_png_filter_rows(const void *d_data, uint32_t width, uint32_t h
 // strategy is what png_plan resolved; the stateful AdaptiveFast is not served here.
 hipError_t launch_png_filter_batch(const void *d_data, uint32_t width, uint32_t image_rows, uint32_t batch, uint32_t bpp, int strategy,
                                    void *d_out, unsigned long long *d_row_sums, hipStream_t stream);
+// Images of individual widths, heights and bytes per pixel: one launch per class of images (png_images_math.h: bytes per
+// pixel, aligned loads, kernel form, staged or not), one workgroup per row of the class.  d_records: the class's l.count
+// records on the device; image k lies at d_data + src, its filtered stream goes to d_out + dst, its rows' sums to
+// d_row_sums[2 * sums_at] on.  Row 0 of every image has no row above, and no row reads another image's bytes.  The
+// strategies are what png_plan resolved, image by image; the stateful AdaptiveFast is not served here.
+hipError_t launch_png_filter_images(const void *d_data, void *d_out, unsigned long long *d_row_sums, const pixo_png_images::Record *d_records,
+                                    const pixo_png_images::Launch &l, hipStream_t stream);
 
 } // namespace pixo_dev

@@ -144,12 +144,18 @@ int reduce_to_palette(Context &c, const void *d_px, const pixo_png_options &o, P
 
 } // namespace
 
+int pixo_capi::png_check_image(uint32_t width, uint32_t height, uint8_t color_type)
+{
+    if (width == 0 || height == 0) return bad_dimensions(width, height);
+    if (width > kPngMaxDimension || height > kPngMaxDimension) return too_large(width, height, kPngMaxDimension);
+    if (color_type > PIXO_RGBA) return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format");
+    return PIXO_OK;
+}
+
 int pixo_capi::png_check_options(const pixo_png_options *o, bool with_data, size_t data_len, uint32_t images)
 {
     PIXO_REQUIRE(o);
-    if (o->width == 0 || o->height == 0) return bad_dimensions(o->width, o->height);
-    if (o->width > kPngMaxDimension || o->height > kPngMaxDimension) return too_large(o->width, o->height, kPngMaxDimension);
-    if (o->color_type > PIXO_RGBA) return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format");
+    if (const int rc = png_check_image(o->width, o->height, o->color_type)) return rc;
     const size_t one = static_cast<size_t>(o->width) * o->height * bytes_per_pixel(o->color_type);
     const size_t want = images <= 1 || one <= SIZE_MAX / images ? one * images : SIZE_MAX; // (a batch whose bytes do not fit size_t: no length is right)
     if (with_data && data_len != want) return bad_length(want, data_len);

@@ -54,6 +54,8 @@ enum : uint64_t {
     PNG_DECODE_BATCH = 1ull << 42, // PNG decode batch entries: one unfilter launch per filter unit and one convert launch per kernel form a sub-batch
     PNG_INFLATE_DEVICE = 1ull << 43, // ... with PIXO_DECODE_DEVICE_INFLATE: the streams of a sub-batch inflated in one launch (png_inflate.hip)
     PNG_INFLATE_HOST_REDO = 1ull << 44, // ... a stream the device did not vouch for was inflated again by the host, whose bytes replaced it
+    PNG_IMAGES = 1ull << 45,       // PNG encode of images of individual sizes: one DEFLATE, scan, compaction and CRC launch over all images of a sub-batch
+    PNG_IMAGES_FILTER = 1ull << 46, // ... and at least one image's rows went through a ragged filter launch (one per class of images)
 };
 }
 

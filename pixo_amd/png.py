@@ -379,6 +379,108 @@ def encode_batch(data, options, batch):
     return _lib.take_files(L, files, lens, batch)
 
 
+# ---- images of individual sizes and colour types in one block ------------------------------------------------------------
+
+# these entries' bits of the route record (a dict of its own: ROUTES above is pinned as the batch entries' complete list)
+IMAGES_ROUTES = {"PNG_IMAGES": 45, "PNG_IMAGES_FILTER": 46}
+ROUTE_PNG_IMAGES, ROUTE_PNG_IMAGES_FILTER = (1 << b for b in IMAGES_ROUTES.values())
+
+
+def _image_records(images):
+    """`images` as (a PngImageC array, its length, the tensor the offsets count from or None): a PngImageC array as it is; a
+    list of (width, height, ColorType, offset) as `decode.decode_png_batch_info` returns; or the list of (tensor, ColorType)
+    views `decode.decode_png_batch_device` returns, whose offsets are the tensors' addresses relative to the first."""
+    if isinstance(images, C.Array) and getattr(images, "_type_", None) is _lib.PngImageC:
+        return images, len(images), None
+    n = len(images)
+    arr = (_lib.PngImageC * max(n, 1))()
+    base = None
+    for i, im in enumerate(images):
+        if len(im) == 2 and hasattr(im[0], "data_ptr"):
+            t, ct = im
+            if base is None:
+                base = t
+            at = t.data_ptr() - base.data_ptr()
+            if at < 0:
+                raise ValueError("image %d lies in front of the first: the offsets count from the first view" % i)
+            arr[i].offset, arr[i].width, arr[i].height, arr[i].color_type = at, t.shape[1], t.shape[0], int(ct)
+        else:
+            w, h, ct, at = im
+            arr[i].offset, arr[i].width, arr[i].height, arr[i].color_type = at, w, h, int(ct)
+    return arr, n, base
+
+
+def _images_block(block, base):
+    """(the views of a decode batch carry their block with them: the first view's address is the block's)"""
+    if block is None:
+        if base is None:
+            raise ValueError("no block: pass the tensor the images' offsets count from")
+        return base.data_ptr()  # (the first view says nothing of the block's size: the address alone)
+    return block
+
+
+def _check_images_block(block, arr, n):
+    """(the C entries take no length for a device block: whatever carries a size is checked here)"""
+    if hasattr(block, "numel") and n:
+        need = max(arr[i].offset + arr[i].width * arr[i].height * (arr[i].color_type + 1) for i in range(n))
+        have = block.numel() * block.element_size()
+        if have < need:
+            raise ValueError("the images end at byte %d, the tensor holds %d" % (need, have))
+
+
+def encode_images_device(block, images, options):
+    """Images of individual sizes and colour types anywhere in one block in HBM (torch tensor / raw pointer) -> list of PNG
+    files (bytes), file i byte for byte what `encode_device` returns for image i with `options` at its width, height and
+    colour type (`options`' own are not read).  `images`: a `_lib.PngImageC` array, a list of (width, height, ColorType,
+    offset), or the (tensor, ColorType) views of `decode.decode_png_batch_device` — then `block` may be None.
+    `options.quantization`, when not Off, is passed on."""
+    L = _lib.load()
+    arr, n, base = _image_records(images)
+    block = _images_block(block, base)
+    _check_images_block(block, arr, n)
+    files, lens, o = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))(), options.to_c()
+    _lib.check(L.pixo_hip_png_encode_images_device(_lib.ptr(block), arr, n, C.byref(o), _quant_arg(options), files, lens))
+    return _lib.take_files(L, files, lens, n)
+
+
+def encode_images_device_into(arena, block, images, options):
+    """The files back to back in `arena` (as `encode_batch_device_into`: a torch uint8 CPU tensor, pinned or not, a numpy
+    uint8 array, or None for a size query).  Returns (offsets, lens); raises BufferTooSmall (`.needed`, `.offsets`, `.lens`)
+    when the files do not fit."""
+    L = _lib.load()
+    arr, n, base = _image_records(images)
+    block = _images_block(block, base)
+    _check_images_block(block, arr, n)
+    o, q = options.to_c(), _quant_arg(options)
+    return _lib.into_arena(lambda ptr, cap, offsets, lens: L.pixo_hip_png_encode_images_device_into(
+        _lib.ptr(block), arr, n, C.byref(o), q, ptr, cap, offsets, lens), arena, n)
+
+
+def encode_images(block_bytes, images, options):
+    """The same for a block in host memory (what `decode.decode_png_batch` works from) -> list of PNG files (bytes)."""
+    L = _lib.load()
+    arr, n, _ = _image_records(images)
+    px = np.ascontiguousarray(block_bytes if not isinstance(block_bytes, (bytes, bytearray)) else np.frombuffer(block_bytes, np.uint8), dtype=np.uint8).reshape(-1)
+    files, lens, o = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))(), options.to_c()
+    _lib.check(L.pixo_hip_png_encode_images(px.ctypes.data, px.size, arr, n, C.byref(o), _quant_arg(options), files, lens))
+    return _lib.take_files(L, files, lens, n)
+
+
+def encode_images_plan(images, options, alignment=0) -> dict:
+    """What the images entries decide for these records, no GPU needed: `sub_first` (sub-batch k is images sub_first[k] ..
+    sub_first[k + 1]), `way_in` (True: a shared filter launch; False: prepared by itself), `run_strategy` (what the
+    reference's rules make of the strategy for each image) and `filter_launches` (summed over the sub-batches) for a block
+    whose address is `alignment` modulo 16."""
+    L = _lib.load()
+    arr, n, _ = _image_records(images)
+    sub_first, subs, launches = (C.c_uint32 * (n + 1))(), C.c_uint32(), C.c_uint32()
+    way, run, o = (C.c_uint8 * max(n, 1))(), (C.c_uint8 * max(n, 1))(), options.to_c()
+    _lib.check(L.pixo_hip_debug_png_encode_images_plan(arr, n, C.byref(o), _quant_arg(options), alignment, sub_first, C.byref(subs), way, run,
+                                                       C.byref(launches)))
+    return {"sub_first": list(sub_first[:subs.value + 1]), "way_in": [bool(v) for v in way[:n]],
+            "run_strategy": [FilterStrategy(v) for v in run[:n]], "filter_launches": launches.value}
+
+
 # ---- lossy mode: palette quantisation and dithering on the device ------------------------------------------------------
 
 class Quantized:
