@@ -437,6 +437,43 @@ inline void resize_batch_device(const std::vector<pixo_resize_source> &sources, 
     } held{block};
     return std::vector<uint8_t>(block, block + n);
 }
+// Images of individual sizes and colour types anywhere in one block, described by pixo_png_image records as a decode batch
+// fills them in (contract: pixo_hip.h).  The sizes alone, on the host: every source at the largest size of its proportions
+// inside box_width x box_height, laid out with 16-byte starts; *total: the end of the last image
+[[nodiscard]] inline std::vector<pixo_png_image> fit_images(const std::vector<pixo_png_image> &src_images, uint32_t box_width, uint32_t box_height,
+                                                            bool no_enlarge = false, size_t *total = nullptr)
+{
+    std::vector<pixo_png_image> fitted(src_images.size());
+    size_t end = 0;
+    const int rc = pixo_hip_resize_images_fit(src_images.data(), (uint32_t)src_images.size(), box_width, box_height,
+                                              no_enlarge ? PIXO_RESIZE_FIT_NO_ENLARGE : 0u, fitted.data(), &end);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    if (total) *total = end;
+    return fitted;
+}
+// Device pixels, enqueued on `stream`: image i at d_src + src_images[i].offset -> dst_images[i]'s size at d_dst + its offset
+inline void resize_images_device(const void *d_src, const std::vector<pixo_png_image> &src_images, void *d_dst,
+                                 const std::vector<pixo_png_image> &dst_images, ResizeAlgorithm algorithm, void *stream = nullptr)
+{
+    if (src_images.size() != dst_images.size()) throw std::invalid_argument("resize_images_device: as many destinations as sources");
+    const int rc = pixo_hip_resize_images_device(d_src, src_images.data(), d_dst, dst_images.data(), (uint32_t)src_images.size(), (uint8_t)algorithm, stream);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+}
+// ... a block in host memory -> one block laid out as dst_images says
+[[nodiscard]] inline std::vector<uint8_t> resize_images(const uint8_t *data, size_t len, const std::vector<pixo_png_image> &src_images,
+                                                        const std::vector<pixo_png_image> &dst_images, ResizeAlgorithm algorithm)
+{
+    if (src_images.size() != dst_images.size()) throw std::invalid_argument("resize_images: as many destinations as sources");
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    const int rc = pixo_hip_resize_images(data, len, src_images.data(), dst_images.data(), (uint32_t)src_images.size(), (uint8_t)algorithm, &block, &n);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    struct Block { // (released also when the copy below throws)
+        uint8_t *p;
+        ~Block() { pixo_hip_free(p); }
+    } held{block};
+    return std::vector<uint8_t>(block, block + n);
+}
 } // namespace resize
 
 namespace decode {

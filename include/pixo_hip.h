@@ -777,6 +777,69 @@ int pixo_hip_debug_png_encode_images_plan(const pixo_png_image *images, uint32_t
                                           const pixo_png_quantization *quantization, uint32_t alignment, uint32_t *sub_first,
                                           uint32_t *sub_count, uint8_t *way_in, uint8_t *run_strategy, uint32_t *filter_launches);
 
+/* ---- resize of images of individual sizes and colour types, anywhere in one block ---- */
+
+/* The link between pixo_hip_png_decode_batch_device and pixo_hip_png_encode_images*: `batch` (1..65535) sources described by
+ * src_images (what a decode batch fills in) become `batch` images described by dst_images, every one of its own size, in one
+ * pass per sub-batch — decode a folder, fit it into a box, write it back, without leaving the device.
+ *
+ * The sizes alone, computed on the HOST, no GPU needed: dst_images[i] receives source i's colour type and the largest size of
+ * source i's proportions inside box_width x box_height, as the reference's front end computes it (calculateResizeDimensions of
+ * its web/src/lib/wasm.ts): in f64, aspect = sw / sh; the size is box_width x round(box_width / aspect), and where that is
+ * taller than the box, round(box_height * aspect) x box_height; round is JavaScript's Math.round (a tie goes up), each side is
+ * at least 1.  With PIXO_RESIZE_FIT_NO_ENLARGE in `flags`, a source that already fits the box keeps its size.  The offsets are
+ * the decode batch's layout: offset[0] = 0, offset[i + 1] = offset[i] + image i's bytes rounded up to 16; *total: the end of the
+ * last image, not rounded; `reserved` is written as zeros.  dst_images may be src_images.  Checks, before anything is written:
+ * src_images, dst_images, total; batch (PIXO_ERR_COMPRESSION, "batch must be 1..65535"); a zero box side
+ * (PIXO_ERR_INVALID_DIMENSIONS) or one above 2^24 (PIXO_ERR_IMAGE_TOO_LARGE); then for i = 0, 1, ... source i: a zero side, a
+ * side above 2^24, a colour type above 3 (PIXO_ERR_INVALID_COLOR_ARG), each with " (image i)" appended; a block beyond 2^62
+ * bytes (PIXO_ERR_COMPRESSION). */
+#define PIXO_RESIZE_FIT_NO_ENLARGE 1u
+int pixo_hip_resize_images_fit(const pixo_png_image *src_images, uint32_t batch, uint32_t box_width, uint32_t box_height,
+                               uint32_t flags, pixo_png_image *dst_images, size_t *total);
+
+/* Image i is src_images[i].width x height pixels of src_images[i].color_type at d_src + src_images[i].offset and becomes
+ * dst_images[i].width x height pixels at d_dst + dst_images[i].offset — any alignment on both sides, any order — byte for byte
+ * what pixo_hip_resize_device writes for (source i -> destination i, that colour type, `algorithm`).  The bytes between
+ * destinations are never written.  Destinations must not overlap each other or a source: the caller's contract, NOT checked.
+ * `reserved` is not read.  src_images and dst_images are HOST arrays and may be released when the call returns.
+ * Every pass is a flat launch over the tiles of all images of a sub-batch, whose workgroups find their image by a binary search:
+ * nearest and bilinear take one launch per bytes-per-pixel value present (at most 4); Lanczos3 one horizontal launch per
+ * bytes-per-pixel value present and ONE vertical launch, whatever `batch` is.  One Lanczos3 table per distinct (source size,
+ * destination size) pair per axis; tables and records go to the device in one copy.  Sub-batches, greedy in index order with at
+ * least one image each, where the Lanczos3 intermediates (source height rows of the image's own destination width, padded to
+ * 16 bytes) would exceed 256 MiB or a launch 2^31 - 1 tiles; they run one behind the other on `stream`.
+ * Enqueue only, ordered like pixo_hip_resize_batch_device, whose buffers these entries share: behind the producer stream's
+ * work, with one host wait for the calling thread's previous batch or images job, whose tables are about to be replaced.
+ * Checks, all before anything is enqueued (no GPU needed for a refusal): src_images, then dst_images; batch
+ * (PIXO_ERR_COMPRESSION, "batch must be 1..65535"); then for i = 0, 1, ... image i: pixo_hip_resize's checks on (source i,
+ * destination i, source i's colour type, algorithm) with that entry's status and message; a colour type of destination i that
+ * differs from source i's (PIXO_ERR_COMPRESSION, "Compression error: colour types differ"); offset + the image's bytes beyond
+ * 2^62 on the source's, then the destination's side (PIXO_ERR_COMPRESSION) — each with " (image i)" appended, the first failing
+ * image answers; then d_src, then d_dst. */
+int pixo_hip_resize_images_device(const void *d_src, const pixo_png_image *src_images, void *d_dst,
+                                  const pixo_png_image *dst_images, uint32_t batch, uint8_t algorithm, void *stream);
+
+/* Same for a block in HOST memory (what pixo_hip_png_decode_batch returns): the checks above with `data` for d_src, then out,
+ * out_len, then data_len below the furthest source's end: PIXO_ERR_INVALID_DATA_LENGTH, "expected <that end> bytes, got
+ * <data_len>".  *out receives one block of *out_len bytes, up to the furthest destination's end, laid out as dst_images says
+ * (the gaps hold nothing of meaning), released with pixo_hip_free.  Returns when the block is complete. */
+int pixo_hip_resize_images(const uint8_t *data, size_t data_len, const pixo_png_image *src_images,
+                           const pixo_png_image *dst_images, uint32_t batch, uint8_t algorithm, uint8_t **out, size_t *out_len);
+
+/* Tests: what the entries above decide for these sizes, computed on the HOST, no GPU needed (offsets are checked, not used; the
+ * checks are the entries' up to the images', then the out-pointers in their order).  Sub-batch k is images sub_first[k] ..
+ * sub_first[k + 1] (room for batch + 1 entries, *sub_count + 1 are written); mid_at[i]: image i's byte offset in its
+ * sub-batch's Lanczos3 intermediate; use_lds[i]: its horizontal pass stages source rows in LDS; tiles_first[i]: its workgroups
+ * in the point pass (256 columns x 4 rows) or the horizontal pass (64 columns x 4 source rows); tiles_second[i]: in the
+ * vertical pass (1024 bytes x 1 row; 0 for nearest and bilinear) — an image has at most 65535 rows of tiles a pass (debug switch
+ * resize_images_rows=n: n), its workgroups stride over the rest; *axis_tables: distinct axis tables built; *launches_first /
+ * *launches_second: launches of the two passes summed over the sub-batches. */
+int pixo_hip_debug_resize_images_plan(const pixo_png_image *src_images, const pixo_png_image *dst_images, uint32_t batch,
+                                      uint8_t algorithm, uint32_t *sub_first, uint32_t *sub_count, uint64_t *mid_at,
+                                      uint8_t *use_lds, uint32_t *tiles_first, uint32_t *tiles_second, uint32_t *axis_tables,
+                                      uint32_t *launches_first, uint32_t *launches_second);
+
 /* ---- runtime ----------------------------------------------------------------------- */
 
 int pixo_hip_device_count(void);            /* 0 when no GPU / no driver              */

@@ -142,6 +142,10 @@ SIGNATURES = {
     "pixo_hip_resize_batch_device": _sig(_rsrcp, _u32, _u32, _u32, _u8, _u8, _vp, _vp, optional=True),
     "pixo_hip_resize_batch": _sig(_rsrcp, _u32, _u32, _u32, _u8, _u8, _u8pp, _szp, optional=True),
     "pixo_hip_debug_resize_batch_plan": _sig(_rsrcp, _u32, _u32, _u32, _u8, _u8, _u32p, _u32p, _u64p, _u8p, _u32p, optional=True),
+    "pixo_hip_resize_images_fit": _sig(_pimgp, _u32, _u32, _u32, _u32, _pimgp, _szp, optional=True),
+    "pixo_hip_resize_images_device": _sig(_vp, _pimgp, _vp, _pimgp, _u32, _u8, _vp, optional=True),
+    "pixo_hip_resize_images": _sig(_vp, _sz, _pimgp, _pimgp, _u32, _u8, _u8pp, _szp, optional=True),
+    "pixo_hip_debug_resize_images_plan": _sig(_pimgp, _pimgp, _u32, _u8, _u32p, _u32p, _u64p, _u8p, _u32p, _u32p, _u32p, _u32p, _u32p, optional=True),
     "pixo_hip_png_decode": _sig(_vp, _sz, _u8pp, _szp, _u32p, _u32p, _u8p),
     "pixo_hip_png_decode_info": _sig(_vp, _sz, _u32p, _u32p, _u8p),
     "pixo_hip_png_decode_device": _sig(_vp, _sz, _vp, _sz, _u32p, _u32p, _u8p, _vp),

@@ -107,6 +107,9 @@ inline int bad_length(size_t expected, size_t got)
 //                      which bounds the scratch, stays)
 //   resize_batch_bytes=n  a sub-batch of pixo_hip_resize_batch* holds at most n bytes of Lanczos3 intermediate (and at least one
 //                      image) instead of 256 MiB: tests reach a sub-batch boundary with small images
+//   resize_images_rows=n  an image of pixo_hip_resize_images* has at most n rows of tiles in a pass instead of 65535 (the single
+//                      entry's grid.y limit): tests reach the kernels' row-stride loops with small images.  resize_batch_bytes
+//                      cuts those entries' sub-batches too
 //   decode_batch_bytes=n  a sub-batch of pixo_hip_png_decode_batch* holds at most n bytes of device staging (inflated streams +
 //                      reconstructed rows; at least one image) instead of 512 MiB: tests reach a sub-batch boundary with small images
 //   no_bands_upload    host pixels are uploaded in one copy instead of MCU-row bands pipelined with the kernels
@@ -131,6 +134,7 @@ struct DebugSwitches {
     uint32_t batch_parts = 0; // (measurements) sub-batches of pixo_hip_jpeg_encode_batch_device_into, 0 = the library's choice
     uint64_t png_batch_bytes = 0; // bytes of prepared stream a sub-batch of the PNG batch entries holds at most, 0 = 64 MiB
     uint64_t resize_batch_bytes = 0; // bytes of Lanczos3 intermediate a sub-batch of the resize batch entries holds at most, 0 = 256 MiB
+    uint32_t resize_images_rows = 0; // rows of tiles an image of pixo_hip_resize_images* has at most in a pass, 0 = 65535
     uint64_t decode_batch_bytes = 0; // bytes of device staging a sub-batch of the PNG decode batch entries holds at most, 0 = 512 MiB
 };
 const DebugSwitches &debug();

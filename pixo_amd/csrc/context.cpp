@@ -84,6 +84,7 @@ DebugSwitches parse_switches(const char *e)
         else if (name == "batch_parts" && num > 0) v.batch_parts = static_cast<uint32_t>(num);
         else if (name == "png_batch_bytes" && num > 0) v.png_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "resize_batch_bytes" && num > 0) v.resize_batch_bytes = static_cast<uint64_t>(num);
+        else if (name == "resize_images_rows" && num > 0) v.resize_images_rows = static_cast<uint32_t>(num > 65535 ? 65535 : num);
         else if (name == "decode_batch_bytes" && num > 0) v.decode_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "spin_budget" && !val.empty()) v.spin_budget = static_cast<uint32_t>(num < 0 ? 0 : num);
         else if (name == "piece_schedule") {

@@ -12,18 +12,42 @@
 //                            alike, whatever the pixel size): per tap the workgroup reads consecutive aligned dwords of one
 //                            intermediate row (rows padded to 16 bytes), the tap's weight is uniform over the workgroup.
 //
-// Each of the three is a __device__ body with two __global__ entries: the single one (one image, its shape in the kernel
-// arguments) and the batch one (blockIdx.z is the image: every workgroup reads its image's ResizeBatchItem, then walks the
-// same body).  N sources of individual sizes go to N images of ONE destination size, written back to back.
+// Each of the three is a __device__ body, which takes its tile's coordinates and the row stride as parameters, with three
+// __global__ entries: the single one (one image, its shape in the kernel arguments; the tile is blockIdx.x / .y), the batch
+// one (blockIdx.z is the image: every workgroup reads its image's ResizeBatchItem, then walks the same body: N sources of
+// individual sizes to N images of ONE destination size, written back to back) and the images one (a flat 1-D grid over
+// the tiles of images of individual source AND destination sizes: every workgroup finds its image's Record by a binary
+// search with its uniform tile index — resize_images_math.h — then walks the same body).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "resize.hpp"
+#include "resize_images_math.h"
 #include "resize_math.h"
 
 namespace {
 
 constexpr int kSegBytes = pixo_dev::kResizeSegBytes; // LDS bytes per staged source row segment (four rows per workgroup: 32 KiB)
+
+namespace rzi = pixo_resize_images;
+static_assert(rzi::kPointTileCols == 64 * 4 && rzi::kPointTileRows == 4 && rzi::kHTileCols == pixo_dev::kResizeHTile && rzi::kHTileRows == 4 &&
+                  rzi::kVTileBytes == 256 * 4 && rzi::kVTileRows == 1,
+              "the tiles the table counts are the workgroups' of the bodies below");
+// The table of a ragged launch was uploaded before the launch and nothing writes it: read through the constant address
+// space, the search (its tile index is blockIdx.x) and the record are scalar loads, the values stay in scalar registers.
+using ConstRecord = const __attribute__((address_space(4))) rzi::Record;
+struct TileOf {
+    ConstRecord *im;
+    uint32_t tx, ty;
+};
+__device__ __forceinline__ TileOf tile_of(const rzi::Record *records, uint32_t count)
+{
+    ConstRecord *table = (ConstRecord *)records;
+    TileOf t;
+    t.im = table + rzi::image_of_tile(table, count, blockIdx.x);
+    rzi::tile_in_image(blockIdx.x, t.im->first_tile, t.im->tiles_x, &t.tx, &t.ty);
+    return t;
+}
 
 // ---- nearest / bilinear -----------------------------------------------------------------------------------------------------
 template <int BPP> __device__ __forceinline__ void store_group(uint8_t *p, const uint8_t (&o)[4 * BPP], uint32_t pixels)
@@ -39,9 +63,9 @@ template <int BPP> __device__ __forceinline__ void store_group(uint8_t *p, const
 
 template <int BPP, int ALGO>
 __device__ __forceinline__ void resize_point_body(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ dst, uint32_t dw,
-                                                  uint32_t dh)
+                                                  uint32_t dh, size_t tile_x, size_t tile_y, size_t tiles_y)
 {
-    const size_t gx = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const size_t gx = tile_x * 64 + threadIdx.x;
     if (gx * 4 >= dw) return;
     const uint32_t x_first = (uint32_t)(gx * 4);
     const uint32_t pixels = dw - x_first < 4 ? dw - x_first : 4;
@@ -55,7 +79,7 @@ __device__ __forceinline__ void resize_point_body(const uint8_t *__restrict__ sr
         if (ALGO == RZ_NEAREST) { x0[k] = rz_nearest_index(x, xr, sw); x1[k] = x0[k]; fx[k] = 0.0f; }
         else rz_bilinear_axis(x, xr, sw, &x0[k], &x1[k], &fx[k]);
     }
-    for (size_t y = (size_t)blockIdx.y * 4 + threadIdx.y; y < dh; y += (size_t)gridDim.y * 4) {
+    for (size_t y = tile_y * 4 + threadIdx.y; y < dh; y += tiles_y * 4) {
         uint8_t o[4 * BPP];
         if (ALGO == RZ_NEAREST) {
             const uint8_t *row = src + (size_t)rz_nearest_index((uint32_t)y, yr, sh) * sw * BPP;
@@ -82,7 +106,7 @@ template <int BPP, int ALGO>
 __global__ __launch_bounds__(256) void resize_point_kernel(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ dst,
                                                            uint32_t dw, uint32_t dh)
 {
-    resize_point_body<BPP, ALGO>(src, sw, sh, dst, dw, dh);
+    resize_point_body<BPP, ALGO>(src, sw, sh, dst, dw, dh, blockIdx.x, blockIdx.y, gridDim.y);
 }
 // Image blockIdx.z of a batch: its own source and column terms, its place in the block of outputs.  (An image of 4 * k + 1 .. 3
 // bytes puts the next one off a dword: store_group looks at the address.)
@@ -91,7 +115,16 @@ __global__ __launch_bounds__(256) void resize_point_batch_kernel(const pixo_dev:
                                                                  uint32_t dw, uint32_t dh)
 {
     const pixo_dev::ResizeBatchItem it = items[blockIdx.z];
-    resize_point_body<BPP, ALGO>(it.src, it.sw, it.sh, dst + (size_t)blockIdx.z * dw * dh * BPP, dw, dh);
+    resize_point_body<BPP, ALGO>(it.src, it.sw, it.sh, dst + (size_t)blockIdx.z * dw * dh * BPP, dw, dh, blockIdx.x, blockIdx.y, gridDim.y);
+}
+// Tile blockIdx.x of a ragged launch: 256 columns x 4 rows of its image's destination; all images of the launch have BPP
+// bytes a pixel.  The image's rows of tiles are capped: the body's row loop strides over the rest.
+template <int BPP, int ALGO>
+__global__ __launch_bounds__(256) void resize_point_images_kernel(const rzi::Record *__restrict__ records, uint32_t count)
+{
+    const TileOf t = tile_of(records, count);
+    resize_point_body<BPP, ALGO>(reinterpret_cast<const uint8_t *>(t.im->src), t.im->sw, t.im->sh, reinterpret_cast<uint8_t *>(t.im->dst), t.im->dw,
+                                 t.im->dh, t.tx, t.ty, t.im->tiles_y);
 }
 
 // ---- Lanczos3, horizontal ------------------------------------------------------------------------------------------------------
@@ -119,19 +152,20 @@ __device__ __forceinline__ uint32_t stage_segment(const uint8_t *img, size_t img
 
 template <int BPP>
 __device__ __forceinline__ void resize_lanczos_h_body(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ mid,
-                                                      size_t mid_stride, uint32_t dw, pixo_dev::ResizeAxisTable t, int use_lds)
+                                                      size_t mid_stride, uint32_t dw, pixo_dev::ResizeAxisTable t, int use_lds, size_t tile_x,
+                                                      size_t tile_y, size_t tiles_y)
 {
     __shared__ __attribute__((aligned(16))) uint8_t seg[4][kSegBytes];
-    const size_t d = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const size_t d = tile_x * 64 + threadIdx.x;
     const bool col = d < dw;
     uint32_t start = 0, off = 0, cnt = 0;
     if (col) { start = t.start[d]; off = t.off[d]; cnt = t.off[d + 1] - off; }
     // the source pixels this wavefront's outputs cover: starts and ends do not decrease with d
-    const size_t d_first = (size_t)blockIdx.x * 64, d_last = d_first + 63 < dw ? d_first + 63 : dw - 1;
+    const size_t d_first = tile_x * 64, d_last = d_first + 63 < dw ? d_first + 63 : dw - 1;
     const uint32_t lo = t.start[d_first];
     const uint32_t hi = t.start[d_last] + (t.off[d_last + 1] - t.off[d_last]);
     const size_t img_bytes = (size_t)sw * sh * BPP;
-    for (size_t yb = (size_t)blockIdx.y * 4; yb < sh; yb += (size_t)gridDim.y * 4) {
+    for (size_t yb = tile_y * 4; yb < sh; yb += tiles_y * 4) {
         const size_t y = yb + threadIdx.y;
         const bool row = y < sh;
         uint32_t shift = 0;
@@ -174,7 +208,7 @@ template <int BPP>
 __global__ __launch_bounds__(256) void resize_lanczos_h_kernel(const uint8_t *__restrict__ src, uint32_t sw, uint32_t sh, uint8_t *__restrict__ mid,
                                                                size_t mid_stride, uint32_t dw, pixo_dev::ResizeAxisTable t, int use_lds)
 {
-    resize_lanczos_h_body<BPP>(src, sw, sh, mid, mid_stride, dw, t, use_lds);
+    resize_lanczos_h_body<BPP>(src, sw, sh, mid, mid_stride, dw, t, use_lds, blockIdx.x, blockIdx.y, gridDim.y);
 }
 // One axis of the batch's tables (ResizeAxisTable's layout at a byte offset of the block)
 __device__ __forceinline__ pixo_dev::ResizeAxisTable batch_axis(const uint8_t *tables, uint64_t at, uint32_t dst)
@@ -193,17 +227,29 @@ __global__ __launch_bounds__(256) void resize_lanczos_h_batch_kernel(const pixo_
                                                                      uint32_t dw)
 {
     const pixo_dev::ResizeBatchItem it = items[blockIdx.z];
-    resize_lanczos_h_body<BPP>(it.src, it.sw, it.sh, mid + it.mid_at, mid_stride, dw, batch_axis(tables, it.h_at, dw), (int)it.use_lds);
+    resize_lanczos_h_body<BPP>(it.src, it.sw, it.sh, mid + it.mid_at, mid_stride, dw, batch_axis(tables, it.h_at, dw), (int)it.use_lds, blockIdx.x,
+                               blockIdx.y, gridDim.y);
+}
+// Tile blockIdx.x of a ragged launch: 64 destination columns x 4 source rows of its image.  Record, tile and row stride are
+// uniform over the workgroup, so the body's row loop — the one that holds the barriers — has the same bounds for all its
+// threads; staged and direct images share a launch, use_lds is the image's.
+template <int BPP>
+__global__ __launch_bounds__(256) void resize_lanczos_h_images_kernel(const rzi::Record *__restrict__ records, uint32_t count,
+                                                                      const uint8_t *__restrict__ tables, uint8_t *__restrict__ mid)
+{
+    const TileOf t = tile_of(records, count);
+    resize_lanczos_h_body<BPP>(reinterpret_cast<const uint8_t *>(t.im->src), t.im->sw, t.im->sh, mid + t.im->mid_at, (size_t)t.im->mid_stride, t.im->dw,
+                               batch_axis(tables, t.im->h_at, t.im->dw), (int)t.im->use_lds, t.tx, t.ty, t.im->tiles_y);
 }
 
 // ---- Lanczos3, vertical ----------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void resize_lanczos_v_body(const uint8_t *__restrict__ mid, size_t mid_stride, uint8_t *__restrict__ dst, size_t row_bytes,
-                                                      uint32_t dh, pixo_dev::ResizeAxisTable t)
+                                                      uint32_t dh, pixo_dev::ResizeAxisTable t, size_t tile_x, size_t tile_y, size_t tiles_y)
 {
-    const size_t b = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t b = (tile_x * 256 + threadIdx.x) * 4;
     if (b >= row_bytes) return;
     const uint32_t n = row_bytes - b < 4 ? (uint32_t)(row_bytes - b) : 4;
-    for (size_t y = blockIdx.y; y < dh; y += gridDim.y) {
+    for (size_t y = tile_y; y < dh; y += tiles_y) {
         const uint32_t start = t.start[y], off = t.off[y], cnt = t.off[y + 1] - off; // uniform over the workgroup
         const uint8_t *p = mid + (size_t)start * mid_stride + b;                       // (b + 4 <= mid_stride: rows are padded)
         float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
@@ -226,7 +272,7 @@ __device__ __forceinline__ void resize_lanczos_v_body(const uint8_t *__restrict_
 __global__ __launch_bounds__(256) void resize_lanczos_v_kernel(const uint8_t *__restrict__ mid, size_t mid_stride, uint8_t *__restrict__ dst,
                                                                size_t row_bytes, uint32_t dh, pixo_dev::ResizeAxisTable t)
 {
-    resize_lanczos_v_body(mid, mid_stride, dst, row_bytes, dh, t);
+    resize_lanczos_v_body(mid, mid_stride, dst, row_bytes, dh, t, blockIdx.x, blockIdx.y, gridDim.y);
 }
 // Image blockIdx.z of a sub-batch: its vertical table, its rows of the intermediate (mid_at is a multiple of 16: rows are padded)
 __global__ __launch_bounds__(256) void resize_lanczos_v_batch_kernel(const pixo_dev::ResizeBatchItem *__restrict__ items,
@@ -234,13 +280,23 @@ __global__ __launch_bounds__(256) void resize_lanczos_v_batch_kernel(const pixo_
                                                                      size_t mid_stride, uint8_t *__restrict__ dst, size_t row_bytes, uint32_t dh)
 {
     const pixo_dev::ResizeBatchItem it = items[blockIdx.z];
-    resize_lanczos_v_body(mid + it.mid_at, mid_stride, dst + (size_t)blockIdx.z * row_bytes * dh, row_bytes, dh, batch_axis(tables, it.v_at, dh));
+    resize_lanczos_v_body(mid + it.mid_at, mid_stride, dst + (size_t)blockIdx.z * row_bytes * dh, row_bytes, dh, batch_axis(tables, it.v_at, dh),
+                          blockIdx.x, blockIdx.y, gridDim.y);
+}
+// Tile blockIdx.x of a ragged launch: 1024 bytes of one destination row of its image, whatever its pixel size: one launch
+// serves every image of a sub-batch.
+__global__ __launch_bounds__(256) void resize_lanczos_v_images_kernel(const rzi::Record *__restrict__ records, uint32_t count,
+                                                                      const uint8_t *__restrict__ tables, const uint8_t *__restrict__ mid)
+{
+    const TileOf t = tile_of(records, count);
+    resize_lanczos_v_body(mid + t.im->mid_at, (size_t)t.im->mid_stride, reinterpret_cast<uint8_t *>(t.im->dst), (size_t)t.im->dw * t.im->bpp, t.im->dh,
+                          batch_axis(tables, t.im->v_at, t.im->dh), t.tx, t.ty, t.im->tiles_y);
 }
 
 uint32_t rows_grid(uint32_t rows, uint32_t per_block) // grid.y: the kernels stride over what does not fit
 {
     const uint32_t g = (rows + per_block - 1) / per_block;
-    return g < 65535u ? g : 65535u;
+    return g < rzi::kRowsCap ? g : rzi::kRowsCap; // (65535: the images entries cap an image's rows of tiles at the same value)
 }
 
 } // namespace
@@ -352,6 +408,56 @@ hipError_t launch_resize_lanczos_v_batch(const ResizeBatchItem *d_items, uint32_
     const dim3 grid(static_cast<unsigned>((row_bytes + 1023) / 1024), rows_grid(dh, 1), n), block(256);
     hipLaunchKernelGGL(resize_lanczos_v_batch_kernel, grid, block, 0, stream, d_items, d_tables, d_mid, resize_mid_stride(dw, bpp), d_dst, row_bytes,
                        dh);
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_point_images(const pixo_resize_images::Record *d_records, uint32_t count, uint32_t tiles, uint32_t bpp, int algorithm,
+                                      hipStream_t stream)
+{
+    if (bpp < 1 || bpp > 4 || count < 1 || tiles < count || tiles > rzi::kMaxTiles || (algorithm != RZ_NEAREST && algorithm != RZ_BILINEAR))
+        return hipErrorInvalidValue;
+    const dim3 grid(tiles), block(64, 4);
+#define PIXO_RZ_POINT(B, A) hipLaunchKernelGGL((resize_point_images_kernel<B, A>), grid, block, 0, stream, d_records, count)
+    if (algorithm == RZ_NEAREST) {
+        switch (bpp) {
+        case 1: PIXO_RZ_POINT(1, RZ_NEAREST); break;
+        case 2: PIXO_RZ_POINT(2, RZ_NEAREST); break;
+        case 3: PIXO_RZ_POINT(3, RZ_NEAREST); break;
+        default: PIXO_RZ_POINT(4, RZ_NEAREST); break;
+        }
+    } else {
+        switch (bpp) {
+        case 1: PIXO_RZ_POINT(1, RZ_BILINEAR); break;
+        case 2: PIXO_RZ_POINT(2, RZ_BILINEAR); break;
+        case 3: PIXO_RZ_POINT(3, RZ_BILINEAR); break;
+        default: PIXO_RZ_POINT(4, RZ_BILINEAR); break;
+        }
+    }
+#undef PIXO_RZ_POINT
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_lanczos_h_images(const pixo_resize_images::Record *d_records, uint32_t count, uint32_t tiles, const uint8_t *d_tables,
+                                          uint8_t *d_mid, uint32_t bpp, hipStream_t stream)
+{
+    if (bpp < 1 || bpp > 4 || count < 1 || tiles < count || tiles > rzi::kMaxTiles) return hipErrorInvalidValue;
+    const dim3 grid(tiles), block(64, 4);
+#define PIXO_RZ_H(B) hipLaunchKernelGGL((resize_lanczos_h_images_kernel<B>), grid, block, 0, stream, d_records, count, d_tables, d_mid)
+    switch (bpp) {
+    case 1: PIXO_RZ_H(1); break;
+    case 2: PIXO_RZ_H(2); break;
+    case 3: PIXO_RZ_H(3); break;
+    default: PIXO_RZ_H(4); break;
+    }
+#undef PIXO_RZ_H
+    return hipGetLastError();
+}
+
+hipError_t launch_resize_lanczos_v_images(const pixo_resize_images::Record *d_records, uint32_t count, uint32_t tiles, const uint8_t *d_tables,
+                                          const uint8_t *d_mid, hipStream_t stream)
+{
+    if (count < 1 || tiles < count || tiles > rzi::kMaxTiles) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resize_lanczos_v_images_kernel, dim3(tiles), dim3(256), 0, stream, d_records, count, d_tables, d_mid);
     return hipGetLastError();
 }
 

@@ -5,6 +5,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "resize_images_math.h"
+
 namespace pixo_dev {
 
 // One axis of a Lanczos3 contribution table as the kernels read it (device pointers): the taps of destination index d are
@@ -55,5 +57,16 @@ hipError_t launch_resize_lanczos_h_batch(const ResizeBatchItem *d_items, uint32_
                                          uint32_t dw, uint32_t bpp, hipStream_t stream);
 hipError_t launch_resize_lanczos_v_batch(const ResizeBatchItem *d_items, uint32_t n, const uint8_t *d_tables, const uint8_t *d_mid, uint8_t *d_dst,
                                          uint32_t dw, uint32_t dh, uint32_t bpp, hipStream_t stream);
+
+// ---- images: n sources of individual sizes -> n images of individual sizes, anywhere (resize_images_math.h) ----------------
+// One flat launch over the `tiles` tiles of `count` records (device memory, as build_table made them for the pass); every image
+// of a point or horizontal launch has `bpp` bytes a pixel, the vertical launch takes images of any.  d_tables: the block of
+// axis tables h_at / v_at count from; d_mid: the sub-batch's intermediate mid_at counts from.
+hipError_t launch_resize_point_images(const pixo_resize_images::Record *d_records, uint32_t count, uint32_t tiles, uint32_t bpp, int algorithm,
+                                      hipStream_t stream);
+hipError_t launch_resize_lanczos_h_images(const pixo_resize_images::Record *d_records, uint32_t count, uint32_t tiles, const uint8_t *d_tables,
+                                          uint8_t *d_mid, uint32_t bpp, hipStream_t stream);
+hipError_t launch_resize_lanczos_v_images(const pixo_resize_images::Record *d_records, uint32_t count, uint32_t tiles, const uint8_t *d_tables,
+                                          const uint8_t *d_mid, hipStream_t stream);
 
 } // namespace pixo_dev

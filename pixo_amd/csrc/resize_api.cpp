@@ -2,12 +2,17 @@
 // reference's order, the Lanczos3 contribution tables (built on the host once per call from resize_math.h, uploaded through
 // the context's pinned staging), the launches of resize.hip.  The batch entries: the plan (tables shared between images of
 // one size, sub-batches that bound the intermediate), one upload of tables and items, one launch per pass and sub-batch.
+// The images entries: sources AND destinations of individual sizes and colour types, described by pixo_png_image records —
+// the fitted sizes, the plan, the records of the flat launches (resize_images_math.h), one launch per pass and pixel size.
 #include "capi_internal.hpp"
 #include "resize.hpp"
 #include "resize_math.h"
 
 #include <algorithm>
+#include <cmath>
 #include <map>
+#include <string>
+#include <utility>
 #include <vector>
 
 using namespace pixo_capi;
@@ -309,9 +314,316 @@ int resize_batch_on_device(Context &c, const pixo_resize_source *sources, uint32
     return PIXO_OK;
 }
 
+// ---- images: n sources of individual sizes and colour types -> n images of individual sizes, anywhere in one block ----------
+namespace rzi = pixo_resize_images;
+
+// JavaScript's Math.round for x >= 0: the nearest integer, a tie towards +infinity (x - floor(x) is exact in f64)
+double js_round(double x)
+{
+    const double f = std::floor(x);
+    return x - f >= 0.5 ? f + 1.0 : f;
+}
+// The largest size of (sw, sh)'s proportions inside the box, as the reference's front end computes it (web/src/lib/wasm.ts
+// calculateResizeDimensions): the box's width and the height that goes with it; if that is too tall, the box's height and
+// the width that goes with it.  f64 throughout, each side at least 1; neither side exceeds the box's.
+void fit_size(uint32_t sw, uint32_t sh, uint32_t box_w, uint32_t box_h, uint32_t *dw, uint32_t *dh)
+{
+    const double aspect = static_cast<double>(sw) / static_cast<double>(sh);
+    double w = box_w, h = js_round(static_cast<double>(box_w) / aspect);
+    if (h > static_cast<double>(box_h)) {
+        h = box_h;
+        w = js_round(static_cast<double>(box_h) * aspect);
+    }
+    *dw = static_cast<uint32_t>(std::max(1.0, w));
+    *dh = static_cast<uint32_t>(std::max(1.0, h));
+}
+
+// What the driver decided for the images, before anything touches a device (also: pixo_hip_debug_resize_images_plan).
+struct ImagesPlan {
+    std::vector<uint32_t> sub_first;                 // sub-batch k is images [sub_first[k], sub_first[k + 1])
+    std::vector<uint64_t> mid_at;                    // per image: its rows' offset in the intermediate of its sub-batch
+    std::vector<uint8_t> use_lds;                    // per image: the horizontal pass stages in LDS
+    std::vector<uint32_t> h_axis, v_axis;            // per image: its axes in `axes`
+    std::vector<uint32_t> tiles_first, tiles_second; // per image: its tiles in the point / horizontal pass, in the vertical pass
+    std::vector<BatchAxis> axes;                     // one per distinct (source, destination) pair per axis
+    size_t table_bytes = 0;                          // all tables, each 16-byte aligned
+    uint64_t mid_bytes = 0;                          // the largest sub-batch's intermediate
+    uint32_t launches_first = 0, launches_second = 0; // launches of the two passes, summed over the sub-batches
+    uint32_t rows_cap = rzi::kRowsCap;
+};
+
+// The images have passed resize_images_checks.  No HIP in here.
+int resize_images_plan(const pixo_png_image *src, const pixo_png_image *dst, uint32_t batch, uint8_t algorithm, ImagesPlan &p)
+{
+    const bool lanczos = algorithm == PIXO_RESIZE_LANCZOS3;
+    p.rows_cap = debug().resize_images_rows ? debug().resize_images_rows : rzi::kRowsCap;
+    p.mid_at.assign(batch, 0);
+    p.use_lds.assign(batch, 0);
+    p.h_axis.assign(batch, 0);
+    p.v_axis.assign(batch, 0);
+    p.tiles_first.assign(batch, 0);
+    p.tiles_second.assign(batch, 0);
+    p.sub_first.assign(1, 0u);
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> h_of, v_of;
+    const auto axis_of = [&](std::map<std::pair<uint32_t, uint32_t>, uint32_t> &seen, uint32_t s, uint32_t d, uint32_t *index) -> int {
+        const auto found = seen.find({s, d});
+        if (found != seen.end()) { *index = found->second; return PIXO_OK; }
+        size_t total = 0;
+        uint32_t span = 0;
+        axis_measure(s, d, &total, &span);
+        if (total > 0xFFFFFFFFull) return fail(PIXO_ERR_COMPRESSION, "Compression error: contribution table too large");
+        BatchAxis a{s, d, span, p.table_bytes, axis_table_bytes(d, total)};
+        p.table_bytes += a.bytes;
+        *index = seen[{s, d}] = static_cast<uint32_t>(p.axes.size());
+        p.axes.push_back(a);
+        return PIXO_OK;
+    };
+    const uint64_t limit = debug().resize_batch_bytes ? debug().resize_batch_bytes : kResizeBatchMidBytes;
+    uint64_t held = 0;                     // the current sub-batch's intermediate so far
+    uint64_t first[5] = {0, 0, 0, 0, 0};   // ... the tiles of its point / horizontal launches so far, by bytes per pixel
+    uint64_t second = 0;                   // ... of its vertical launch
+    for (uint32_t i = 0; i < batch; ++i) {
+        const uint32_t bpp = bytes_per_pixel(src[i].color_type);
+        uint64_t rows = 0;
+        if (lanczos) {
+            int rc;
+            if ((rc = axis_of(h_of, src[i].width, dst[i].width, &p.h_axis[i])) || (rc = axis_of(v_of, src[i].height, dst[i].height, &p.v_axis[i]))) return rc;
+            p.use_lds[i] = pixo_dev::resize_h_uses_lds(p.axes[p.h_axis[i]].max_span, bpp);
+            rows = static_cast<uint64_t>(pixo_dev::resize_mid_stride(dst[i].width, bpp)) * src[i].height; // (at most 2^26 * 2^24)
+        }
+        const uint64_t a = rzi::tile_count(lanczos ? rzi::PASS_H : rzi::PASS_POINT, src[i].height, dst[i].width, dst[i].height, bpp, p.rows_cap);
+        const uint64_t b = lanczos ? rzi::tile_count(rzi::PASS_V, src[i].height, dst[i].width, dst[i].height, bpp, p.rows_cap) : 0;
+        // every sub-batch holds at least one image; a launch's tiles stay within 31 bits (one image's do: tiles_of)
+        if (i > p.sub_first.back() && (held + rows > limit || first[bpp] + a > rzi::kMaxTiles || second + b > rzi::kMaxTiles)) {
+            p.sub_first.push_back(i);
+            held = second = 0;
+            std::fill(first, first + 5, uint64_t{0});
+        }
+        if (first[bpp] == 0) p.launches_first += 1;
+        if (lanczos && second == 0) p.launches_second += 1;
+        p.mid_at[i] = held;
+        p.tiles_first[i] = static_cast<uint32_t>(a);
+        p.tiles_second[i] = static_cast<uint32_t>(b);
+        held += rows;
+        first[bpp] += a;
+        second += b;
+        p.mid_bytes = std::max(p.mid_bytes, held);
+    }
+    p.sub_first.push_back(batch);
+    return PIXO_OK;
+}
+
+// The checks the images entries share, in their order (include/pixo_hip.h).  *src_end / *dst_end: the furthest image's end.
+int resize_images_checks(const pixo_png_image *src_images, const pixo_png_image *dst_images, uint32_t batch, uint8_t algorithm, uint64_t *src_end,
+                         uint64_t *dst_end)
+{
+    PIXO_REQUIRE(src_images);
+    PIXO_REQUIRE(dst_images);
+    int rc = batch_in_range(batch);
+    if (rc) return rc;
+    const uint64_t most = uint64_t{1} << 62; // (an image is at most 2^50 bytes)
+    *src_end = *dst_end = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        const std::string where = " (image " + std::to_string(i) + ")";
+        const pixo_png_image &a = src_images[i], &b = dst_images[i];
+        pixo_resize_options o;
+        o.src_width = a.width; o.src_height = a.height;
+        o.dst_width = b.width; o.dst_height = b.height;
+        o.color_type = a.color_type; o.algorithm = algorithm;
+        size_t in_bytes = 0, out_bytes = 0;
+        if ((rc = resize_plan(&o, true, 0, &in_bytes, &out_bytes))) return fail(rc, t_error + where);
+        if (b.color_type != a.color_type) return fail(PIXO_ERR_COMPRESSION, "Compression error: colour types differ" + where);
+        if (a.offset > most || a.offset + in_bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch input too large" + where);
+        if (b.offset > most || b.offset + out_bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large" + where);
+        *src_end = std::max<uint64_t>(*src_end, a.offset + in_bytes);
+        *dst_end = std::max<uint64_t>(*dst_end, b.offset + out_bytes);
+    }
+    return PIXO_OK;
+}
+
+// Enqueues the images on `s`: d_src + src[i].offset -> d_dst + dst[i].offset.  The tables and the records of every pass and
+// sub-batch go up in one copy; the sub-batches follow each other on `s`, so the intermediate is reused in stream order.
+// Shares the batch entries' buffers and their event: the two kinds of job take turns as two batches do.
+int resize_images_on_device(Context &c, const uint8_t *d_src, const pixo_png_image *src, uint8_t *d_dst, const pixo_png_image *dst, uint32_t batch,
+                            uint8_t algorithm, hipStream_t s)
+{
+    ImagesPlan p;
+    int rc = resize_images_plan(src, dst, batch, algorithm, p);
+    if (rc) return rc;
+    const bool lanczos = algorithm == PIXO_RESIZE_LANCZOS3;
+    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1), passes = lanczos ? 2 : 1;
+    note_route((lanczos ? route::RESIZE_LANCZOS3 : algorithm == PIXO_RESIZE_NEAREST ? route::RESIZE_NEAREST : route::RESIZE_BILINEAR) |
+               route::RESIZE_IMAGES | (subs > 1 ? route::SUB_BATCHES : 0));
+    if (!c.rb_done) HIP_TRY(hipEventCreateWithFlags(&c.rb_done, hipEventDisableTiming));
+    // the job before may still be reading the tables and the records, and the staging may still be on its way: all of them
+    // are about to change.  The call's only host wait.
+    HIP_TRY(hipEventSynchronize(c.rb_done));
+    // everything is reserved before any address is handed out (a growing reserve frees first: a device-wide wait)
+    const size_t up_bytes = p.table_bytes + static_cast<size_t>(passes) * batch * sizeof(rzi::Record);
+    if ((rc = c.rb_stage.reserve(up_bytes)) || (rc = c.rb_tables.reserve(up_bytes)) || (rc = c.rb_mid.reserve(p.mid_bytes))) return rc;
+    uint8_t *stage = c.rb_stage.as<uint8_t>();
+    const unsigned builders = static_cast<unsigned>(std::min<size_t>({kResizeBatchTableThreads, p.axes.size(), p.table_bytes / kResizeBatchTableShare + 1}));
+    run_on_threads(builders, [&](unsigned k) {
+        for (size_t a = k; a < p.axes.size(); a += std::max(builders, 1u)) (void)fill_axis(p.axes[a].src, p.axes[a].dst, stage + p.axes[a].at);
+    });
+    // the records: pass after pass, inside a pass sub-batch after sub-batch (table_bytes is a multiple of 16)
+    rzi::Record *records = reinterpret_cast<rzi::Record *>(stage + p.table_bytes);
+    struct Enqueued {
+        rzi::Launch l;
+        int pass;
+        size_t first_record; // in `records`
+    };
+    std::vector<Enqueued> launches;
+    std::vector<rzi::Item> items;
+    std::vector<rzi::Record> table;
+    std::vector<rzi::Launch> of_pass;
+    std::vector<uint32_t> record_item;
+    for (uint32_t k = 0; k < subs; ++k) {
+        const uint32_t first = p.sub_first[k], n = p.sub_first[k + 1] - first;
+        items.clear();
+        for (uint32_t i = first; i < first + n; ++i) {
+            const uint32_t bpp = bytes_per_pixel(src[i].color_type);
+            items.push_back(rzi::Item{reinterpret_cast<uint64_t>(d_src) + src[i].offset, reinterpret_cast<uint64_t>(d_dst) + dst[i].offset, p.mid_at[i],
+                                      lanczos ? pixo_dev::resize_mid_stride(dst[i].width, bpp) : 0, lanczos ? p.axes[p.h_axis[i]].at : 0,
+                                      lanczos ? p.axes[p.v_axis[i]].at : 0, src[i].width, src[i].height, dst[i].width, dst[i].height, bpp, p.use_lds[i]});
+        }
+        for (uint32_t pass = 0; pass < passes; ++pass) {
+            const int which = !lanczos ? rzi::PASS_POINT : pass == 0 ? rzi::PASS_H : rzi::PASS_V;
+            if (!rzi::build_table(items, which, p.rows_cap, table, of_pass, record_item))
+                return fail(PIXO_ERR_COMPRESSION, "Compression error: resize launch too large"); // (the plan cuts before that)
+            const size_t at = static_cast<size_t>(pass) * batch + first;
+            std::copy(table.begin(), table.end(), records + at);
+            for (const rzi::Launch &l : of_pass) launches.push_back(Enqueued{l, which, at + l.first_record});
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(c.rb_tables.p, stage, up_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c.rb_done, s)); // (until the job's own record: the upload)
+    const uint8_t *d_tables = c.rb_tables.as<uint8_t>();
+    const rzi::Record *d_records = reinterpret_cast<const rzi::Record *>(d_tables + p.table_bytes);
+    for (const Enqueued &e : launches) { // (in the order built: a sub-batch's horizontal launches, its vertical one, the next sub-batch's)
+        const rzi::Record *r = d_records + e.first_record;
+        if (e.pass == rzi::PASS_POINT) HIP_TRY(pixo_dev::launch_resize_point_images(r, e.l.count, e.l.tiles, e.l.bpp, algorithm, s));
+        else if (e.pass == rzi::PASS_H)
+            HIP_TRY(pixo_dev::launch_resize_lanczos_h_images(r, e.l.count, e.l.tiles, d_tables, c.rb_mid.as<uint8_t>(), e.l.bpp, s));
+        else HIP_TRY(pixo_dev::launch_resize_lanczos_v_images(r, e.l.count, e.l.tiles, d_tables, c.rb_mid.as<uint8_t>(), s));
+    }
+    HIP_TRY(hipEventRecord(c.rb_done, s));
+    return PIXO_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int pixo_hip_resize_images_fit(const pixo_png_image *src_images, uint32_t batch, uint32_t box_width, uint32_t box_height, uint32_t flags,
+                               pixo_png_image *dst_images, size_t *total)
+{
+    PIXO_REQUIRE(src_images);
+    PIXO_REQUIRE(dst_images);
+    PIXO_REQUIRE(total);
+    int rc = batch_in_range(batch);
+    if (rc) return rc;
+    if (box_width == 0 || box_height == 0) return bad_dimensions(box_width, box_height);
+    if (box_width > RZ_MAX_DIMENSION || box_height > RZ_MAX_DIMENSION) return too_large(box_width, box_height, RZ_MAX_DIMENSION);
+    for (uint32_t i = 0; i < batch; ++i) { // nothing is written before every image has passed
+        const std::string where = " (image " + std::to_string(i) + ")";
+        const pixo_png_image &a = src_images[i];
+        if (a.width == 0 || a.height == 0) { rc = bad_dimensions(a.width, a.height); return fail(rc, t_error + where); }
+        if (a.width > RZ_MAX_DIMENSION || a.height > RZ_MAX_DIMENSION) { rc = too_large(a.width, a.height, RZ_MAX_DIMENSION); return fail(rc, t_error + where); }
+        if (a.color_type > PIXO_RGBA)
+            return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid color type: " + std::to_string(a.color_type) +
+                                                        ". Expected 0 (Gray), 1 (GrayAlpha), 2 (Rgb), or 3 (Rgba)" + where);
+    }
+    uint64_t at = 0, end = 0;
+    std::vector<pixo_png_image> fitted(batch); // (dst_images may be src_images)
+    for (uint32_t i = 0; i < batch; ++i) {
+        const pixo_png_image &a = src_images[i];
+        pixo_png_image b{};
+        b.color_type = a.color_type;
+        if ((flags & PIXO_RESIZE_FIT_NO_ENLARGE) && a.width <= box_width && a.height <= box_height) { b.width = a.width; b.height = a.height; }
+        else fit_size(a.width, a.height, box_width, box_height, &b.width, &b.height);
+        b.offset = at;
+        end = at + static_cast<uint64_t>(b.width) * b.height * bytes_per_pixel(b.color_type); // (at most 2^16 images of 2^50 bytes: below 2^64)
+        at = (end + 15) & ~uint64_t{15};
+        fitted[i] = b;
+    }
+    if (end > (uint64_t{1} << 62)) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large");
+    std::copy(fitted.begin(), fitted.end(), dst_images);
+    *total = static_cast<size_t>(end);
+    return PIXO_OK;
+}
+
+int pixo_hip_resize_images_device(const void *d_src, const pixo_png_image *src_images, void *d_dst, const pixo_png_image *dst_images, uint32_t batch,
+                                  uint8_t algorithm, void *stream)
+{
+    uint64_t src_end = 0, dst_end = 0;
+    int rc = resize_images_checks(src_images, dst_images, batch, algorithm, &src_end, &dst_end);
+    if (rc) return rc;
+    PIXO_REQUIRE(d_src);
+    PIXO_REQUIRE(d_dst);
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    return resize_images_on_device(*c, static_cast<const uint8_t *>(d_src), src_images, static_cast<uint8_t *>(d_dst), dst_images, batch, algorithm, s);
+}
+
+int pixo_hip_resize_images(const uint8_t *data, size_t data_len, const pixo_png_image *src_images, const pixo_png_image *dst_images, uint32_t batch,
+                           uint8_t algorithm, uint8_t **out, size_t *out_len)
+{
+    uint64_t src_end = 0, dst_end = 0;
+    int rc = resize_images_checks(src_images, dst_images, batch, algorithm, &src_end, &dst_end);
+    if (rc) return rc;
+    PIXO_REQUIRE(data);
+    PIXO_REQUIRE(out);
+    PIXO_REQUIRE(out_len);
+    if (data_len < src_end) return bad_length(static_cast<size_t>(src_end), data_len);
+    PIXO_THREAD_CONTEXT(c);
+    if ((rc = upload(c, c.rb_in, data, static_cast<size_t>(src_end))) || (rc = reserve16(c.rb_out, static_cast<size_t>(dst_end)))) return rc;
+    uint8_t *block = alloc_file(static_cast<size_t>(dst_end));
+    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    rc = resize_images_on_device(c, c.rb_in.as<uint8_t>(), src_images, c.rb_out.as<uint8_t>(), dst_images, batch, algorithm, c.stream);
+    if (!rc) {
+        const hipError_t e = hipMemcpyAsync(block, c.rb_out.p, static_cast<size_t>(dst_end), hipMemcpyDeviceToHost, c.stream);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    }
+    const hipError_t e = hipStreamSynchronize(c.stream); // (also after a failure: the upload reads the caller's pixels)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (rc) { free_file(block); return rc; }
+    *out = block;
+    *out_len = static_cast<size_t>(dst_end);
+    return PIXO_OK;
+}
+
+int pixo_hip_debug_resize_images_plan(const pixo_png_image *src_images, const pixo_png_image *dst_images, uint32_t batch, uint8_t algorithm,
+                                      uint32_t *sub_first, uint32_t *sub_count, uint64_t *mid_at, uint8_t *use_lds, uint32_t *tiles_first,
+                                      uint32_t *tiles_second, uint32_t *axis_tables, uint32_t *launches_first, uint32_t *launches_second)
+{
+    uint64_t src_end = 0, dst_end = 0;
+    int rc = resize_images_checks(src_images, dst_images, batch, algorithm, &src_end, &dst_end);
+    if (rc) return rc;
+    PIXO_REQUIRE(sub_first);
+    PIXO_REQUIRE(sub_count);
+    PIXO_REQUIRE(mid_at);
+    PIXO_REQUIRE(use_lds);
+    PIXO_REQUIRE(tiles_first);
+    PIXO_REQUIRE(tiles_second);
+    PIXO_REQUIRE(axis_tables);
+    PIXO_REQUIRE(launches_first);
+    PIXO_REQUIRE(launches_second);
+    ImagesPlan p;
+    if ((rc = resize_images_plan(src_images, dst_images, batch, algorithm, p))) return rc;
+    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
+    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    std::copy(p.mid_at.begin(), p.mid_at.end(), mid_at);
+    std::copy(p.use_lds.begin(), p.use_lds.end(), use_lds);
+    std::copy(p.tiles_first.begin(), p.tiles_first.end(), tiles_first);
+    std::copy(p.tiles_second.begin(), p.tiles_second.end(), tiles_second);
+    *axis_tables = static_cast<uint32_t>(p.axes.size());
+    *launches_first = p.launches_first;
+    *launches_second = p.launches_second;
+    return PIXO_OK;
+}
 
 int pixo_hip_resize_batch_device(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height, uint8_t color_type,
                                  uint8_t algorithm, void *d_dst, void *stream)

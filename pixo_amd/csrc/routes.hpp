@@ -56,6 +56,7 @@ enum : uint64_t {
     PNG_INFLATE_HOST_REDO = 1ull << 44, // ... a stream the device did not vouch for was inflated again by the host, whose bytes replaced it
     PNG_IMAGES = 1ull << 45,       // PNG encode of images of individual sizes: one DEFLATE, scan, compaction and CRC launch over all images of a sub-batch
     PNG_IMAGES_FILTER = 1ull << 46, // ... and at least one image's rows went through a ragged filter launch (one per class of images)
+    RESIZE_IMAGES = 1ull << 47,    // resize images entries: one flat launch per pass and pixel size over all images of a sub-batch (beside the algorithm's bit)
 };
 }
 

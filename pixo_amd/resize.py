@@ -13,8 +13,8 @@ from .color import ColorType
 MAX_DIMENSION = 1 << 24
 
 # this module's bits of the route record (pixo_hip_debug_routes; pixo_amd/csrc/routes.hpp)
-ROUTES = {"RESIZE_NEAREST": 36, "RESIZE_BILINEAR": 37, "RESIZE_LANCZOS3": 38, "RESIZE_BATCH": 41}
-ROUTE_RESIZE_NEAREST, ROUTE_RESIZE_BILINEAR, ROUTE_RESIZE_LANCZOS3, ROUTE_RESIZE_BATCH = (1 << b for b in ROUTES.values())
+ROUTES = {"RESIZE_NEAREST": 36, "RESIZE_BILINEAR": 37, "RESIZE_LANCZOS3": 38, "RESIZE_BATCH": 41, "RESIZE_IMAGES": 47}
+ROUTE_RESIZE_NEAREST, ROUTE_RESIZE_BILINEAR, ROUTE_RESIZE_LANCZOS3, ROUTE_RESIZE_BATCH, ROUTE_RESIZE_IMAGES = (1 << b for b in ROUTES.values())
 
 
 class ResizeAlgorithm(enum.IntEnum):
@@ -167,6 +167,88 @@ def resize_batch_plan(sizes, dst_width, dst_height, color_type, algorithm) -> di
     _lib.check(rc)
     return dict(sub_first=list(sub_first[:subs.value + 1]), mid_at=list(mid_at[:n]), use_lds=[bool(v) for v in use_lds[:n]],
                 axis_tables=tables.value)
+
+
+# ---- images of individual sizes and colour types, anywhere in one block (include/pixo_hip.h) --------------------------------
+# The records are the ones `decode.decode_png_batch_info` returns and `png.encode_images*` take: a `_lib.PngImageC` array, a list
+# of (width, height, ColorType, offset), or the (tensor, ColorType) views of `decode.decode_png_batch_device`.
+FIT_NO_ENLARGE = 1  # PIXO_RESIZE_FIT_NO_ENLARGE
+
+
+def _records(images):
+    from .png import _image_records
+    return _image_records(images)
+
+
+def _records_end(arr, n) -> int:
+    return max(arr[i].offset + arr[i].width * arr[i].height * _bpp(arr[i].color_type) for i in range(n)) if n else 0
+
+
+def fit_images(images, box_width, box_height, no_enlarge=False):
+    """([(width, height, ColorType, offset)], total): every image at the largest size of its proportions inside box_width x
+    box_height (the reference front end's `calculateResizeDimensions`), in its own colour type, laid out as a decode batch
+    lays its block out — every offset a multiple of 16, `total` the end of the last image.  `no_enlarge`: an image that fits
+    the box keeps its size.  Sizes only: no GPU."""
+    L = _lib.load()
+    arr, n, _ = _records(images)
+    out, total = (_lib.PngImageC * max(n, 1))(), C.c_size_t()
+    _lib.check(L.pixo_hip_resize_images_fit(arr, n, box_width, box_height, FIT_NO_ENLARGE if no_enlarge else 0, out, C.byref(total)))
+    return [(im.width, im.height, ColorType(im.color_type), im.offset) for im in out[:n]], total.value
+
+
+def resize_images_device(d_src, src_images, d_dst, dst_images, algorithm, stream=0) -> None:
+    """Image i of `src_images` in the block `d_src` (torch tensor / raw pointer; None with the views of a decode batch, which
+    carry their block) -> `dst_images[i]`'s size at its offset in `d_dst`, byte for byte what `resize_device` writes for that
+    pair; the bytes between destinations are left as they are.  Destinations must not overlap each other or a source (not
+    checked).  One launch per pass and pixel size whatever the number of images.  Enqueue only, ordered like `resize_device`."""
+    from .png import _images_block
+    L = _lib.load()
+    src, n, base = _records(src_images)
+    dst, m, _ = _records(dst_images)
+    if m != n:
+        raise ValueError("%d sources, %d destinations" % (n, m))
+    d_src = _images_block(d_src, base)
+    for what, block, arr in (("sources", d_src, src), ("destinations", d_dst, dst)):
+        if hasattr(block, "numel") and n and all(_bpp(arr[i].color_type) for i in range(n)):
+            need, have = _records_end(arr, n), _lib.nbytes(block)
+            if have < need:
+                raise ValueError("the %s end at byte %d, the tensor holds %d" % (what, need, have))
+    rc = L.pixo_hip_resize_images_device(_lib.ptr(d_src), src, _lib.ptr(d_dst), dst, n, int(algorithm), C.c_void_p(stream) if stream else None)
+    _lib.check(rc)
+
+
+def resize_images(block_bytes, src_images, dst_images, algorithm) -> list:
+    """The same for a block in host memory (what `decode.decode_png_batch` works from) -> a list of bytes, image i at
+    `dst_images[i]`'s size."""
+    L = _lib.load()
+    src, n, _ = _records(src_images)
+    dst, m, _ = _records(dst_images)
+    if m != n:
+        raise ValueError("%d sources, %d destinations" % (n, m))
+    px = _flat(np.frombuffer(block_bytes, np.uint8) if isinstance(block_bytes, (bytes, bytearray)) else block_bytes)
+    out, out_len = C.POINTER(C.c_uint8)(), C.c_size_t()
+    _lib.check(L.pixo_hip_resize_images(px.ctypes.data, px.size, src, dst, n, int(algorithm), C.byref(out), C.byref(out_len)))
+    block = _lib.take(L, out, out_len)
+    return [block[im.offset:im.offset + im.width * im.height * _bpp(im.color_type)] for im in dst[:n]]
+
+
+def resize_images_plan(src_images, dst_images, algorithm) -> dict:
+    """What the images entries decide for these records, computed on the host (no GPU): `sub_first`, `mid_at`, `use_lds` and
+    `axis_tables` as `resize_batch_plan`; `tiles_first` / `tiles_second` (each image's workgroups in the point or horizontal
+    pass and in the vertical pass) and `launches_first` / `launches_second` (the passes' launches summed over the sub-batches)."""
+    L = _lib.load()
+    src, n, _ = _records(src_images)
+    dst, m, _ = _records(dst_images)
+    if m != n:
+        raise ValueError("%d sources, %d destinations" % (n, m))
+    sub_first, mid_at, use_lds = (C.c_uint32 * (n + 1))(), (C.c_uint64 * max(n, 1))(), (C.c_uint8 * max(n, 1))()
+    t1, t2 = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+    subs, tables, l1, l2 = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc = L.pixo_hip_debug_resize_images_plan(src, dst, n, int(algorithm), sub_first, C.byref(subs), mid_at, use_lds, t1, t2, C.byref(tables),
+                                             C.byref(l1), C.byref(l2))
+    _lib.check(rc)
+    return dict(sub_first=list(sub_first[:subs.value + 1]), mid_at=list(mid_at[:n]), use_lds=[bool(v) for v in use_lds[:n]],
+                tiles_first=list(t1[:n]), tiles_second=list(t2[:n]), axis_tables=tables.value, launches_first=l1.value, launches_second=l2.value)
 
 
 def resize_image(data, src_width, src_height, dst_width, dst_height, color_type: int, algorithm: int) -> bytes:
