@@ -21,6 +21,7 @@
 //   (a loop over pixo::resize::resize)                  pixo::resize::resize_batch / resize_batch_device
 //   (a loop over pixo::decode::decode_png)              pixo::decode::decode_png_batch
 //   (a loop over pixo::png::encode, one size each)      pixo::png::encode_images
+//   (a loop over pixo::jpeg::encode, one size each)     pixo::jpeg::encode_images / encode_images_device
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -172,6 +173,52 @@ inline void encode_into(std::vector<uint8_t> &output, const uint8_t *data, size_
 [[nodiscard]] inline std::vector<uint8_t> encode(const std::vector<uint8_t> &data, const JpegOptions &options)
 {
     return encode(data.data(), data.size(), options);
+}
+
+// Images of individual sizes, gray or RGB, anywhere in one block (image i at images[i].offset: the records of
+// decode::decode_png_batch and resize::fit_images) -> their files, file i byte for byte what `encode` makes of image i with
+// `options` at its width, height and colour type; the options' own are not read (contract: pixo_hip.h).  With baseline options
+// the launches follow the classes of images present, not their number.  The host form takes the block in host memory, the
+// device form (encode_images_device) a block in HBM on the current HIP device.
+namespace detail {
+template <class Call> std::vector<std::vector<uint8_t>> images_files(size_t count, Call &&call)
+{
+    const uint32_t batch = static_cast<uint32_t>(count > 0xFFFFFFFFull ? 0xFFFFFFFFull : count);
+    std::vector<uint8_t *> files(batch ? batch : 1, nullptr);
+    std::vector<size_t> lens(batch ? batch : 1, 0);
+    const int rc = call(batch, files.data(), lens.data());
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    struct Blocks { // (released also when a copy below throws)
+        std::vector<uint8_t *> &files;
+        ~Blocks() { for (uint8_t *f : files) pixo_hip_free(f); }
+    } blocks{files};
+    std::vector<std::vector<uint8_t>> out(batch);
+    for (uint32_t i = 0; i < batch; ++i) out[i].assign(files[i], files[i] + lens[i]);
+    return out;
+}
+} // namespace detail
+[[nodiscard]] inline std::vector<std::vector<uint8_t>> encode_images(const uint8_t *block, size_t len, const std::vector<pixo_png_image> &images,
+                                                                     const JpegOptions &options)
+{
+    const pixo_jpeg_options c = options.to_c();
+    const pixo_png_image none{}; // (no images: the batch check answers, not the null check in front of it)
+    return detail::images_files(images.size(), [&](uint32_t batch, uint8_t **files, size_t *lens) {
+        return pixo_hip_jpeg_encode_images(block, len, images.empty() ? &none : images.data(), batch, &c, files, lens);
+    });
+}
+[[nodiscard]] inline std::vector<std::vector<uint8_t>> encode_images(const std::vector<uint8_t> &block, const std::vector<pixo_png_image> &images,
+                                                                     const JpegOptions &options)
+{
+    return encode_images(block.data(), block.size(), images, options);
+}
+[[nodiscard]] inline std::vector<std::vector<uint8_t>> encode_images_device(const void *d_pixels, const std::vector<pixo_png_image> &images,
+                                                                            const JpegOptions &options)
+{
+    const pixo_jpeg_options c = options.to_c();
+    const pixo_png_image none{};
+    return detail::images_files(images.size(), [&](uint32_t batch, uint8_t **files, size_t *lens) {
+        return pixo_hip_jpeg_encode_images_device(d_pixels, images.empty() ? &none : images.data(), batch, &c, files, lens);
+    });
 }
 
 } // namespace jpeg

@@ -777,6 +777,53 @@ int pixo_hip_debug_png_encode_images_plan(const pixo_png_image *images, uint32_t
                                           const pixo_png_quantization *quantization, uint32_t alignment, uint32_t *sub_first,
                                           uint32_t *sub_count, uint8_t *way_in, uint8_t *run_strategy, uint32_t *filter_launches);
 
+/* ---- JPEG encode of images of individual sizes and colour types, anywhere in one block ---- */
+
+/* The JPEG end of the chain decode batch -> fit -> resize images: `batch` images anywhere in one block in HBM on the current
+ * HIP device, described by the records the PNG images entries take — image i is images[i].width x images[i].height pixels of
+ * images[i].color_type (PIXO_GRAY or PIXO_RGB), tightly packed, at d_pixels + images[i].offset (any alignment, gaps and
+ * overlaps allowed: the pixels are only read; `reserved` is not read).  `options` is a template: its width, height and
+ * color_type are NOT read; quality, subsampling, restart interval, optimize_huffman, progressive and trellis_quant hold for
+ * every image.  File i is byte for byte what pixo_hip_jpeg_encode_device returns for image i alone, called with `options`
+ * after image i's width, height and colour type are written into it: every preset, quality and subsampling.
+ * The shared way in — no progressive scans, no optimised tables, no restart markers in the image's scan: the batch entry's
+ * condition for one pass —: all images of a sub-batch go through one coefficient launch per class present (gray, or RGB at the
+ * template's subsampling, times the load form: aligned rows, rows at any address, images narrower than 4 pixels), then one
+ * coding pass and one stuffing pass per colour class, every image a byte-aligned segment of its own size: the number of
+ * launches follows the classes present, not `batch`.  Every other image is encoded by itself in index order, and so is a
+ * sub-batch whose single-pass launch gave up its bounded waits (PIXO route FALLBACK).
+ * Sub-batches are greedy in index order, at least one image each, at most 2^22 blocks of 64 coefficients (512 MiB of tuple,
+ * 836 MiB of packed streams; PIXO_HIP_DEBUG jpeg_images_blocks=n lowers it); a sub-batch also ends where the way changes.
+ * files[i] / lens[i] receive `batch` files, each a block from the pinned pool that the caller releases with pixo_hip_free;
+ * after a failure no block stays allocated.  Checks, all before the thread's context is touched, in this order: null options;
+ * the template's quality and Some(0) restart interval as pixo_hip_jpeg_encode_device checks them; null d_pixels; null images;
+ * batch in 1..65535; null files, null lens; then for i = 0, 1, ... image i with the single entry's statuses and messages, each
+ * with " (image i)" appended: a zero side, a side above 65535, a colour type that is not PIXO_GRAY or PIXO_RGB
+ * (PIXO_ERR_UNSUPPORTED_COLOR_TYPE, also for GrayAlpha and RGBA: alpha is not dropped), then offset + the image's bytes beyond
+ * 2^62 (PIXO_ERR_COMPRESSION). */
+int pixo_hip_jpeg_encode_images_device(const void *d_pixels, const pixo_png_image *images, uint32_t batch, const pixo_jpeg_options *options,
+                                       uint8_t **files, size_t *lens);
+/* The same, the files back to back in `arena` in host memory (pinned or pageable), as pixo_hip_jpeg_encode_batch_device_into:
+ * no gaps, offsets[0] = 0, offsets / lens filled in also with PIXO_ERR_BUFFER_TOO_SMALL, a null arena with capacity 0 is a
+ * size query.  A device arena is refused (PIXO_ERR_COMPRESSION): the headers differ per image and are written by the host.
+ * Checks as above with `offsets` in the place of `files`. */
+int pixo_hip_jpeg_encode_images_device_into(const void *d_pixels, const pixo_png_image *images, uint32_t batch, const pixo_jpeg_options *options,
+                                            uint8_t *arena, size_t capacity, size_t *offsets, size_t *lens);
+/* ... and for a block in host memory, uploaded up to the furthest image's end: the checks above with `data` for d_pixels, then
+ * data_len below that end: PIXO_ERR_INVALID_DATA_LENGTH, "expected <that end> bytes, got <data_len>". */
+int pixo_hip_jpeg_encode_images(const uint8_t *data, size_t data_len, const pixo_png_image *images, uint32_t batch,
+                                const pixo_jpeg_options *options, uint8_t **files, size_t *lens);
+/* Tests: what the entries above decide, no GPU and no pixels needed.  alignment (0..15): d_pixels modulo 16.  Sub-batch k is
+ * images sub_first[k] .. sub_first[k + 1] (room for batch + 1 entries, *sub_count + 1 are written); way_in[i]: 1 shared, 0 by
+ * itself; load_form[i]: 0 aligned, 1 funnel, 2 bytes, from image i's first byte's address and its row length; first_group[i]:
+ * the first group of 192 blocks of image i within its colour class's coding pass in its sub-batch (0 for the single way);
+ * *coef_launches / *entropy_passes: coefficient launches / coding passes (each with its stuffing pass) summed over the
+ * sub-batches.  Checks as the entries' (no pixels; alignment behind batch; the seven out-pointers in the place of files and
+ * lens). */
+int pixo_hip_debug_jpeg_encode_images_plan(const pixo_png_image *images, uint32_t batch, const pixo_jpeg_options *options, uint32_t alignment,
+                                           uint32_t *sub_first, uint32_t *sub_count, uint8_t *way_in, uint8_t *load_form, uint64_t *first_group,
+                                           uint32_t *coef_launches, uint32_t *entropy_passes);
+
 /* ---- resize of images of individual sizes and colour types, anywhere in one block ---- */
 
 /* The link between pixo_hip_png_decode_batch_device and pixo_hip_png_encode_images*: `batch` (1..65535) sources described by

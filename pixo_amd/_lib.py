@@ -102,6 +102,10 @@ SIGNATURES = {
     "pixo_hip_jpeg_encode_device_into": _sig(_vp, _optp, _vp, _sz, _szp),
     "pixo_hip_jpeg_encode_batch_device": _sig(_vp, _optp, _u32, _u8pp, _szp),
     "pixo_hip_jpeg_encode_batch_device_into": _sig(_vp, _optp, _u32, _vp, _sz, _szp, _szp),
+    "pixo_hip_jpeg_encode_images_device": _sig(_vp, _pimgp, _u32, _optp, _u8pp, _szp, optional=True),
+    "pixo_hip_jpeg_encode_images_device_into": _sig(_vp, _pimgp, _u32, _optp, _vp, _sz, _szp, _szp, optional=True),
+    "pixo_hip_jpeg_encode_images": _sig(_vp, _sz, _pimgp, _u32, _optp, _u8pp, _szp, optional=True),
+    "pixo_hip_debug_jpeg_encode_images_plan": _sig(_pimgp, _u32, _optp, _u32, _u32p, _u32p, _u8p, _u8p, _u64p, _u32p, _u32p, optional=True),
     "pixo_hip_debug_lookback_fallbacks": _sig(ret=_u64),
     "pixo_hip_debug_routes": _sig(_int, ret=_u64, optional=True),
     "pixo_hip_debug_dispatch_gate": _sig(_u64p, _u64p, optional=True),

@@ -41,6 +41,7 @@
 #include "baseline_plan.hpp"
 #include "routes.hpp"
 #include "png_images_math.h"
+#include "jpeg_images.hpp"
 
 namespace pixo_capi {
 
@@ -110,6 +111,8 @@ inline int bad_length(size_t expected, size_t got)
 //   resize_images_rows=n  an image of pixo_hip_resize_images* has at most n rows of tiles in a pass instead of 65535 (the single
 //                      entry's grid.y limit): tests reach the kernels' row-stride loops with small images.  resize_batch_bytes
 //                      cuts those entries' sub-batches too
+//   jpeg_images_blocks=n  a sub-batch of pixo_hip_jpeg_encode_images* holds at most n blocks of 64 coefficients (and at least one image)
+//                      instead of 2^22: tests cross a sub-batch seam with small images
 //   decode_batch_bytes=n  a sub-batch of pixo_hip_png_decode_batch* holds at most n bytes of device staging (inflated streams +
 //                      reconstructed rows; at least one image) instead of 512 MiB: tests reach a sub-batch boundary with small images
 //   no_bands_upload    host pixels are uploaded in one copy instead of MCU-row bands pipelined with the kernels
@@ -135,6 +138,7 @@ struct DebugSwitches {
     uint64_t png_batch_bytes = 0; // bytes of prepared stream a sub-batch of the PNG batch entries holds at most, 0 = 64 MiB
     uint64_t resize_batch_bytes = 0; // bytes of Lanczos3 intermediate a sub-batch of the resize batch entries holds at most, 0 = 256 MiB
     uint32_t resize_images_rows = 0; // rows of tiles an image of pixo_hip_resize_images* has at most in a pass, 0 = 65535
+    uint64_t jpeg_images_blocks = 0; // blocks a sub-batch of the JPEG images entries holds at most, 0 = 2^22 (jpeg_images_math.h)
     uint64_t decode_batch_bytes = 0; // bytes of device staging a sub-batch of the PNG decode batch entries holds at most, 0 = 512 MiB
 };
 const DebugSwitches &debug();
@@ -245,6 +249,8 @@ struct Context {
     Buf p_in, p_out, p_sums, p_scratch; // PNG filter stage
     Buf h_sums{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... p_sums copied to the host
     Buf p_images, h_images{Buf::Mem::Pinned, Buf::Grow::Exact}; // the records of a ragged filter launch (png_images_math.h) and what they go up from
+    Buf j_tables, h_jtables{Buf::Mem::Pinned, Buf::Grow::Headroom}; // JPEG images (jpeg_images_api.cpp): a sub-batch's tile and segment records and what they go up from
+    Buf j_out;                       // ... the stuffed scans of its RGB pass (the gray pass's lie in e_out) until both have been delivered
     // PNG reductions (png_reduce_api.cpp)
     Buf q_work{Buf::Mem::Device, Buf::Grow::Exact};  // one PngWork: analysis, key lookup table, index map, histogram, pair counts
     Buf h_qwork{Buf::Mem::Pinned, Buf::Grow::Exact}; // ... its host side: results come down into it, tables go up from it

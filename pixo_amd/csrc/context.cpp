@@ -85,6 +85,7 @@ DebugSwitches parse_switches(const char *e)
         else if (name == "png_batch_bytes" && num > 0) v.png_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "resize_batch_bytes" && num > 0) v.resize_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "resize_images_rows" && num > 0) v.resize_images_rows = static_cast<uint32_t>(num > 65535 ? 65535 : num);
+        else if (name == "jpeg_images_blocks" && num > 0) v.jpeg_images_blocks = static_cast<uint64_t>(num);
         else if (name == "decode_batch_bytes" && num > 0) v.decode_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "spin_budget" && !val.empty()) v.spin_budget = static_cast<uint32_t>(num < 0 ? 0 : num);
         else if (name == "piece_schedule") {
@@ -157,7 +158,7 @@ template <class F> void each_buf(Context &c, F &&f)
 {
     Buf *bufs[] = {&c.d_px, &c.d_coef, &c.h_coef, &c.e_tables, &c.e_hist, &c.e_count, &c.e_len, &c.e_off, &c.e_tmp, &c.e_totals, &c.e_stream,
                    &c.e_tile_ff, &c.e_tile_base, &c.e_out, &c.e_seg_bytes, &c.e_seg_off, &c.e_code_state, &c.e_stuff_state, &c.e_pc_state,
-                   &c.e_pc_spill, &c.e_chain, &c.e_seams, &c.e_segs, &c.h_segs, &c.p_in, &c.p_out, &c.p_sums, &c.p_scratch, &c.h_sums, &c.p_images, &c.h_images,
+                   &c.e_pc_spill, &c.e_chain, &c.e_seams, &c.e_segs, &c.h_segs, &c.p_in, &c.p_out, &c.p_sums, &c.p_scratch, &c.h_sums, &c.p_images, &c.h_images, &c.j_tables, &c.h_jtables, &c.j_out,
                    &c.q_work, &c.h_qwork, &c.q_index, &c.q_rows, &c.z_tok, &c.z_slots, &c.z_prev, &c.z_info, &c.z_stream, &c.z_crc, &c.h_zinfo,
                    &c.k_samples, &c.h_ksamples, &c.k_work, &c.h_kwork, &c.k_lut, &c.k_carry,
                    &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank, &c.h_file, &c.r_in, &c.r_out, &c.r_mid, &c.r_tables,

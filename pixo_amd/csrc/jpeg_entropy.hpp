@@ -101,6 +101,11 @@ struct SegArgs {
     // packed stream begins at word var_word[k] of d_stream (blocks / groups / stream_words are not used then)
     uint32_t var = 0;
     uint64_t var_word[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // RAGGED segments (images of individual sizes, launch_scan_code_ragged / launch_stuff_fused_ragged): segment k has its own
+    // block count, groups, tuple planes and packed stream — record k of this device table of nsegs + 1
+    // pixo_jpeg_images::SegRecord (jpeg_images_math.h), which a group searches by its first_group.  `groups` then holds the
+    // groups of ALL segments; blocks / stream_words / var are not used.
+    const void *rag = nullptr;
 };
 uint32_t seg_groups(uint64_t seg_blocks);
 uint32_t seg_max_gap();
@@ -136,6 +141,17 @@ hipError_t launch_stuff_fused(const uint32_t *d_stream, unsigned long long *d_co
                               bool state_is_zero, uint8_t *d_out, uint64_t out_cap, unsigned long long *host_totals, hipStream_t s,
                               unsigned long long *d_out_chain = nullptr, uint32_t piece = 0, const SegArgs *seg = nullptr,
                               uint32_t spin_budget = 1u << 20);
+// The RAGGED forms of the two (seg.rag set, seg.groups the pass's groups): a.y is the tuple's base — every segment's planes
+// lie at its record's block offsets from it (a.cb / a.cr are not read) — and d_stream the base of the segments' packed streams.
+// The same state layout, waits and hand-offs; the look-back's block sums of segment k lie at word (first_group >> 6) + k.
+size_t fused_code_state_words_ragged(uint64_t nsegs, uint64_t groups);
+hipError_t launch_scan_code_ragged(const ScanArgs &a, const SegArgs &seg, unsigned long long *d_state, bool state_is_zero, uint32_t *d_stream,
+                                   unsigned long long *d_clear, size_t clear_words, unsigned long long *host_totals, hipStream_t s,
+                                   uint32_t spin_budget = 1u << 20);
+hipError_t launch_stuff_fused_ragged(const uint32_t *d_stream, unsigned long long *d_code_state, size_t code_state_words, uint64_t max_stream_bytes,
+                                     uint64_t first_tile, uint64_t tiles, unsigned long long *d_state, bool state_is_zero, uint8_t *d_out,
+                                     uint64_t out_cap, unsigned long long *host_totals, hipStream_t s, const SegArgs &seg,
+                                     uint32_t spin_budget = 1u << 20);
 // (d_out_chain, piece: the piece's bytes go to d_out + d_out_chain[piece] (piece 0: d_out); d_out_chain[piece + 1] receives
 // where they end; d_state[1] / host_totals[1] count this piece's bytes only)
 

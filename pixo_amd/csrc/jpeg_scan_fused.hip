@@ -34,6 +34,7 @@
 
 #include "dispatch_gate.hpp"
 #include "jpeg_entropy.hpp"
+#include "jpeg_images_math.h"
 #include "jpeg_scan_block.h"
 #include "jpeg_scan_dev.h"
 
@@ -48,13 +49,17 @@ namespace {
 // aligned with the segments (the last group of a segment is partly empty), a segment's first group is the floor of its
 // groups' look-back — nothing crosses a segment — and its last group leaves the segment's length in seg.bits.  How the
 // segments follow each other in the file is the stuffing kernel's business.
+// SEG == 2 (ragged segments: images of individual sizes — SegArgs::rag): segment k has its own block count, groups, tuple
+// planes and packed stream, record k of a device table; a group finds its record by binary search over the records' first
+// groups (uniform across the workgroup: scalar loads).  No surplus groups: the grid is the records' groups summed.
+using RagRecord = const __attribute__((address_space(4))) pixo_jpeg_images::SegRecord;
 #ifdef PIXO_TIMELINE // (experiment builds only, tools/scan_timeline.py: where a group's time goes; 100 MHz constant clock)
 __device__ unsigned long long g_timeline[8192 * 8];
 #define PIXO_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_timeline[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define PIXO_STAMP(k) do { } while (0)
 #endif
-template <int MODE, bool SEG>
+template <int MODE, int SEG>
 __global__ __launch_bounds__(kGroup) __attribute__((amdgpu_waves_per_eu(6, 6))) void scan_code_kernel
 (const ScanArgs a, unsigned long long *state, uint32_t *stream, unsigned long long *clear, uint32_t clear_words,
  unsigned long long *host_totals, const ScanPiece piece, const SegArgs seg, uint32_t spin_budget, const GateMark gate)
@@ -73,7 +78,18 @@ __global__ __launch_bounds__(kGroup) __attribute__((amdgpu_waves_per_eu(6, 6))) 
     const uint64_t g = blockIdx.x; // (one group per workgroup; see the note on dispatch order at the top of the file)
     // the group's place: segment, first ticket of the segment (the look-back's floor), blocks
     uint64_t floor_g = 0, first_in_chain = g * kGroup, nblocks_chain = a.nblocks, sidx = 0;
-    if (SEG) {
+    const int16_t *plane_y = a.y, *plane_cb = a.cb, *plane_cr = a.cr;
+    if (SEG == 2) {
+        RagRecord *rag = (RagRecord *)seg.rag;
+        sidx = pixo_jpeg_images::segment_of_group(rag, (uint32_t)seg.nsegs, (uint32_t)g);
+        floor_g = rag[sidx].first_group;
+        nblocks_chain = rag[sidx].blocks;
+        first_in_chain = (g - floor_g) * kGroup;
+        stream += rag[sidx].stream_word;
+        plane_y = a.y + (size_t)rag[sidx].y_block * 64;
+        plane_cb = a.y + (size_t)rag[sidx].cb_block * 64;
+        plane_cr = a.y + (size_t)rag[sidx].cr_block * 64;
+    } else if (SEG) {
         sidx = g / seg.groups;
         floor_g = sidx * seg.groups;
         const uint64_t seg_first_block = sidx * seg.blocks;
@@ -81,13 +97,15 @@ __global__ __launch_bounds__(kGroup) __attribute__((amdgpu_waves_per_eu(6, 6))) 
         first_in_chain = (g - floor_g) * kGroup;
         stream += sidx * seg.stream_words;
     }
-    const bool surplus = SEG && first_in_chain >= nblocks_chain; // (the last segment is shorter: its surplus groups only do the housekeeping)
-    const uint64_t ngroups_total = SEG ? seg.nsegs * seg.groups : (a.nblocks + kGroup - 1) / kGroup;
+    const bool surplus = SEG == 1 && first_in_chain >= nblocks_chain; // (the last segment is shorter: its surplus groups only do the housekeeping)
+    const uint64_t ngroups_total = SEG == 2 ? seg.groups : (SEG ? seg.nsegs * seg.groups : (a.nblocks + kGroup - 1) / kGroup);
     unsigned long long *desc = state + 2, *tails = state + 2 + ngroups_total;
     // block sums of the two-level look-back: per chain (the scan; a segment) one word per 64 groups, behind the tails — in copies
     // (sup_layout, jpeg_scan_dev.h: this is copy 0)
-    unsigned long long *sup = state + 2 + 2 * ngroups_total + (SEG ? sidx * ((seg.groups + 63) >> 6) : 0);
-    const SupLayout sl = sup_layout(ngroups_total, SEG ? seg.nsegs * ((seg.groups + 63) >> 6) + 1 : ((ngroups_total + 63) >> 6) + 1);
+    // (ragged: segment k's sums from word (floor >> 6) + k — its (groups + 63) / 64 words end in front of the next segment's)
+    unsigned long long *sup = state + 2 + 2 * ngroups_total + (SEG == 2 ? (floor_g >> 6) + sidx : (SEG ? sidx * ((seg.groups + 63) >> 6) : 0));
+    const SupLayout sl = sup_layout(ngroups_total, SEG == 2 ? (ngroups_total >> 6) + seg.nsegs + 1
+                                                            : (SEG ? seg.nsegs * ((seg.groups + 63) >> 6) + 1 : ((ngroups_total + 63) >> 6) + 1));
     unsigned long long *const host_abort = host_totals ? host_totals + 3 : nullptr;
     // A scan coded piece by piece (ScanPiece, jpeg_entropy.hpp): the piece's stream is byte-aligned with the SCAN — its
     // first `lead` bits are the end of the piece before — so that the stuffing kernel can work on it without a shift.
@@ -100,14 +118,14 @@ __global__ __launch_bounds__(kGroup) __attribute__((amdgpu_waves_per_eu(6, 6))) 
     // the group through LDS for perfectly coalesced loads cost 24 KiB per group and 60 more VGPRs for the addresses:
     // half the occupancy.)
     const bool live = !surplus && first_in_chain + lane < nblocks_chain;
-    const uint64_t s = piece.first_block + (SEG ? sidx * seg.blocks : 0) + first_in_chain + lane;
+    const uint64_t s = piece.first_block + (SEG == 1 ? sidx * seg.blocks : 0) + first_in_chain + lane;
     uint32_t w[32];
     // DC predictor: the previous block of the same component (jpeg/mod.rs:1417-1419); the scan's first blocks start
     // from the seed (0, or the DCs above a band); a segment's first blocks from 0 (jpeg/mod.rs:1441-1444)
     int prev_dc = 0, cls = 0;
     {
         const BlockRef ref = block_of(MODE, live ? s : 0);
-        const int16_t *base = ref.comp == 0 ? a.y : (ref.comp == 1 ? a.cb : a.cr);
+        const int16_t *base = ref.comp == 0 ? plane_y : (ref.comp == 1 ? plane_cb : plane_cr);
         const v4u *p = reinterpret_cast<const v4u *>(base + ref.index * 64);
 #pragma unroll
         for (int r = 0; r < 8; r++) {
@@ -799,7 +817,7 @@ __global__ __launch_bounds__(1024) void seg_layout_kernel(const unsigned long lo
 // into them + the two marker bytes behind a segment's last tile), so the look-back over all tiles before it gives its
 // place in the output whatever the segments' lengths; the last tile of segment k also stores where the segment ends
 // (seg.out_end[k], device and pinned mailbox: a batch's files are cut there) and — restart intervals — writes RSTn.
-template <bool SEG>
+template <int SEG>
 __global__ __launch_bounds__(kStuffThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void stuff_fused_kernel(const uint32_t *stream, const unsigned long long *code_state,
                                                                    uint32_t shift, uint32_t band, unsigned long long *state,
                                                                    uint8_t *out, uint32_t out_skew, uint64_t out_cap, uint64_t tile_offset,
@@ -856,7 +874,8 @@ __global__ __launch_bounds__(kStuffThreads) __attribute__((amdgpu_waves_per_eu(4
         sidx = lo;
         local_t = t - seg.layout[1 + sidx];
         nbytes = seg.bytes[sidx];
-        stream += seg.var ? seg.var_word[sidx] : sidx * seg.stream_words;
+        if (SEG == 2) stream += ((RagRecord *)seg.rag)[sidx].stream_word;
+        else stream += seg.var ? seg.var_word[sidx] : sidx * seg.stream_words;
     } else {
         const uint64_t total_bits = code_state[1];
         nbytes = band ? (total_bits - (shift < total_bits ? shift : total_bits)) / 8 : (total_bits + 7) / 8;
@@ -1038,9 +1057,9 @@ hipError_t launch_scan_code(const ScanArgs &a, unsigned long long *d_state, bool
     const GateMark gm = gate.mark();
 #define PIXO_LAUNCH_CODE(MODE, SEG) hipLaunchKernelGGL((scan_code_kernel<MODE, SEG>), dim3(grid), dim3(kGroup), 0, s, a, d_state, d_stream, d_clear, cw, host_totals, piece, seg, spin_budget, gm)
     if (seg_or_null) {
-        if (a.mode == 2) PIXO_LAUNCH_CODE(2, true); else if (a.mode == 1) PIXO_LAUNCH_CODE(1, true); else PIXO_LAUNCH_CODE(0, true);
+        if (a.mode == 2) PIXO_LAUNCH_CODE(2, 1); else if (a.mode == 1) PIXO_LAUNCH_CODE(1, 1); else PIXO_LAUNCH_CODE(0, 1);
     } else {
-        if (a.mode == 2) PIXO_LAUNCH_CODE(2, false); else if (a.mode == 1) PIXO_LAUNCH_CODE(1, false); else PIXO_LAUNCH_CODE(0, false);
+        if (a.mode == 2) PIXO_LAUNCH_CODE(2, 0); else if (a.mode == 1) PIXO_LAUNCH_CODE(1, 0); else PIXO_LAUNCH_CODE(0, 0);
     }
 #undef PIXO_LAUNCH_CODE
     return hipGetLastError();
@@ -1151,11 +1170,56 @@ hipError_t launch_stuff_fused(const uint32_t *d_stream, unsigned long long *d_co
     const DispatchGate gate(s, tiles); // (held until the kernel is enqueued: dispatch_gate.hpp)
     const GateMark gm = gate.mark();
     if (seg_or_null)
-        hipLaunchKernelGGL(stuff_fused_kernel<true>, dim3((unsigned)tiles), dim3(kStuffThreads), 0, s, d_stream, d_code_state, shift, band ? 1u : 0u,
+        hipLaunchKernelGGL(stuff_fused_kernel<1>, dim3((unsigned)tiles), dim3(kStuffThreads), 0, s, d_stream, d_code_state, shift, band ? 1u : 0u,
                            d_state, d_out, out_skew, out_cap, first_tile, d_code_state, (uint32_t)code_state_words, host_totals, d_out_chain, piece, seg, spin_budget, gm);
     else
-        hipLaunchKernelGGL(stuff_fused_kernel<false>, dim3((unsigned)tiles), dim3(kStuffThreads), 0, s, d_stream, d_code_state, shift, band ? 1u : 0u,
+        hipLaunchKernelGGL(stuff_fused_kernel<0>, dim3((unsigned)tiles), dim3(kStuffThreads), 0, s, d_stream, d_code_state, shift, band ? 1u : 0u,
                            d_state, d_out, out_skew, out_cap, first_tile, d_code_state, (uint32_t)code_state_words, host_totals, d_out_chain, piece, seg, spin_budget, gm);
+    return hipGetLastError();
+}
+
+// ---- ragged segments (images of individual sizes) ---------------------------------------------------------------------------
+size_t fused_code_state_words_ragged(uint64_t nsegs, uint64_t groups)
+{ // abort flag, total bits, per group: descriptor + tail, the segments' block sums (scan_code_kernel<MODE, 2>)
+    const SupLayout sl = sup_layout(groups, (groups >> 6) + nsegs + 1);
+    return 2 + 2 * (size_t)groups + (size_t)sl.copies * sl.stride;
+}
+hipError_t launch_scan_code_ragged(const ScanArgs &a, const SegArgs &seg, unsigned long long *d_state, bool state_is_zero, uint32_t *d_stream,
+                                   unsigned long long *d_clear, size_t clear_words, unsigned long long *host_totals, hipStream_t s, uint32_t spin_budget)
+{
+    const uint64_t ngroups = seg.groups;
+    if (host_totals) host_totals[3] = 0;
+    if (!seg.rag || seg.nsegs == 0 || seg.nsegs > 0xFFFFu || ngroups < seg.nsegs || ngroups > 0x7FFFFFFFull || clear_words > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (!state_is_zero) {
+        hipError_t e = hipMemsetAsync(d_state, 0, fused_code_state_words_ragged(seg.nsegs, ngroups) * 8, s);
+        if (e != hipSuccess) return e;
+    }
+    const unsigned grid = (unsigned)ngroups;
+    const uint32_t cw = d_clear ? (uint32_t)clear_words : 0u;
+    const ScanPiece piece{0, 0, nullptr, nullptr};
+    const DispatchGate gate(s, ngroups); // (held until the kernel is enqueued: dispatch_gate.hpp)
+    const GateMark gm = gate.mark();
+#define PIXO_LAUNCH_CODE(MODE) hipLaunchKernelGGL((scan_code_kernel<MODE, 2>), dim3(grid), dim3(kGroup), 0, s, a, d_state, d_stream, d_clear, cw, host_totals, piece, seg, spin_budget, gm)
+    if (a.mode == 2) PIXO_LAUNCH_CODE(2); else if (a.mode == 1) PIXO_LAUNCH_CODE(1); else PIXO_LAUNCH_CODE(0);
+#undef PIXO_LAUNCH_CODE
+    return hipGetLastError();
+}
+hipError_t launch_stuff_fused_ragged(const uint32_t *d_stream, unsigned long long *d_code_state, size_t code_state_words, uint64_t max_stream_bytes,
+                                     uint64_t first_tile, uint64_t tiles, unsigned long long *d_state, bool state_is_zero, uint8_t *d_out,
+                                     uint64_t out_cap, unsigned long long *host_totals, hipStream_t s, const SegArgs &seg, uint32_t spin_budget)
+{
+    const uint32_t out_skew = (uint32_t)(reinterpret_cast<uintptr_t>(d_out) & 15);
+    d_out -= out_skew;
+    out_cap += out_skew;
+    if (first_tile == 0 && !state_is_zero) { // (a continuation keeps the descriptors of the tiles before it)
+        hipError_t e = hipMemsetAsync(d_state, 0, fused_stuff_state_words(max_stream_bytes) * 8, s);
+        if (e != hipSuccess) return e;
+    }
+    if (tiles == 0) tiles = 1;
+    if (!seg.rag || tiles > 0x7FFFFFFFull || code_state_words > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const DispatchGate gate(s, tiles); // (held until the kernel is enqueued: dispatch_gate.hpp)
+    hipLaunchKernelGGL(stuff_fused_kernel<2>, dim3((unsigned)tiles), dim3(kStuffThreads), 0, s, d_stream, d_code_state, 0u, 0u, d_state, d_out, out_skew,
+                       out_cap, first_tile, d_code_state, (uint32_t)code_state_words, host_totals, nullptr, 0u, seg, spin_budget, gate.mark());
     return hipGetLastError();
 }
 

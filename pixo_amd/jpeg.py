@@ -341,6 +341,67 @@ def encode_batch_device_into(arena, d_pixels, options: JpegOptions, batch: int):
         _dev_ptr(d_pixels), C.byref(oc), batch, ptr, cap, offsets, lens), arena, batch)
 
 
+# ---- images of individual sizes and colour types anywhere in one block (pixo_hip_jpeg_encode_images*) ------------------------
+# The records are the ones `png.encode_images*` take: a `_lib.PngImageC` array, a list of (width, height, ColorType, offset),
+# or the (tensor, ColorType) views of `decode.decode_png_batch_device` / `resize.resize_images_device`.
+
+def _records(images, block):
+    from . import png
+    arr, n, base = png._image_records(images)
+    if block is not None or base is not None:
+        block = png._images_block(block, base)
+        png._check_images_block(block, arr, n)
+    return arr, n, block
+
+
+def encode_images_device(d_pixels, records, options: JpegOptions):
+    """Images of individual sizes, gray or RGB, anywhere in one block in HBM (torch tensor / raw pointer; None with tensor
+    views) -> list of JPEG files (bytes), file i byte for byte what `encode_device` returns for image i with `options` at its
+    width, height and colour type (`options`' own are not read).  With baseline options (no progressive scans, no optimised
+    tables, no restart markers) the number of launches follows the classes of images present, not their number."""
+    L = _lib.load()
+    arr, n, block = _records(records, d_pixels)
+    files, lens, oc = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))(), options._c()
+    _lib.check(L.pixo_hip_jpeg_encode_images_device(_lib.ptr(block), arr, n, C.byref(oc), files, lens))
+    return _lib.take_files(L, files, lens, n)
+
+
+def encode_images_device_into(arena, d_pixels, records, options: JpegOptions):
+    """The files back to back in `arena` (as `encode_batch_device_into`: a torch uint8 CPU tensor, pinned or not, a numpy
+    uint8 array, or None for a size query; a device arena is refused).  Returns (offsets, lens); raises BufferTooSmall
+    (`.needed`, `.offsets`, `.lens`) when the files do not fit."""
+    L = _lib.load()
+    arr, n, block = _records(records, d_pixels)
+    oc = options._c()
+    return _lib.into_arena(lambda ptr, cap, offsets, lens: L.pixo_hip_jpeg_encode_images_device_into(
+        _lib.ptr(block), arr, n, C.byref(oc), ptr, cap, offsets, lens), arena, n)
+
+
+def encode_images(block, records, options: JpegOptions):
+    """The same for a block in host memory (bytes or a numpy uint8 array) -> list of JPEG files (bytes)."""
+    L = _lib.load()
+    arr, n, _ = _records(records, None)
+    px = np.ascontiguousarray(block if not isinstance(block, (bytes, bytearray)) else np.frombuffer(block, np.uint8), dtype=np.uint8).reshape(-1)
+    files, lens, oc = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))(), options._c()
+    _lib.check(L.pixo_hip_jpeg_encode_images(px.ctypes.data, px.size, arr, n, C.byref(oc), files, lens))
+    return _lib.take_files(L, files, lens, n)
+
+
+def encode_images_plan(records, options: JpegOptions, alignment=0) -> dict:
+    """What the images entries decide for these records, no GPU needed: `sub_first` (sub-batch k is images sub_first[k] ..
+    sub_first[k + 1]), `way_in` (True: the shared launches; False: encoded by itself), `load_form` (0 aligned, 1 funnel, 2
+    bytes), `first_group` (the image's first group of 192 blocks in its colour class's coding pass), `coef_launches` and
+    `entropy_passes` (summed over the sub-batches) for a block whose address is `alignment` modulo 16."""
+    L = _lib.load()
+    arr, n, _ = _records(records, None)
+    sub_first, subs, coef, passes = (C.c_uint32 * (n + 1))(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    way, load, group, oc = (C.c_uint8 * max(n, 1))(), (C.c_uint8 * max(n, 1))(), (C.c_uint64 * max(n, 1))(), options._c()
+    _lib.check(L.pixo_hip_debug_jpeg_encode_images_plan(arr, n, C.byref(oc), alignment, sub_first, C.byref(subs), way, load, group,
+                                                        C.byref(coef), C.byref(passes)))
+    return {"sub_first": list(sub_first[:subs.value + 1]), "way_in": [bool(v) for v in way[:n]], "load_form": list(load[:n]),
+            "first_group": list(group[:n]), "coef_launches": coef.value, "entropy_passes": passes.value}
+
+
 def encode_batch_multi(arena, pixels, options: JpegOptions, batch: int, devices):
     """`pixo_hip_jpeg_encode_batch_multi`: `batch` equally sized images — a device tensor / pointer on any GPU of this process,
     or a numpy array in host memory — encoded by `devices` (one contiguous run of images each; a device may be listed more than
@@ -425,6 +486,9 @@ ROUTES = {
 for _name, _bit in ROUTES.items():
     globals()["ROUTE_" + _name] = 1 << _bit
 del _name, _bit
+# ... and the images entries' bit (encode_images*): at least one sub-batch went through the ragged launches
+IMAGES_ROUTES = {"JPEG_IMAGES": 48}
+ROUTE_JPEG_IMAGES = 1 << IMAGES_ROUTES["JPEG_IMAGES"]
 
 
 def debug_routes(clear: bool = True) -> int:
