@@ -22,6 +22,7 @@
 //   (a loop over pixo::decode::decode_png)              pixo::decode::decode_png_batch
 //   (a loop over pixo::png::encode, one size each)      pixo::png::encode_images
 //   (a loop over pixo::jpeg::encode, one size each)     pixo::jpeg::encode_images / encode_images_device
+//   (bin) to_grayscale / rgba_to_rgb / gray_alpha_to_gray  bin/pixo.rs:478  pixo::convert::convert / convert_images / convert_images_device
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -522,6 +523,67 @@ inline void resize_images_device(const void *d_src, const std::vector<pixo_png_i
     return std::vector<uint8_t>(block, block + n);
 }
 } // namespace resize
+
+// Colour conversion between a decode and an encode (contract: pixo_hip.h): drop the alpha channel in front of a JPEG, or go
+// gray, for one image or for N images of individual sizes and colour types in one pass.
+namespace convert {
+enum class Target : uint8_t { Opaque = PIXO_CONVERT_OPAQUE, Gray = PIXO_CONVERT_GRAY };
+namespace detail {
+inline std::vector<uint8_t> take_block(uint8_t *block, size_t n)
+{
+    struct Block { // (released also when the copy below throws)
+        uint8_t *p;
+        ~Block() { pixo_hip_free(p); }
+    } held{block};
+    return std::vector<uint8_t>(block, block + n);
+}
+} // namespace detail
+// The sizes alone, on the host: every source at its own size in the colour type `target` gives it, laid out with 16-byte
+// starts; *total: the end of the last image
+[[nodiscard]] inline std::vector<pixo_png_image> layout_images(const std::vector<pixo_png_image> &src_images, Target target, size_t *total = nullptr)
+{
+    std::vector<pixo_png_image> laid(src_images.size());
+    size_t end = 0;
+    const int rc = pixo_hip_convert_images_layout(src_images.data(), (uint32_t)src_images.size(), (uint8_t)target, laid.data(), &end);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    if (total) *total = end;
+    return laid;
+}
+// Device pixels, enqueued on `stream`: image i at d_src + src_images[i].offset -> dst_images[i]'s colour type at d_dst + its offset
+inline void convert_images_device(const void *d_src, const std::vector<pixo_png_image> &src_images, void *d_dst,
+                                  const std::vector<pixo_png_image> &dst_images, void *stream = nullptr)
+{
+    if (src_images.size() != dst_images.size()) throw std::invalid_argument("convert_images_device: as many destinations as sources");
+    const int rc = pixo_hip_convert_images_device(d_src, src_images.data(), d_dst, dst_images.data(), (uint32_t)src_images.size(), stream);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+}
+// ... a block in host memory -> one block laid out as dst_images says
+[[nodiscard]] inline std::vector<uint8_t> convert_images(const uint8_t *data, size_t len, const std::vector<pixo_png_image> &src_images,
+                                                         const std::vector<pixo_png_image> &dst_images)
+{
+    if (src_images.size() != dst_images.size()) throw std::invalid_argument("convert_images: as many destinations as sources");
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    const int rc = pixo_hip_convert_images(data, len, src_images.data(), dst_images.data(), (uint32_t)src_images.size(), &block, &n);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    return detail::take_block(block, n);
+}
+// One image: device pixels, enqueued on `stream` ...
+inline void convert_device(const void *d_src, uint32_t width, uint32_t height, ColorType src, ColorType dst, void *d_dst, void *stream = nullptr)
+{
+    const int rc = pixo_hip_convert_device(d_src, width, height, (uint8_t)src, (uint8_t)dst, d_dst, stream);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+}
+// ... host pixels -> the converted pixels
+[[nodiscard]] inline std::vector<uint8_t> convert(const uint8_t *data, size_t len, uint32_t width, uint32_t height, ColorType src, ColorType dst)
+{
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    const int rc = pixo_hip_convert(data, len, width, height, (uint8_t)src, (uint8_t)dst, &block, &n);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    return detail::take_block(block, n);
+}
+} // namespace convert
 
 namespace decode {
 // decode/png.rs:18-28

@@ -887,6 +887,70 @@ int pixo_hip_debug_resize_images_plan(const pixo_png_image *src_images, const pi
                                       uint8_t *use_lds, uint32_t *tiles_first, uint32_t *tiles_second, uint32_t *axis_tables,
                                       uint32_t *launches_first, uint32_t *launches_second);
 
+/* ---- colour conversion: drop alpha or go gray, one image or N images of individual sizes, one pass ---- */
+
+/* What the reference's front end does between a decode and an encode (src/bin/pixo.rs:478-513 gray_alpha_to_gray, rgba_to_rgb,
+ * to_grayscale; :619-638 where it applies them), on pixels that stay in HBM.  The pairs (source colour type -> destination
+ * colour type) that exist: equal types (a copy); GrayAlpha -> Gray (byte 0 of every pixel); Rgba -> Rgb (bytes 0..2);
+ * Rgb -> Gray and Rgba -> Gray ((77 r + 150 g + 29 b + 128) >> 8, alpha ignored).  Every other pair — Gray -> Rgb, anything
+ * that adds alpha — has no counterpart in the reference and is refused (PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color
+ * type for this format").  The two targets a caller names instead of a pair: */
+#define PIXO_CONVERT_OPAQUE 0 /* in front of a JPEG: GrayAlpha -> Gray, Rgba -> Rgb, Gray and Rgb kept */
+#define PIXO_CONVERT_GRAY 1   /* the front end's --grayscale: everything -> Gray */
+
+/* The destinations `target` gives the sources, on the HOST only: dst_images[i] has source i's size and the colour type the
+ * target gives it, laid out as a decode batch lays its block out — offset[0] = 0, every image rounded up to 16 bytes, *total the
+ * end of the last image (not rounded), `reserved` zeros; the sources' offsets are not read.  dst_images may be src_images.
+ * Checks, nothing is written before all have passed: src_images, dst_images, total; batch (PIXO_ERR_COMPRESSION, "batch must be
+ * 1..65535"); an unknown target (PIXO_ERR_COMPRESSION, "unknown convert target"); then for i = 0, 1, ... source i: a zero side
+ * (PIXO_ERR_INVALID_DIMENSIONS), a side above 2^24 (PIXO_ERR_IMAGE_TOO_LARGE), a colour type above 3
+ * (PIXO_ERR_INVALID_COLOR_ARG), each with " (image i)" appended; a block beyond 2^62 bytes (PIXO_ERR_COMPRESSION). */
+int pixo_hip_convert_images_layout(const pixo_png_image *src_images, uint32_t batch, uint8_t target, pixo_png_image *dst_images,
+                                   size_t *total);
+/* `batch` images anywhere in two blocks in HBM on the current HIP device: image i of src_images[i].width x height pixels of
+ * src_images[i].color_type at d_src + src_images[i].offset -> the same pixels in dst_images[i].color_type at d_dst +
+ * dst_images[i].offset, byte for byte what pixo_hip_convert_device writes for that image alone; the bytes between destinations
+ * are left as they are.  Any alignment of either block and of every offset: an image whose two addresses are multiples of 16 —
+ * what the decode batch's, pixo_hip_resize_images_fit's and the layout's offsets give in blocks so aligned — moves in 16-byte
+ * loads and stores, any other image byte by byte.  Destinations must not overlap each other or a source (not checked).  One
+ * launch per (conversion, aligned or not) present — at most 10 — whatever `batch` is; a launch holds at most 2^31 - 1
+ * workgroups, batches beyond that run as sub-batches (greedy in index order, at least one image), one behind the other on
+ * `stream`.  Enqueue only, ordered like pixo_hip_resize_images_device: behind the work of the producer stream; the one host
+ * wait is for the calling thread's previous convert job, whose records are about to be replaced.
+ * Checks, all before anything is enqueued (no GPU needed for a refusal): src_images, dst_images; batch (PIXO_ERR_COMPRESSION,
+ * "batch must be 1..65535"); then for i = 0, 1, ... image i: a zero side or a side above 2^24 of the source, then of the
+ * destination; a colour type above 3 of the source, then of the destination (PIXO_ERR_INVALID_COLOR_ARG); sizes that differ
+ * between source i and destination i (PIXO_ERR_COMPRESSION, "Compression error: sizes differ"); a pair that is none of the
+ * above (PIXO_ERR_UNSUPPORTED_COLOR_TYPE); offset + the image's bytes beyond 2^62 on the source's, then the destination's side
+ * (PIXO_ERR_COMPRESSION) — each with " (image i)" appended, the first failing image answers; then d_src, d_dst. */
+int pixo_hip_convert_images_device(const void *d_src, const pixo_png_image *src_images, void *d_dst, const pixo_png_image *dst_images,
+                                   uint32_t batch, void *stream);
+/* The same for a block in HOST memory: *out receives one block of *out_len = the furthest destination's end bytes laid out as
+ * dst_images says (the gaps hold nothing of meaning), released with pixo_hip_free.  The checks above, then data, out, out_len,
+ * then data_len below the furthest source's end: PIXO_ERR_INVALID_DATA_LENGTH, "expected <that end> bytes, got <data_len>". */
+int pixo_hip_convert_images(const uint8_t *data, size_t data_len, const pixo_png_image *src_images, const pixo_png_image *dst_images,
+                            uint32_t batch, uint8_t **out, size_t *out_len);
+/* One image: width x height pixels of src_color_type at d_src -> dst_color_type at d_dst (device memory, any alignment).
+ * Enqueue only, ordered like pixo_hip_resize_device.  Checks: a zero side, a side above 2^24, src_color_type then
+ * dst_color_type above 3, a pair that does not exist, then d_src, d_dst. */
+int pixo_hip_convert_device(const void *d_src, uint32_t width, uint32_t height, uint8_t src_color_type, uint8_t dst_color_type,
+                            void *d_dst, void *stream);
+/* ... host pixels in, a block released with pixo_hip_free out.  The checks above up to the pair, then out, out_len, data_len
+ * other than width * height * source bytes per pixel (PIXO_ERR_INVALID_DATA_LENGTH), then data. */
+int pixo_hip_convert(const uint8_t *data, size_t data_len, uint32_t width, uint32_t height, uint8_t src_color_type,
+                     uint8_t dst_color_type, uint8_t **out, size_t *out_len);
+/* Tests: what pixo_hip_convert_images_device decides for these records when d_src is src_align and d_dst is dst_align modulo
+ * 16, computed on the HOST, no GPU needed (the entry's checks up to the images', then the out-pointers in their order).
+ * Sub-batch k is images sub_first[k] .. sub_first[k + 1] (room for batch + 1 entries, *sub_count + 1 are written); kind[i]:
+ * 0 copy, 1 GrayAlpha -> Gray, 2 Rgba -> Rgb, 3 Rgb -> Gray, 4 Rgba -> Gray; form[i]: 0 aligned, 1 bytes; tiles[i]: image
+ * i's workgroups, one per pixo_hip_debug_convert_tile_pixels() pixels, at most 65536 (debug switch convert_images_tiles=n: n,
+ * and a launch then holds at most 2n), which stride over the rest; *launches: summed over the sub-batches. */
+int pixo_hip_debug_convert_images_plan(const pixo_png_image *src_images, const pixo_png_image *dst_images, uint32_t batch,
+                                       uint32_t src_align, uint32_t dst_align, uint32_t *sub_first, uint32_t *sub_count,
+                                       uint8_t *kind, uint8_t *form, uint32_t *tiles, uint32_t *launches);
+/* Pixels of a tile, what one workgroup of the conversion kernels takes in a step (tests place their sizes by it). */
+uint32_t pixo_hip_debug_convert_tile_pixels(void);
+
 /* ---- runtime ----------------------------------------------------------------------- */
 
 int pixo_hip_device_count(void);            /* 0 when no GPU / no driver              */

@@ -9,8 +9,8 @@ Host-side mirror of the reference's public API for this path:
 
 Everything below this package is the C ABI of include/pixo_hip.h (pixo_amd/libpixo_hip.so).
 """
-from . import decode, error, jpeg, png, resize  # noqa: F401
+from . import convert, decode, error, jpeg, png, resize  # noqa: F401
 from .color import ColorType  # noqa: F401
 from .error import Error  # noqa: F401
 
-__all__ = ["ColorType", "Error", "decode", "error", "jpeg", "png", "resize"]
+__all__ = ["ColorType", "Error", "convert", "decode", "error", "jpeg", "png", "resize"]

@@ -150,6 +150,13 @@ SIGNATURES = {
     "pixo_hip_resize_images_device": _sig(_vp, _pimgp, _vp, _pimgp, _u32, _u8, _vp, optional=True),
     "pixo_hip_resize_images": _sig(_vp, _sz, _pimgp, _pimgp, _u32, _u8, _u8pp, _szp, optional=True),
     "pixo_hip_debug_resize_images_plan": _sig(_pimgp, _pimgp, _u32, _u8, _u32p, _u32p, _u64p, _u8p, _u32p, _u32p, _u32p, _u32p, _u32p, optional=True),
+    "pixo_hip_convert_images_layout": _sig(_pimgp, _u32, _u8, _pimgp, _szp, optional=True),
+    "pixo_hip_convert_images_device": _sig(_vp, _pimgp, _vp, _pimgp, _u32, _vp, optional=True),
+    "pixo_hip_convert_images": _sig(_vp, _sz, _pimgp, _pimgp, _u32, _u8pp, _szp, optional=True),
+    "pixo_hip_convert_device": _sig(_vp, _u32, _u32, _u8, _u8, _vp, _vp, optional=True),
+    "pixo_hip_convert": _sig(_vp, _sz, _u32, _u32, _u8, _u8, _u8pp, _szp, optional=True),
+    "pixo_hip_debug_convert_images_plan": _sig(_pimgp, _pimgp, _u32, _u32, _u32, _u32p, _u32p, _u8p, _u8p, _u32p, _u32p, optional=True),
+    "pixo_hip_debug_convert_tile_pixels": _sig(ret=_u32, optional=True),
     "pixo_hip_png_decode": _sig(_vp, _sz, _u8pp, _szp, _u32p, _u32p, _u8p),
     "pixo_hip_png_decode_info": _sig(_vp, _sz, _u32p, _u32p, _u8p),
     "pixo_hip_png_decode_device": _sig(_vp, _sz, _vp, _sz, _u32p, _u32p, _u8p, _vp),

@@ -17,6 +17,7 @@
 //                    the PNG batch entries: segments, sub-batches, the batched tail
 //   png_quantize_api.cpp  PNG lossy mode: gate, histogram and median cut on the host, the kernels of png_quantize.hip, the extern "C" quantize entries
 //   resize_api.cpp   the extern "C" resize entry points, the Lanczos3 contribution tables; the resize batch entries: plan, sub-batches
+//   convert_api.cpp  the extern "C" colour-conversion entry points: layout, checks, plan, sub-batches, the launches of convert.hip
 //   png_decode_api.cpp  the extern "C" PNG decode entry points: chunk walk and checks, the host inflate (png_inflate.cpp), the runs of rows,
 //                    the launches of png_unfilter.hip; the decode batch entries: two-phase checks, the inflate pool, plan, sub-batches
 #pragma once
@@ -111,6 +112,8 @@ inline int bad_length(size_t expected, size_t got)
 //   resize_images_rows=n  an image of pixo_hip_resize_images* has at most n rows of tiles in a pass instead of 65535 (the single
 //                      entry's grid.y limit): tests reach the kernels' row-stride loops with small images.  resize_batch_bytes
 //                      cuts those entries' sub-batches too
+//   convert_images_tiles=n  an image of pixo_hip_convert* has at most n tiles instead of 65536 and a launch at most 2n instead of
+//                      2^31 - 1 (convert_math.h): tests reach the kernels' stride loop and a sub-batch seam with small images
 //   jpeg_images_blocks=n  a sub-batch of pixo_hip_jpeg_encode_images* holds at most n blocks of 64 coefficients (and at least one image)
 //                      instead of 2^22: tests cross a sub-batch seam with small images
 //   decode_batch_bytes=n  a sub-batch of pixo_hip_png_decode_batch* holds at most n bytes of device staging (inflated streams +
@@ -138,6 +141,7 @@ struct DebugSwitches {
     uint64_t png_batch_bytes = 0; // bytes of prepared stream a sub-batch of the PNG batch entries holds at most, 0 = 64 MiB
     uint64_t resize_batch_bytes = 0; // bytes of Lanczos3 intermediate a sub-batch of the resize batch entries holds at most, 0 = 256 MiB
     uint32_t resize_images_rows = 0; // rows of tiles an image of pixo_hip_resize_images* has at most in a pass, 0 = 65535
+    uint32_t convert_images_tiles = 0; // tiles an image of the convert entries has at most, 0 = 65536; a launch then holds at most twice as many
     uint64_t jpeg_images_blocks = 0; // blocks a sub-batch of the JPEG images entries holds at most, 0 = 2^22 (jpeg_images_math.h)
     uint64_t decode_batch_bytes = 0; // bytes of device staging a sub-batch of the PNG decode batch entries holds at most, 0 = 512 MiB
 };
@@ -290,6 +294,11 @@ struct Context {
     Buf rb_tables;                                       // the axis tables of a call, behind them its ResizeBatchItem per image
     Buf rb_stage{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here on the host, uploaded from here in one copy
     hipEvent_t rb_done = nullptr;                        // the last batch job (it reads rb_tables, writes rb_mid) has run
+    // colour conversion (convert_api.cpp, convert.hip)
+    Buf cv_in{Buf::Mem::Device, Buf::Grow::Exact}, cv_out{Buf::Mem::Device, Buf::Grow::Exact}; // host entries: the block of sources up, the block of destinations down
+    Buf cv_records;                                        // the records of a call's launches (convert_math.h), sub-batch after sub-batch
+    Buf h_cv_records{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... built here on the host, uploaded from here, one copy per sub-batch
+    hipEvent_t cv_done = nullptr;                          // the last convert job (it reads cv_records) has run
     // PNG decode (png_decode_api.cpp, png_unfilter.hip)
     Buf u_inflated{Buf::Mem::Pinned, Buf::Grow::Exact};  // the inflated stream (a batch: all its streams): the host inflate writes it, the upload reads it
     Buf u_stream{Buf::Mem::Device, Buf::Grow::Exact};    // ... on the device

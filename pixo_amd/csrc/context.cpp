@@ -85,6 +85,7 @@ DebugSwitches parse_switches(const char *e)
         else if (name == "png_batch_bytes" && num > 0) v.png_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "resize_batch_bytes" && num > 0) v.resize_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "resize_images_rows" && num > 0) v.resize_images_rows = static_cast<uint32_t>(num > 65535 ? 65535 : num);
+        else if (name == "convert_images_tiles" && num > 0) v.convert_images_tiles = static_cast<uint32_t>(num > 65536 ? 65536 : num);
         else if (name == "jpeg_images_blocks" && num > 0) v.jpeg_images_blocks = static_cast<uint64_t>(num);
         else if (name == "decode_batch_bytes" && num > 0) v.decode_batch_bytes = static_cast<uint64_t>(num);
         else if (name == "spin_budget" && !val.empty()) v.spin_budget = static_cast<uint32_t>(num < 0 ? 0 : num);
@@ -162,7 +163,7 @@ template <class F> void each_buf(Context &c, F &&f)
                    &c.q_work, &c.h_qwork, &c.q_index, &c.q_rows, &c.z_tok, &c.z_slots, &c.z_prev, &c.z_info, &c.z_stream, &c.z_crc, &c.h_zinfo,
                    &c.k_samples, &c.h_ksamples, &c.k_work, &c.h_kwork, &c.k_lut, &c.k_carry,
                    &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank, &c.h_file, &c.r_in, &c.r_out, &c.r_mid, &c.r_tables,
-                   &c.r_stage, &c.rb_in, &c.rb_out, &c.rb_mid, &c.rb_tables, &c.rb_stage, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables,
+                   &c.r_stage, &c.rb_in, &c.rb_out, &c.rb_mid, &c.rb_tables, &c.rb_stage, &c.cv_in, &c.cv_out, &c.cv_records, &c.h_cv_records, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables,
                    &c.h_zin, &c.u_zin, &c.u_zout, &c.h_zout, &c.h_uruns, &c.u_runs};
     for (Buf *b : bufs) f(*b);
 }
@@ -211,6 +212,8 @@ void Context::release()
     r_done = nullptr;
     if (rb_done) (void)hipEventDestroy(rb_done);
     rb_done = nullptr;
+    if (cv_done) (void)hipEventDestroy(cv_done);
+    cv_done = nullptr;
     if (u_done) (void)hipEventDestroy(u_done);
     u_done = nullptr;
     stream = nullptr; ready = false;

@@ -23,6 +23,7 @@ SOURCES = {  # profile name prefix -> the files its kernel is compiled from
     "trellis": ["jpeg_trellis.hip", "jpeg_trellis.h", "jpeg_trellis.hpp"],
     "c5": ["png_filter.hip", "png_filter.hpp", "png_filter_math.h"],
     "resize": ["resize.hip", "resize.hpp", "resize_math.h", "resize_images_math.h"],
+    "convert": ["convert.hip", "convert.hpp", "convert_math.h"],
     "c": TILE,  # c2, c2_444, c2_unaligned, c3
 }
 
