@@ -632,6 +632,63 @@ struct PngImage {
     }
     return out;
 }
+
+// decode/jpeg.rs:22-31
+struct JpegImage {
+    uint32_t width = 0;
+    uint32_t height = 0;
+    std::vector<uint8_t> pixels;
+    ColorType color_type = ColorType::Rgb;
+};
+// pixo::decode::decode_jpeg (decode/jpeg.rs:738): a baseline file -> Gray or Rgb pixels, byte for byte libjpeg-turbo's
+// defaults (contract, refusals and the departures from the reference's decoder: pixo_hip.h)
+[[nodiscard]] inline JpegImage decode_jpeg(const uint8_t *data, size_t len)
+{
+    uint8_t *buf = nullptr;
+    size_t n = 0;
+    JpegImage im;
+    uint8_t ct = 0;
+    const int rc = pixo_hip_jpeg_decode(data, len, &buf, &n, &im.width, &im.height, &ct);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    im.pixels.assign(buf, buf + n);
+    pixo_hip_free(buf);
+    im.color_type = static_cast<ColorType>(ct);
+    return im;
+}
+[[nodiscard]] inline JpegImage decode_jpeg(const std::vector<uint8_t> &data) { return decode_jpeg(data.data(), data.size()); }
+// Batches: N files -> N images, image i what decode_jpeg makes of file i.  one_thread: the entropy decodes run on the calling
+// thread instead of the library's small pool.
+[[nodiscard]] inline std::vector<JpegImage> decode_jpeg_batch(const std::vector<pixo_png_file> &files, bool one_thread = false)
+{
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    std::vector<pixo_png_image> images(files.size() ? files.size() : 1);
+    const int rc = pixo_hip_jpeg_decode_batch(files.data(), (uint32_t)files.size(), one_thread ? PIXO_DECODE_ONE_THREAD : 0u, &block, &n, images.data());
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    struct Block { // (released also when a copy below throws)
+        uint8_t *p;
+        ~Block() { pixo_hip_free(p); }
+    } held{block};
+    std::vector<JpegImage> out(files.size());
+    for (size_t i = 0; i < files.size(); ++i) {
+        const pixo_png_image &im = images[i];
+        out[i].width = im.width; out[i].height = im.height; out[i].color_type = static_cast<ColorType>(im.color_type);
+        out[i].pixels.assign(block + im.offset, block + im.offset + (size_t)im.width * im.height * (im.color_type + 1u));
+    }
+    return out;
+}
+// ... into caller storage on the device (enqueue only on `stream`): image i at d_pixels + the returned records' offset, the
+// records what resize::fit_images, resize::resize_images_device and jpeg::encode_images_device take unchanged.
+inline std::vector<pixo_png_image> decode_jpeg_batch_device(const std::vector<pixo_png_file> &files, void *d_pixels, size_t capacity,
+                                                            void *stream = nullptr, bool one_thread = false)
+{
+    std::vector<pixo_png_image> images(files.size() ? files.size() : 1);
+    const int rc = pixo_hip_jpeg_decode_batch_device(files.data(), (uint32_t)files.size(), one_thread ? PIXO_DECODE_ONE_THREAD : 0u, d_pixels, capacity,
+                                                     images.data(), stream);
+    if (rc != PIXO_OK) throw Error::from_status(rc);
+    images.resize(files.size());
+    return images;
+}
 } // namespace decode
 
 // The reference's flat wasm export `resizeImage` (src/wasm.rs:183-201), same seven arguments.

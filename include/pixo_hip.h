@@ -735,6 +735,77 @@ int pixo_hip_debug_zlib_inflate_batch_device(const pixo_png_file *streams, uint3
  * sub-batches), [4] the whole call.  The block is released again. */
 int pixo_hip_debug_png_decode_batch_timed(const pixo_png_file *files, uint32_t batch, uint32_t flags, double ms[5]);
 
+/* ---- JPEG decode: baseline files -> pixels, single and in batches (pixo::decode::decode_jpeg, src/decode/jpeg.rs:738) ----
+ * The pixels are byte for byte what libjpeg-turbo produces with its defaults (islow IDCT, fancy upsampling, no smoothing): one
+ * component gives PIXO_GRAY, three give PIXO_RGB.  The marker walk and the Huffman decode run on the host; dequantisation,
+ * IDCT, chroma upsampling, colour conversion and the crop run on the device and leave the pixels in device memory.
+ * Accepted: SOF0 with 8-bit precision; one component (its sampling factors are ignored), or three with luma 1x1, 2x1 or 2x2 and
+ * both chroma 1x1 (4:4:4, 4:2:2, 4:2:0); one interleaved scan; any restart interval; up to four tables of each kind, redefined
+ * between segments; DQT with 8- or 16-bit entries; APPn, COM and fill bytes in front of markers are skipped.
+ * Refused, in the reference's words (PIXO_ERR_INVALID_DECODE "Decode error: ...", PIXO_ERR_UNSUPPORTED_DECODE "Unsupported:
+ * ..."), in the order of its marker walk: "not a JPEG file", "unexpected end of file", "truncated marker", "invalid marker
+ * length", the segments' length and table-id messages, "progressive JPEG not supported", "{n}-bit precision not supported",
+ * "{n} components not supported", "no image data found".  Refused with messages of this library, at SOS behind the
+ * reference's checks and in this order: no frame in front of the scan (Invalid); any other sampling, 4:4:0 included
+ * (Unsupported); a scan whose components are not the frame's, in its order (Unsupported); an Adobe APP14 transform other than
+ * 1 on three components (Unsupported); component ids 'R', 'G', 'B' (Unsupported); a quantisation or Huffman table the scan
+ * uses and no segment defined (Invalid); a scan of less than two bits per block (Invalid); at DHT, lengths that describe no
+ * prefix code (Invalid).  And from the entropy decode (Invalid): an entropy-coded segment that ends early, a code that no table
+ * holds, a coefficient index past 63, a missing or out-of-sequence RSTn.
+ * Two departures from the reference, on purpose.  (1) It returns a partly decoded picture when the scan breaks off; this
+ * library refuses.  (2) Its three defects are not reproduced: the odd part of its IDCT is 2^-13 of its size, its bit reader
+ * drops unconsumed bits at a restart marker, and its nearest-sample upsampling and 8-bit colour constants agree with no other
+ * decoder.  A width or height of zero is no special case: the image has no bytes.
+ * Crafted coefficients: the kernel computes in 32 bits with unsigned wrap and clamps to 0..255; libjpeg computes in long and
+ * indexes a masked table.  The two agree while no intermediate leaves 32 bits and every descaled sample lies in -512..511 — no
+ * encoder of 8-bit pixels leaves either; the bound on the dequantised block and its derivation: jpeg_decode_math.h. */
+
+/* A baseline JPEG file in host memory -> *pixels (width * height * channels bytes, released with pixo_hip_free). */
+int pixo_hip_jpeg_decode(const uint8_t *file, size_t len, uint8_t **pixels, size_t *pixels_len, uint32_t *width, uint32_t *height,
+                         uint8_t *color_type);
+/* What pixo_hip_jpeg_decode would report, from the walk up to SOS alone — no entropy decode, no GPU. */
+int pixo_hip_jpeg_decode_info(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint8_t *color_type);
+/* The same into caller storage on the device, d_pixels of `capacity` bytes at any alignment (PIXO_ERR_BUFFER_TOO_SMALL, with
+ * *width, *height and *color_type set, when that is less than the image).  Enqueue only, ordered like
+ * pixo_hip_png_decode_device; every refusal comes before anything is enqueued. */
+int pixo_hip_jpeg_decode_device(const uint8_t *file, size_t len, void *d_pixels, size_t capacity, uint32_t *width, uint32_t *height,
+                                uint8_t *color_type, void *stream);
+/* The layout of a batch alone (as pixo_hip_png_decode_batch_info): the walks only — no entropy decode, no GPU. */
+int pixo_hip_jpeg_decode_batch_info(const pixo_png_file *files, uint32_t batch, pixo_png_image *images, size_t *total);
+/* `batch` (1..65535) files -> their pixels at d_pixels + images[i].offset, image i byte for byte what pixo_hip_jpeg_decode
+ * returns for file i; offsets as in the PNG batch (multiples of 16; the bytes between two images and behind the last are never
+ * written), so that pixo_hip_resize_images_fit, pixo_hip_resize_images_device, pixo_hip_convert_images_device,
+ * pixo_hip_jpeg_encode_images_device and pixo_hip_png_encode_images_device take `images` unchanged.  The scans are decoded on up
+ * to 8 host threads (the caller among them; PIXO_DECODE_ONE_THREAD: the caller alone) straight into pinned staging in the
+ * order the kernel loads them; the records go up in one copy, a sub-batch's coefficients in a second, then one launch per class
+ * present (gray, 4:4:4, 4:2:2, 4:2:0, each in a form with 16-byte stores and one with byte stores for images at odd addresses),
+ * whatever `batch` is.  Batches whose coefficients exceed 512 MiB run as sub-batches, one behind the other on `stream`.
+ * Enqueue only; the one host wait is for the calling thread's previous JPEG decode job.  Checks as
+ * pixo_hip_png_decode_batch_device, in its order, all before anything is enqueued: phase 1 the walks (a refusal leaves `images`
+ * untouched), phase 2 the entropy decodes; the failing file with the lowest index answers, " (image i)" appended, whatever the
+ * thread count.  PIXO_DECODE_DEVICE_INFLATE is ignored. */
+int pixo_hip_jpeg_decode_batch_device(const pixo_png_file *files, uint32_t batch, uint32_t flags, void *d_pixels, size_t capacity,
+                                      pixo_png_image *images, void *stream);
+/* The same with the block in HOST memory, released with pixo_hip_free. */
+int pixo_hip_jpeg_decode_batch(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len,
+                               pixo_png_image *images);
+/* Tests: what the batch entries decide, computed on the HOST from phase 1 (no GPU): sub-batch k is images sub_first[k] ..
+ * sub_first[k + 1] (room for batch + 1 entries, *sub_count + 1 are written); classes[i]: 0 gray, 1 4:4:4, 2 4:2:2, 3 4:2:0;
+ * *launches summed over the sub-batches (forms as for a 16-byte aligned d_pixels); *threads: host threads that would decode. */
+int pixo_hip_debug_jpeg_decode_batch_plan(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint32_t *sub_first,
+                                          uint32_t *sub_count, uint8_t *classes, uint32_t *launches, uint32_t *threads);
+/* Tests, host only: the QUANTISED coefficients of component `component` as the entropy decoder read them, 64 per block in zigzag
+ * order, the blocks in raster order of the component's padded plane (*blocks_w x *blocks_h).  `capacity` counts int16 values
+ * (less than blocks * 64: PIXO_ERR_BUFFER_TOO_SMALL with the two counts set). */
+int pixo_hip_debug_jpeg_decode_coefficients(const uint8_t *file, size_t len, uint32_t component, int16_t *out, size_t capacity,
+                                            uint32_t *blocks_w, uint32_t *blocks_h);
+/* The tile of whole MCUs a workgroup of the decode kernel owns (tests place their tile boundaries by it). */
+void pixo_hip_jpeg_decode_tile_mcus(uint32_t *mcus_x, uint32_t *mcus_y);
+/* MEASUREMENT only (tools/jpeg_decode_batch_timing.py): pixo_hip_jpeg_decode_batch with its legs timed — ms[0] the entropy
+ * decodes (host clock), [1] uploads, [2] kernels, [3] the copy of the block to the host (HIP events, summed over the
+ * sub-batches), [4] the whole call.  The block is released again. */
+int pixo_hip_debug_jpeg_decode_batch_timed(const pixo_png_file *files, uint32_t batch, uint32_t flags, double ms[5]);
+
 /* ---- PNG encode of images of individual sizes and colour types, anywhere in one block ---- */
 
 /* `batch` images anywhere in one block in HBM on the current HIP device: image i is images[i].width x images[i].height pixels

@@ -168,6 +168,16 @@ SIGNATURES = {
     "pixo_hip_png_decode_batch": _sig(_pfilep, _u32, _u32, _u8pp, _szp, _pimgp, optional=True),
     "pixo_hip_debug_png_decode_batch_plan": _sig(_pfilep, _u32, _u32, _u32p, _u32p, _u64p, _u32p, _u32p, _u32p, optional=True),
     "pixo_hip_debug_png_decode_batch_timed": _sig(_pfilep, _u32, _u32, C.POINTER(_dbl), optional=True),
+    "pixo_hip_jpeg_decode": _sig(_vp, _sz, _u8pp, _szp, _u32p, _u32p, _u8p, optional=True),
+    "pixo_hip_jpeg_decode_info": _sig(_vp, _sz, _u32p, _u32p, _u8p, optional=True),
+    "pixo_hip_jpeg_decode_device": _sig(_vp, _sz, _vp, _sz, _u32p, _u32p, _u8p, _vp, optional=True),
+    "pixo_hip_jpeg_decode_batch_info": _sig(_pfilep, _u32, _pimgp, _szp, optional=True),
+    "pixo_hip_jpeg_decode_batch_device": _sig(_pfilep, _u32, _u32, _vp, _sz, _pimgp, _vp, optional=True),
+    "pixo_hip_jpeg_decode_batch": _sig(_pfilep, _u32, _u32, _u8pp, _szp, _pimgp, optional=True),
+    "pixo_hip_debug_jpeg_decode_batch_plan": _sig(_pfilep, _u32, _u32, _u32p, _u32p, _u8p, _u32p, _u32p, optional=True),
+    "pixo_hip_debug_jpeg_decode_coefficients": _sig(_vp, _sz, _u32, _vp, _sz, _u32p, _u32p, optional=True),
+    "pixo_hip_jpeg_decode_tile_mcus": _sig(_u32p, _u32p, ret=None, optional=True),
+    "pixo_hip_debug_jpeg_decode_batch_timed": _sig(_pfilep, _u32, _u32, C.POINTER(_dbl), optional=True),
     "pixo_hip_png_encode_images_device": _sig(_vp, _pimgp, _u32, _poptp, _qoptp, _u8pp, _szp, optional=True),
     "pixo_hip_png_encode_images_device_into": _sig(_vp, _pimgp, _u32, _poptp, _qoptp, _vp, _sz, _szp, _szp, optional=True),
     "pixo_hip_png_encode_images": _sig(_vp, _sz, _pimgp, _u32, _poptp, _qoptp, _u8pp, _szp, optional=True),

@@ -20,6 +20,9 @@
 //   convert_api.cpp  the extern "C" colour-conversion entry points: layout, checks, plan, sub-batches, the launches of convert.hip
 //   png_decode_api.cpp  the extern "C" PNG decode entry points: chunk walk and checks, the host inflate (png_inflate.cpp), the runs of rows,
 //                    the launches of png_unfilter.hip; the decode batch entries: two-phase checks, the inflate pool, plan, sub-batches
+//   jpeg_decode_host.cpp  JPEG decode on the host (no HIP): the marker walk and its checks, the entropy decoder into the kernel's layout
+//   jpeg_decode_api.cpp  the extern "C" JPEG decode entry points: two-phase checks, the entropy decodes on the decode pool, plan,
+//                    sub-batches, the launches of jpeg_decode.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -314,6 +317,13 @@ struct Context {
     Buf h_uruns{Buf::Mem::Pinned, Buf::Grow::Headroom};  // a sub-batch's runs of rows, which are known only behind its inflate
     Buf u_runs{Buf::Mem::Device, Buf::Grow::Exact};      // ... on the device
     hipEvent_t u_done = nullptr;                         // the last decode job (it reads all of the above) has run
+    // JPEG decode (jpeg_decode_api.cpp, jpeg_decode.hip)
+    Buf jd_hcoef{Buf::Mem::Pinned, Buf::Grow::Exact};    // a call's quantised coefficients in the kernel's layout: the entropy decoders write them, the uploads read them
+    Buf jd_coef{Buf::Mem::Device, Buf::Grow::Exact};     // ... one sub-batch's on the device
+    Buf jd_hrecords{Buf::Mem::Pinned, Buf::Grow::Headroom}; // the records of a call's launches (jpeg_decode_math.h), built here, uploaded from here
+    Buf jd_records{Buf::Mem::Device, Buf::Grow::Exact};  // ... on the device
+    Buf jd_out{Buf::Mem::Device, Buf::Grow::Exact};      // host entries: the pixels before they go down
+    hipEvent_t jd_done = nullptr;                        // the last JPEG decode job (it reads all of the above) has run
 
     // Small results for the host, one field per purpose: pinned, allocated once with the stream (ensure).
     struct Mailbox {

@@ -164,7 +164,8 @@ template <class F> void each_buf(Context &c, F &&f)
                    &c.k_samples, &c.h_ksamples, &c.k_work, &c.h_kwork, &c.k_lut, &c.k_carry,
                    &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank, &c.h_file, &c.r_in, &c.r_out, &c.r_mid, &c.r_tables,
                    &c.r_stage, &c.rb_in, &c.rb_out, &c.rb_mid, &c.rb_tables, &c.rb_stage, &c.cv_in, &c.cv_out, &c.cv_records, &c.h_cv_records, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables,
-                   &c.h_zin, &c.u_zin, &c.u_zout, &c.h_zout, &c.h_uruns, &c.u_runs};
+                   &c.h_zin, &c.u_zin, &c.u_zout, &c.h_zout, &c.h_uruns, &c.u_runs,
+                   &c.jd_hcoef, &c.jd_coef, &c.jd_hrecords, &c.jd_records, &c.jd_out};
     for (Buf *b : bufs) f(*b);
 }
 } // namespace
@@ -216,6 +217,8 @@ void Context::release()
     cv_done = nullptr;
     if (u_done) (void)hipEventDestroy(u_done);
     u_done = nullptr;
+    if (jd_done) (void)hipEventDestroy(jd_done);
+    jd_done = nullptr;
     stream = nullptr; ready = false;
 }
 

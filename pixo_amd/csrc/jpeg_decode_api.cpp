@@ -1,0 +1,432 @@
+// jpeg_decode_api.cpp — the extern "C" JPEG decode entry points (pixo::decode::decode_jpeg, reference src/decode/jpeg.rs:738):
+// the marker walk and the entropy decode on the host (jpeg_decode_host.cpp), dequantisation, IDCT, upsampling, colour conversion
+// and the crop on the device (jpeg_decode.hip).  N files -> N images back to back in device memory, described by the records the
+// PNG decode batch fills in (pixo_png_image); the single entries are the batch of one, their refusals without " (image 0)".
+//
+// Two phases of checks, both before anything is enqueued.  Phase 1, per file in index order: the walk from SOI to SOS.  In the
+// reference's order and words: "not a JPEG file"; per marker "unexpected end of file", "truncated marker", "invalid marker
+// length", then the segment's own checks (SOF0: length, precision, component count, truncation, sampling factors of zero, table
+// id; SOF2: progressive; DHT, DQT, DRI: table ids and lengths; SOS: empty, component count, truncation, table ids); "no image
+// data found" at EOI.  Ours, at SOS behind the reference's: no frame yet; a sampling other than 4:4:4 / 4:2:2 / 4:2:0
+// (Unsupported); a scan whose components are not the frame's in order (Unsupported); an Adobe transform other than 1 on three
+// components (Unsupported); component ids R, G, B (Unsupported); a quantisation or Huffman table the scan uses and no segment
+// defined; a scan shorter than two bits per block.  Ours at DHT: code lengths that describe no prefix code.  Phase 2, the
+// entropy decodes on up to 8 host threads (PIXO_DECODE_ONE_THREAD: on the caller): a scan that breaks off, a code no table
+// holds, a coefficient index past 63, a missing or out-of-sequence RSTn.  The failing file with the lowest index answers.
+// A width or height of zero is no special case: such an image has no MCUs, no tiles and no bytes.
+#include "capi_internal.hpp"
+#include "jpeg_decode.hpp"
+#include "jpeg_decode_host.hpp"
+
+#include <algorithm>
+#include <atomic>
+
+using namespace pixo_capi;
+namespace jd = pixo_jdec;
+namespace jh = pixo_jdec_host;
+
+namespace {
+
+constexpr uint64_t kDecodeBatchBytes = uint64_t{512} << 20; // coefficients one sub-batch holds at most (debug switch decode_batch_bytes)
+constexpr uint32_t kDecodeBatchThreads = 8;                 // host threads that decode a batch's scans, the caller among them, at most
+
+inline uint64_t round16(uint64_t n) { return (n + 15) & ~uint64_t{15}; }
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+int status_of(jh::Kind k, const std::string &msg, const std::string &where)
+{
+    if (k == jh::OK) return PIXO_OK;
+    return k == jh::UNSUPPORTED ? fail(PIXO_ERR_UNSUPPORTED_DECODE, "Unsupported: " + msg + where) : fail(PIXO_ERR_INVALID_DECODE, "Decode error: " + msg + where);
+}
+
+struct DecodeBatch {
+    std::vector<jh::File> files;
+    std::vector<pixo_png_image> images;
+    std::vector<uint64_t> coef_at; // where each image's coefficients start in the call's staging (multiples of 8192)
+    uint64_t total = 0, staging = 0;
+    uint32_t threads = 1;
+    bool single = false; // a single entry: refusals carry no " (image 0)"
+    double entropy_ms = 0;
+    std::string where(uint32_t i) const { return single ? std::string() : " (image " + std::to_string(i) + ")"; }
+};
+
+// Phase 1 behind `files` and `batch`: per file its `data`, then the walk; the block's layout.  No HIP, no entropy decode.
+int batch_walk(const pixo_png_file *files, uint32_t batch, DecodeBatch &b)
+{
+    b.files.resize(batch);
+    b.images.resize(batch);
+    b.coef_at.resize(batch);
+    for (uint32_t i = 0; i < batch; ++i) {
+        if (!files[i].data) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'data'" + b.where(i));
+        std::string msg;
+        const jh::Kind k = jh::walk(files[i].data, files[i].len, b.files[i], &msg);
+        if (const int rc = status_of(k, msg, b.where(i))) return rc;
+    }
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        const jh::File &f = b.files[i];
+        b.coef_at[i] = b.staging;
+        b.staging += f.coef_bytes();
+        const uint64_t end = at + f.pixel_bytes();
+        pixo_png_image &im = b.images[i];
+        std::memset(&im, 0, sizeof im);
+        im.offset = at; im.width = f.width; im.height = f.height; im.color_type = f.color_type();
+        b.total = end;
+        at = round16(end);
+    }
+    return PIXO_OK;
+}
+
+// Phase 2: every scan decoded to stage + coef_at on up to kDecodeBatchThreads threads, which hand back (kind, message) — fail()
+// is the calling thread's; the failing file with the lowest index decides, whoever decoded it.
+int batch_entropy(DecodeBatch &b, uint8_t *stage, uint32_t flags)
+{
+    const uint32_t batch = static_cast<uint32_t>(b.files.size());
+    b.threads = (flags & PIXO_DECODE_ONE_THREAD) ? 1u : std::min(batch, kDecodeBatchThreads);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<jh::Kind> kind(batch, jh::OK);
+    std::vector<std::string> msg(batch);
+    std::atomic<uint32_t> next{0};
+    run_on_threads(b.threads, [&](unsigned) {
+        for (uint32_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < batch;)
+            kind[i] = jh::entropy_decode(b.files[i], reinterpret_cast<int16_t *>(stage + b.coef_at[i]), &msg[i]);
+    });
+    b.entropy_ms = ms_since(t0);
+    for (uint32_t i = 0; i < batch; ++i)
+        if (const int rc = status_of(kind[i], msg[i], b.where(i))) return rc;
+    return PIXO_OK;
+}
+
+// What the driver decided, before anything touches a device (also: pixo_hip_debug_jpeg_decode_batch_plan)
+struct DecodePlan {
+    std::vector<uint32_t> sub_first; // sub-batch k is images [sub_first[k], sub_first[k + 1])
+    struct Launch { uint32_t sub, cls, form, first_record, count, tiles; };
+    std::vector<Launch> launches;      // in stream order
+    std::vector<jd::Record> records;   // launch after launch
+    uint64_t coef_bytes = 0;           // the largest sub-batch's
+};
+// d_pixels: the address the offsets count from (the plan entry: 0, any 16-byte aligned block)
+int decode_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodePlan &p)
+{
+    const uint32_t batch = static_cast<uint32_t>(b.files.size());
+    const uint64_t limit = debug().decode_batch_bytes ? debug().decode_batch_bytes : kDecodeBatchBytes;
+    p.sub_first.assign(1, 0);
+    uint64_t held = 0;
+    for (uint32_t i = 0; i < batch; ++i) {
+        const uint64_t need = b.files[i].coef_bytes();
+        if (i > p.sub_first.back() && held + need > limit) { // every sub-batch holds at least one image
+            p.sub_first.push_back(i);
+            held = 0;
+        }
+        held += need;
+        p.coef_bytes = std::max(p.coef_bytes, held);
+    }
+    p.sub_first.push_back(batch);
+    for (uint32_t k = 0; k + 1 < p.sub_first.size(); ++k) {
+        const uint32_t first = p.sub_first[k], end = p.sub_first[k + 1];
+        for (uint32_t cls = 0; cls < jd::kClasses; ++cls)
+            for (uint32_t form = 0; form < jd::kForms; ++form) {
+                const uint32_t record0 = static_cast<uint32_t>(p.records.size());
+                uint64_t tiles = 0;
+                for (uint32_t i = first; i < end; ++i) {
+                    const jh::File &f = b.files[i];
+                    const uint32_t mine = (d_pixels + static_cast<uintptr_t>(b.images[i].offset)) % 16 == 0 ? jd::F_ALIGNED : jd::F_BYTES;
+                    if (static_cast<uint32_t>(f.cls) != cls || mine != form || f.mcus_x == 0 || f.mcus_y == 0) continue;
+                    jd::Record r;
+                    std::memset(&r, 0, sizeof r);
+                    for (uint32_t c = 0; c < f.ncomp; ++c) {
+                        r.coef_at[c] = b.coef_at[i] - b.coef_at[first] + f.plane_at(c);
+                        std::memcpy(r.q[c], f.q[f.comp[c].tq], sizeof r.q[c]);
+                    }
+                    r.out_at = b.images[i].offset;
+                    r.width = f.width; r.height = f.height; r.mcus_x = f.mcus_x; r.mcus_y = f.mcus_y;
+                    r.tiles_x = jd::tiles_x_of(f.mcus_x);
+                    r.tiles = r.tiles_x * jd::tiles_y_of(f.mcus_y); // (at most 512 x 2048)
+                    if (tiles + r.tiles > jd::kMaxTiles) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch too large for one launch");
+                    r.first_tile = static_cast<uint32_t>(tiles);
+                    tiles += r.tiles;
+                    p.records.push_back(r);
+                }
+                if (p.records.size() > record0)
+                    p.launches.push_back({k, cls, form, record0, static_cast<uint32_t>(p.records.size()) - record0, static_cast<uint32_t>(tiles)});
+            }
+    }
+    return PIXO_OK;
+}
+
+struct BatchLegs { // timed: events around the device legs of every sub-batch
+    std::vector<hipEvent_t> e;
+    ~BatchLegs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    int mark(hipStream_t s)
+    {
+        hipEvent_t x = nullptr;
+        HIP_TRY(hipEventCreate(&x));
+        e.push_back(x);
+        HIP_TRY(hipEventRecord(x, s));
+        return PIXO_OK;
+    }
+};
+
+// Everything behind phase 1: waits for this thread's previous JPEG decode job (the call's one host wait), decodes the scans into
+// the pinned staging, then enqueues on `s`: all records in one copy; per sub-batch its coefficients in one copy and one launch
+// per class and form present.  Nothing is enqueued after a refusal.
+int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs = nullptr)
+{
+    const uint32_t batch = static_cast<uint32_t>(b.files.size());
+    if (!c.jd_done) HIP_TRY(hipEventCreateWithFlags(&c.jd_done, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(c.jd_done)); // the job before may still be reading the pinned buffers this one is about to write
+    int rc;
+    if ((rc = c.jd_hcoef.reserve(std::max<uint64_t>(b.staging, 16)))) return rc;
+    if ((rc = batch_entropy(b, c.jd_hcoef.as<uint8_t>(), flags))) return rc;
+    DecodePlan p;
+    if ((rc = decode_plan(b, reinterpret_cast<uintptr_t>(d_pixels), p))) return rc;
+    if (p.launches.empty()) return PIXO_OK; // (images without pixels only)
+    // everything is reserved before any address is handed out
+    const size_t record_bytes = p.records.size() * sizeof(jd::Record);
+    if ((rc = c.jd_hrecords.reserve(record_bytes)) || (rc = c.jd_records.reserve(record_bytes)) || (rc = c.jd_coef.reserve(p.coef_bytes))) return rc;
+    std::memcpy(c.jd_hrecords.p, p.records.data(), record_bytes);
+    HIP_TRY(hipMemcpyAsync(c.jd_records.p, c.jd_hrecords.p, record_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c.jd_done, s)); // (until the job's own record: whatever has been enqueued when a later step fails)
+    size_t il = 0;
+    for (uint32_t k = 0; k + 1 < p.sub_first.size(); ++k) {
+        const uint64_t from = b.coef_at[p.sub_first[k]];
+        const uint64_t bytes = (p.sub_first[k + 1] < batch ? b.coef_at[p.sub_first[k + 1]] : b.staging) - from;
+        if (legs && (rc = legs->mark(s))) return rc;
+        if (bytes) HIP_TRY(hipMemcpyAsync(c.jd_coef.p, c.jd_hcoef.as<uint8_t>() + from, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(c.jd_done, s));
+        if (legs && (rc = legs->mark(s))) return rc;
+        for (; il < p.launches.size() && p.launches[il].sub == k; ++il) {
+            const DecodePlan::Launch &l = p.launches[il];
+            HIP_TRY(pixo_dev::launch_jpeg_decode(c.jd_records.as<jd::Record>() + l.first_record, l.count, l.tiles, static_cast<int>(l.cls), static_cast<int>(l.form),
+                                                 c.jd_coef.as<uint8_t>(), d_pixels, s));
+        }
+        if (legs && (rc = legs->mark(s))) return rc;
+        HIP_TRY(hipEventRecord(c.jd_done, s));
+    }
+    return PIXO_OK;
+}
+
+// The batch entries' first two checks
+int batch_head(const pixo_png_file *files, uint32_t batch)
+{
+    PIXO_REQUIRE(files);
+    return batch_in_range(batch);
+}
+void report(const DecodeBatch &b, pixo_png_image *images) { std::copy(b.images.begin(), b.images.end(), images); }
+
+// Host files -> one block of the pinned pool the caller owns.  legs_ms: [0] entropy decode, [1] uploads, [2] kernels, [3] the copy down
+int decode_batch_to_block(DecodeBatch &b, const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len, pixo_png_image *images,
+                          double *legs_ms)
+{
+    int rc = batch_walk(files, batch, b);
+    if (rc) return rc;
+    if (images) report(b, images);
+    PIXO_THREAD_CONTEXT(c);
+    const size_t n = static_cast<size_t>(b.total);
+    if ((rc = reserve16(c.jd_out, std::max<size_t>(n, 16)))) return rc;
+    BatchLegs legs;
+    if ((rc = decode_batch_on_device(c, b, flags, c.jd_out.as<uint8_t>(), c.stream, legs_ms ? &legs : nullptr))) return rc;
+    uint8_t *block = pool_take(std::max<size_t>(n, 1));
+    if (!block) block = alloc_file(std::max<size_t>(n, 1));
+    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    hipError_t e = hipSuccess;
+    hipEvent_t down[2] = {nullptr, nullptr};
+    if (legs_ms) for (hipEvent_t &x : down) if (e == hipSuccess) e = hipEventCreate(&x);
+    if (legs_ms && e == hipSuccess) e = hipEventRecord(down[0], c.stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(block, c.jd_out.p, n, hipMemcpyDeviceToHost, c.stream);
+    if (legs_ms && e == hipSuccess) e = hipEventRecord(down[1], c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (legs_ms && e == hipSuccess) {
+        legs_ms[0] = b.entropy_ms;
+        legs_ms[1] = legs_ms[2] = legs_ms[3] = 0;
+        float ms = 0;
+        for (size_t k = 0; k + 2 < legs.e.size() && e == hipSuccess; k += 3)
+            for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+                e = hipEventElapsedTime(&ms, legs.e[k + i], legs.e[k + i + 1]);
+                legs_ms[1 + i] += ms;
+            }
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, down[0], down[1]);
+        legs_ms[3] = ms;
+    }
+    for (hipEvent_t x : down) if (x) (void)hipEventDestroy(x);
+    if (e != hipSuccess) { free_file(block); return hip_fail(e, "jpeg decode"); }
+    *out = block;
+    *out_len = n;
+    return PIXO_OK;
+}
+
+int batch_to_device(DecodeBatch &b, const pixo_png_file *files, uint32_t batch, uint32_t flags, void *d_pixels, size_t capacity, pixo_png_image *images, void *stream)
+{
+    int rc = batch_walk(files, batch, b);
+    if (rc) return rc;
+    report(b, images);
+    if (capacity < b.total) return too_small(static_cast<size_t>(b.total));
+    if (b.total) PIXO_REQUIRE(d_pixels);
+    Context *c = nullptr;
+    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    return decode_batch_on_device(*c, b, flags, static_cast<uint8_t *>(d_pixels), s);
+}
+
+} // namespace
+
+extern "C" {
+
+int pixo_hip_jpeg_decode_batch_info(const pixo_png_file *files, uint32_t batch, pixo_png_image *images, size_t *total)
+{
+    int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(images);
+    PIXO_REQUIRE(total);
+    DecodeBatch b;
+    if ((rc = batch_walk(files, batch, b))) return rc;
+    report(b, images);
+    *total = static_cast<size_t>(b.total);
+    return PIXO_OK;
+}
+
+int pixo_hip_jpeg_decode_batch_device(const pixo_png_file *files, uint32_t batch, uint32_t flags, void *d_pixels, size_t capacity,
+                                      pixo_png_image *images, void *stream)
+{
+    CallerStorageScope storage(d_pixels != nullptr && capacity != 0);
+    const int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(images);
+    DecodeBatch b;
+    return batch_to_device(b, files, batch, flags, d_pixels, capacity, images, stream);
+}
+
+int pixo_hip_jpeg_decode_batch(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len, pixo_png_image *images)
+{
+    const int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(out);
+    PIXO_REQUIRE(out_len);
+    PIXO_REQUIRE(images);
+    DecodeBatch b;
+    return decode_batch_to_block(b, files, batch, flags, out, out_len, images, nullptr);
+}
+
+int pixo_hip_debug_jpeg_decode_batch_plan(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint32_t *sub_first, uint32_t *sub_count,
+                                          uint8_t *classes, uint32_t *launches, uint32_t *threads)
+{
+    int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(sub_first);
+    PIXO_REQUIRE(sub_count);
+    PIXO_REQUIRE(classes);
+    PIXO_REQUIRE(launches);
+    PIXO_REQUIRE(threads);
+    DecodeBatch b;
+    if ((rc = batch_walk(files, batch, b))) return rc;
+    DecodePlan p;
+    if ((rc = decode_plan(b, 0, p))) return rc;
+    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
+    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    for (uint32_t i = 0; i < batch; ++i) classes[i] = static_cast<uint8_t>(b.files[i].cls);
+    *launches = static_cast<uint32_t>(p.launches.size());
+    *threads = (flags & PIXO_DECODE_ONE_THREAD) ? 1u : std::min(batch, kDecodeBatchThreads);
+    return PIXO_OK;
+}
+
+int pixo_hip_debug_jpeg_decode_batch_timed(const pixo_png_file *files, uint32_t batch, uint32_t flags, double ms[5])
+{
+    const int rc0 = batch_head(files, batch);
+    if (rc0) return rc0;
+    PIXO_REQUIRE(ms);
+    uint8_t *block = nullptr;
+    size_t n = 0;
+    DecodeBatch b;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = decode_batch_to_block(b, files, batch, flags, &block, &n, nullptr, ms);
+    if (rc) return rc;
+    ms[4] = ms_since(t0);
+    free_file(block);
+    return PIXO_OK;
+}
+
+int pixo_hip_jpeg_decode(const uint8_t *file, size_t len, uint8_t **pixels, size_t *pixels_len, uint32_t *width, uint32_t *height, uint8_t *color_type)
+{
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(pixels);
+    PIXO_REQUIRE(pixels_len);
+    PIXO_REQUIRE(width);
+    PIXO_REQUIRE(height);
+    PIXO_REQUIRE(color_type);
+    const pixo_png_file one = {file, len};
+    pixo_png_image im;
+    DecodeBatch b;
+    b.single = true;
+    const int rc = decode_batch_to_block(b, &one, 1, PIXO_DECODE_ONE_THREAD, pixels, pixels_len, &im, nullptr);
+    if (rc) return rc;
+    *width = im.width; *height = im.height; *color_type = im.color_type;
+    return PIXO_OK;
+}
+
+int pixo_hip_jpeg_decode_info(const uint8_t *file, size_t len, uint32_t *width, uint32_t *height, uint8_t *color_type)
+{
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(width);
+    PIXO_REQUIRE(height);
+    PIXO_REQUIRE(color_type);
+    const pixo_png_file one = {file, len};
+    DecodeBatch b;
+    b.single = true;
+    const int rc = batch_walk(&one, 1, b);
+    if (rc) return rc;
+    *width = b.images[0].width; *height = b.images[0].height; *color_type = b.images[0].color_type;
+    return PIXO_OK;
+}
+
+int pixo_hip_jpeg_decode_device(const uint8_t *file, size_t len, void *d_pixels, size_t capacity, uint32_t *width, uint32_t *height,
+                                uint8_t *color_type, void *stream)
+{
+    CallerStorageScope storage(d_pixels != nullptr && capacity != 0);
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(width);
+    PIXO_REQUIRE(height);
+    PIXO_REQUIRE(color_type);
+    const pixo_png_file one = {file, len};
+    pixo_png_image im;
+    std::memset(&im, 0, sizeof im);
+    DecodeBatch b;
+    b.single = true;
+    const int rc = batch_to_device(b, &one, 1, PIXO_DECODE_ONE_THREAD, d_pixels, capacity, &im, stream);
+    if (!b.images.empty() && (rc == PIXO_OK || rc == PIXO_ERR_BUFFER_TOO_SMALL)) { *width = im.width; *height = im.height; *color_type = im.color_type; }
+    return rc;
+}
+
+int pixo_hip_debug_jpeg_decode_coefficients(const uint8_t *file, size_t len, uint32_t component, int16_t *out, size_t capacity, uint32_t *blocks_w,
+                                            uint32_t *blocks_h)
+{
+    PIXO_REQUIRE(file);
+    PIXO_REQUIRE(blocks_w);
+    PIXO_REQUIRE(blocks_h);
+    jh::File f;
+    std::string msg;
+    int rc = status_of(jh::walk(file, len, f, &msg), msg, "");
+    if (rc) return rc;
+    if (component >= f.ncomp) return fail(PIXO_ERR_COMPRESSION, "Compression error: no such component");
+    *blocks_w = f.blocks_w(component);
+    *blocks_h = f.blocks_h(component);
+    const uint64_t blocks = static_cast<uint64_t>(*blocks_w) * *blocks_h;
+    if (capacity < blocks * 64) return too_small(static_cast<size_t>(blocks * 64 * sizeof(int16_t)));
+    if (blocks) PIXO_REQUIRE(out);
+    std::vector<int16_t> coef(static_cast<size_t>(f.coef_bytes() / 2));
+    if ((rc = status_of(jh::entropy_decode(f, coef.data(), &msg), msg, ""))) return rc;
+    const int16_t *plane = coef.data() + f.plane_at(component) / 2;
+    for (uint64_t b = 0; b < blocks; ++b)
+        for (uint32_t k = 0; k < 64; ++k) out[b * 64 + k] = plane[jd::coef_index(b, jh::kZigzag[k])];
+    return PIXO_OK;
+}
+
+void pixo_hip_jpeg_decode_tile_mcus(uint32_t *mcus_x, uint32_t *mcus_y)
+{
+    if (mcus_x) *mcus_x = jd::kTileMcusX;
+    if (mcus_y) *mcus_y = jd::kTileMcusY;
+}
+
+} // extern "C"

@@ -1,9 +1,10 @@
-"""`pixo::decode` on the MI355X (reference src/decode/png.rs): a PNG file -> 8-bit pixels.  The chunk walk, its checks and the
+"""`pixo::decode` on the MI355X (reference src/decode/png.rs, src/decode/jpeg.rs): a PNG or baseline JPEG file -> 8-bit pixels.  The chunk walk, its checks and the
 inflate run on the host, in the reference's order and with its messages; row reconstruction and the conversion to pixels run
 on the device — and, for the batch entries with `device_inflate=True`, the inflate too (one wavefront per stream; the single entries
 keep the host inflate: one stream is one wavefront).  Mirrors `PngImage` and `decode_png`; `decode_png_info` and `decode_png_device` are what a caller needs to keep
-the pixels in device memory for `resize.resize_device`, `jpeg.encode_device` and `png.encode_device`.  JPEG decode is not
-provided.  No CPU fallback."""
+the pixels in device memory for `resize.resize_device`, `jpeg.encode_device` and `png.encode_device`.  JPEG decode (`decode_jpeg*`, below): marker walk and
+Huffman decode on the host, IDCT, upsampling and colour conversion on the device, pinned byte for byte to libjpeg-turbo's
+defaults, not to the reference's decoder.  No CPU fallback."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -205,3 +206,148 @@ def inflate_zlib_batch_debug(streams, expected, out, out_at):
     verdict, produced, adler, ms = (C.c_uint32 * max(n, 1))(), (C.c_uint64 * max(n, 1))(), (C.c_uint32 * max(n, 1))(), C.c_double()
     _lib.check(L.pixo_hip_debug_zlib_inflate_batch_device(arr, n, exp, out.ctypes.data, at, verdict, produced, adler, C.byref(ms)))
     return list(verdict[:n]), list(produced[:n]), list(adler[:n]), ms.value
+
+
+# ---- JPEG decode: baseline files -> pixels, byte for byte libjpeg-turbo's defaults (include/pixo_hip.h) -------------------------
+@dataclass(frozen=True)
+class JpegImage:
+    """jpeg.rs:22-31"""
+    width: int
+    height: int
+    pixels: bytes
+    color_type: ColorType
+
+
+JPEG_CLASSES = ("gray", "444", "422", "420")  # pixo_hip_debug_jpeg_decode_batch_plan's classes
+
+
+def decode_jpeg_tile_mcus():
+    """(MCUs across, MCUs down) of the tile a workgroup of the decode kernel owns (jpeg_decode_math.h)."""
+    x, y = C.c_uint32(), C.c_uint32()
+    _lib.load().pixo_hip_jpeg_decode_tile_mcus(C.byref(x), C.byref(y))
+    return x.value, y.value
+
+
+def decode_jpeg(data) -> JpegImage:
+    """A baseline JPEG file (bytes) -> JpegImage with host pixels: Gray for one component, Rgb for three."""
+    L = _lib.load()
+    f = _file(data)
+    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    w, h, ct = C.c_uint32(), C.c_uint32(), C.c_uint8()
+    _lib.check(L.pixo_hip_jpeg_decode(f.ctypes.data, f.size, C.byref(out), C.byref(n), C.byref(w), C.byref(h), C.byref(ct)))
+    return JpegImage(w.value, h.value, _lib.take(L, out, n), ColorType(ct.value))
+
+
+def decode_jpeg_info(data):
+    """(width, height, ColorType) of the pixels decode_jpeg would return: the walk up to SOS only — no entropy decode, no GPU."""
+    L = _lib.load()
+    f = _file(data)
+    w, h, ct = C.c_uint32(), C.c_uint32(), C.c_uint8()
+    _lib.check(L.pixo_hip_jpeg_decode_info(f.ctypes.data, f.size, C.byref(w), C.byref(h), C.byref(ct)))
+    return w.value, h.value, ColorType(ct.value)
+
+
+def decode_jpeg_device(data, out=None, stream=None):
+    """A baseline JPEG file (host bytes) -> a uint8 torch tensor (height, width, channels) on the current device.  Enqueue
+    only, ordered like decode_png_device.  `out`: a contiguous uint8 device tensor to decode into; BufferTooSmall carries the
+    bytes needed in `.needed`.  Returns (tensor, ColorType)."""
+    import torch
+    L = _lib.load()
+    f = _file(data)
+    w, h, ct = C.c_uint32(), C.c_uint32(), C.c_uint8()
+    if out is None:
+        iw, ih, ict = decode_jpeg_info(f)
+        out = torch.empty((ih, iw, ict.bytes_per_pixel()), dtype=torch.uint8, device="cuda")
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    rc = L.pixo_hip_jpeg_decode_device(f.ctypes.data, f.size, out.data_ptr(), _lib.nbytes(out), C.byref(w), C.byref(h), C.byref(ct),
+                                       C.c_void_p(stream) if stream else None)
+    _lib.check(rc, needed=w.value * h.value * ColorType(ct.value).bytes_per_pixel() if rc == -9 else None)
+    color = ColorType(ct.value)
+    n = w.value * h.value * color.bytes_per_pixel()
+    return out.reshape(-1)[:n].view(h.value, w.value, color.bytes_per_pixel()), color
+
+
+def decode_jpeg_batch_info(files):
+    """([(width, height, ColorType, offset)], total) of the block decode_jpeg_batch_device writes, as decode_png_batch_info."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    images, total = (_lib.PngImageC * max(len(held), 1))(), C.c_size_t()
+    _lib.check(L.pixo_hip_jpeg_decode_batch_info(arr, len(held), images, C.byref(total)))
+    return [(im.width, im.height, ColorType(im.color_type), im.offset) for im in images[:len(held)]], total.value
+
+
+def decode_jpeg_batch(files, one_thread=False) -> list:
+    """JPEG files (bytes) -> [JpegImage] with host pixels, image i what decode_jpeg makes of file i.  The scans are decoded on
+    up to 8 host threads unless `one_thread`."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    images = (_lib.PngImageC * max(len(held), 1))()
+    out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
+    _lib.check(L.pixo_hip_jpeg_decode_batch(arr, len(held), _flags(one_thread, False), C.byref(out), C.byref(n), images))
+    block = _lib.take(L, out, n)
+    return [JpegImage(im.width, im.height, block[im.offset:im.offset + _bytes_of(im)], ColorType(im.color_type)) for im in images[:len(held)]]
+
+
+def decode_jpeg_batch_device(files, out=None, stream=None, one_thread=False, records=False):
+    """JPEG files (host bytes) -> [(uint8 tensor view (height, width, channels), ColorType)], views into ONE uint8 device
+    tensor: `out` (contiguous, any alignment; the bytes between two images are left as they are), or one allocated from
+    decode_jpeg_batch_info.  Enqueue only; BufferTooSmall carries the total in `.needed`.  `records`: also return the block and
+    the pixo_png_image records, which resize.fit_images, resize.resize_images_device, convert, jpeg.encode_images_device and
+    png.encode_images_device take unchanged: (views, out, images)."""
+    import torch
+    L = _lib.load()
+    arr, held = _files_c(files)
+    images = (_lib.PngImageC * max(len(held), 1))()
+    if out is None:
+        out = torch.empty(max(decode_jpeg_batch_info(held)[1], 1), dtype=torch.uint8, device="cuda")
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda
+    if stream is None:
+        stream = torch.cuda.current_stream().cuda_stream
+    rc = L.pixo_hip_jpeg_decode_batch_device(arr, len(held), _flags(one_thread, False), out.data_ptr(), _lib.nbytes(out), images,
+                                             C.c_void_p(stream) if stream else None)
+    last = images[len(held) - 1] if held else None
+    _lib.check(rc, needed=last.offset + _bytes_of(last) if rc == -9 else None)
+    flat = out.reshape(-1)
+    views = [(flat[im.offset:im.offset + _bytes_of(im)].view(im.height, im.width, ColorType(im.color_type).bytes_per_pixel()), ColorType(im.color_type))
+             for im in images[:len(held)]]
+    return (views, out, images) if records else views
+
+
+def decode_jpeg_batch_plan(files, one_thread=False) -> dict:
+    """What the batch entries decide for these files, computed on the host (no GPU): `sub_first`, `classes` (per image, of
+    JPEG_CLASSES), `launches` (summed over the sub-batches) and `threads`."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    n = len(held)
+    sub_first, classes = (C.c_uint32 * (n + 1))(), (C.c_uint8 * max(n, 1))()
+    subs, launches, threads = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _lib.check(L.pixo_hip_debug_jpeg_decode_batch_plan(arr, n, ONE_THREAD if one_thread else 0, sub_first, C.byref(subs), classes, C.byref(launches),
+                                                       C.byref(threads)))
+    return dict(sub_first=list(sub_first[:subs.value + 1]), classes=[JPEG_CLASSES[k] for k in classes[:n]], launches=launches.value,
+                threads=threads.value)
+
+
+def decode_jpeg_coefficients(data, component: int) -> np.ndarray:
+    """The quantised coefficients of one component as the host's entropy decoder read them: int16 (blocks down, blocks across,
+    64), zigzag order within a block, the component's padded plane.  Host only (tests)."""
+    L = _lib.load()
+    f = _file(data)
+    bw, bh = C.c_uint32(), C.c_uint32()
+    rc = L.pixo_hip_debug_jpeg_decode_coefficients(f.ctypes.data, f.size, component, None, 0, C.byref(bw), C.byref(bh))
+    if rc != -9:
+        _lib.check(rc)
+    out = np.zeros((bh.value, bw.value, 64), np.int16)
+    if out.size:
+        _lib.check(L.pixo_hip_debug_jpeg_decode_coefficients(f.ctypes.data, f.size, component, out.ctypes.data, out.size, C.byref(bw), C.byref(bh)))
+    return out
+
+
+def decode_jpeg_batch_timed(files, one_thread=False):
+    """MEASUREMENT: decode_jpeg_batch with its legs timed -> [entropy decode, uploads, kernels, copy down, whole call] in ms."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    ms = (C.c_double * 5)()
+    _lib.check(L.pixo_hip_debug_jpeg_decode_batch_timed(arr, len(held), ONE_THREAD if one_thread else 0, ms))
+    return list(ms)

@@ -140,6 +140,10 @@ extern "C" {
                            color_type: *mut u8) -> c_int;
     fn pixo_hip_png_decode_batch(files: *const CPngFile, batch: u32, flags: u32, out: *mut *mut u8, out_len: *mut usize,
                                  images: *mut CPngImage) -> c_int;
+    fn pixo_hip_jpeg_decode(file: *const u8, len: usize, pixels: *mut *mut u8, pixels_len: *mut usize, width: *mut u32, height: *mut u32,
+                            color_type: *mut u8) -> c_int;
+    fn pixo_hip_jpeg_decode_batch(files: *const CPngFile, batch: u32, flags: u32, out: *mut *mut u8, out_len: *mut usize,
+                                  images: *mut CPngImage) -> c_int;
     fn pixo_hip_free(p: *mut u8);
     fn pixo_hip_copy_file(dst: *mut u8, src: *const u8, n: usize);
     fn pixo_hip_last_error() -> *const c_char;
@@ -488,6 +492,56 @@ pub mod decode {
             pixo_hip_free(p);
         }
         Ok(PngImage { width, height, pixels, color_type: color_type_of(ct) })
+    }
+
+    /// `pixo::decode::JpegImage` (`src/decode/jpeg.rs:22-31`)
+    #[derive(Debug, Clone, PartialEq, Eq)]
+    pub struct JpegImage {
+        pub width: u32,
+        pub height: u32,
+        pub pixels: Vec<u8>,
+        pub color_type: ColorType,
+    }
+
+    /// `pixo::decode::decode_jpeg(data)` (`src/decode/jpeg.rs:738`): a baseline file to Gray or Rgb pixels, byte for byte what
+    /// libjpeg-turbo produces with its defaults — not the reference decoder's pixels; a scan that breaks off is an
+    /// error, not a partly decoded picture.
+    pub fn decode_jpeg(data: &[u8]) -> Result<JpegImage> {
+        let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
+        let (mut width, mut height, mut ct) = (0u32, 0u32, 0u8);
+        let rc = unsafe { pixo_hip_jpeg_decode(data.as_ptr(), data.len(), &mut p, &mut n, &mut width, &mut height, &mut ct) };
+        if rc != 0 { return Err(error_of(rc)); }
+        let mut pixels = Vec::<u8>::with_capacity(n);
+        unsafe {
+            pixo_hip_copy_file(pixels.as_mut_ptr(), p, n);
+            pixels.set_len(n);
+            pixo_hip_free(p);
+        }
+        Ok(JpegImage { width, height, pixels, color_type: color_type_of(ct) })
+    }
+
+    /// A loop over `decode_jpeg` in one call (`pixo_hip_jpeg_decode_batch`): the entropy decodes run on a small pool of host
+    /// threads (`one_thread`: on the calling thread), one launch per class of images present whatever their number.
+    pub fn decode_jpeg_batch(files: &[&[u8]], one_thread: bool) -> Result<Vec<JpegImage>> {
+        let c_files: Vec<CPngFile> = files.iter().map(|f| CPngFile { data: f.as_ptr(), len: f.len() }).collect();
+        let mut images = vec![CPngImage { offset: 0, width: 0, height: 0, color_type: 0, reserved: [0; 7] }; files.len().max(1)];
+        let (mut p, mut n) = (std::ptr::null_mut::<u8>(), 0usize);
+        let list = if files.is_empty() { std::ptr::null() } else { c_files.as_ptr() };
+        let flags = if one_thread { DECODE_ONE_THREAD } else { 0 };
+        let rc = unsafe { pixo_hip_jpeg_decode_batch(list, files.len() as u32, flags, &mut p, &mut n, images.as_mut_ptr()) };
+        if rc != 0 { return Err(error_of(rc)); }
+        let mut out = Vec::with_capacity(files.len());
+        for im in &images[..files.len()] {
+            let bytes = im.width as usize * im.height as usize * (im.color_type as usize + 1);
+            let mut pixels = Vec::<u8>::with_capacity(bytes);
+            unsafe {
+                pixo_hip_copy_file(pixels.as_mut_ptr(), p.add(im.offset as usize), bytes);
+                pixels.set_len(bytes);
+            }
+            out.push(JpegImage { width: im.width, height: im.height, pixels, color_type: color_type_of(im.color_type) });
+        }
+        unsafe { pixo_hip_free(p) };
+        Ok(out)
     }
 }
 
