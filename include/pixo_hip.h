@@ -794,6 +794,9 @@ int pixo_hip_jpeg_decode_batch(const pixo_png_file *files, uint32_t batch, uint3
  * *launches summed over the sub-batches (forms as for a 16-byte aligned d_pixels); *threads: host threads that would decode. */
 int pixo_hip_debug_jpeg_decode_batch_plan(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint32_t *sub_first,
                                           uint32_t *sub_count, uint8_t *classes, uint32_t *launches, uint32_t *threads);
+/* Tests, host only (no GPU): the quantisation tables the kernel would be handed — q[i][c][n]: image i's record, component c, natural
+ * order; room for batch * 3 * 64 values.  A gray image's components 1 and 2, and an image without MCUs, are zeros. */
+int pixo_hip_debug_jpeg_decode_batch_tables(const pixo_png_file *files, uint32_t batch, uint16_t *q);
 /* Tests, host only: the QUANTISED coefficients of component `component` as the entropy decoder read them, 64 per block in zigzag
  * order, the blocks in raster order of the component's padded plane (*blocks_w x *blocks_h).  `capacity` counts int16 values
  * (less than blocks * 64: PIXO_ERR_BUFFER_TOO_SMALL with the two counts set). */

@@ -175,6 +175,7 @@ SIGNATURES = {
     "pixo_hip_jpeg_decode_batch_device": _sig(_pfilep, _u32, _u32, _vp, _sz, _pimgp, _vp, optional=True),
     "pixo_hip_jpeg_decode_batch": _sig(_pfilep, _u32, _u32, _u8pp, _szp, _pimgp, optional=True),
     "pixo_hip_debug_jpeg_decode_batch_plan": _sig(_pfilep, _u32, _u32, _u32p, _u32p, _u8p, _u32p, _u32p, optional=True),
+    "pixo_hip_debug_jpeg_decode_batch_tables": _sig(_pfilep, _u32, _vp, optional=True),
     "pixo_hip_debug_jpeg_decode_coefficients": _sig(_vp, _sz, _u32, _vp, _sz, _u32p, _u32p, optional=True),
     "pixo_hip_jpeg_decode_tile_mcus": _sig(_u32p, _u32p, ret=None, optional=True),
     "pixo_hip_debug_jpeg_decode_batch_timed": _sig(_pfilep, _u32, _u32, C.POINTER(_dbl), optional=True),

@@ -105,6 +105,7 @@ struct DecodePlan {
     struct Launch { uint32_t sub, cls, form, first_record, count, tiles; };
     std::vector<Launch> launches;      // in stream order
     std::vector<jd::Record> records;   // launch after launch
+    std::vector<uint32_t> record_image; // the image each record was made from
     uint64_t coef_bytes = 0;           // the largest sub-batch's
 };
 // d_pixels: the address the offsets count from (the plan entry: 0, any 16-byte aligned block)
@@ -148,6 +149,7 @@ int decode_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodePlan &p)
                     r.first_tile = static_cast<uint32_t>(tiles);
                     tiles += r.tiles;
                     p.records.push_back(r);
+                    p.record_image.push_back(i);
                 }
                 if (p.records.size() > record0)
                     p.launches.push_back({k, cls, form, record0, static_cast<uint32_t>(p.records.size()) - record0, static_cast<uint32_t>(tiles)});
@@ -329,6 +331,20 @@ int pixo_hip_debug_jpeg_decode_batch_plan(const pixo_png_file *files, uint32_t b
     for (uint32_t i = 0; i < batch; ++i) classes[i] = static_cast<uint8_t>(b.files[i].cls);
     *launches = static_cast<uint32_t>(p.launches.size());
     *threads = (flags & PIXO_DECODE_ONE_THREAD) ? 1u : std::min(batch, kDecodeBatchThreads);
+    return PIXO_OK;
+}
+
+int pixo_hip_debug_jpeg_decode_batch_tables(const pixo_png_file *files, uint32_t batch, uint16_t *q)
+{
+    int rc = batch_head(files, batch);
+    if (rc) return rc;
+    PIXO_REQUIRE(q);
+    DecodeBatch b;
+    if ((rc = batch_walk(files, batch, b))) return rc;
+    DecodePlan p;
+    if ((rc = decode_plan(b, 0, p))) return rc;
+    std::memset(q, 0, static_cast<size_t>(batch) * sizeof p.records[0].q);
+    for (size_t k = 0; k < p.records.size(); ++k) std::memcpy(q + static_cast<size_t>(p.record_image[k]) * 3 * 64, p.records[k].q, sizeof p.records[k].q);
     return PIXO_OK;
 }
 

@@ -9,6 +9,13 @@
 // EXTREME COEFFICIENTS.  Everything is 32-bit with unsigned wrap (no undefined behaviour) and the result is clamped to 0..255.
 // libjpeg computes in `long` and indexes a masked range-limit table instead of clamping; the two agree as long as (a) no
 // intermediate leaves 32 bits and (b) every descaled sample lies in -512..511.  No encoder of 8-bit pixels leaves either.
+// Beyond (b) the samples here are the CLAMPED ones; libjpeg's C transform wraps there (its table is indexed modulo 1024), while
+// a libjpeg-turbo with its SIMD transform was seen to saturate as this code does (lone coefficients with samples to +-1248).
+// MEASURED against libjpeg-turbo (tests/jpeg_decode_arith.py, byte for byte): the largest lone dequantised coefficient that (b)
+// allows — DC -4100 .. +4091; AC, either sign, from 2126 at (1, 1) to 4091 at (0, 4), (4, 0) and (4, 4) —, the same on DC +-1016,
+// dense blocks at 0.6 .. 0.9 of the bound below, and files with their tables times 2 and times 4 (dequantised values to +-3768).
+// With tables times 16 (values to +-15072, samples to +-2333) the pixels are still the clamped ones of 64-bit arithmetic, and
+// 3 to 17 % of a file's bytes differ from libjpeg-turbo's.
 // (a), derived.  One 8-point pass computes sums of products input x constant.  With a_k the sum of the constants' magnitudes
 // that input k meets on its way to any intermediate of the pass,
 //     a = {8192, 32501, 10703, 71869, 8192, 50643, 19570, 35521}        (k = 0..7; e.g. a_3 = 25172 + 20995 + 16069 + 9633)
@@ -16,8 +23,9 @@
 // and every intermediate of the row pass at most sum_c a_c |ws[r][c]| + 2^17.  With A_k = a_k / 8192 (1, 3.97, 1.31, 8.78, 1,
 // 6.19, 2.39, 4.34) both passes stay inside 31 bits when
 //     W(d) = sum over (r, c) of A_r * A_c * |d[r][c]|  <=  65000         (d: the DEQUANTISED block)
-// — a sufficient bound, not a necessary one: a lone DC may reach 65000, a lone coefficient (3, 3) 843.  within_bound() below
-// evaluates it; the tests keep their files inside it.
+// — a sufficient bound, not a necessary one: a lone DC may reach 65000, a lone coefficient (3, 3) 843, while the measured cases
+// above reach W = 163,000 (a lone (3, 3) of 2127) and, at tables times 16, W = 395,000 without an intermediate leaving 32 bits.
+// within_bound() below evaluates it; the committed test files lie inside it.
 #pragma once
 #include <stdint.h>
 

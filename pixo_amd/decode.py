@@ -329,6 +329,16 @@ def decode_jpeg_batch_plan(files, one_thread=False) -> dict:
                 threads=threads.value)
 
 
+def decode_jpeg_batch_tables(files) -> np.ndarray:
+    """The quantisation tables in the records the batch entries would hand the kernel: uint16 (images, 3, 64), natural order;
+    zeros for the components a gray image lacks.  Host only (tests)."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    out = np.zeros((len(held), 3, 64), np.uint16)
+    _lib.check(L.pixo_hip_debug_jpeg_decode_batch_tables(arr, len(held), out.ctypes.data))
+    return out
+
+
 def decode_jpeg_coefficients(data, component: int) -> np.ndarray:
     """The quantised coefficients of one component as the host's entropy decoder read them: int16 (blocks down, blocks across,
     64), zigzag order within a block, the component's padded plane.  Host only (tests)."""

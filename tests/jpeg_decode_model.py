@@ -3,7 +3,8 @@ standard (ITU T.81 F.2.2), the "islow" integer inverse DCT (jidctint), fancy h2v
 filters with alternating rounding constants) and jdcolor's 16-bit fixed point.  Written from the algorithms, not from the
 kernel: whole planes, Python integers and int64 arrays (nothing wraps), no tiles, no halo.  `decode(data)` gives
 (width, height, pixels as a uint8 array, colour type 0 gray / 2 RGB); `coefficients(data)` the quantised coefficients per
-component, zigzag order.  Refusals raise Refused(kind, message) with the library's words."""
+component, zigzag order; `pixels(frame, coefficients)` is decode() behind the entropy decoder, for coefficients that were
+never written to a file, and `unclamped(blocks)` the IDCT's samples in front of the clamp.  Refusals raise Refused(kind, message) with the library's words."""
 import numpy as np
 
 ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -210,11 +211,15 @@ def dequantised(f, coefs, ci):
     return nat.reshape(nat.shape[0], nat.shape[1], 8, 8)
 
 
+def unclamped(blk):
+    """Dequantised blocks (..., 8, 8) -> their descaled samples in front of the + 128 and the clamp"""
+    ws = np.swapaxes(_idct8(np.swapaxes(blk, -1, -2), 11), -1, -2)  # columns
+    return _idct8(ws, 18)                                            # rows
+
+
 def plane(f, coefs, ci):
     """Component ci's padded plane of samples"""
-    blk = dequantised(f, coefs, ci)
-    ws = np.swapaxes(_idct8(np.swapaxes(blk, -1, -2), 11), -1, -2)  # columns
-    out = np.clip(_idct8(ws, 18) + 128, 0, 255)                      # rows
+    out = np.clip(unclamped(dequantised(f, coefs, ci)) + 128, 0, 255)
     by, bx = out.shape[:2]
     return out.transpose(0, 2, 1, 3).reshape(by * 8, bx * 8)
 
@@ -256,7 +261,20 @@ def _rgb(y, cb, cr):
 
 def decode(d):
     """(width, height, uint8 pixels (h, w) or (h, w, 3), colour type)"""
-    f, coefs = coefficients(d)
+    return pixels(*coefficients(d))
+
+
+def frame(width, height, comps, q):
+    """The Frame of a file that was never written.  comps: [dict(h, v, tq)]; q: {id: 64 values in ZIGZAG order}"""
+    f = Frame()
+    f.width, f.height, f.comps, f.q = width, height, [dict(c) for c in comps], q
+    if len(f.comps) == 1:
+        f.comps[0]["h"] = f.comps[0]["v"] = 1
+    return f
+
+
+def pixels(f, coefs):
+    """decode() behind the entropy decoder: coefs per component (blocks down, blocks across, 64), zigzag order"""
     W, H = f.width, f.height
     planes = [plane(f, coefs, ci) for ci in range(len(f.comps))]
     if len(f.comps) == 1:
