@@ -869,7 +869,9 @@ int pixo_hip_debug_png_encode_images_plan(const pixo_png_image *images, uint32_t
  * Sub-batches are greedy in index order, at least one image each, at most 2^22 blocks of 64 coefficients (512 MiB of tuple,
  * 836 MiB of packed streams; PIXO_HIP_DEBUG jpeg_images_blocks=n lowers it); a sub-batch also ends where the way changes.
  * files[i] / lens[i] receive `batch` files, each a block from the pinned pool that the caller releases with pixo_hip_free;
- * after a failure no block stays allocated.  Checks, all before the thread's context is touched, in this order: null options;
+ * after a failure no block stays allocated.  The scans of a sub-batch reach the files in one copy per colour class through
+ * the context's pinned buffer, or — when every destination is pinned and the scans total 4 MiB x max(1, images / 64) or more —
+ * file by file straight into the destinations (PIXO route JPEG_IMAGES_DIRECT, bit 49, beside JPEG_IMAGES).  Checks, all before the thread's context is touched, in this order: null options;
  * the template's quality and Some(0) restart interval as pixo_hip_jpeg_encode_device checks them; null d_pixels; null images;
  * batch in 1..65535; null files, null lens; then for i = 0, 1, ... image i with the single entry's statuses and messages, each
  * with " (image i)" appended: a zero side, a side above 65535, a colour type that is not PIXO_GRAY or PIXO_RGB

@@ -211,7 +211,7 @@ int shared_sub_batch(Context &c, const void *d_px, const pixo_png_image *images,
     const ji::TileRecord *d_tiles = c.j_tables.as<ji::TileRecord>();
     const ji::SegRecord *d_segs = reinterpret_cast<const ji::SegRecord *>(c.j_tables.as<uint8_t>() + tile_bytes);
     // ---- one coefficient launch per class present
-    note_route(route::JPEG_IMAGES | route::TWO_KERNEL | route::SEGMENTED_TUPLE | route::SINGLE_PASS_TUPLE);
+    note_route(route::TWO_KERNEL | route::SEGMENTED_TUPLE | route::SINGLE_PASS_TUPLE);
     for (const ji::CoefLaunch &l : t.launches)
         HIP_TRY(pd::launch_jpeg_images_coeffs(l.mode, l.load, d_tiles + l.first_record, l.count, l.tiles, c.d_coef.as<int16_t>(),
                                               qt_all + (o.quality - 1) * pixo_host::kDeviceQtFloats, c.stream));
@@ -232,6 +232,7 @@ int shared_sub_batch(Context &c, const void *d_px, const pixo_png_image *images,
         }
         ends_at += cp.count;
     }
+    note_route(route::JPEG_IMAGES); // (no pass gave up: this sub-batch's files come from the ragged launches)
     // ---- the files, in index order
     ClassHead head[2];
     for (uint32_t i = 0; i < nb; ++i)
@@ -258,6 +259,7 @@ int shared_sub_batch(Context &c, const void *d_px, const pixo_png_image *images,
     }
     const size_t all_bytes = static_cast<size_t>(pass_bytes[0] + pass_bytes[1]);
     if (direct && all_bytes >= (size_t{4} << 20) * std::max<size_t>(1, nb / 64)) { // (large files: each scan by a copy of its own, no second pass over it)
+        note_route(route::JPEG_IMAGES_DIRECT);
         hipError_t e = hipSuccess;
         for (uint32_t i = 0; i < nb && e == hipSuccess; ++i)
             if (scan_len[i])

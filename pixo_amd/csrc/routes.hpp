@@ -58,6 +58,7 @@ enum : uint64_t {
     PNG_IMAGES_FILTER = 1ull << 46, // ... and at least one image's rows went through a ragged filter launch (one per class of images)
     RESIZE_IMAGES = 1ull << 47,    // resize images entries: one flat launch per pass and pixel size over all images of a sub-batch (beside the algorithm's bit)
     JPEG_IMAGES = RESIZE_IMAGES << 1, // (bit 48) JPEG encode of images of individual sizes: at least one sub-batch went through the ragged launches (beside TWO_KERNEL, SEGMENTED_TUPLE)
+    JPEG_IMAGES_DIRECT = JPEG_IMAGES << 1, // (bit 49) ... and a sub-batch's scans travelled file by file straight into pinned destinations (large files: pool blocks or a pinned arena)
 };
 }
 

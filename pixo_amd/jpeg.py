@@ -486,9 +486,11 @@ ROUTES = {
 for _name, _bit in ROUTES.items():
     globals()["ROUTE_" + _name] = 1 << _bit
 del _name, _bit
-# ... and the images entries' bit (encode_images*): at least one sub-batch went through the ragged launches
-IMAGES_ROUTES = {"JPEG_IMAGES": 48}
+# ... and the images entries' bits (encode_images*): at least one sub-batch went through the ragged launches; a sub-batch's
+# scans were copied file by file straight into pinned destinations (large files into pool blocks or a pinned arena)
+IMAGES_ROUTES = {"JPEG_IMAGES": 48, "JPEG_IMAGES_DIRECT": 49}
 ROUTE_JPEG_IMAGES = 1 << IMAGES_ROUTES["JPEG_IMAGES"]
+ROUTE_JPEG_IMAGES_DIRECT = 1 << IMAGES_ROUTES["JPEG_IMAGES_DIRECT"]
 
 
 def debug_routes(clear: bool = True) -> int:

@@ -374,8 +374,9 @@ def test_single_pass_kernels_that_give_up_waiting_fall_back_to_the_multi_pass_ke
     """The look-back kernels bound their waits.  With a budget of zero polls every wait for another
     workgroup fails at once: the kernels raise their abort flag instead of spinning, the host sees it in the pinned mailbox
     and codes the scan again with the multi-pass kernels — same bytes, no hang; the fallback counter shows that it happened.
-    In a fresh process (the switch is read at start-up) over plain files, pieces, batches, restart segments, bands and
-    progressive files."""
+    In a fresh process (the switch is read at start-up) over plain files, pieces, batches, restart segments, bands,
+    progressive files and the images entry (one sub-batch and several, into blocks and into an arena; the default budget
+    afterwards falls back no more)."""
     import subprocess, sys, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys, numpy as np, torch; sys.path.insert(0, 'tests'); import synth, oracle_lib as O; from pixo_amd import jpeg\n"
@@ -405,7 +406,11 @@ def test_single_pass_kernels_that_give_up_waiting_fall_back_to_the_multi_pass_ke
             "    okw = {('trellis' if k == 'trellis_quant' else k): v for k, v in kw.items()}\n"
             "    assert jpeg.encode(px, opts(w, h, ss, progressive=True, **kw)) == O.encode(px, O.make_options(w, h, 2, 80, ss, progressive=True, **okw)), (w, h, kw)\n"
             "n3 = jpeg.lookback_fallbacks(); assert n3 >= n2 + 3, (n2, n3)\n"
-            "print('fallbacks', n3)")
+            # the images entry (jpeg_images_cases.py): segments of 63 to 129 groups give up, the sub-batch goes the single way
+            "import jpeg_images_cases as K\n"
+            "print('images entry', K.give_up_of_the_images_entry())\n"
+            "n4 = jpeg.lookback_fallbacks(); assert n4 >= n3 + 5, (n3, n4)\n"
+            "print('fallbacks', n4)")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, PIXO_HIP_DEBUG="spin_budget=0"),
                        timeout=600, cwd=root)
     assert r.returncode == 0 and "fallbacks" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])

@@ -35,10 +35,12 @@ def test_symbols_are_declared_listed_and_exported():
 def test_route_bit_is_new():
     routes = open(os.path.join(ROOT, "pixo_amd", "csrc", "routes.hpp")).read()
     assert re.search(r"\bRESIZE_IMAGES = 1ull << 47,", routes) and re.search(r"\bJPEG_IMAGES = RESIZE_IMAGES << 1,", routes)  # bit 48
-    assert jpeg.IMAGES_ROUTES == {"JPEG_IMAGES": 48} and jpeg.ROUTE_JPEG_IMAGES == 1 << 48
+    assert re.search(r"\bJPEG_IMAGES_DIRECT = JPEG_IMAGES << 1,", routes)  # bit 49: the direct copies of large files
+    assert jpeg.IMAGES_ROUTES == {"JPEG_IMAGES": 48, "JPEG_IMAGES_DIRECT": 49}
+    assert jpeg.ROUTE_JPEG_IMAGES == 1 << 48 and jpeg.ROUTE_JPEG_IMAGES_DIRECT == 1 << 49
     taken = set(png.ROUTES.values()) | set(png.IMAGES_ROUTES.values()) | set(jpeg.ROUTES.values()) | set(decode.ROUTES.values()) | \
         set(decode.INFLATE_ROUTES.values()) | set(resize.ROUTES.values())
-    assert 48 not in taken
+    assert 48 not in taken and 49 not in taken
 
 
 def images_c(*rows):
