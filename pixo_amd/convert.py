@@ -12,9 +12,8 @@ colour types in one pass, on pixels that stay in HBM.  The contract of every ent
 import ctypes as C
 import enum
 
-import numpy as np
-
 from . import _lib
+from ._images import bpp, check_block, flat_u8, image_bytes, image_records, images_block, pair
 from .color import ColorType
 
 
@@ -29,31 +28,6 @@ KINDS = ("copy", "gray_alpha_to_gray", "rgba_to_rgb", "rgb_to_gray", "rgba_to_gr
 FORMS = ("aligned", "bytes")  # ... and form[i]
 
 
-def _bpp(color_type) -> int:
-    return int(color_type) + 1 if 0 <= int(color_type) <= 3 else 0
-
-
-def _flat(data):
-    return np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data, dtype=np.uint8).reshape(-1)
-
-
-def _records(images):
-    from .png import _image_records
-    return _image_records(images)
-
-
-def _pair(src_images, dst_images):
-    src, n, base = _records(src_images)
-    dst, m, _ = _records(dst_images)
-    if m != n:
-        raise ValueError("%d sources, %d destinations" % (n, m))
-    return src, dst, n, base
-
-
-def _records_end(arr, n) -> int:
-    return max(arr[i].offset + arr[i].width * arr[i].height * _bpp(arr[i].color_type) for i in range(n)) if n else 0
-
-
 def tile_pixels() -> int:
     """Pixels one workgroup of the conversion kernels takes in a step (tests place their sizes by it)."""
     return _lib.load().pixo_hip_debug_convert_tile_pixels()
@@ -64,7 +38,7 @@ def layout_images(images, target):
     out as a decode batch lays its block out — every offset a multiple of 16, `total` the end of the last image.  Sizes
     only: no GPU."""
     L = _lib.load()
-    arr, n, _ = _records(images)
+    arr, n, _ = image_records(images)
     out, total = (_lib.PngImageC * max(n, 1))(), C.c_size_t()
     _lib.check(L.pixo_hip_convert_images_layout(arr, n, int(target), out, C.byref(total)))
     return [(im.width, im.height, ColorType(im.color_type), im.offset) for im in out[:n]], total.value
@@ -76,27 +50,23 @@ def convert_images_device(d_src, src_images, d_dst, dst_images, stream=0) -> Non
     `convert_device` writes for that image; the bytes between destinations are left as they are.  Destinations must not
     overlap each other or a source (not checked).  One launch per conversion present and alignment class, whatever the number
     of images.  Enqueue only, ordered like `resize.resize_images_device`."""
-    from .png import _images_block
     L = _lib.load()
-    src, dst, n, base = _pair(src_images, dst_images)
-    d_src = _images_block(d_src, base)
-    for what, block, arr in (("sources", d_src, src), ("destinations", d_dst, dst)):
-        if hasattr(block, "numel") and n and all(_bpp(arr[i].color_type) for i in range(n)):
-            need, have = _records_end(arr, n), _lib.nbytes(block)
-            if have < need:
-                raise ValueError("the %s end at byte %d, the tensor holds %d" % (what, need, have))
+    src, dst, n, base = pair(src_images, dst_images)
+    d_src = images_block(d_src, base)
+    check_block("sources", d_src, src, n)
+    check_block("destinations", d_dst, dst, n)
     _lib.check(L.pixo_hip_convert_images_device(_lib.ptr(d_src), src, _lib.ptr(d_dst), dst, n, C.c_void_p(stream) if stream else None))
 
 
 def convert_images(block_bytes, src_images, dst_images) -> list:
     """The same for a block in host memory -> a list of bytes, image i in `dst_images[i]`'s colour type."""
     L = _lib.load()
-    src, dst, n, _ = _pair(src_images, dst_images)
-    px = _flat(block_bytes)
+    src, dst, n, _ = pair(src_images, dst_images)
+    px = flat_u8(block_bytes)
     out, out_len = C.POINTER(C.c_uint8)(), C.c_size_t()
     _lib.check(L.pixo_hip_convert_images(px.ctypes.data, px.size, src, dst, n, C.byref(out), C.byref(out_len)))
     block = _lib.take(L, out, out_len)
-    return [block[im.offset:im.offset + im.width * im.height * _bpp(im.color_type)] for im in dst[:n]]
+    return [block[im.offset:im.offset + image_bytes(im)] for im in dst[:n]]
 
 
 def convert_images_plan(src_images, dst_images, src_align=0, dst_align=0) -> dict:
@@ -105,7 +75,7 @@ def convert_images_plan(src_images, dst_images, src_align=0, dst_align=0) -> dic
     `kind` (an index into KINDS), `form` (into FORMS) and `tiles` (its workgroups), and `launches` (summed over the
     sub-batches)."""
     L = _lib.load()
-    src, dst, n, _ = _pair(src_images, dst_images)
+    src, dst, n, _ = pair(src_images, dst_images)
     sub_first, subs, launches = (C.c_uint32 * (n + 1))(), C.c_uint32(), C.c_uint32()
     kind, form, tiles = (C.c_uint8 * max(n, 1))(), (C.c_uint8 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
     _lib.check(L.pixo_hip_debug_convert_images_plan(src, dst, n, src_align, dst_align, sub_first, C.byref(subs), kind, form, tiles, C.byref(launches)))
@@ -117,8 +87,8 @@ def convert_device(d_src, width, height, src_color_type, dst_color_type, d_dst, 
     any alignment).  Enqueue only, ordered like `resize.resize_device`."""
     L = _lib.load()
     for what, block, ct in (("source", d_src, src_color_type), ("destination", d_dst, dst_color_type)):
-        if hasattr(block, "numel") and _bpp(ct):
-            need, have = width * height * _bpp(ct), _lib.nbytes(block)
+        if hasattr(block, "numel") and bpp(ct):
+            need, have = width * height * bpp(ct), _lib.nbytes(block)
             if have < need:
                 raise ValueError("the %s needs %d bytes, the tensor holds %d" % (what, need, have))
     _lib.check(L.pixo_hip_convert_device(_lib.ptr(d_src), width, height, int(src_color_type), int(dst_color_type), _lib.ptr(d_dst),
@@ -128,7 +98,7 @@ def convert_device(d_src, width, height, src_color_type, dst_color_type, d_dst, 
 def convert(data, width, height, src_color_type, dst_color_type) -> bytes:
     """Host pixels -> the converted pixels (bytes)."""
     L = _lib.load()
-    px = _flat(data)
+    px = flat_u8(data)
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     _lib.check(L.pixo_hip_convert(px.ctypes.data, px.size, width, height, int(src_color_type), int(dst_color_type), C.byref(out), C.byref(n)))
     return _lib.take(L, out, n)
@@ -136,20 +106,20 @@ def convert(data, width, height, src_color_type, dst_color_type) -> bytes:
 
 # ---- the reference front end's three functions (src/bin/pixo.rs:478-513): flat pixel data of any length ----------------------
 def _run(data, src_ct, dst_ct) -> bytes:
-    px = _flat(data)
-    bpp = _bpp(src_ct)
-    if px.size % bpp:
-        raise ValueError("%d bytes are no whole number of %d-byte pixels" % (px.size, bpp))
-    pixels = px.size // bpp
+    px = flat_u8(data)
+    size = bpp(src_ct)
+    if px.size % size:
+        raise ValueError("%d bytes are no whole number of %d-byte pixels" % (px.size, size))
+    pixels = px.size // size
     if pixels == 0:
         return b""
     # (a run of pixels is an image of one row, or of rows of 2^24 with the last pixels in a call of their own)
     side, out = 1 << 24, []
     whole = pixels // side
     if whole:
-        out.append(convert(px[:whole * side * bpp], side, whole, src_ct, dst_ct))
+        out.append(convert(px[:whole * side * size], side, whole, src_ct, dst_ct))
     if pixels % side:
-        out.append(convert(px[whole * side * bpp:], pixels % side, 1, src_ct, dst_ct))
+        out.append(convert(px[whole * side * size:], pixels % side, 1, src_ct, dst_ct))
     return b"".join(out)
 
 

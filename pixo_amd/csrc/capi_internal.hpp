@@ -23,6 +23,8 @@
 //   jpeg_decode_host.cpp  JPEG decode on the host (no HIP): the marker walk and its checks, the entropy decoder into the kernel's layout
 //   jpeg_decode_api.cpp  the extern "C" JPEG decode entry points: two-phase checks, the entropy decodes on the decode pool, plan,
 //                    sub-batches, the launches of jpeg_decode.hip
+//   batch_steps.hpp  (a header of the host files only) the steps the batch drivers above share: per-record checks, layout, the
+//                    sub-batch cut, the caller's stream, the job fence, the host entries' tail
 #pragma once
 #include <hip/hip_runtime.h>
 

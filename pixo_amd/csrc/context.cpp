@@ -2,7 +2,7 @@
 // device and pinned host buffers), the pool in which contexts outlive their threads, device selection, debug switches.
 #include <algorithm>
 
-#include "capi_internal.hpp"
+#include "batch_steps.hpp"
 #include "jpeg_kernels.hpp"
 #include "jpeg_trellis.hpp"
 
@@ -321,6 +321,38 @@ int context_on_current_device(Context **out)
     if (rc) return rc;
     if ((rc = order_after_producer(c))) return rc;
     *out = &c;
+    return PIXO_OK;
+}
+
+// ---- the batch drivers' shared steps (batch_steps.hpp) -----------------------------------------------------------------
+int caller_stream_context(void *stream, Context **c, hipStream_t *s)
+{
+    if (const int rc = context_on_current_device(c)) return rc; // (records the producer stream's event)
+    *s = static_cast<hipStream_t>(stream);
+    if ((*c)->producer_done) HIP_TRY(hipStreamWaitEvent(*s, (*c)->producer_done, 0));
+    return PIXO_OK;
+}
+
+int await_last_job(hipEvent_t &fence)
+{
+    if (!fence) HIP_TRY(hipEventCreateWithFlags(&fence, hipEventDisableTiming));
+    // The job before this one on the context may still be reading the tables and records, and its pinned staging may still be on
+    // its way up: this job is about to overwrite both.  It is the call's only host wait — everything behind it is enqueued — and it
+    // waits for the job before, not for the stream: what the caller enqueued since is not waited for.
+    HIP_TRY(hipEventSynchronize(fence));
+    return PIXO_OK;
+}
+
+int bad_color_type(uint8_t ct, const std::string &where)
+{
+    return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid color type: " + std::to_string(ct) + ". Expected 0 (Gray), 1 (GrayAlpha), 2 (Rgb), or 3 (Rgba)" + where);
+}
+
+int record_extent(uint64_t offset, uint64_t bytes, const char *what, const std::string &where, uint64_t *furthest)
+{
+    const uint64_t most = uint64_t{1} << 62;
+    if (offset > most || offset + bytes > most) return fail(PIXO_ERR_COMPRESSION, std::string("Compression error: batch ") + what + " too large" + where);
+    *furthest = std::max(*furthest, offset + bytes);
     return PIXO_OK;
 }
 

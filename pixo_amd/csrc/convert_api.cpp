@@ -2,7 +2,8 @@
 // an encode (src/bin/pixo.rs:478-513, 619-638), on pixels that stay in HBM.  The layout a target gives a batch, the checks in
 // the order include/pixo_hip.h documents, the plan (kind, form and tiles per image, sub-batches whose launches stay within
 // their tiles), the records of the flat launches (convert_math.h), one launch per class of images present (convert.hip).
-#include "capi_internal.hpp"
+// The steps every batch driver takes, and their order: DESIGN.md §4.0; the shared ones: batch_steps.hpp.
+#include "batch_steps.hpp"
 #include "convert.hpp"
 
 #include <algorithm>
@@ -14,10 +15,6 @@ namespace cv = pixo_convert;
 
 namespace {
 
-int bad_color_type(uint8_t ct, const std::string &where)
-{
-    return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid color type: " + std::to_string(ct) + ". Expected 0 (Gray), 1 (GrayAlpha), 2 (Rgb), or 3 (Rgba)" + where);
-}
 // A zero side, a side above 2^24 (the resize entries' limit, which bounds an image at 2^50 bytes)
 int check_sides(uint32_t w, uint32_t h, const std::string &where)
 {
@@ -36,30 +33,25 @@ int convert_images_checks(const pixo_png_image *src_images, const pixo_png_image
     PIXO_REQUIRE(dst_images);
     int rc = batch_in_range(batch);
     if (rc) return rc;
-    const uint64_t most = uint64_t{1} << 62; // (an image is at most 2^50 bytes)
     *src_end = *dst_end = 0;
     for (uint32_t i = 0; i < batch; ++i) {
-        const std::string where = " (image " + std::to_string(i) + ")";
+        const std::string here = where(i);
         const pixo_png_image &a = src_images[i], &b = dst_images[i];
-        if ((rc = check_sides(a.width, a.height, where)) || (rc = check_sides(b.width, b.height, where))) return rc;
-        if (a.color_type > PIXO_RGBA) return bad_color_type(a.color_type, where);
-        if (b.color_type > PIXO_RGBA) return bad_color_type(b.color_type, where);
-        if (a.width != b.width || a.height != b.height) return fail(PIXO_ERR_COMPRESSION, "Compression error: sizes differ" + where);
+        if ((rc = check_sides(a.width, a.height, here)) || (rc = check_sides(b.width, b.height, here))) return rc;
+        if (a.color_type > PIXO_RGBA) return bad_color_type(a.color_type, here);
+        if (b.color_type > PIXO_RGBA) return bad_color_type(b.color_type, here);
+        if (a.width != b.width || a.height != b.height) return fail(PIXO_ERR_COMPRESSION, "Compression error: sizes differ" + here);
         if (cv::kind_of(a.color_type, b.color_type) == cv::K_NONE)
-            return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format" + where);
-        const uint64_t pixels = static_cast<uint64_t>(a.width) * a.height;
-        const uint64_t in_bytes = pixels * bytes_per_pixel(a.color_type), out_bytes = pixels * bytes_per_pixel(b.color_type);
-        if (a.offset > most || a.offset + in_bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch input too large" + where);
-        if (b.offset > most || b.offset + out_bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large" + where);
-        *src_end = std::max(*src_end, a.offset + in_bytes);
-        *dst_end = std::max(*dst_end, b.offset + out_bytes);
+            return fail(PIXO_ERR_UNSUPPORTED_COLOR_TYPE, "Unsupported color type for this format" + here);
+        if ((rc = record_extent(a.offset, image_bytes(a), "input", here, src_end)) || (rc = record_extent(b.offset, image_bytes(b), "output", here, dst_end)))
+            return rc;
     }
     return PIXO_OK;
 }
 
 // What the driver decided for the images, before anything touches a device (also: pixo_hip_debug_convert_images_plan).
 struct ImagesPlan {
-    std::vector<uint32_t> sub_first; // sub-batch k is images [sub_first[k], sub_first[k + 1])
+    SubBatches sub_first;
     std::vector<uint8_t> kind, form; // per image
     std::vector<uint32_t> tiles;     // per image: its workgroups
     uint32_t launches = 0;           // summed over the sub-batches: one per class present in each
@@ -69,7 +61,6 @@ void convert_images_plan(const pixo_png_image *src, const pixo_png_image *dst, u
 {
     const uint32_t cap = image_tiles_cap();
     const uint64_t limit = launch_tiles_cap();
-    p.sub_first.assign(1, 0u);
     p.kind.assign(batch, 0);
     p.form.assign(batch, 0);
     p.tiles.assign(batch, 0);
@@ -77,18 +68,15 @@ void convert_images_plan(const pixo_png_image *src, const pixo_png_image *dst, u
     for (uint32_t i = 0; i < batch; ++i) {
         const int kind = cv::kind_of(src[i].color_type, dst[i].color_type), form = cv::form_of(src_base + src[i].offset, dst_base + dst[i].offset);
         const uint32_t c = cv::class_of(kind, form), t = cv::tiles_of(static_cast<uint64_t>(src[i].width) * src[i].height, cap);
-        // every sub-batch holds at least one image; one image's tiles stay within a launch (tiles_of)
-        if (i > p.sub_first.back() && held[c] + t > limit) {
-            p.sub_first.push_back(i);
-            std::fill(held, held + cv::kClasses, uint64_t{0});
-        }
+        // (one image's tiles stay within a launch: tiles_of)
+        if (p.sub_first.starts_at(i, held[c] + t > limit)) std::fill(held, held + cv::kClasses, uint64_t{0});
         if (held[c] == 0) p.launches += 1;
         held[c] += t;
         p.kind[i] = static_cast<uint8_t>(kind);
         p.form[i] = static_cast<uint8_t>(form);
         p.tiles[i] = t;
     }
-    p.sub_first.push_back(batch);
+    p.sub_first.close(batch);
 }
 
 // Enqueues the images on `s`: d_src + src[i].offset -> d_dst + dst[i].offset.  The records of all sub-batches are built in the
@@ -98,13 +86,10 @@ int convert_images_on_device(Context &c, const uint8_t *d_src, const pixo_png_im
 {
     ImagesPlan p;
     convert_images_plan(src, dst, batch, reinterpret_cast<uint64_t>(d_src), reinterpret_cast<uint64_t>(d_dst), p);
-    if (!c.cv_done) HIP_TRY(hipEventCreateWithFlags(&c.cv_done, hipEventDisableTiming));
-    // the job before may still be reading the records, and the staging may still be on its way: both are about to change.
-    // The call's only host wait.
-    HIP_TRY(hipEventSynchronize(c.cv_done));
+    int rc = await_last_job(c.cv_done); // (it reads cv_records, which go up from h_cv_records)
+    if (rc) return rc;
     // everything is reserved before any address is handed out (a growing reserve frees first)
     const size_t up_bytes = static_cast<size_t>(batch) * sizeof(cv::Record);
-    int rc;
     if ((rc = c.h_cv_records.reserve(up_bytes)) || (rc = c.cv_records.reserve(up_bytes))) return rc;
     cv::Record *stage = c.h_cv_records.as<cv::Record>();
     const cv::Record *d_records = c.cv_records.as<cv::Record>();
@@ -149,20 +134,6 @@ int convert_on_device(const uint8_t *d_src, uint32_t width, uint32_t height, uin
                                      cv::tiles_of(pixels, image_tiles_cap()), s));
     return PIXO_OK;
 }
-// The tail of the host entries: the block comes down, the stream is waited for, the caller owns the block
-int download_block(Context &c, int rc, uint8_t *block, size_t n, uint8_t **out, size_t *out_len)
-{
-    if (!rc) {
-        const hipError_t e = hipMemcpyAsync(block, c.cv_out.p, n, hipMemcpyDeviceToHost, c.stream);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
-    }
-    const hipError_t e = hipStreamSynchronize(c.stream); // (also after a failure: the upload reads the caller's pixels)
-    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-    if (rc) { free_file(block); return rc; }
-    *out = block;
-    *out_len = n;
-    return PIXO_OK;
-}
 
 } // namespace
 
@@ -177,25 +148,18 @@ int pixo_hip_convert_images_layout(const pixo_png_image *src_images, uint32_t ba
     if (rc) return rc;
     if (cv::target_type(target, 0) < 0) return fail(PIXO_ERR_COMPRESSION, "Compression error: unknown convert target " + std::to_string(target));
     for (uint32_t i = 0; i < batch; ++i) { // nothing is written before every image has passed
-        const std::string where = " (image " + std::to_string(i) + ")";
         const pixo_png_image &a = src_images[i];
-        if ((rc = check_sides(a.width, a.height, where))) return rc;
-        if (a.color_type > PIXO_RGBA) return bad_color_type(a.color_type, where);
+        if ((rc = check_sides(a.width, a.height, where(i)))) return rc;
+        if (a.color_type > PIXO_RGBA) return bad_color_type(a.color_type, where(i));
     }
     uint64_t at = 0, end = 0;
     std::vector<pixo_png_image> laid(batch); // (dst_images may be src_images)
     for (uint32_t i = 0; i < batch; ++i) {
-        const pixo_png_image &a = src_images[i];
-        pixo_png_image b{};
-        b.width = a.width; b.height = a.height;
-        b.color_type = static_cast<uint8_t>(cv::target_type(target, a.color_type));
-        b.offset = at;
-        end = at + static_cast<uint64_t>(b.width) * b.height * bytes_per_pixel(b.color_type); // (at <= 2^62 + 15, an image at most 2^50 bytes)
+        const pixo_png_image &a = src_images[i]; // (at <= 2^62 + 15, an image at most 2^50 bytes: no wrap)
+        laid[i] = lay_out(at, a.width, a.height, static_cast<uint8_t>(cv::target_type(target, a.color_type)), &end);
         if (end > (uint64_t{1} << 62)) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large");
-        at = (end + 15) & ~uint64_t{15};
-        laid[i] = b;
     }
-    std::copy(laid.begin(), laid.end(), dst_images);
+    report(laid, dst_images);
     *total = static_cast<size_t>(end);
     return PIXO_OK;
 }
@@ -208,10 +172,7 @@ int pixo_hip_convert_images_device(const void *d_src, const pixo_png_image *src_
     if (rc) return rc;
     PIXO_REQUIRE(d_src);
     PIXO_REQUIRE(d_dst);
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return convert_images_on_device(*c, static_cast<const uint8_t *>(d_src), src_images, static_cast<uint8_t *>(d_dst), dst_images, batch, s);
 }
 
@@ -230,7 +191,7 @@ int pixo_hip_convert_images(const uint8_t *data, size_t data_len, const pixo_png
     uint8_t *block = alloc_file(static_cast<size_t>(dst_end));
     if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
     rc = convert_images_on_device(c, c.cv_in.as<uint8_t>(), src_images, c.cv_out.as<uint8_t>(), dst_images, batch, c.stream);
-    return download_block(c, rc, block, static_cast<size_t>(dst_end), out, out_len);
+    return download_block(c, rc, block, c.cv_out.p, static_cast<size_t>(dst_end), out, out_len);
 }
 
 int pixo_hip_convert_device(const void *d_src, uint32_t width, uint32_t height, uint8_t src_color_type, uint8_t dst_color_type, void *d_dst, void *stream)
@@ -240,10 +201,7 @@ int pixo_hip_convert_device(const void *d_src, uint32_t width, uint32_t height, 
     if (rc) return rc;
     PIXO_REQUIRE(d_src);
     PIXO_REQUIRE(d_dst);
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return convert_on_device(static_cast<const uint8_t *>(d_src), width, height, src_color_type, kind, static_cast<uint8_t *>(d_dst), s);
 }
 
@@ -264,7 +222,7 @@ int pixo_hip_convert(const uint8_t *data, size_t data_len, uint32_t width, uint3
     uint8_t *block = alloc_file(out_bytes);
     if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
     rc = convert_on_device(c.cv_in.as<uint8_t>(), width, height, src_color_type, kind, c.cv_out.as<uint8_t>(), c.stream);
-    return download_block(c, rc, block, out_bytes, out, out_len);
+    return download_block(c, rc, block, c.cv_out.p, out_bytes, out, out_len);
 }
 
 int pixo_hip_debug_convert_images_plan(const pixo_png_image *src_images, const pixo_png_image *dst_images, uint32_t batch, uint32_t src_align,
@@ -282,8 +240,7 @@ int pixo_hip_debug_convert_images_plan(const pixo_png_image *src_images, const p
     PIXO_REQUIRE(launches);
     ImagesPlan p;
     convert_images_plan(src_images, dst_images, batch, src_align & 15u, dst_align & 15u, p);
-    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
-    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    p.sub_first.report(sub_first, sub_count);
     std::copy(p.kind.begin(), p.kind.end(), kind);
     std::copy(p.form.begin(), p.form.end(), form);
     std::copy(p.tiles.begin(), p.tiles.end(), tiles);

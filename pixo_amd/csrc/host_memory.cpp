@@ -5,7 +5,7 @@
 
 #include <algorithm>
 
-#include "capi_internal.hpp"
+#include "batch_steps.hpp"
 
 namespace pixo_capi {
 
@@ -181,6 +181,36 @@ int hand_over(const std::vector<uint8_t> &v, uint8_t **out, size_t *out_len)
     big_copy(p, v.data(), v.size());
     *out = p;
     *out_len = v.size();
+    return PIXO_OK;
+}
+
+// ---- the host entries' tail (batch_steps.hpp says which entries take which, and why) ------------------------------------------
+int download_block(Context &c, int rc, uint8_t *block, const void *d_from, size_t n, uint8_t **out, size_t *out_len)
+{
+    if (!rc) {
+        const hipError_t e = hipMemcpyAsync(block, d_from, n, hipMemcpyDeviceToHost, c.stream);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    }
+    const hipError_t e = hipStreamSynchronize(c.stream); // (also after a failure: the uploads read the caller's pixels)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (rc) { free_file(block); return rc; }
+    *out = block;
+    *out_len = n;
+    return PIXO_OK;
+}
+
+int download_pooled(Context &c, const void *d_from, size_t n, const char *what, uint8_t **out, size_t *out_len, hipEvent_t *around)
+{
+    uint8_t *block = pool_take(std::max<size_t>(n, 1));
+    if (!block) block = alloc_file(std::max<size_t>(n, 1));
+    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
+    hipError_t e = around ? hipEventRecord(around[0], c.stream) : hipSuccess;
+    if (e == hipSuccess && n) e = hipMemcpyAsync(block, d_from, n, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess && around) e = hipEventRecord(around[1], c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) { free_file(block); return hip_fail(e, what); }
+    *out = block;
+    *out_len = n;
     return PIXO_OK;
 }
 

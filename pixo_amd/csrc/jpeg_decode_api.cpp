@@ -14,7 +14,8 @@
 // entropy decodes on up to 8 host threads (PIXO_DECODE_ONE_THREAD: on the caller): a scan that breaks off, a code no table
 // holds, a coefficient index past 63, a missing or out-of-sequence RSTn.  The failing file with the lowest index answers.
 // A width or height of zero is no special case: such an image has no MCUs, no tiles and no bytes.
-#include "capi_internal.hpp"
+// The steps every batch driver takes, and their order: DESIGN.md §4.0; the shared ones: batch_steps.hpp.
+#include "batch_steps.hpp"
 #include "jpeg_decode.hpp"
 #include "jpeg_decode_host.hpp"
 
@@ -30,11 +31,6 @@ namespace {
 constexpr uint64_t kDecodeBatchBytes = uint64_t{512} << 20; // coefficients one sub-batch holds at most (debug switch decode_batch_bytes)
 constexpr uint32_t kDecodeBatchThreads = 8;                 // host threads that decode a batch's scans, the caller among them, at most
 
-inline uint64_t round16(uint64_t n) { return (n + 15) & ~uint64_t{15}; }
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 int status_of(jh::Kind k, const std::string &msg, const std::string &where)
 {
     if (k == jh::OK) return PIXO_OK;
@@ -49,7 +45,7 @@ struct DecodeBatch {
     uint32_t threads = 1;
     bool single = false; // a single entry: refusals carry no " (image 0)"
     double entropy_ms = 0;
-    std::string where(uint32_t i) const { return single ? std::string() : " (image " + std::to_string(i) + ")"; }
+    std::string where(uint32_t i) const { return single ? std::string() : pixo_capi::where(i); }
 };
 
 // Phase 1 behind `files` and `batch`: per file its `data`, then the walk; the block's layout.  No HIP, no entropy decode.
@@ -69,12 +65,7 @@ int batch_walk(const pixo_png_file *files, uint32_t batch, DecodeBatch &b)
         const jh::File &f = b.files[i];
         b.coef_at[i] = b.staging;
         b.staging += f.coef_bytes();
-        const uint64_t end = at + f.pixel_bytes();
-        pixo_png_image &im = b.images[i];
-        std::memset(&im, 0, sizeof im);
-        im.offset = at; im.width = f.width; im.height = f.height; im.color_type = f.color_type();
-        b.total = end;
-        at = round16(end);
+        b.images[i] = lay_out(at, f.width, f.height, f.color_type(), &b.total);
     }
     return PIXO_OK;
 }
@@ -101,7 +92,7 @@ int batch_entropy(DecodeBatch &b, uint8_t *stage, uint32_t flags)
 
 // What the driver decided, before anything touches a device (also: pixo_hip_debug_jpeg_decode_batch_plan)
 struct DecodePlan {
-    std::vector<uint32_t> sub_first; // sub-batch k is images [sub_first[k], sub_first[k + 1])
+    SubBatches sub_first;
     struct Launch { uint32_t sub, cls, form, first_record, count, tiles; };
     std::vector<Launch> launches;      // in stream order
     std::vector<jd::Record> records;   // launch after launch
@@ -113,18 +104,14 @@ int decode_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodePlan &p)
 {
     const uint32_t batch = static_cast<uint32_t>(b.files.size());
     const uint64_t limit = debug().decode_batch_bytes ? debug().decode_batch_bytes : kDecodeBatchBytes;
-    p.sub_first.assign(1, 0);
     uint64_t held = 0;
     for (uint32_t i = 0; i < batch; ++i) {
         const uint64_t need = b.files[i].coef_bytes();
-        if (i > p.sub_first.back() && held + need > limit) { // every sub-batch holds at least one image
-            p.sub_first.push_back(i);
-            held = 0;
-        }
+        if (p.sub_first.starts_at(i, held + need > limit)) held = 0;
         held += need;
         p.coef_bytes = std::max(p.coef_bytes, held);
     }
-    p.sub_first.push_back(batch);
+    p.sub_first.close(batch);
     for (uint32_t k = 0; k + 1 < p.sub_first.size(); ++k) {
         const uint32_t first = p.sub_first[k], end = p.sub_first[k + 1];
         for (uint32_t cls = 0; cls < jd::kClasses; ++cls)
@@ -158,28 +145,14 @@ int decode_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodePlan &p)
     return PIXO_OK;
 }
 
-struct BatchLegs { // timed: events around the device legs of every sub-batch
-    std::vector<hipEvent_t> e;
-    ~BatchLegs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    int mark(hipStream_t s)
-    {
-        hipEvent_t x = nullptr;
-        HIP_TRY(hipEventCreate(&x));
-        e.push_back(x);
-        HIP_TRY(hipEventRecord(x, s));
-        return PIXO_OK;
-    }
-};
-
 // Everything behind phase 1: waits for this thread's previous JPEG decode job (the call's one host wait), decodes the scans into
 // the pinned staging, then enqueues on `s`: all records in one copy; per sub-batch its coefficients in one copy and one launch
 // per class and form present.  Nothing is enqueued after a refusal.
 int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs = nullptr)
 {
     const uint32_t batch = static_cast<uint32_t>(b.files.size());
-    if (!c.jd_done) HIP_TRY(hipEventCreateWithFlags(&c.jd_done, hipEventDisableTiming));
-    HIP_TRY(hipEventSynchronize(c.jd_done)); // the job before may still be reading the pinned buffers this one is about to write
-    int rc;
+    int rc = await_last_job(c.jd_done); // (it reads jd_records and jd_coef, which go up from the pinned jd_hrecords and jd_hcoef)
+    if (rc) return rc;
     if ((rc = c.jd_hcoef.reserve(std::max<uint64_t>(b.staging, 16)))) return rc;
     if ((rc = batch_entropy(b, c.jd_hcoef.as<uint8_t>(), flags))) return rc;
     DecodePlan p;
@@ -210,37 +183,28 @@ int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *
     return PIXO_OK;
 }
 
-// The batch entries' first two checks
-int batch_head(const pixo_png_file *files, uint32_t batch)
-{
-    PIXO_REQUIRE(files);
-    return batch_in_range(batch);
-}
-void report(const DecodeBatch &b, pixo_png_image *images) { std::copy(b.images.begin(), b.images.end(), images); }
-
 // Host files -> one block of the pinned pool the caller owns.  legs_ms: [0] entropy decode, [1] uploads, [2] kernels, [3] the copy down
 int decode_batch_to_block(DecodeBatch &b, const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len, pixo_png_image *images,
                           double *legs_ms)
 {
     int rc = batch_walk(files, batch, b);
     if (rc) return rc;
-    if (images) report(b, images);
+    if (images) report(b.images, images);
     PIXO_THREAD_CONTEXT(c);
     const size_t n = static_cast<size_t>(b.total);
     if ((rc = reserve16(c.jd_out, std::max<size_t>(n, 16)))) return rc;
     BatchLegs legs;
     if ((rc = decode_batch_on_device(c, b, flags, c.jd_out.as<uint8_t>(), c.stream, legs_ms ? &legs : nullptr))) return rc;
-    uint8_t *block = pool_take(std::max<size_t>(n, 1));
-    if (!block) block = alloc_file(std::max<size_t>(n, 1));
-    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
     hipError_t e = hipSuccess;
-    hipEvent_t down[2] = {nullptr, nullptr};
-    if (legs_ms) for (hipEvent_t &x : down) if (e == hipSuccess) e = hipEventCreate(&x);
-    if (legs_ms && e == hipSuccess) e = hipEventRecord(down[0], c.stream);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(block, c.jd_out.p, n, hipMemcpyDeviceToHost, c.stream);
-    if (legs_ms && e == hipSuccess) e = hipEventRecord(down[1], c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    if (legs_ms && e == hipSuccess) {
+    struct Down { // timed: events around the copy down
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Down() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } down;
+    if (legs_ms) for (hipEvent_t &x : down.e) if ((e = hipEventCreate(&x)) != hipSuccess) return hip_fail(e, "jpeg decode");
+    uint8_t *block = nullptr;
+    size_t got = 0;
+    if ((rc = download_pooled(c, c.jd_out.p, n, "jpeg decode", &block, &got, legs_ms ? down.e : nullptr))) return rc;
+    if (legs_ms) {
         legs_ms[0] = b.entropy_ms;
         legs_ms[1] = legs_ms[2] = legs_ms[3] = 0;
         float ms = 0;
@@ -249,13 +213,12 @@ int decode_batch_to_block(DecodeBatch &b, const pixo_png_file *files, uint32_t b
                 e = hipEventElapsedTime(&ms, legs.e[k + i], legs.e[k + i + 1]);
                 legs_ms[1 + i] += ms;
             }
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, down[0], down[1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, down.e[0], down.e[1]);
         legs_ms[3] = ms;
+        if (e != hipSuccess) { free_file(block); return hip_fail(e, "jpeg decode"); }
     }
-    for (hipEvent_t x : down) if (x) (void)hipEventDestroy(x);
-    if (e != hipSuccess) { free_file(block); return hip_fail(e, "jpeg decode"); }
     *out = block;
-    *out_len = n;
+    *out_len = got;
     return PIXO_OK;
 }
 
@@ -263,13 +226,10 @@ int batch_to_device(DecodeBatch &b, const pixo_png_file *files, uint32_t batch, 
 {
     int rc = batch_walk(files, batch, b);
     if (rc) return rc;
-    report(b, images);
+    report(b.images, images);
     if (capacity < b.total) return too_small(static_cast<size_t>(b.total));
     if (b.total) PIXO_REQUIRE(d_pixels);
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return decode_batch_on_device(*c, b, flags, static_cast<uint8_t *>(d_pixels), s);
 }
 
@@ -285,7 +245,7 @@ int pixo_hip_jpeg_decode_batch_info(const pixo_png_file *files, uint32_t batch, 
     PIXO_REQUIRE(total);
     DecodeBatch b;
     if ((rc = batch_walk(files, batch, b))) return rc;
-    report(b, images);
+    report(b.images, images);
     *total = static_cast<size_t>(b.total);
     return PIXO_OK;
 }
@@ -326,8 +286,7 @@ int pixo_hip_debug_jpeg_decode_batch_plan(const pixo_png_file *files, uint32_t b
     if ((rc = batch_walk(files, batch, b))) return rc;
     DecodePlan p;
     if ((rc = decode_plan(b, 0, p))) return rc;
-    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
-    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    p.sub_first.report(sub_first, sub_count);
     for (uint32_t i = 0; i < batch; ++i) classes[i] = static_cast<uint8_t>(b.files[i].cls);
     *launches = static_cast<uint32_t>(p.launches.size());
     *threads = (flags & PIXO_DECODE_ONE_THREAD) ? 1u : std::min(batch, kDecodeBatchThreads);

@@ -17,9 +17,10 @@
 // the files are laid out in index order only then.  Headers differ per image (SOF0 holds the size), so every file is framed
 // on the host; scans travel file by file straight into pinned destinations when they are large, and in one copy per pass
 // through the context's pinned buffer when they are small (1024 thumbnails: two copies instead of 1024).
+// The steps every batch driver takes, and their order: DESIGN.md §4.0; the shared ones: batch_steps.hpp.
 #include <algorithm>
 
-#include "capi_internal.hpp"
+#include "batch_steps.hpp"
 
 using namespace pixo_capi;
 namespace ji = pixo_jpeg_images;
@@ -34,7 +35,7 @@ struct ImagesPlan {
         bool shared = false; // the shared way in: ragged launches; otherwise encode_file by itself
     };
     std::vector<Image> image;
-    std::vector<uint32_t> sub_first; // sub-batch k: images sub_first[k] .. sub_first[k + 1]
+    SubBatches sub_first;
 };
 
 bool shared_way(const pixo_jpeg_options &o, const pixo_host::Geometry &g)
@@ -46,7 +47,6 @@ void plan_images(const pixo_png_image *images, uint32_t batch, const pixo_jpeg_o
 {
     const uint64_t limit = debug().jpeg_images_blocks ? debug().jpeg_images_blocks : ji::kSubBatchBlocks;
     p.image.resize(batch);
-    p.sub_first.assign(1, 0);
     uint64_t blocks = 0;
     for (uint32_t i = 0; i < batch; ++i) {
         ImagesPlan::Image &x = p.image[i];
@@ -57,13 +57,10 @@ void plan_images(const pixo_png_image *images, uint32_t batch, const pixo_jpeg_o
         x.g = geometry_of(x.o);
         x.shared = shared_way(x.o, x.g);
         const uint64_t b = x.g.y_blocks + 2 * x.g.c_blocks;
-        if (i > p.sub_first.back() && (blocks + b > limit || x.shared != p.image[i - 1].shared)) {
-            p.sub_first.push_back(i);
-            blocks = 0;
-        }
+        if (p.sub_first.starts_at(i, blocks + b > limit || (i && x.shared != p.image[i - 1].shared))) blocks = 0; // (also where the way in changes)
         blocks += b;
     }
-    p.sub_first.push_back(batch);
+    p.sub_first.close(batch);
 }
 int rgb_mode(const pixo_jpeg_options &o) { return o.subsampling == PIXO_S420 ? ji::MODE_420 : ji::MODE_444; }
 // The items of a shared sub-batch, in index order; base: the address of the block's first byte
@@ -313,7 +310,7 @@ int jpeg_images(Context &c, const void *d_px, const pixo_png_image *images, cons
 {
     ImagesPlan p;
     plan_images(images, batch, o, p);
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size()) - 1;
+    const uint32_t subs = p.sub_first.count();
     if (subs > 1) note_route(route::SUB_BATCHES);
     for (uint32_t part = 0; part < subs; ++part) {
         const uint32_t first = p.sub_first[part], end = p.sub_first[part + 1];
@@ -376,19 +373,16 @@ int images_checks(const pixo_jpeg_options *options, const void *pixels, const ch
 }
 int images_check_each(const pixo_jpeg_options &o, const pixo_png_image *images, uint32_t batch, uint64_t *block_end)
 {
-    uint64_t furthest = 0;
+    *block_end = 0;
     for (uint32_t i = 0; i < batch; ++i) {
-        const std::string where = " (image " + std::to_string(i) + ")";
         const pixo_png_image &im = images[i];
         pixo_jpeg_options x = o;
         x.width = im.width; x.height = im.height; x.color_type = im.color_type;
         std::string msg;
-        if (const int rc = pixo_host::validate(x, false, 0, msg)) return fail(rc, msg + where);
-        const uint64_t bytes = static_cast<uint64_t>(im.width) * im.height * bytes_per_pixel(im.color_type), most = uint64_t{1} << 62;
-        if (im.offset > most || im.offset + bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch input too large" + where);
-        furthest = std::max(furthest, im.offset + bytes);
+        int rc = pixo_host::validate(x, false, 0, msg);
+        if (rc) return fail(rc, msg + where(i));
+        if ((rc = record_extent(im.offset, image_bytes(im), "input", where(i), block_end))) return rc;
     }
-    *block_end = furthest;
     return PIXO_OK;
 }
 
@@ -458,9 +452,8 @@ int pixo_hip_debug_jpeg_encode_images_plan(const pixo_png_image *images, uint32_
     if ((rc = images_check_each(*options, images, batch, &end))) return rc;
     ImagesPlan p;
     plan_images(images, batch, *options, p);
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size()) - 1;
-    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
-    *sub_count = subs;
+    const uint32_t subs = p.sub_first.count();
+    p.sub_first.report(sub_first, sub_count);
     *coef_launches = *entropy_passes = 0;
     for (uint32_t i = 0; i < batch; ++i) {
         way_in[i] = p.image[i].shared ? 1 : 0;

@@ -12,7 +12,8 @@
 // row in row order with a filter byte above 4, a palette image without PLTE.  All of it is known on the host before a kernel starts
 // — except under PIXO_DECODE_DEVICE_INFLATE, where what follows the zlib header checks is known only behind the inflate launch of
 // the file's sub-batch: d_pixels is unspecified after such a refusal (status, message and index are the same).
-#include "capi_internal.hpp"
+// The steps every batch driver takes, and their order: DESIGN.md §4.0; the shared ones: batch_steps.hpp.
+#include "batch_steps.hpp"
 #include "png_deflate_math.h"
 #include "png_inflate.hpp"
 #include "png_inflate_dev.hpp"
@@ -211,10 +212,6 @@ struct Legs { // timed: events around the three device legs
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     ~Legs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
 };
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 
 // Everything behind the walk: inflate into the context's pinned buffer, the checks that need the stream, upload, the two kernels
 // on `s`, the pixels left at d_out (device memory of f.pixel_bytes() bytes).  Enqueue only; c.u_done is recorded behind the job.
@@ -222,10 +219,8 @@ int decode_on_device(Context &c, const PngFile &f, uint8_t *d_out, hipStream_t s
 {
     const uint64_t row = f.row_bytes(), pitch = pixo_dev::unfilter_pitch(row);
     const size_t expected = static_cast<size_t>(f.height) * (row + 1); // (2^24 rows of at most 2^27 + 1 bytes: fits 64 bits)
-    // the job before may still be reading the pinned buffers this one is about to write
-    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
-    HIP_TRY(hipEventSynchronize(c.u_done));
-    int rc;
+    int rc = await_last_job(c.u_done); // (it reads the pinned u_inflated and h_utables)
+    if (rc) return rc;
     if ((rc = c.u_inflated.reserve(expected))) return rc;
     uint8_t *stream = c.u_inflated.as<uint8_t>();
     auto t0 = std::chrono::steady_clock::now();
@@ -272,7 +267,7 @@ int decode_on_device(Context &c, const PngFile &f, uint8_t *d_out, hipStream_t s
     return PIXO_OK;
 }
 
-void report(const PngFile &f, uint32_t *width, uint32_t *height, uint8_t *color_type)
+void report_file(const PngFile &f, uint32_t *width, uint32_t *height, uint8_t *color_type)
 {
     *width = f.width; *height = f.height; *color_type = f.out_color_type();
 }
@@ -291,12 +286,7 @@ int decode_to_block(const uint8_t *file, size_t len, uint8_t **pixels, size_t *p
     if ((rc = reserve16(c.u_out, n))) return rc;
     Legs legs;
     if ((rc = decode_on_device(c, f, c.u_out.as<uint8_t>(), c.stream, legs_ms ? &legs : nullptr))) return rc;
-    uint8_t *block = pool_take(n);
-    if (!block) block = alloc_file(n);
-    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
-    hipError_t e = hipMemcpyAsync(block, c.u_out.p, n, hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) { free_file(block); return hip_fail(e, "png decode"); }
+    if ((rc = download_pooled(c, c.u_out.p, n, "png decode", pixels, pixels_len))) return rc;
     if (legs_ms) {
         float ms = 0;
         for (int i = 0; i < 3; ++i) {
@@ -304,9 +294,7 @@ int decode_to_block(const uint8_t *file, size_t len, uint8_t **pixels, size_t *p
             (i == 0 ? t_stats.upload_ms : i == 1 ? t_stats.unfilter_ms : t_stats.convert_ms) = ms;
         }
     }
-    report(f, width, height, color_type);
-    *pixels = block;
-    *pixels_len = n;
+    report_file(f, width, height, color_type);
     return PIXO_OK;
 }
 
@@ -315,8 +303,6 @@ constexpr uint64_t kDecodeBatchBytes = uint64_t{512} << 20; // device staging (s
                                                             // (debug switch decode_batch_bytes)
 constexpr uint32_t kDecodeBatchThreads = 8;                 // host threads that inflate a batch, the caller among them, at most
 constexpr uint32_t kFilterUnits[6] = {1, 2, 3, 4, 6, 8};
-
-inline uint64_t round16(uint64_t n) { return (n + 15) & ~uint64_t{15}; }
 
 struct BatchFile {
     PngFile f;
@@ -341,10 +327,9 @@ int batch_walk(const pixo_png_file *files, uint32_t batch, bool join, DecodeBatc
     b.files.resize(batch);
     b.images.resize(batch);
     for (uint32_t i = 0; i < batch; ++i) {
-        const std::string where = " (image " + std::to_string(i) + ")";
-        if (!files[i].data) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'data'" + where);
+        if (!files[i].data) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'data'" + where(i));
         const int rc = png_walk(files[i].data, files[i].len, join, b.files[i].f);
-        if (rc) return fail(rc, t_error + where);
+        if (rc) return fail(rc, t_error + where(i));
     }
     uint64_t at = 0;
     for (uint32_t i = 0; i < batch; ++i) {
@@ -354,13 +339,11 @@ int batch_walk(const pixo_png_file *files, uint32_t batch, bool join, DecodeBatc
         x.expected = static_cast<uint64_t>(x.f.height) * (x.row + 1);
         x.in_at = b.staging;
         b.staging += round16(x.expected);
-        const uint64_t end = at + x.f.pixel_bytes(); // (an image is at most 2^50 bytes: no wrap below the limit)
+        uint64_t end = 0; // (an image is at most 2^50 bytes: no wrap below the limit)
+        const pixo_png_image im = lay_out(at, x.f.width, x.f.height, x.f.out_color_type(), &end);
         if (end > (uint64_t{1} << 62)) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large");
-        pixo_png_image &im = b.images[i];
-        std::memset(&im, 0, sizeof im);
-        im.offset = at; im.width = x.f.width; im.height = x.f.height; im.color_type = x.f.out_color_type();
+        b.images[i] = im;
         b.total = end;
-        at = round16(end);
     }
     return PIXO_OK;
 }
@@ -391,13 +374,13 @@ int batch_inflate(DecodeBatch &b, uint8_t *stage, uint32_t flags)
     });
     b.inflate_ms = ms_since(t0);
     for (uint32_t i = 0; i < batch; ++i)
-        if (const int rc = inflate_status(b.files[i].kind, b.files[i].msg)) return fail(rc, t_error + " (image " + std::to_string(i) + ")");
+        if (const int rc = inflate_status(b.files[i].kind, b.files[i].msg)) return fail(rc, t_error + where(i));
     return PIXO_OK;
 }
 
 // What the driver decided, before anything touches a device (also: pixo_hip_debug_png_decode_batch_plan)
 struct DecodeBatchPlan {
-    std::vector<uint32_t> sub_first;        // sub-batch k is images [sub_first[k], sub_first[k + 1])
+    SubBatches sub_first;
     std::vector<uint64_t> rows_at;          // per image: its rows' offset in its sub-batch's rows buffer
     std::vector<uint32_t> kernel;           // per image: the convert kernel form (pixo_dev::ConvertKernel)
     uint64_t stream_bytes = 0, rows_bytes = 0; // the largest sub-batch's
@@ -415,15 +398,11 @@ void decode_batch_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodeBatchPlan
     const uint64_t limit = debug().decode_batch_bytes ? debug().decode_batch_bytes : kDecodeBatchBytes;
     p.rows_at.assign(batch, 0);
     p.kernel.assign(batch, 0);
-    p.sub_first.assign(1, 0);
     uint64_t held = 0, rows = 0;
     for (uint32_t i = 0; i < batch; ++i) {
         const BatchFile &x = b.files[i];
         const uint64_t mine = x.f.height * x.pitch, need = round16(x.expected) + mine;
-        if (i > p.sub_first.back() && held + need > limit) { // every sub-batch holds at least one image
-            p.sub_first.push_back(i);
-            held = rows = 0;
-        }
+        if (p.sub_first.starts_at(i, held + need > limit)) held = rows = 0;
         p.rows_at[i] = rows;
         rows += mine;
         held += need;
@@ -432,7 +411,7 @@ void decode_batch_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodeBatchPlan
         p.kernel[i] = pixo_dev::convert_kernel_of(convert_of(x.f.color_type, x.f.depth), static_cast<uint64_t>(x.f.width) * bytes_per_pixel(x.f.out_color_type()),
                                                   d_pixels + static_cast<uintptr_t>(b.images[i].offset));
     }
-    p.sub_first.push_back(batch);
+    p.sub_first.close(batch);
     for (uint32_t k = 0; k + 1 < p.sub_first.size(); ++k) {
         const uint32_t first = p.sub_first[k], end = p.sub_first[k + 1];
         for (const uint32_t unit : kFilterUnits) {
@@ -459,19 +438,6 @@ void decode_batch_plan(const DecodeBatch &b, uintptr_t d_pixels, DecodeBatchPlan
         }
     }
 }
-
-struct BatchLegs { // timed: events around the device legs of every sub-batch
-    std::vector<hipEvent_t> e;
-    ~BatchLegs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    int mark(hipStream_t s)
-    {
-        hipEvent_t x = nullptr;
-        HIP_TRY(hipEventCreate(&x));
-        e.push_back(x);
-        HIP_TRY(hipEventRecord(x, s));
-        return PIXO_OK;
-    }
-};
 
 // The tables of a batch in the pinned staging: descriptions, runs, block tables, a palette table per palette image; every section
 // starts at a multiple of 16.  Reserves every buffer the launches of a batch use: nothing has been handed out yet.
@@ -540,15 +506,14 @@ int decode_batch_device_inflate(Context &c, DecodeBatch &b, uint32_t flags, uint
 int decode_batch_on_device(Context &c, DecodeBatch &b, uint32_t flags, uint8_t *d_pixels, hipStream_t s, BatchLegs *legs = nullptr)
 {
     const uint32_t batch = static_cast<uint32_t>(b.files.size());
-    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
-    HIP_TRY(hipEventSynchronize(c.u_done)); // the job before may still be reading the pinned buffers this one is about to write
+    int rc = await_last_job(c.u_done); // (it reads the pinned u_inflated, h_utables, h_zin and h_uruns)
+    if (rc) return rc;
     if (flags & PIXO_DECODE_DEVICE_INFLATE) return decode_batch_device_inflate(c, b, flags, d_pixels, s, legs);
-    int rc;
     if ((rc = c.u_inflated.reserve(b.staging))) return rc;
     if ((rc = batch_inflate(b, c.u_inflated.as<uint8_t>(), flags))) return rc;
     DecodeBatchPlan p;
     decode_batch_plan(b, reinterpret_cast<uintptr_t>(d_pixels), p);
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
+    const uint32_t subs = p.sub_first.count();
     note_route(route::PNG_DECODE_BATCH | (subs > 1 ? route::SUB_BATCHES : 0));
 
     BatchTables t;
@@ -623,7 +588,7 @@ int decode_batch_device_inflate(Context &c, DecodeBatch &b, uint32_t flags, uint
     int rc;
     DecodeBatchPlan p; // (no runs are known yet: the cuts, the rows' places and the conversion launches do not need them)
     decode_batch_plan(b, reinterpret_cast<uintptr_t>(d_pixels), p);
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
+    const uint32_t subs = p.sub_first.count();
     note_route(route::PNG_DECODE_BATCH | route::PNG_INFLATE_DEVICE | (subs > 1 ? route::SUB_BATCHES : 0));
     BatchTables t;
     if ((rc = batch_tables(c, b, p, d_pixels, t))) return rc;
@@ -714,11 +679,11 @@ int decode_batch_device_inflate(Context &c, DecodeBatch &b, uint32_t flags, uint
         uint64_t at = 0;
         for (uint32_t i = first, j = 0; i < end; at += b.files[i].f.height, ++i) {
             BatchFile &x = b.files[i];
-            const std::string where = " (image " + std::to_string(i) + ")";
+            const std::string here = where(i);
             const uint8_t *bytes = filters + at;
             uint64_t stride = 1;
             if (j < suspect.size() && suspect[j] == i) {
-                if ((rc = inflate_status(x.kind, x.msg))) return fail(rc, t_error + where);
+                if ((rc = inflate_status(x.kind, x.msg))) return fail(rc, t_error + here);
                 bytes = c.u_inflated.as<uint8_t>() + redo_at[j];
                 stride = x.row + 1;
                 HIP_TRY(hipMemcpyAsync(c.u_stream.as<uint8_t>() + h_images[i].stream_at, bytes, x.expected, hipMemcpyHostToDevice, s));
@@ -728,8 +693,8 @@ int decode_batch_device_inflate(Context &c, DecodeBatch &b, uint32_t flags, uint
             }
             uint32_t bad_row = 0;
             x.runs = find_runs(bytes, x.f.height, stride, &bad_row);
-            if (bad_row < x.f.height) return fail(invalid("invalid filter type: " + std::to_string(bytes[bad_row * stride])), t_error + where);
-            if (x.f.color_type == CT_INDEXED && !x.f.has_plte) return fail(invalid("missing PLTE chunk"), t_error + where);
+            if (bad_row < x.f.height) return fail(invalid("invalid filter type: " + std::to_string(bytes[bad_row * stride])), t_error + here);
+            if (x.f.color_type == CT_INDEXED && !x.f.has_plte) return fail(invalid("missing PLTE chunk"), t_error + here);
         }
         // the runs of this sub-batch by filter unit, as decode_batch_plan lays them out
         pixo_dev::UnfilterBatchRun *runs = c.h_uruns.as<pixo_dev::UnfilterBatchRun>();
@@ -775,16 +740,14 @@ int inflate_batch_debug(Context &c, const pixo_png_file *streams, uint32_t n, co
     int rc;
     uint64_t block = 0, in_bytes = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        const std::string where = " (image " + std::to_string(i) + ")";
-        if (!streams[i].data) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'data'" + where);
-        if (streams[i].len < 6) return fail(invalid("zlib stream too short"), t_error + where);
-        if (out_at[i] > (uint64_t{1} << 40) || expected[i] > (uint64_t{1} << 40)) return fail(PIXO_ERR_COMPRESSION, "Compression error: region too large" + where);
+        if (!streams[i].data) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'data'" + where(i));
+        if (streams[i].len < 6) return fail(invalid("zlib stream too short"), t_error + where(i));
+        if (out_at[i] > (uint64_t{1} << 40) || expected[i] > (uint64_t{1} << 40)) return fail(PIXO_ERR_COMPRESSION, "Compression error: region too large" + where(i));
         block = std::max(block, out_at[i] + expected[i]);
         in_bytes += round16(streams[i].len - 6) + pixo_dev::kInflateInputAlign;
     }
     if (block) PIXO_REQUIRE(out);
-    if (!c.u_done) HIP_TRY(hipEventCreateWithFlags(&c.u_done, hipEventDisableTiming));
-    HIP_TRY(hipEventSynchronize(c.u_done));
+    if ((rc = await_last_job(c.u_done))) return rc;
     const size_t input_at = static_cast<size_t>(n) * sizeof(InflateStream), status_bytes = static_cast<size_t>(n) * sizeof(InflateStatus);
     if ((rc = c.h_zin.reserve(input_at + in_bytes)) || (rc = c.u_zin.reserve(input_at + in_bytes)) || (rc = c.u_zout.reserve(status_bytes)) ||
         (rc = c.h_zout.reserve(status_bytes)) || (rc = c.u_stream.reserve(block + pixo_dev::kUnfilterPiece)))
@@ -821,46 +784,35 @@ int inflate_batch_debug(Context &c, const pixo_png_file *streams, uint32_t n, co
     return PIXO_OK;
 }
 
-// The batch entries' first two checks
-int batch_head(const pixo_png_file *files, uint32_t batch)
-{
-    PIXO_REQUIRE(files);
-    return batch_in_range(batch);
-}
-void report(const DecodeBatch &b, pixo_png_image *images) { std::copy(b.images.begin(), b.images.end(), images); }
-
 // Host files -> one block of the pinned pool the caller owns
 int decode_batch_to_block(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t **out, size_t *out_len, pixo_png_image *images, double *legs_ms)
 {
     DecodeBatch b;
     int rc = batch_walk(files, batch, true, b);
     if (rc) return rc;
-    report(b, images);
+    report(b.images, images);
     if ((flags & PIXO_DECODE_DEVICE_INFLATE) && (rc = batch_zlib_heads(b, flags))) return rc;
     PIXO_THREAD_CONTEXT(c);
     const size_t n = static_cast<size_t>(b.total);
     if ((rc = reserve16(c.u_out, n))) return rc;
     BatchLegs legs;
     if ((rc = decode_batch_on_device(c, b, flags, c.u_out.as<uint8_t>(), c.stream, legs_ms ? &legs : nullptr))) return rc;
-    uint8_t *block = pool_take(n);
-    if (!block) block = alloc_file(n);
-    if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
-    hipError_t e = hipMemcpyAsync(block, c.u_out.p, n, hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) { free_file(block); return hip_fail(e, "png decode batch"); }
+    uint8_t *block = nullptr;
+    size_t got = 0;
+    if ((rc = download_pooled(c, c.u_out.p, n, "png decode batch", &block, &got))) return rc;
     if (legs_ms) {
         legs_ms[0] = b.inflate_ms;
         legs_ms[1] = legs_ms[2] = legs_ms[3] = 0;
         for (size_t k = 0; k + 3 < legs.e.size(); k += 4)
             for (int i = 0; i < 3; ++i) {
                 float ms = 0;
-                e = hipEventElapsedTime(&ms, legs.e[k + i], legs.e[k + i + 1]);
+                const hipError_t e = hipEventElapsedTime(&ms, legs.e[k + i], legs.e[k + i + 1]);
                 if (e != hipSuccess) { free_file(block); return hip_fail(e, "hipEventElapsedTime"); }
                 legs_ms[1 + i] += ms;
             }
     }
     *out = block;
-    *out_len = n;
+    *out_len = got;
     return PIXO_OK;
 }
 
@@ -876,7 +828,7 @@ int pixo_hip_png_decode_batch_info(const pixo_png_file *files, uint32_t batch, p
     PIXO_REQUIRE(total);
     DecodeBatch b;
     if ((rc = batch_walk(files, batch, false, b))) return rc;
-    report(b, images);
+    report(b.images, images);
     *total = static_cast<size_t>(b.total);
     return PIXO_OK;
 }
@@ -890,14 +842,11 @@ int pixo_hip_png_decode_batch_device(const pixo_png_file *files, uint32_t batch,
     PIXO_REQUIRE(images);
     DecodeBatch b;
     if ((rc = batch_walk(files, batch, true, b))) return rc;
-    report(b, images);
+    report(b.images, images);
     if (capacity < b.total) return too_small(static_cast<size_t>(b.total));
     PIXO_REQUIRE(d_pixels);
     if ((flags & PIXO_DECODE_DEVICE_INFLATE) && (rc = batch_zlib_heads(b, flags))) return rc;
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return decode_batch_on_device(*c, b, flags, static_cast<uint8_t *>(d_pixels), s);
 }
 
@@ -931,8 +880,7 @@ int pixo_hip_debug_png_decode_batch_plan(const pixo_png_file *files, uint32_t ba
     if (rc) return rc;
     DecodeBatchPlan p;
     decode_batch_plan(b, 0, p);
-    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
-    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    p.sub_first.report(sub_first, sub_count);
     for (uint32_t i = 0; i < batch; ++i) runs_per_image[i] = b.files[i].runs.pairs.size() / 2;
     *unfilter_launches = static_cast<uint32_t>(p.unfilter.size());
     *convert_launches = static_cast<uint32_t>(p.convert.size());
@@ -976,7 +924,7 @@ int pixo_hip_png_decode_info(const uint8_t *file, size_t len, uint32_t *width, u
     PngFile f;
     const int rc = png_walk(file, len, false, f);
     if (rc) return rc;
-    report(f, width, height, color_type);
+    report_file(f, width, height, color_type);
     return PIXO_OK;
 }
 
@@ -991,13 +939,10 @@ int pixo_hip_png_decode_device(const uint8_t *file, size_t len, void *d_pixels, 
     PngFile f;
     int rc = png_walk(file, len, true, f);
     if (rc) return rc;
-    report(f, width, height, color_type);
+    report_file(f, width, height, color_type);
     if (capacity < f.pixel_bytes()) return too_small(f.pixel_bytes());
     PIXO_REQUIRE(d_pixels);
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return decode_on_device(*c, f, static_cast<uint8_t *>(d_pixels), s);
 }
 

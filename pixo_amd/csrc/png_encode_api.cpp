@@ -5,7 +5,8 @@
 // There is one tail (tail_begin, tail_finish, tail_deliver) over a table of segments (png_deflate_math.h ZSegment): a single
 // file and a bare zlib stream are a table of one, the batch entries run N equal images through it at once, the images
 // entries N images of individual sizes and colour types.
-#include "capi_internal.hpp"
+// The steps every batch driver takes, and their order: DESIGN.md §4.0; the shared ones: batch_steps.hpp.
+#include "batch_steps.hpp"
 #include "png_deflate.hpp"
 #include "png_filter.hpp"
 
@@ -468,7 +469,7 @@ struct ImagesPlan {
         bool batched = false; // the batched way in: a ragged filter launch; otherwise png_segment_of_image
     };
     std::vector<Image> image;
-    std::vector<uint32_t> sub_first; // sub-batch k: images sub_first[k] .. sub_first[k + 1]
+    SubBatches sub_first;
 };
 // Sub-batches: greedy in index order under 64 MiB of unreduced stream (debug switch png_batch_bytes) and kBatchChunks chunks,
 // at least one image each.  The way in is the image's own: png_plan with ITS area and height (an area of at most 4096 pixels
@@ -477,7 +478,6 @@ int plan_images(const pixo_png_image *images, uint32_t batch, const pixo_png_opt
 {
     const uint64_t limit = debug().png_batch_bytes ? debug().png_batch_bytes : (uint64_t{64} << 20);
     p.image.resize(batch);
-    p.sub_first.assign(1, 0);
     uint64_t bytes = 0, chunks = 0;
     for (uint32_t i = 0; i < batch; ++i) {
         ImagesPlan::Image &x = p.image[i];
@@ -491,14 +491,11 @@ int plan_images(const pixo_png_image *images, uint32_t batch, const pixo_png_opt
         if (const int rc = png_plan(x.o.width, x.o.height, static_cast<uint64_t>(x.o.width) * x.o.height, x.bpp, o.filter_strategy, o.flags, &x.run, &seq)) return rc;
         x.batched = !q && !o.optimize_alpha && !o.reduce_color_type && !o.reduce_palette && !seq;
         const uint64_t c = seg_chunks(x.full);
-        if (i > p.sub_first.back() && (bytes + x.full > limit || chunks + c > kBatchChunks)) {
-            p.sub_first.push_back(i);
-            bytes = chunks = 0;
-        }
+        if (p.sub_first.starts_at(i, bytes + x.full > limit || chunks + c > kBatchChunks)) bytes = chunks = 0;
         bytes += x.full;
         chunks += c;
     }
-    p.sub_first.push_back(batch);
+    p.sub_first.close(batch);
     return PIXO_OK;
 }
 // The items of a sub-batch's ragged launches: its batched images in index order, stream i at segment i's place.
@@ -525,7 +522,7 @@ int png_images(Context &c, const void *d_px, const pixo_png_image *images, const
     ImagesPlan p;
     int rc = plan_images(images, batch, o, q, p);
     if (rc) return rc;
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size()) - 1;
+    const uint32_t subs = p.sub_first.count();
     note_route(route::PNG_IMAGES | (subs > 1 ? route::SUB_BATCHES : 0));
     for (uint32_t part = 0; part < subs; ++part) {
         const uint32_t first = p.sub_first[part], end = p.sub_first[part + 1], nb = end - first, waits0 = sink.waits;
@@ -632,16 +629,13 @@ int png_images_checks(const pixo_png_options *options, const void *pixels, bool 
 }
 int png_images_check_each(const pixo_png_image *images, uint32_t batch, uint64_t *block_end)
 {
-    uint64_t furthest = 0;
+    *block_end = 0;
     for (uint32_t i = 0; i < batch; ++i) {
-        const std::string where = " (image " + std::to_string(i) + ")";
         const pixo_png_image &im = images[i];
-        if (const int rc = png_check_image(im.width, im.height, im.color_type)) return fail(rc, t_error + where);
-        const uint64_t bytes = static_cast<uint64_t>(im.width) * im.height * bytes_per_pixel(im.color_type), most = uint64_t{1} << 62; // (an image is at most 2^50 bytes)
-        if (im.offset > most || im.offset + bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch input too large" + where);
-        furthest = std::max(furthest, im.offset + bytes);
+        int rc = png_check_image(im.width, im.height, im.color_type);
+        if (rc) return fail(rc, t_error + where(i));
+        if ((rc = record_extent(im.offset, image_bytes(im), "input", where(i), block_end))) return rc;
     }
-    *block_end = furthest;
     return PIXO_OK;
 }
 
@@ -862,9 +856,8 @@ int pixo_hip_debug_png_encode_images_plan(const pixo_png_image *images, uint32_t
     if ((rc = png_images_check_each(images, batch, &end))) return rc;
     ImagesPlan p;
     if ((rc = plan_images(images, batch, *options, quantization, p))) return rc;
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size()) - 1;
-    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
-    *sub_count = subs;
+    const uint32_t subs = p.sub_first.count();
+    p.sub_first.report(sub_first, sub_count);
     *filter_launches = 0;
     for (uint32_t i = 0; i < batch; ++i) { way_in[i] = p.image[i].batched ? 1 : 0; run_strategy[i] = static_cast<uint8_t>(p.image[i].run); }
     for (uint32_t k = 0; k < subs; ++k) {

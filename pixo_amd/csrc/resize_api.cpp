@@ -4,7 +4,8 @@
 // one size, sub-batches that bound the intermediate), one upload of tables and items, one launch per pass and sub-batch.
 // The images entries: sources AND destinations of individual sizes and colour types, described by pixo_png_image records —
 // the fitted sizes, the plan, the records of the flat launches (resize_images_math.h), one launch per pass and pixel size.
-#include "capi_internal.hpp"
+// The steps every batch driver takes, and their order: DESIGN.md §4.0; the shared ones: batch_steps.hpp.
+#include "batch_steps.hpp"
 #include "resize.hpp"
 #include "resize_math.h"
 
@@ -30,9 +31,7 @@ int resize_plan(const pixo_resize_options *o, bool device, size_t data_len, size
     if (o->src_width > M || o->src_height > M || o->dst_width > M || o->dst_height > M)
         return too_large(std::max(o->src_width, o->dst_width), std::max(o->src_height, o->dst_height), M);
     // (the C struct can carry codes the reference's enums cannot: answered like the flat entry's own checks)
-    if (o->color_type > PIXO_RGBA)
-        return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid color type: " + std::to_string(o->color_type) +
-                                                    ". Expected 0 (Gray), 1 (GrayAlpha), 2 (Rgb), or 3 (Rgba)");
+    if (o->color_type > PIXO_RGBA) return bad_color_type(o->color_type);
     if (o->algorithm > PIXO_RESIZE_LANCZOS3)
         return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid resize algorithm: " + std::to_string(o->algorithm) +
                                                     ". Expected 0 (Nearest), 1 (Bilinear), or 2 (Lanczos3)");
@@ -103,15 +102,13 @@ pixo_dev::ResizeAxisTable axis_on_device(const uint8_t *d_base, uint32_t dst)
 // The tables of (src_w -> dst_w, src_h -> dst_h) in c.r_tables, uploaded on `s`; kept while the shape repeats.
 int lanczos_tables(Context &c, const pixo_resize_options &o, hipStream_t s)
 {
-    if (!c.r_done) HIP_TRY(hipEventCreateWithFlags(&c.r_done, hipEventDisableTiming));
     const uint32_t want[4] = {o.src_width, o.dst_width, o.src_height, o.dst_height};
-    if (c.r_tables.known == 1 && std::equal(want, want + 4, c.r_dims)) return PIXO_OK;
-    // the job before may still be reading the tables, and the staging may still be on its way: both are about to change
-    HIP_TRY(hipEventSynchronize(c.r_done));
+    if (c.r_tables.known == 1 && std::equal(want, want + 4, c.r_dims)) return PIXO_OK; // (a job of this context uploaded them: r_done exists)
+    int rc = await_last_job(c.r_done); // (it reads r_tables, which go up from r_stage)
+    if (rc) return rc;
     const size_t h_total = axis_weights(o.src_width, o.dst_width), v_total = axis_weights(o.src_height, o.dst_height);
     const size_t h_bytes = axis_table_bytes(o.dst_width, h_total), v_bytes = axis_table_bytes(o.dst_height, v_total);
     if (h_total > 0xFFFFFFFFull || v_total > 0xFFFFFFFFull) return fail(PIXO_ERR_COMPRESSION, "Compression error: contribution table too large");
-    int rc;
     if ((rc = c.r_stage.reserve(h_bytes + v_bytes)) || (rc = c.r_tables.reserve(h_bytes + v_bytes))) return rc;
     c.r_tables.known = 0;
     uint8_t *stage = c.r_stage.as<uint8_t>();
@@ -172,13 +169,47 @@ struct BatchAxis {
     uint32_t max_span; // of a horizontal axis: the widest source span of one tile
     size_t at, bytes;  // its table in the block of tables
 };
-struct BatchPlan {
-    std::vector<uint32_t> sub_first;      // sub-batch k is images [sub_first[k], sub_first[k + 1])
+// The axis tables of a call: one per distinct (source, destination) pair per axis (a batch to one size: per distinct source
+// width and per distinct source height)
+struct AxisTables {
+    std::vector<BatchAxis> axes;
+    size_t table_bytes = 0; // all tables, each 16-byte aligned
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> h_of, v_of;
+    // *index: the table of src -> dst among `axes`, measured and given its place when `seen` (h_of or v_of) has not met the pair
+    int find(std::map<std::pair<uint32_t, uint32_t>, uint32_t> &seen, uint32_t src, uint32_t dst, uint32_t *index)
+    {
+        const auto found = seen.find({src, dst});
+        if (found != seen.end()) { *index = found->second; return PIXO_OK; }
+        size_t total = 0;
+        uint32_t span = 0;
+        axis_measure(src, dst, &total, &span);
+        if (total > 0xFFFFFFFFull) return fail(PIXO_ERR_COMPRESSION, "Compression error: contribution table too large");
+        const BatchAxis a{src, dst, span, table_bytes, axis_table_bytes(dst, total)};
+        table_bytes += a.bytes;
+        *index = seen[{src, dst}] = static_cast<uint32_t>(axes.size());
+        axes.push_back(a);
+        return PIXO_OK;
+    }
+};
+// The tables at stage + axes[k].at.  The weights are host work (a sine in f64 each) and the axes are independent: a ragged batch,
+// with up to two tables per image, builds them on several threads (64 x 1080p -> 320x180 of individual sizes: 7.4 ms on one)
+void build_axis_tables(uint8_t *stage, const AxisTables &t)
+{
+    const unsigned builders = static_cast<unsigned>(std::min<size_t>({kResizeBatchTableThreads, t.axes.size(), t.table_bytes / kResizeBatchTableShare + 1}));
+    run_on_threads(builders, [&](unsigned k) {
+        for (size_t a = k; a < t.axes.size(); a += std::max(builders, 1u)) (void)fill_axis(t.axes[a].src, t.axes[a].dst, stage + t.axes[a].at);
+    });
+}
+void note_resize_route(uint8_t algorithm, uint64_t entry, uint32_t subs)
+{
+    note_route((algorithm == PIXO_RESIZE_LANCZOS3 ? route::RESIZE_LANCZOS3 : algorithm == PIXO_RESIZE_NEAREST ? route::RESIZE_NEAREST : route::RESIZE_BILINEAR) |
+               entry | (subs > 1 ? route::SUB_BATCHES : 0));
+}
+struct BatchPlan : AxisTables {
+    SubBatches sub_first;
     std::vector<uint64_t> mid_at;         // per image: its rows' offset in the intermediate of its sub-batch
     std::vector<uint8_t> use_lds;         // per image: the horizontal pass stages in LDS
     std::vector<uint32_t> h_axis, v_axis; // per image: its axes in `axes`
-    std::vector<BatchAxis> axes;          // one per distinct source width and per distinct source height (the destination is the batch's)
-    size_t table_bytes = 0;               // all tables, each 16-byte aligned
     uint64_t mid_bytes = 0;               // the largest sub-batch's intermediate
 };
 
@@ -187,45 +218,26 @@ int resize_batch_plan(const pixo_resize_source *src, uint32_t batch, uint32_t dw
 {
     p.mid_at.assign(batch, 0);
     p.use_lds.assign(batch, 0);
-    p.sub_first.assign(1, 0u);
     if (algorithm != PIXO_RESIZE_LANCZOS3) { // no tables, no intermediate: never cut
-        p.sub_first.push_back(batch);
+        p.sub_first.close(batch);
         return PIXO_OK;
     }
     p.h_axis.assign(batch, 0);
     p.v_axis.assign(batch, 0);
-    // one table per distinct (src, dst) pair per axis
-    std::map<uint32_t, uint32_t> h_of, v_of;
-    const auto axis_of = [&](std::map<uint32_t, uint32_t> &seen, uint32_t s, uint32_t d, uint32_t *index) -> int {
-        const auto found = seen.find(s);
-        if (found != seen.end()) { *index = found->second; return PIXO_OK; }
-        size_t total = 0;
-        uint32_t span = 0;
-        axis_measure(s, d, &total, &span);
-        if (total > 0xFFFFFFFFull) return fail(PIXO_ERR_COMPRESSION, "Compression error: contribution table too large");
-        BatchAxis a{s, d, span, p.table_bytes, axis_table_bytes(d, total)};
-        p.table_bytes += a.bytes;
-        *index = seen[s] = static_cast<uint32_t>(p.axes.size());
-        p.axes.push_back(a);
-        return PIXO_OK;
-    };
     const uint64_t limit = debug().resize_batch_bytes ? debug().resize_batch_bytes : kResizeBatchMidBytes;
     const uint64_t stride = pixo_dev::resize_mid_stride(dw, bpp);
     uint64_t held = 0; // the current sub-batch's intermediate so far
     for (uint32_t i = 0; i < batch; ++i) {
         int rc;
-        if ((rc = axis_of(h_of, src[i].width, dw, &p.h_axis[i])) || (rc = axis_of(v_of, src[i].height, dh, &p.v_axis[i]))) return rc;
+        if ((rc = p.find(p.h_of, src[i].width, dw, &p.h_axis[i])) || (rc = p.find(p.v_of, src[i].height, dh, &p.v_axis[i]))) return rc;
         p.use_lds[i] = pixo_dev::resize_h_uses_lds(p.axes[p.h_axis[i]].max_span, bpp);
         const uint64_t rows = stride * src[i].height; // (at most 2^26 * 2^24)
-        if (i > p.sub_first.back() && held + rows > limit) { // every sub-batch holds at least one image
-            p.sub_first.push_back(i);
-            held = 0;
-        }
+        if (p.sub_first.starts_at(i, held + rows > limit)) held = 0;
         p.mid_at[i] = held;
         held += rows;
         p.mid_bytes = std::max(p.mid_bytes, held);
     }
-    p.sub_first.push_back(batch);
+    p.sub_first.close(batch);
     return PIXO_OK;
 }
 
@@ -243,7 +255,7 @@ int resize_batch_checks(const pixo_resize_source *sources, uint32_t batch, uint3
         o.dst_width = dw; o.dst_height = dh;
         o.color_type = color_type; o.algorithm = algorithm;
         size_t in_bytes = 0;
-        if ((rc = resize_plan(&o, true, 0, &in_bytes, out_bytes))) return fail(rc, t_error + " (image " + std::to_string(i) + ")");
+        if ((rc = resize_plan(&o, true, 0, &in_bytes, out_bytes))) return fail(rc, t_error + where(i));
     }
     if (*out_bytes > (size_t{1} << 62) / batch) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large");
     return PIXO_OK;
@@ -251,7 +263,7 @@ int resize_batch_checks(const pixo_resize_source *sources, uint32_t batch, uint3
 int resize_batch_pixels_given(const pixo_resize_source *sources, uint32_t batch)
 {
     for (uint32_t i = 0; i < batch; ++i)
-        if (!sources[i].pixels) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'pixels' (image " + std::to_string(i) + ")");
+        if (!sources[i].pixels) return fail(PIXO_ERR_COMPRESSION, "Compression error: null argument 'pixels'" + where(i));
     return PIXO_OK;
 }
 
@@ -266,23 +278,14 @@ int resize_batch_on_device(Context &c, const pixo_resize_source *sources, uint32
     int rc = resize_batch_plan(sources, batch, dw, dh, bpp, algorithm, p);
     if (rc) return rc;
     const bool lanczos = algorithm == PIXO_RESIZE_LANCZOS3;
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1);
-    note_route((lanczos ? route::RESIZE_LANCZOS3 : algorithm == PIXO_RESIZE_NEAREST ? route::RESIZE_NEAREST : route::RESIZE_BILINEAR) |
-               route::RESIZE_BATCH | (subs > 1 ? route::SUB_BATCHES : 0));
-    if (!c.rb_done) HIP_TRY(hipEventCreateWithFlags(&c.rb_done, hipEventDisableTiming));
-    // the batch before may still be reading the tables and the items, and the staging may still be on its way: all of them are
-    // about to change.  The call's only host wait.
-    HIP_TRY(hipEventSynchronize(c.rb_done));
+    const uint32_t subs = p.sub_first.count();
+    note_resize_route(algorithm, route::RESIZE_BATCH, subs);
+    if ((rc = await_last_job(c.rb_done))) return rc; // (it reads rb_tables, which go up from rb_stage)
     // everything is reserved before any address is handed out (a growing reserve frees first: a device-wide wait)
     const size_t up_bytes = p.table_bytes + static_cast<size_t>(batch) * sizeof(pixo_dev::ResizeBatchItem);
     if ((rc = c.rb_stage.reserve(up_bytes)) || (rc = c.rb_tables.reserve(up_bytes)) || (rc = c.rb_mid.reserve(p.mid_bytes))) return rc;
     uint8_t *stage = c.rb_stage.as<uint8_t>();
-    // the weights are host work (a sine in f64 each) and the axes are independent: a ragged batch, with up to two tables per
-    // image, builds them on several threads (64 x 1080p -> 320x180 of individual sizes: 7.4 ms on one)
-    const unsigned builders = static_cast<unsigned>(std::min<size_t>({kResizeBatchTableThreads, p.axes.size(), p.table_bytes / kResizeBatchTableShare + 1}));
-    run_on_threads(builders, [&](unsigned k) {
-        for (size_t a = k; a < p.axes.size(); a += std::max(builders, 1u)) (void)fill_axis(p.axes[a].src, p.axes[a].dst, stage + p.axes[a].at);
-    });
+    build_axis_tables(stage, p);
     pixo_dev::ResizeBatchItem *items = reinterpret_cast<pixo_dev::ResizeBatchItem *>(stage + p.table_bytes); // (table_bytes is a multiple of 16)
     for (uint32_t i = 0; i < batch; ++i) {
         pixo_dev::ResizeBatchItem &it = items[i];
@@ -339,14 +342,12 @@ void fit_size(uint32_t sw, uint32_t sh, uint32_t box_w, uint32_t box_h, uint32_t
 }
 
 // What the driver decided for the images, before anything touches a device (also: pixo_hip_debug_resize_images_plan).
-struct ImagesPlan {
-    std::vector<uint32_t> sub_first;                 // sub-batch k is images [sub_first[k], sub_first[k + 1])
+struct ImagesPlan : AxisTables {
+    SubBatches sub_first;
     std::vector<uint64_t> mid_at;                    // per image: its rows' offset in the intermediate of its sub-batch
     std::vector<uint8_t> use_lds;                    // per image: the horizontal pass stages in LDS
     std::vector<uint32_t> h_axis, v_axis;            // per image: its axes in `axes`
     std::vector<uint32_t> tiles_first, tiles_second; // per image: its tiles in the point / horizontal pass, in the vertical pass
-    std::vector<BatchAxis> axes;                     // one per distinct (source, destination) pair per axis
-    size_t table_bytes = 0;                          // all tables, each 16-byte aligned
     uint64_t mid_bytes = 0;                          // the largest sub-batch's intermediate
     uint32_t launches_first = 0, launches_second = 0; // launches of the two passes, summed over the sub-batches
     uint32_t rows_cap = rzi::kRowsCap;
@@ -363,21 +364,6 @@ int resize_images_plan(const pixo_png_image *src, const pixo_png_image *dst, uin
     p.v_axis.assign(batch, 0);
     p.tiles_first.assign(batch, 0);
     p.tiles_second.assign(batch, 0);
-    p.sub_first.assign(1, 0u);
-    std::map<std::pair<uint32_t, uint32_t>, uint32_t> h_of, v_of;
-    const auto axis_of = [&](std::map<std::pair<uint32_t, uint32_t>, uint32_t> &seen, uint32_t s, uint32_t d, uint32_t *index) -> int {
-        const auto found = seen.find({s, d});
-        if (found != seen.end()) { *index = found->second; return PIXO_OK; }
-        size_t total = 0;
-        uint32_t span = 0;
-        axis_measure(s, d, &total, &span);
-        if (total > 0xFFFFFFFFull) return fail(PIXO_ERR_COMPRESSION, "Compression error: contribution table too large");
-        BatchAxis a{s, d, span, p.table_bytes, axis_table_bytes(d, total)};
-        p.table_bytes += a.bytes;
-        *index = seen[{s, d}] = static_cast<uint32_t>(p.axes.size());
-        p.axes.push_back(a);
-        return PIXO_OK;
-    };
     const uint64_t limit = debug().resize_batch_bytes ? debug().resize_batch_bytes : kResizeBatchMidBytes;
     uint64_t held = 0;                     // the current sub-batch's intermediate so far
     uint64_t first[5] = {0, 0, 0, 0, 0};   // ... the tiles of its point / horizontal launches so far, by bytes per pixel
@@ -387,15 +373,14 @@ int resize_images_plan(const pixo_png_image *src, const pixo_png_image *dst, uin
         uint64_t rows = 0;
         if (lanczos) {
             int rc;
-            if ((rc = axis_of(h_of, src[i].width, dst[i].width, &p.h_axis[i])) || (rc = axis_of(v_of, src[i].height, dst[i].height, &p.v_axis[i]))) return rc;
+            if ((rc = p.find(p.h_of, src[i].width, dst[i].width, &p.h_axis[i])) || (rc = p.find(p.v_of, src[i].height, dst[i].height, &p.v_axis[i]))) return rc;
             p.use_lds[i] = pixo_dev::resize_h_uses_lds(p.axes[p.h_axis[i]].max_span, bpp);
             rows = static_cast<uint64_t>(pixo_dev::resize_mid_stride(dst[i].width, bpp)) * src[i].height; // (at most 2^26 * 2^24)
         }
         const uint64_t a = rzi::tile_count(lanczos ? rzi::PASS_H : rzi::PASS_POINT, src[i].height, dst[i].width, dst[i].height, bpp, p.rows_cap);
         const uint64_t b = lanczos ? rzi::tile_count(rzi::PASS_V, src[i].height, dst[i].width, dst[i].height, bpp, p.rows_cap) : 0;
-        // every sub-batch holds at least one image; a launch's tiles stay within 31 bits (one image's do: tiles_of)
-        if (i > p.sub_first.back() && (held + rows > limit || first[bpp] + a > rzi::kMaxTiles || second + b > rzi::kMaxTiles)) {
-            p.sub_first.push_back(i);
+        // a launch's tiles stay within 31 bits (one image's do: tiles_of)
+        if (p.sub_first.starts_at(i, held + rows > limit || first[bpp] + a > rzi::kMaxTiles || second + b > rzi::kMaxTiles)) {
             held = second = 0;
             std::fill(first, first + 5, uint64_t{0});
         }
@@ -409,7 +394,7 @@ int resize_images_plan(const pixo_png_image *src, const pixo_png_image *dst, uin
         second += b;
         p.mid_bytes = std::max(p.mid_bytes, held);
     }
-    p.sub_first.push_back(batch);
+    p.sub_first.close(batch);
     return PIXO_OK;
 }
 
@@ -421,22 +406,18 @@ int resize_images_checks(const pixo_png_image *src_images, const pixo_png_image 
     PIXO_REQUIRE(dst_images);
     int rc = batch_in_range(batch);
     if (rc) return rc;
-    const uint64_t most = uint64_t{1} << 62; // (an image is at most 2^50 bytes)
     *src_end = *dst_end = 0;
     for (uint32_t i = 0; i < batch; ++i) {
-        const std::string where = " (image " + std::to_string(i) + ")";
+        const std::string here = where(i);
         const pixo_png_image &a = src_images[i], &b = dst_images[i];
         pixo_resize_options o;
         o.src_width = a.width; o.src_height = a.height;
         o.dst_width = b.width; o.dst_height = b.height;
         o.color_type = a.color_type; o.algorithm = algorithm;
         size_t in_bytes = 0, out_bytes = 0;
-        if ((rc = resize_plan(&o, true, 0, &in_bytes, &out_bytes))) return fail(rc, t_error + where);
-        if (b.color_type != a.color_type) return fail(PIXO_ERR_COMPRESSION, "Compression error: colour types differ" + where);
-        if (a.offset > most || a.offset + in_bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch input too large" + where);
-        if (b.offset > most || b.offset + out_bytes > most) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large" + where);
-        *src_end = std::max<uint64_t>(*src_end, a.offset + in_bytes);
-        *dst_end = std::max<uint64_t>(*dst_end, b.offset + out_bytes);
+        if ((rc = resize_plan(&o, true, 0, &in_bytes, &out_bytes))) return fail(rc, t_error + here);
+        if (b.color_type != a.color_type) return fail(PIXO_ERR_COMPRESSION, "Compression error: colour types differ" + here);
+        if ((rc = record_extent(a.offset, in_bytes, "input", here, src_end)) || (rc = record_extent(b.offset, out_bytes, "output", here, dst_end))) return rc;
     }
     return PIXO_OK;
 }
@@ -451,21 +432,14 @@ int resize_images_on_device(Context &c, const uint8_t *d_src, const pixo_png_ima
     int rc = resize_images_plan(src, dst, batch, algorithm, p);
     if (rc) return rc;
     const bool lanczos = algorithm == PIXO_RESIZE_LANCZOS3;
-    const uint32_t subs = static_cast<uint32_t>(p.sub_first.size() - 1), passes = lanczos ? 2 : 1;
-    note_route((lanczos ? route::RESIZE_LANCZOS3 : algorithm == PIXO_RESIZE_NEAREST ? route::RESIZE_NEAREST : route::RESIZE_BILINEAR) |
-               route::RESIZE_IMAGES | (subs > 1 ? route::SUB_BATCHES : 0));
-    if (!c.rb_done) HIP_TRY(hipEventCreateWithFlags(&c.rb_done, hipEventDisableTiming));
-    // the job before may still be reading the tables and the records, and the staging may still be on its way: all of them
-    // are about to change.  The call's only host wait.
-    HIP_TRY(hipEventSynchronize(c.rb_done));
+    const uint32_t subs = p.sub_first.count(), passes = lanczos ? 2 : 1;
+    note_resize_route(algorithm, route::RESIZE_IMAGES, subs);
+    if ((rc = await_last_job(c.rb_done))) return rc; // (it reads rb_tables, which go up from rb_stage)
     // everything is reserved before any address is handed out (a growing reserve frees first: a device-wide wait)
     const size_t up_bytes = p.table_bytes + static_cast<size_t>(passes) * batch * sizeof(rzi::Record);
     if ((rc = c.rb_stage.reserve(up_bytes)) || (rc = c.rb_tables.reserve(up_bytes)) || (rc = c.rb_mid.reserve(p.mid_bytes))) return rc;
     uint8_t *stage = c.rb_stage.as<uint8_t>();
-    const unsigned builders = static_cast<unsigned>(std::min<size_t>({kResizeBatchTableThreads, p.axes.size(), p.table_bytes / kResizeBatchTableShare + 1}));
-    run_on_threads(builders, [&](unsigned k) {
-        for (size_t a = k; a < p.axes.size(); a += std::max(builders, 1u)) (void)fill_axis(p.axes[a].src, p.axes[a].dst, stage + p.axes[a].at);
-    });
+    build_axis_tables(stage, p);
     // the records: pass after pass, inside a pass sub-batch after sub-batch (table_bytes is a multiple of 16)
     rzi::Record *records = reinterpret_cast<rzi::Record *>(stage + p.table_bytes);
     struct Enqueued {
@@ -526,29 +500,21 @@ int pixo_hip_resize_images_fit(const pixo_png_image *src_images, uint32_t batch,
     if (box_width == 0 || box_height == 0) return bad_dimensions(box_width, box_height);
     if (box_width > RZ_MAX_DIMENSION || box_height > RZ_MAX_DIMENSION) return too_large(box_width, box_height, RZ_MAX_DIMENSION);
     for (uint32_t i = 0; i < batch; ++i) { // nothing is written before every image has passed
-        const std::string where = " (image " + std::to_string(i) + ")";
         const pixo_png_image &a = src_images[i];
-        if (a.width == 0 || a.height == 0) { rc = bad_dimensions(a.width, a.height); return fail(rc, t_error + where); }
-        if (a.width > RZ_MAX_DIMENSION || a.height > RZ_MAX_DIMENSION) { rc = too_large(a.width, a.height, RZ_MAX_DIMENSION); return fail(rc, t_error + where); }
-        if (a.color_type > PIXO_RGBA)
-            return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid color type: " + std::to_string(a.color_type) +
-                                                        ". Expected 0 (Gray), 1 (GrayAlpha), 2 (Rgb), or 3 (Rgba)" + where);
+        if (a.width == 0 || a.height == 0) { rc = bad_dimensions(a.width, a.height); return fail(rc, t_error + where(i)); }
+        if (a.width > RZ_MAX_DIMENSION || a.height > RZ_MAX_DIMENSION) { rc = too_large(a.width, a.height, RZ_MAX_DIMENSION); return fail(rc, t_error + where(i)); }
+        if (a.color_type > PIXO_RGBA) return bad_color_type(a.color_type, where(i));
     }
     uint64_t at = 0, end = 0;
     std::vector<pixo_png_image> fitted(batch); // (dst_images may be src_images)
     for (uint32_t i = 0; i < batch; ++i) {
         const pixo_png_image &a = src_images[i];
-        pixo_png_image b{};
-        b.color_type = a.color_type;
-        if ((flags & PIXO_RESIZE_FIT_NO_ENLARGE) && a.width <= box_width && a.height <= box_height) { b.width = a.width; b.height = a.height; }
-        else fit_size(a.width, a.height, box_width, box_height, &b.width, &b.height);
-        b.offset = at;
-        end = at + static_cast<uint64_t>(b.width) * b.height * bytes_per_pixel(b.color_type); // (at most 2^16 images of 2^50 bytes: below 2^64)
-        at = (end + 15) & ~uint64_t{15};
-        fitted[i] = b;
+        uint32_t w = a.width, h = a.height;
+        if (!(flags & PIXO_RESIZE_FIT_NO_ENLARGE) || w > box_width || h > box_height) fit_size(a.width, a.height, box_width, box_height, &w, &h);
+        fitted[i] = lay_out(at, w, h, a.color_type, &end); // (at most 2^16 images of 2^50 bytes: below 2^64)
     }
     if (end > (uint64_t{1} << 62)) return fail(PIXO_ERR_COMPRESSION, "Compression error: batch output too large");
-    std::copy(fitted.begin(), fitted.end(), dst_images);
+    report(fitted, dst_images);
     *total = static_cast<size_t>(end);
     return PIXO_OK;
 }
@@ -561,10 +527,7 @@ int pixo_hip_resize_images_device(const void *d_src, const pixo_png_image *src_i
     if (rc) return rc;
     PIXO_REQUIRE(d_src);
     PIXO_REQUIRE(d_dst);
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return resize_images_on_device(*c, static_cast<const uint8_t *>(d_src), src_images, static_cast<uint8_t *>(d_dst), dst_images, batch, algorithm, s);
 }
 
@@ -583,16 +546,7 @@ int pixo_hip_resize_images(const uint8_t *data, size_t data_len, const pixo_png_
     uint8_t *block = alloc_file(static_cast<size_t>(dst_end));
     if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
     rc = resize_images_on_device(c, c.rb_in.as<uint8_t>(), src_images, c.rb_out.as<uint8_t>(), dst_images, batch, algorithm, c.stream);
-    if (!rc) {
-        const hipError_t e = hipMemcpyAsync(block, c.rb_out.p, static_cast<size_t>(dst_end), hipMemcpyDeviceToHost, c.stream);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
-    }
-    const hipError_t e = hipStreamSynchronize(c.stream); // (also after a failure: the upload reads the caller's pixels)
-    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-    if (rc) { free_file(block); return rc; }
-    *out = block;
-    *out_len = static_cast<size_t>(dst_end);
-    return PIXO_OK;
+    return download_block(c, rc, block, c.rb_out.p, static_cast<size_t>(dst_end), out, out_len);
 }
 
 int pixo_hip_debug_resize_images_plan(const pixo_png_image *src_images, const pixo_png_image *dst_images, uint32_t batch, uint8_t algorithm,
@@ -613,8 +567,7 @@ int pixo_hip_debug_resize_images_plan(const pixo_png_image *src_images, const pi
     PIXO_REQUIRE(launches_second);
     ImagesPlan p;
     if ((rc = resize_images_plan(src_images, dst_images, batch, algorithm, p))) return rc;
-    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
-    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    p.sub_first.report(sub_first, sub_count);
     std::copy(p.mid_at.begin(), p.mid_at.end(), mid_at);
     std::copy(p.use_lds.begin(), p.use_lds.end(), use_lds);
     std::copy(p.tiles_first.begin(), p.tiles_first.end(), tiles_first);
@@ -632,10 +585,7 @@ int pixo_hip_resize_batch_device(const pixo_resize_source *sources, uint32_t bat
     int rc = resize_batch_checks(sources, batch, dst_width, dst_height, color_type, algorithm, &out_bytes);
     if (rc || (rc = resize_batch_pixels_given(sources, batch))) return rc;
     PIXO_REQUIRE(d_dst);
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return resize_batch_on_device(*c, sources, batch, dst_width, dst_height, color_type, algorithm, static_cast<uint8_t *>(d_dst), s);
 }
 
@@ -661,16 +611,7 @@ int pixo_hip_resize_batch(const pixo_resize_source *sources, uint32_t batch, uin
     uint8_t *block = alloc_file(all_out);
     if (!block) return fail(PIXO_ERR_COMPRESSION, "Compression error: out of host memory");
     rc = resize_batch_on_device(c, on_device.data(), batch, dst_width, dst_height, color_type, algorithm, c.rb_out.as<uint8_t>(), c.stream);
-    if (!rc) {
-        const hipError_t e = hipMemcpyAsync(block, c.rb_out.p, all_out, hipMemcpyDeviceToHost, c.stream);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
-    }
-    const hipError_t e = hipStreamSynchronize(c.stream); // (also after a failure: the uploads read the caller's pixels)
-    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-    if (rc) { free_file(block); return rc; }
-    *out = block;
-    *out_len = all_out;
-    return PIXO_OK;
+    return download_block(c, rc, block, c.rb_out.p, all_out, out, out_len);
 }
 
 int pixo_hip_debug_resize_batch_plan(const pixo_resize_source *sources, uint32_t batch, uint32_t dst_width, uint32_t dst_height, uint8_t color_type,
@@ -687,8 +628,7 @@ int pixo_hip_debug_resize_batch_plan(const pixo_resize_source *sources, uint32_t
     PIXO_REQUIRE(axis_tables);
     BatchPlan p;
     if ((rc = resize_batch_plan(sources, batch, dst_width, dst_height, bytes_per_pixel(color_type), algorithm, p))) return rc;
-    std::copy(p.sub_first.begin(), p.sub_first.end(), sub_first);
-    *sub_count = static_cast<uint32_t>(p.sub_first.size() - 1);
+    p.sub_first.report(sub_first, sub_count);
     std::copy(p.mid_at.begin(), p.mid_at.end(), mid_at);
     std::copy(p.use_lds.begin(), p.use_lds.end(), use_lds);
     *axis_tables = static_cast<uint32_t>(p.axes.size());
@@ -729,9 +669,7 @@ int pixo_hip_resize(const uint8_t *data, size_t data_len, const pixo_resize_opti
 int pixo_hip_resize_image(const uint8_t *data, size_t data_len, uint32_t src_width, uint32_t src_height, uint32_t dst_width,
                           uint32_t dst_height, uint8_t color_type, uint8_t algorithm, uint8_t **out, size_t *out_len)
 { // wasm.rs:183-201: color_type_from_u8, then resize_algorithm_from_u8, then the builder
-    if (color_type > PIXO_RGBA)
-        return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid color type: " + std::to_string(color_type) +
-                                                    ". Expected 0 (Gray), 1 (GrayAlpha), 2 (Rgb), or 3 (Rgba)");
+    if (color_type > PIXO_RGBA) return bad_color_type(color_type);
     if (algorithm > PIXO_RESIZE_LANCZOS3)
         return fail(PIXO_ERR_INVALID_COLOR_ARG, "Invalid resize algorithm: " + std::to_string(algorithm) +
                                                     ". Expected 0 (Nearest), 1 (Bilinear), or 2 (Lanczos3)");
@@ -749,10 +687,7 @@ int pixo_hip_resize_device(const void *d_src, const pixo_resize_options *options
     if (rc) return rc;
     PIXO_REQUIRE(d_src);
     PIXO_REQUIRE(d_dst);
-    Context *c = nullptr;
-    if ((rc = context_on_current_device(&c))) return rc; // (records the producer stream's event)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (c->producer_done) HIP_TRY(hipStreamWaitEvent(s, c->producer_done, 0));
+    PIXO_CALLER_STREAM_CONTEXT(c, s, stream);
     return resize_on_device(*c, static_cast<const uint8_t *>(d_src), *options, static_cast<uint8_t *>(d_dst), s);
 }
 

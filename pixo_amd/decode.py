@@ -11,6 +11,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._images import flat_u8, image_bytes
 from .color import ColorType
 
 
@@ -24,7 +25,7 @@ class PngImage:
 
 
 def _file(data) -> np.ndarray:
-    return np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+    return flat_u8(data if isinstance(data, np.ndarray) else bytes(data))
 
 
 def pass_rows() -> int:
@@ -98,10 +99,6 @@ def _files_c(files):
     return arr, held
 
 
-def _bytes_of(im) -> int:
-    return im.width * im.height * ColorType(im.color_type).bytes_per_pixel()
-
-
 def decode_png_batch_info(files):
     """([(width, height, ColorType, offset)], total) of the block decode_png_batch_device writes: image i at `offset`, every
     offset a multiple of 16, `total` the end of the last image.  The walks and their checks only — no inflate, no GPU."""
@@ -122,7 +119,7 @@ def decode_png_batch(files, one_thread=False, device_inflate=False) -> list:
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     _lib.check(L.pixo_hip_png_decode_batch(arr, len(held), _flags(one_thread, device_inflate), C.byref(out), C.byref(n), images))
     block = _lib.take(L, out, n)
-    return [PngImage(im.width, im.height, block[im.offset:im.offset + _bytes_of(im)], ColorType(im.color_type)) for im in images[:len(held)]]
+    return [PngImage(im.width, im.height, block[im.offset:im.offset + image_bytes(im)], ColorType(im.color_type)) for im in images[:len(held)]]
 
 
 def decode_png_batch_device(files, out=None, stream=None, one_thread=False, device_inflate=False) -> list:
@@ -143,9 +140,9 @@ def decode_png_batch_device(files, out=None, stream=None, one_thread=False, devi
     rc = L.pixo_hip_png_decode_batch_device(arr, len(held), _flags(one_thread, device_inflate), out.data_ptr(), _lib.nbytes(out), images,
                                             C.c_void_p(stream) if stream else None)
     last = images[len(held) - 1] if held else None
-    _lib.check(rc, needed=last.offset + _bytes_of(last) if rc == -9 else None)
+    _lib.check(rc, needed=last.offset + image_bytes(last) if rc == -9 else None)
     flat = out.reshape(-1)
-    return [(flat[im.offset:im.offset + _bytes_of(im)].view(im.height, im.width, ColorType(im.color_type).bytes_per_pixel()), ColorType(im.color_type))
+    return [(flat[im.offset:im.offset + image_bytes(im)].view(im.height, im.width, ColorType(im.color_type).bytes_per_pixel()), ColorType(im.color_type))
             for im in images[:len(held)]]
 
 
@@ -287,7 +284,7 @@ def decode_jpeg_batch(files, one_thread=False) -> list:
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     _lib.check(L.pixo_hip_jpeg_decode_batch(arr, len(held), _flags(one_thread, False), C.byref(out), C.byref(n), images))
     block = _lib.take(L, out, n)
-    return [JpegImage(im.width, im.height, block[im.offset:im.offset + _bytes_of(im)], ColorType(im.color_type)) for im in images[:len(held)]]
+    return [JpegImage(im.width, im.height, block[im.offset:im.offset + image_bytes(im)], ColorType(im.color_type)) for im in images[:len(held)]]
 
 
 def decode_jpeg_batch_device(files, out=None, stream=None, one_thread=False, records=False):
@@ -308,9 +305,9 @@ def decode_jpeg_batch_device(files, out=None, stream=None, one_thread=False, rec
     rc = L.pixo_hip_jpeg_decode_batch_device(arr, len(held), _flags(one_thread, False), out.data_ptr(), _lib.nbytes(out), images,
                                              C.c_void_p(stream) if stream else None)
     last = images[len(held) - 1] if held else None
-    _lib.check(rc, needed=last.offset + _bytes_of(last) if rc == -9 else None)
+    _lib.check(rc, needed=last.offset + image_bytes(last) if rc == -9 else None)
     flat = out.reshape(-1)
-    views = [(flat[im.offset:im.offset + _bytes_of(im)].view(im.height, im.width, ColorType(im.color_type).bytes_per_pixel()), ColorType(im.color_type))
+    views = [(flat[im.offset:im.offset + image_bytes(im)].view(im.height, im.width, ColorType(im.color_type).bytes_per_pixel()), ColorType(im.color_type))
              for im in images[:len(held)]]
     return (views, out, images) if records else views
 

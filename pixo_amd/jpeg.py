@@ -25,6 +25,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from ._images import check_block, flat_u8, image_records, images_block
 from .color import ColorType
 from . import error
 from .error import from_status
@@ -132,10 +133,10 @@ class JpegOptionsBuilder:
 
 
 def _as_u8(data):
-    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
-    if a.dtype != np.uint8:
+    """flat_u8 for pixels: an array of another type is refused, not converted"""
+    if isinstance(data, np.ndarray) and data.dtype != np.uint8:
         raise TypeError("pixel data must be bytes-like / uint8")
-    return np.ascontiguousarray(a).reshape(-1)
+    return flat_u8(data if isinstance(data, np.ndarray) else memoryview(data))
 
 
 def encode(data, options: JpegOptions) -> bytes:
@@ -346,11 +347,10 @@ def encode_batch_device_into(arena, d_pixels, options: JpegOptions, batch: int):
 # or the (tensor, ColorType) views of `decode.decode_png_batch_device` / `resize.resize_images_device`.
 
 def _records(images, block):
-    from . import png
-    arr, n, base = png._image_records(images)
+    arr, n, base = image_records(images)
     if block is not None or base is not None:
-        block = png._images_block(block, base)
-        png._check_images_block(block, arr, n)
+        block = images_block(block, base)
+        check_block("images", block, arr, n)
     return arr, n, block
 
 
@@ -381,7 +381,7 @@ def encode_images(block, records, options: JpegOptions):
     """The same for a block in host memory (bytes or a numpy uint8 array) -> list of JPEG files (bytes)."""
     L = _lib.load()
     arr, n, _ = _records(records, None)
-    px = np.ascontiguousarray(block if not isinstance(block, (bytes, bytearray)) else np.frombuffer(block, np.uint8), dtype=np.uint8).reshape(-1)
+    px = flat_u8(block)
     files, lens, oc = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))(), options._c()
     _lib.check(L.pixo_hip_jpeg_encode_images(px.ctypes.data, px.size, arr, n, C.byref(oc), files, lens))
     return _lib.take_files(L, files, lens, n)

@@ -8,6 +8,7 @@ import enum
 import numpy as np
 
 from . import _lib
+from ._images import check_block, flat_u8, image_records, images_block
 from .color import ColorType
 
 
@@ -284,7 +285,7 @@ def zlib_compress(data, level=6, bpp=0, row=0, effort=0):
     match search tries besides 1 and its hash table's (0: none); effort: 0 the default finder, 1 the high effort that
     `EFFORT_HIGH` selects for whole files (anything else raises)."""
     L = _lib.load()
-    a = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    a = flat_u8(data)
     p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     rc = L.pixo_hip_zlib_compress_effort(a.ctypes.data if a.size else None, a.size, level, bpp, row, effort, C.byref(p), C.byref(n))
     _lib.check(rc)
@@ -386,48 +387,6 @@ IMAGES_ROUTES = {"PNG_IMAGES": 45, "PNG_IMAGES_FILTER": 46}
 ROUTE_PNG_IMAGES, ROUTE_PNG_IMAGES_FILTER = (1 << b for b in IMAGES_ROUTES.values())
 
 
-def _image_records(images):
-    """`images` as (a PngImageC array, its length, the tensor the offsets count from or None): a PngImageC array as it is; a
-    list of (width, height, ColorType, offset) as `decode.decode_png_batch_info` returns; or the list of (tensor, ColorType)
-    views `decode.decode_png_batch_device` returns, whose offsets are the tensors' addresses relative to the first."""
-    if isinstance(images, C.Array) and getattr(images, "_type_", None) is _lib.PngImageC:
-        return images, len(images), None
-    n = len(images)
-    arr = (_lib.PngImageC * max(n, 1))()
-    base = None
-    for i, im in enumerate(images):
-        if len(im) == 2 and hasattr(im[0], "data_ptr"):
-            t, ct = im
-            if base is None:
-                base = t
-            at = t.data_ptr() - base.data_ptr()
-            if at < 0:
-                raise ValueError("image %d lies in front of the first: the offsets count from the first view" % i)
-            arr[i].offset, arr[i].width, arr[i].height, arr[i].color_type = at, t.shape[1], t.shape[0], int(ct)
-        else:
-            w, h, ct, at = im
-            arr[i].offset, arr[i].width, arr[i].height, arr[i].color_type = at, w, h, int(ct)
-    return arr, n, base
-
-
-def _images_block(block, base):
-    """(the views of a decode batch carry their block with them: the first view's address is the block's)"""
-    if block is None:
-        if base is None:
-            raise ValueError("no block: pass the tensor the images' offsets count from")
-        return base.data_ptr()  # (the first view says nothing of the block's size: the address alone)
-    return block
-
-
-def _check_images_block(block, arr, n):
-    """(the C entries take no length for a device block: whatever carries a size is checked here)"""
-    if hasattr(block, "numel") and n:
-        need = max(arr[i].offset + arr[i].width * arr[i].height * (arr[i].color_type + 1) for i in range(n))
-        have = block.numel() * block.element_size()
-        if have < need:
-            raise ValueError("the images end at byte %d, the tensor holds %d" % (need, have))
-
-
 def encode_images_device(block, images, options):
     """Images of individual sizes and colour types anywhere in one block in HBM (torch tensor / raw pointer) -> list of PNG
     files (bytes), file i byte for byte what `encode_device` returns for image i with `options` at its width, height and
@@ -435,9 +394,9 @@ def encode_images_device(block, images, options):
     offset), or the (tensor, ColorType) views of `decode.decode_png_batch_device` — then `block` may be None.
     `options.quantization`, when not Off, is passed on."""
     L = _lib.load()
-    arr, n, base = _image_records(images)
-    block = _images_block(block, base)
-    _check_images_block(block, arr, n)
+    arr, n, base = image_records(images)
+    block = images_block(block, base)
+    check_block("images", block, arr, n)
     files, lens, o = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))(), options.to_c()
     _lib.check(L.pixo_hip_png_encode_images_device(_lib.ptr(block), arr, n, C.byref(o), _quant_arg(options), files, lens))
     return _lib.take_files(L, files, lens, n)
@@ -448,9 +407,9 @@ def encode_images_device_into(arena, block, images, options):
     uint8 array, or None for a size query).  Returns (offsets, lens); raises BufferTooSmall (`.needed`, `.offsets`, `.lens`)
     when the files do not fit."""
     L = _lib.load()
-    arr, n, base = _image_records(images)
-    block = _images_block(block, base)
-    _check_images_block(block, arr, n)
+    arr, n, base = image_records(images)
+    block = images_block(block, base)
+    check_block("images", block, arr, n)
     o, q = options.to_c(), _quant_arg(options)
     return _lib.into_arena(lambda ptr, cap, offsets, lens: L.pixo_hip_png_encode_images_device_into(
         _lib.ptr(block), arr, n, C.byref(o), q, ptr, cap, offsets, lens), arena, n)
@@ -459,8 +418,8 @@ def encode_images_device_into(arena, block, images, options):
 def encode_images(block_bytes, images, options):
     """The same for a block in host memory (what `decode.decode_png_batch` works from) -> list of PNG files (bytes)."""
     L = _lib.load()
-    arr, n, _ = _image_records(images)
-    px = np.ascontiguousarray(block_bytes if not isinstance(block_bytes, (bytes, bytearray)) else np.frombuffer(block_bytes, np.uint8), dtype=np.uint8).reshape(-1)
+    arr, n, _ = image_records(images)
+    px = flat_u8(block_bytes)
     files, lens, o = (C.POINTER(C.c_uint8) * max(n, 1))(), (C.c_size_t * max(n, 1))(), options.to_c()
     _lib.check(L.pixo_hip_png_encode_images(px.ctypes.data, px.size, arr, n, C.byref(o), _quant_arg(options), files, lens))
     return _lib.take_files(L, files, lens, n)
@@ -472,7 +431,7 @@ def encode_images_plan(images, options, alignment=0) -> dict:
     reference's rules make of the strategy for each image) and `filter_launches` (summed over the sub-batches) for a block
     whose address is `alignment` modulo 16."""
     L = _lib.load()
-    arr, n, _ = _image_records(images)
+    arr, n, _ = image_records(images)
     sub_first, subs, launches = (C.c_uint32 * (n + 1))(), C.c_uint32(), C.c_uint32()
     way, run, o = (C.c_uint8 * max(n, 1))(), (C.c_uint8 * max(n, 1))(), options.to_c()
     _lib.check(L.pixo_hip_debug_png_encode_images_plan(arr, n, C.byref(o), _quant_arg(options), alignment, sub_first, C.byref(subs), way, run,

@@ -8,6 +8,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._images import bpp as _bpp, check_block, flat_u8, image_bytes, image_records, images_block, pair
 from .color import ColorType
 
 MAX_DIMENSION = 1 << 24
@@ -67,14 +68,10 @@ class ResizeOptionsBuilder:
         return ResizeOptions(**self._v)
 
 
-def _flat(data) -> np.ndarray:
-    return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-
-
 def resize(data, options: ResizeOptions) -> bytes:
     """Host pixels -> the resized pixels."""
     L = _lib.load()
-    px = _flat(data)
+    px = flat_u8(data)
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     o = options._c()
     rc = L.pixo_hip_resize(px.ctypes.data, px.size, C.byref(o), C.byref(out), C.byref(n))
@@ -86,7 +83,7 @@ def resize_into(output, data, options: ResizeOptions) -> int:
     """Writes into `output` (a writable uint8 numpy array); returns the bytes written.  BufferTooSmall carries the bytes
     needed in `.needed`."""
     L = _lib.load()
-    px = _flat(data)
+    px = flat_u8(data)
     assert output.dtype == np.uint8 and output.flags["C_CONTIGUOUS"] and output.flags["WRITEABLE"]
     n = C.c_size_t()
     o = options._c()
@@ -103,11 +100,6 @@ def resize_device(d_src, options: ResizeOptions, d_dst, stream=0) -> None:
     o = options._c()
     rc = L.pixo_hip_resize_device(_lib.ptr(d_src), C.byref(o), _lib.ptr(d_dst), C.c_void_p(stream) if stream else None)
     _lib.check(rc)
-
-
-def _bpp(color_type) -> int:
-    """Bytes per pixel; 0 for a code that is no colour type (the library refuses it with its own message: no size to check)"""
-    return int(color_type) + 1 if 0 <= int(color_type) <= 3 else 0
 
 
 def _sources_c(sources, bpp, address):
@@ -144,7 +136,7 @@ def resize_batch(sources, dst_width, dst_height, color_type, algorithm) -> list:
     """Host pixels: a list of (pixels, width, height) -> a list of bytes, image i what `resize` makes of source i."""
     L = _lib.load()
     bpp = _bpp(color_type)
-    held = [(_flat(px), w, h) for px, w, h in sources]
+    held = [(flat_u8(px), w, h) for px, w, h in sources]
     arr = _sources_c(held, bpp, _lib.address)
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     rc = L.pixo_hip_resize_batch(arr, len(held), dst_width, dst_height, int(color_type), int(algorithm), C.byref(out), C.byref(n))
@@ -175,22 +167,13 @@ def resize_batch_plan(sizes, dst_width, dst_height, color_type, algorithm) -> di
 FIT_NO_ENLARGE = 1  # PIXO_RESIZE_FIT_NO_ENLARGE
 
 
-def _records(images):
-    from .png import _image_records
-    return _image_records(images)
-
-
-def _records_end(arr, n) -> int:
-    return max(arr[i].offset + arr[i].width * arr[i].height * _bpp(arr[i].color_type) for i in range(n)) if n else 0
-
-
 def fit_images(images, box_width, box_height, no_enlarge=False):
     """([(width, height, ColorType, offset)], total): every image at the largest size of its proportions inside box_width x
     box_height (the reference front end's `calculateResizeDimensions`), in its own colour type, laid out as a decode batch
     lays its block out — every offset a multiple of 16, `total` the end of the last image.  `no_enlarge`: an image that fits
     the box keeps its size.  Sizes only: no GPU."""
     L = _lib.load()
-    arr, n, _ = _records(images)
+    arr, n, _ = image_records(images)
     out, total = (_lib.PngImageC * max(n, 1))(), C.c_size_t()
     _lib.check(L.pixo_hip_resize_images_fit(arr, n, box_width, box_height, FIT_NO_ENLARGE if no_enlarge else 0, out, C.byref(total)))
     return [(im.width, im.height, ColorType(im.color_type), im.offset) for im in out[:n]], total.value
@@ -201,18 +184,11 @@ def resize_images_device(d_src, src_images, d_dst, dst_images, algorithm, stream
     carry their block) -> `dst_images[i]`'s size at its offset in `d_dst`, byte for byte what `resize_device` writes for that
     pair; the bytes between destinations are left as they are.  Destinations must not overlap each other or a source (not
     checked).  One launch per pass and pixel size whatever the number of images.  Enqueue only, ordered like `resize_device`."""
-    from .png import _images_block
     L = _lib.load()
-    src, n, base = _records(src_images)
-    dst, m, _ = _records(dst_images)
-    if m != n:
-        raise ValueError("%d sources, %d destinations" % (n, m))
-    d_src = _images_block(d_src, base)
-    for what, block, arr in (("sources", d_src, src), ("destinations", d_dst, dst)):
-        if hasattr(block, "numel") and n and all(_bpp(arr[i].color_type) for i in range(n)):
-            need, have = _records_end(arr, n), _lib.nbytes(block)
-            if have < need:
-                raise ValueError("the %s end at byte %d, the tensor holds %d" % (what, need, have))
+    src, dst, n, base = pair(src_images, dst_images)
+    d_src = images_block(d_src, base)
+    check_block("sources", d_src, src, n)
+    check_block("destinations", d_dst, dst, n)
     rc = L.pixo_hip_resize_images_device(_lib.ptr(d_src), src, _lib.ptr(d_dst), dst, n, int(algorithm), C.c_void_p(stream) if stream else None)
     _lib.check(rc)
 
@@ -221,15 +197,12 @@ def resize_images(block_bytes, src_images, dst_images, algorithm) -> list:
     """The same for a block in host memory (what `decode.decode_png_batch` works from) -> a list of bytes, image i at
     `dst_images[i]`'s size."""
     L = _lib.load()
-    src, n, _ = _records(src_images)
-    dst, m, _ = _records(dst_images)
-    if m != n:
-        raise ValueError("%d sources, %d destinations" % (n, m))
-    px = _flat(np.frombuffer(block_bytes, np.uint8) if isinstance(block_bytes, (bytes, bytearray)) else block_bytes)
+    src, dst, n, _ = pair(src_images, dst_images)
+    px = flat_u8(block_bytes)
     out, out_len = C.POINTER(C.c_uint8)(), C.c_size_t()
     _lib.check(L.pixo_hip_resize_images(px.ctypes.data, px.size, src, dst, n, int(algorithm), C.byref(out), C.byref(out_len)))
     block = _lib.take(L, out, out_len)
-    return [block[im.offset:im.offset + im.width * im.height * _bpp(im.color_type)] for im in dst[:n]]
+    return [block[im.offset:im.offset + image_bytes(im)] for im in dst[:n]]
 
 
 def resize_images_plan(src_images, dst_images, algorithm) -> dict:
@@ -237,10 +210,7 @@ def resize_images_plan(src_images, dst_images, algorithm) -> dict:
     `axis_tables` as `resize_batch_plan`; `tiles_first` / `tiles_second` (each image's workgroups in the point or horizontal
     pass and in the vertical pass) and `launches_first` / `launches_second` (the passes' launches summed over the sub-batches)."""
     L = _lib.load()
-    src, n, _ = _records(src_images)
-    dst, m, _ = _records(dst_images)
-    if m != n:
-        raise ValueError("%d sources, %d destinations" % (n, m))
+    src, dst, n, _ = pair(src_images, dst_images)
     sub_first, mid_at, use_lds = (C.c_uint32 * (n + 1))(), (C.c_uint64 * max(n, 1))(), (C.c_uint8 * max(n, 1))()
     t1, t2 = (C.c_uint32 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
     subs, tables, l1, l2 = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
@@ -254,7 +224,7 @@ def resize_images_plan(src_images, dst_images, algorithm) -> dict:
 def resize_image(data, src_width, src_height, dst_width, dst_height, color_type: int, algorithm: int) -> bytes:
     """The wasm export `resizeImage`: seven flat arguments, its error strings."""
     L = _lib.load()
-    px = _flat(data)
+    px = flat_u8(data)
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
     if not (0 <= color_type <= 255 and 0 <= algorithm <= 255):
         raise ValueError("color_type and algorithm are u8")
