@@ -657,13 +657,15 @@ struct JpegImage {
 }
 [[nodiscard]] inline JpegImage decode_jpeg(const std::vector<uint8_t> &data) { return decode_jpeg(data.data(), data.size()); }
 // Batches: N files -> N images, image i what decode_jpeg makes of file i.  one_thread: the entropy decodes run on the calling
-// thread instead of the library's small pool.
-[[nodiscard]] inline std::vector<JpegImage> decode_jpeg_batch(const std::vector<pixo_png_file> &files, bool one_thread = false)
+// thread instead of the library's small pool.  device_entropy (opt-in): the Huffman decode runs on the device; the host decodes
+// again only what the device does not vouch for, and the images and refusals are the same (PIXO_DECODE_DEVICE_ENTROPY).
+[[nodiscard]] inline std::vector<JpegImage> decode_jpeg_batch(const std::vector<pixo_png_file> &files, bool one_thread = false, bool device_entropy = false)
 {
     uint8_t *block = nullptr;
     size_t n = 0;
     std::vector<pixo_png_image> images(files.size() ? files.size() : 1);
-    const int rc = pixo_hip_jpeg_decode_batch(files.data(), (uint32_t)files.size(), one_thread ? PIXO_DECODE_ONE_THREAD : 0u, &block, &n, images.data());
+    const uint32_t flags = (one_thread ? PIXO_DECODE_ONE_THREAD : 0u) | (device_entropy ? PIXO_DECODE_DEVICE_ENTROPY : 0u);
+    const int rc = pixo_hip_jpeg_decode_batch(files.data(), (uint32_t)files.size(), flags, &block, &n, images.data());
     if (rc != PIXO_OK) throw Error::from_status(rc);
     struct Block { // (released also when a copy below throws)
         uint8_t *p;
@@ -680,11 +682,11 @@ struct JpegImage {
 // ... into caller storage on the device (enqueue only on `stream`): image i at d_pixels + the returned records' offset, the
 // records what resize::fit_images, resize::resize_images_device and jpeg::encode_images_device take unchanged.
 inline std::vector<pixo_png_image> decode_jpeg_batch_device(const std::vector<pixo_png_file> &files, void *d_pixels, size_t capacity,
-                                                            void *stream = nullptr, bool one_thread = false)
+                                                            void *stream = nullptr, bool one_thread = false, bool device_entropy = false)
 {
     std::vector<pixo_png_image> images(files.size() ? files.size() : 1);
-    const int rc = pixo_hip_jpeg_decode_batch_device(files.data(), (uint32_t)files.size(), one_thread ? PIXO_DECODE_ONE_THREAD : 0u, d_pixels, capacity,
-                                                     images.data(), stream);
+    const uint32_t flags = (one_thread ? PIXO_DECODE_ONE_THREAD : 0u) | (device_entropy ? PIXO_DECODE_DEVICE_ENTROPY : 0u);
+    const int rc = pixo_hip_jpeg_decode_batch_device(files.data(), (uint32_t)files.size(), flags, d_pixels, capacity, images.data(), stream);
     if (rc != PIXO_OK) throw Error::from_status(rc);
     images.resize(files.size());
     return images;

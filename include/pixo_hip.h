@@ -684,6 +684,22 @@ typedef struct pixo_png_image {
  * At most 11 launches a sub-batch.  The single-file entries never inflate on the device: one stream is one wavefront. */
 #define PIXO_DECODE_DEVICE_INFLATE 2u
 
+/* flags bit 2 (opt-in; the JPEG batch entries only, the PNG entries ignore it as the JPEG entries ignore bit 1; the single JPEG
+ * entries take no flags and keep the host decoder): the Huffman decode of the scans runs ON THE DEVICE (jpeg_entropy_dec.hip).
+ * Per sub-batch the raw scans and one record per file go up in one copy instead of the coefficients; a lane decodes a
+ * subsequence of 128 scan bytes, exit states are handed from lane to lane until nothing changes (some launches, with a host wait
+ * for a counter behind each; at most 132 rounds a file), then one launch each verifies the chains, writes the coefficients and
+ * sums the DC differences, the status records come down, and the decode launches follow on coefficients that never left the
+ * device.  The device VOUCHES for a file or does not; it never refuses one.  Every file it does not vouch for is decoded again
+ * by the host's decoder, whose coefficients replace the device's at that file's place — or whose refusal is the call's.  The
+ * host decodes from the start: files with a restart interval, files without MCUs, scans below 16 bytes and scans of 2^28 bytes
+ * and more.  Image i stays byte for byte what the entry returns without the flag, and a refused batch is refused with the same
+ * status and words, the failing file with the lowest index answering.  What changes in the contract, under this flag only:
+ * phase 1 is still complete before anything is enqueued, but phase-2 refusals come AFTER the entropy launches of their
+ * sub-batch, and with several sub-batches after earlier sub-batches' images were written: d_pixels is unspecified after a
+ * refusal.  The calls wait on the host at least twice per sub-batch.  The sub-batch limit counts records and scans too. */
+#define PIXO_DECODE_DEVICE_ENTROPY 4u
+
 /* The layout alone: `images` (batch entries) and *total (the end of the last image, not rounded) from the walks of the files — no
  * inflate, no GPU.  What a caller of pixo_hip_png_decode_batch_device allocates from. */
 int pixo_hip_png_decode_batch_info(const pixo_png_file *files, uint32_t batch, pixo_png_image *images, size_t *total);
@@ -783,7 +799,8 @@ int pixo_hip_jpeg_decode_batch_info(const pixo_png_file *files, uint32_t batch, 
  * Enqueue only; the one host wait is for the calling thread's previous JPEG decode job.  Checks as
  * pixo_hip_png_decode_batch_device, in its order, all before anything is enqueued: phase 1 the walks (a refusal leaves `images`
  * untouched), phase 2 the entropy decodes; the failing file with the lowest index answers, " (image i)" appended, whatever the
- * thread count.  PIXO_DECODE_DEVICE_INFLATE is ignored. */
+ * thread count.  PIXO_DECODE_DEVICE_INFLATE is ignored; PIXO_DECODE_DEVICE_ENTROPY (opt-in): the Huffman decode on the device,
+ * described at the flag. */
 int pixo_hip_jpeg_decode_batch_device(const pixo_png_file *files, uint32_t batch, uint32_t flags, void *d_pixels, size_t capacity,
                                       pixo_png_image *images, void *stream);
 /* The same with the block in HOST memory, released with pixo_hip_free. */
@@ -806,8 +823,31 @@ int pixo_hip_debug_jpeg_decode_coefficients(const uint8_t *file, size_t len, uin
 void pixo_hip_jpeg_decode_tile_mcus(uint32_t *mcus_x, uint32_t *mcus_y);
 /* MEASUREMENT only (tools/jpeg_decode_batch_timing.py): pixo_hip_jpeg_decode_batch with its legs timed — ms[0] the entropy
  * decodes (host clock), [1] uploads, [2] kernels, [3] the copy of the block to the host (HIP events, summed over the
- * sub-batches), [4] the whole call.  The block is released again. */
+ * sub-batches), [4] the whole call.  The block is released again.  With PIXO_DECODE_DEVICE_ENTROPY [0] is the host's share
+ * (building records, reading status records, decoding again what the device did not vouch for), [1] the uploads of the
+ * coefficients the host decoded; the device leg: pixo_hip_debug_jpeg_entropy_last. */
 int pixo_hip_debug_jpeg_decode_batch_timed(const pixo_png_file *files, uint32_t batch, uint32_t flags, double ms[5]);
+
+/* The device Huffman decode's geometry (tests place their boundaries by it): bytes of a subsequence, subsequences a workgroup
+ * owns, the round cap of a call, the shortest scan that goes to the device.  Any pointer may be null. */
+void pixo_hip_jpeg_entropy_geometry(uint32_t *sub_bytes, uint32_t *group_subs, uint32_t *round_cap, uint32_t *min_scan_bytes);
+/* Tests, host only (no GPU): what the batch entries decide under `flags` — on_device[i]: 1 when PIXO_DECODE_DEVICE_ENTROPY is
+ * set and file i's scan would be decoded on the device, 0 when the host decodes it from the start; the sub-batches as
+ * pixo_hip_debug_jpeg_decode_batch_plan reports them (which honours the flag too). */
+int pixo_hip_debug_jpeg_entropy_plan(const pixo_png_file *files, uint32_t batch, uint32_t flags, uint8_t *on_device, uint32_t *sub_first,
+                                     uint32_t *sub_count);
+/* Tests: the device Huffman decode alone, all files in one sub-batch, no host decoder behind it.  Per file four words in
+ * info: vouched (0 / 1), why not (0 vouched, 1 a dead state or a flawed lane in the chain, 2 the states had not settled at the round cap, 3 the
+ * chain ends in front of the last block, 4 the host decodes this file from the start), subsequences, rounds used.  The
+ * coefficients of component `component` of every vouched file that has one, in the format of
+ * pixo_hip_debug_jpeg_decode_coefficients, at out + out_at[i] (int16 values; the caller sizes them by that entry); other files'
+ * places are left alone.  round_cap: 0 for the library's, or a smaller one. */
+int pixo_hip_debug_jpeg_entropy_batch(const pixo_png_file *files, uint32_t batch, uint32_t component, uint32_t round_cap, int16_t *out,
+                                      const uint64_t *out_at, uint32_t *info);
+/* MEASUREMENT (tools/jpeg_entropy_timing.py): of the calling thread's last batch call with PIXO_DECODE_DEVICE_ENTROPY — the
+ * device leg in ms (HIP events from the scans' upload to the DC launch, the host waits between the launches included, summed
+ * over the sub-batches), the most rounds a file used, the files sent to the device, the files the host decoded again. */
+void pixo_hip_debug_jpeg_entropy_last(double *device_ms, uint32_t *rounds, uint32_t *files_device, uint32_t *files_redone);
 
 /* ---- PNG encode of images of individual sizes and colour types, anywhere in one block ---- */
 

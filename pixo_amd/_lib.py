@@ -179,6 +179,10 @@ SIGNATURES = {
     "pixo_hip_debug_jpeg_decode_coefficients": _sig(_vp, _sz, _u32, _vp, _sz, _u32p, _u32p, optional=True),
     "pixo_hip_jpeg_decode_tile_mcus": _sig(_u32p, _u32p, ret=None, optional=True),
     "pixo_hip_debug_jpeg_decode_batch_timed": _sig(_pfilep, _u32, _u32, C.POINTER(_dbl), optional=True),
+    "pixo_hip_jpeg_entropy_geometry": _sig(_u32p, _u32p, _u32p, _u32p, ret=None, optional=True),
+    "pixo_hip_debug_jpeg_entropy_plan": _sig(_pfilep, _u32, _u32, _u8p, _u32p, _u32p, optional=True),
+    "pixo_hip_debug_jpeg_entropy_batch": _sig(_pfilep, _u32, _u32, _u32, _vp, _u64p, _u32p, optional=True),
+    "pixo_hip_debug_jpeg_entropy_last": _sig(C.POINTER(_dbl), _u32p, _u32p, _u32p, ret=None, optional=True),
     "pixo_hip_png_encode_images_device": _sig(_vp, _pimgp, _u32, _poptp, _qoptp, _u8pp, _szp, optional=True),
     "pixo_hip_png_encode_images_device_into": _sig(_vp, _pimgp, _u32, _poptp, _qoptp, _vp, _sz, _szp, _szp, optional=True),
     "pixo_hip_png_encode_images": _sig(_vp, _sz, _pimgp, _u32, _poptp, _qoptp, _u8pp, _szp, optional=True),

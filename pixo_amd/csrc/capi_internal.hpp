@@ -325,6 +325,11 @@ struct Context {
     Buf jd_hrecords{Buf::Mem::Pinned, Buf::Grow::Headroom}; // the records of a call's launches (jpeg_decode_math.h), built here, uploaded from here
     Buf jd_records{Buf::Mem::Device, Buf::Grow::Exact};  // ... on the device
     Buf jd_out{Buf::Mem::Device, Buf::Grow::Exact};      // host entries: the pixels before they go down
+    Buf jd_hscan{Buf::Mem::Pinned, Buf::Grow::Headroom};  // PIXO_DECODE_DEVICE_ENTROPY: a sub-batch's file records (jpeg_entropy_dec_math.h) and raw scans, built here, uploaded from here
+    Buf jd_scan{Buf::Mem::Device, Buf::Grow::Exact};     // ... on the device
+    Buf jd_states{Buf::Mem::Device, Buf::Grow::Headroom}; // ... the lanes' states, block counts and first blocks, the workgroups' border states
+    Buf jd_estatus{Buf::Mem::Device, Buf::Grow::Headroom}; // ... the launches' counters and the files' status records
+    Buf jd_hestatus{Buf::Mem::Pinned, Buf::Grow::Headroom}; // ... copied to the host
     hipEvent_t jd_done = nullptr;                        // the last JPEG decode job (it reads all of the above) has run
 
     // Small results for the host, one field per purpose: pinned, allocated once with the stream (ensure).

@@ -165,7 +165,7 @@ template <class F> void each_buf(Context &c, F &&f)
                    &c.t_raw, &c.t_trail, &c.t_plain, &c.g_flags, &c.g_rank, &c.g_by_rank, &c.h_file, &c.r_in, &c.r_out, &c.r_mid, &c.r_tables,
                    &c.r_stage, &c.rb_in, &c.rb_out, &c.rb_mid, &c.rb_tables, &c.rb_stage, &c.cv_in, &c.cv_out, &c.cv_records, &c.h_cv_records, &c.u_inflated, &c.u_stream, &c.u_rows, &c.u_out, &c.u_tables, &c.h_utables,
                    &c.h_zin, &c.u_zin, &c.u_zout, &c.h_zout, &c.h_uruns, &c.u_runs,
-                   &c.jd_hcoef, &c.jd_coef, &c.jd_hrecords, &c.jd_records, &c.jd_out};
+                   &c.jd_hcoef, &c.jd_coef, &c.jd_hrecords, &c.jd_records, &c.jd_out, &c.jd_hscan, &c.jd_scan, &c.jd_states, &c.jd_estatus, &c.jd_hestatus};
     for (Buf *b : bufs) f(*b);
 }
 } // namespace

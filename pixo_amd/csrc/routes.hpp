@@ -59,6 +59,8 @@ enum : uint64_t {
     RESIZE_IMAGES = 1ull << 47,    // resize images entries: one flat launch per pass and pixel size over all images of a sub-batch (beside the algorithm's bit)
     JPEG_IMAGES = RESIZE_IMAGES << 1, // (bit 48) JPEG encode of images of individual sizes: at least one sub-batch went through the ragged launches (beside TWO_KERNEL, SEGMENTED_TUPLE)
     JPEG_IMAGES_DIRECT = JPEG_IMAGES << 1, // (bit 49) ... and a sub-batch's scans travelled file by file straight into pinned destinations (large files: pool blocks or a pinned arena)
+    JPEG_ENTROPY_DEVICE = JPEG_IMAGES_DIRECT << 1, // (bit 50) JPEG decode batch entries with PIXO_DECODE_DEVICE_ENTROPY: at least one scan of the call was decoded on the device (jpeg_entropy_dec.hip)
+    JPEG_ENTROPY_HOST_REDO = JPEG_ENTROPY_DEVICE << 1, // (bit 51) ... at least one file the device did not vouch for was decoded by the host, whose coefficients or whose refusal stood
 };
 }
 

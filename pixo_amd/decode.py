@@ -86,8 +86,17 @@ INFLATE_ROUTES = {"PNG_INFLATE_DEVICE": 43, "PNG_INFLATE_HOST_REDO": 44}
 INFLATE_OK, INFLATE_FAILED, INFLATE_NEEDS_HOST = 0, 1, 2  # the device verdicts (png_inflate_math.h)
 
 
-def _flags(one_thread, device_inflate) -> int:
-    return (ONE_THREAD if one_thread else 0) | (DEVICE_INFLATE if device_inflate else 0)
+DEVICE_ENTROPY = 4  # PIXO_DECODE_DEVICE_ENTROPY: the JPEG batch entries decode the Huffman scans on the device (opt-in)
+# ... and the bits of that path
+ENTROPY_ROUTES = {"JPEG_ENTROPY_DEVICE": 50, "JPEG_ENTROPY_HOST_REDO": 51}
+ROUTE_JPEG_ENTROPY_DEVICE = 1 << ENTROPY_ROUTES["JPEG_ENTROPY_DEVICE"]
+ROUTE_JPEG_ENTROPY_HOST_REDO = 1 << ENTROPY_ROUTES["JPEG_ENTROPY_HOST_REDO"]
+# why the device does not vouch for a file (jpeg_entropy_dec_math.h; 4: the host decodes the file from the start)
+ENTROPY_VOUCHED, ENTROPY_CHAIN_DEAD, ENTROPY_NOT_SETTLED, ENTROPY_SHORT, ENTROPY_HOST = 0, 1, 2, 3, 4
+
+
+def _flags(one_thread, device_inflate, device_entropy=False) -> int:
+    return (ONE_THREAD if one_thread else 0) | (DEVICE_INFLATE if device_inflate else 0) | (DEVICE_ENTROPY if device_entropy else 0)
 
 
 def _files_c(files):
@@ -275,24 +284,26 @@ def decode_jpeg_batch_info(files):
     return [(im.width, im.height, ColorType(im.color_type), im.offset) for im in images[:len(held)]], total.value
 
 
-def decode_jpeg_batch(files, one_thread=False) -> list:
+def decode_jpeg_batch(files, one_thread=False, device_entropy=False) -> list:
     """JPEG files (bytes) -> [JpegImage] with host pixels, image i what decode_jpeg makes of file i.  The scans are decoded on
-    up to 8 host threads unless `one_thread`."""
+    up to 8 host threads unless `one_thread` — or, with `device_entropy`, on the device (jpeg_entropy_dec.hip); the host then
+    decodes again only the files the device did not vouch for.  The images, and a refusal's status and words, are the same."""
     L = _lib.load()
     arr, held = _files_c(files)
     images = (_lib.PngImageC * max(len(held), 1))()
     out, n = C.POINTER(C.c_uint8)(), C.c_size_t()
-    _lib.check(L.pixo_hip_jpeg_decode_batch(arr, len(held), _flags(one_thread, False), C.byref(out), C.byref(n), images))
+    _lib.check(L.pixo_hip_jpeg_decode_batch(arr, len(held), _flags(one_thread, False, device_entropy), C.byref(out), C.byref(n), images))
     block = _lib.take(L, out, n)
     return [JpegImage(im.width, im.height, block[im.offset:im.offset + image_bytes(im)], ColorType(im.color_type)) for im in images[:len(held)]]
 
 
-def decode_jpeg_batch_device(files, out=None, stream=None, one_thread=False, records=False):
+def decode_jpeg_batch_device(files, out=None, stream=None, one_thread=False, records=False, device_entropy=False):
     """JPEG files (host bytes) -> [(uint8 tensor view (height, width, channels), ColorType)], views into ONE uint8 device
     tensor: `out` (contiguous, any alignment; the bytes between two images are left as they are), or one allocated from
     decode_jpeg_batch_info.  Enqueue only; BufferTooSmall carries the total in `.needed`.  `records`: also return the block and
     the pixo_png_image records, which resize.fit_images, resize.resize_images_device, convert, jpeg.encode_images_device and
-    png.encode_images_device take unchanged: (views, out, images)."""
+    png.encode_images_device take unchanged: (views, out, images).  `device_entropy`: as decode_jpeg_batch; the call then waits
+    on the host several times per sub-batch, and after a refusal that only the scans show `out` is unspecified."""
     import torch
     L = _lib.load()
     arr, held = _files_c(files)
@@ -302,7 +313,7 @@ def decode_jpeg_batch_device(files, out=None, stream=None, one_thread=False, rec
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.is_cuda
     if stream is None:
         stream = torch.cuda.current_stream().cuda_stream
-    rc = L.pixo_hip_jpeg_decode_batch_device(arr, len(held), _flags(one_thread, False), out.data_ptr(), _lib.nbytes(out), images,
+    rc = L.pixo_hip_jpeg_decode_batch_device(arr, len(held), _flags(one_thread, False, device_entropy), out.data_ptr(), _lib.nbytes(out), images,
                                              C.c_void_p(stream) if stream else None)
     last = images[len(held) - 1] if held else None
     _lib.check(rc, needed=last.offset + image_bytes(last) if rc == -9 else None)
@@ -312,18 +323,21 @@ def decode_jpeg_batch_device(files, out=None, stream=None, one_thread=False, rec
     return (views, out, images) if records else views
 
 
-def decode_jpeg_batch_plan(files, one_thread=False) -> dict:
+def decode_jpeg_batch_plan(files, one_thread=False, device_entropy=False) -> dict:
     """What the batch entries decide for these files, computed on the host (no GPU): `sub_first`, `classes` (per image, of
-    JPEG_CLASSES), `launches` (summed over the sub-batches) and `threads`."""
+    JPEG_CLASSES), `launches` (summed over the sub-batches), `threads` and `on_device` (per image: with `device_entropy`, whether
+    its scan goes to the device)."""
     L = _lib.load()
     arr, held = _files_c(files)
     n = len(held)
     sub_first, classes = (C.c_uint32 * (n + 1))(), (C.c_uint8 * max(n, 1))()
     subs, launches, threads = C.c_uint32(), C.c_uint32(), C.c_uint32()
-    _lib.check(L.pixo_hip_debug_jpeg_decode_batch_plan(arr, n, ONE_THREAD if one_thread else 0, sub_first, C.byref(subs), classes, C.byref(launches),
-                                                       C.byref(threads)))
+    flags = _flags(one_thread, False, device_entropy)
+    _lib.check(L.pixo_hip_debug_jpeg_decode_batch_plan(arr, n, flags, sub_first, C.byref(subs), classes, C.byref(launches), C.byref(threads)))
+    on_device, sub_first2, subs2 = (C.c_uint8 * max(n, 1))(), (C.c_uint32 * (n + 1))(), C.c_uint32()
+    _lib.check(L.pixo_hip_debug_jpeg_entropy_plan(arr, n, flags, on_device, sub_first2, C.byref(subs2)))
     return dict(sub_first=list(sub_first[:subs.value + 1]), classes=[JPEG_CLASSES[k] for k in classes[:n]], launches=launches.value,
-                threads=threads.value)
+                threads=threads.value, on_device=[bool(x) for x in on_device[:n]])
 
 
 def decode_jpeg_batch_tables(files) -> np.ndarray:
@@ -351,10 +365,55 @@ def decode_jpeg_coefficients(data, component: int) -> np.ndarray:
     return out
 
 
-def decode_jpeg_batch_timed(files, one_thread=False):
-    """MEASUREMENT: decode_jpeg_batch with its legs timed -> [entropy decode, uploads, kernels, copy down, whole call] in ms."""
+def decode_jpeg_batch_timed(files, one_thread=False, device_entropy=False):
+    """MEASUREMENT: decode_jpeg_batch with its legs timed -> [entropy decode, uploads, kernels, copy down, whole call] in ms.
+    With `device_entropy` [0] is the host's share and decode_jpeg_entropy_last() gives the device leg."""
     L = _lib.load()
     arr, held = _files_c(files)
     ms = (C.c_double * 5)()
-    _lib.check(L.pixo_hip_debug_jpeg_decode_batch_timed(arr, len(held), ONE_THREAD if one_thread else 0, ms))
+    _lib.check(L.pixo_hip_debug_jpeg_decode_batch_timed(arr, len(held), _flags(one_thread, False, device_entropy), ms))
     return list(ms)
+
+
+def decode_jpeg_entropy_geometry() -> dict:
+    """The device Huffman decode's geometry (jpeg_entropy_dec_math.h): `sub_bytes` of a subsequence, `group_subs` subsequences a
+    workgroup owns, `round_cap` of a call, `min_scan_bytes` of a scan that goes to the device."""
+    g = [C.c_uint32() for _ in range(4)]
+    _lib.load().pixo_hip_jpeg_entropy_geometry(*[C.byref(x) for x in g])
+    return dict(sub_bytes=g[0].value, group_subs=g[1].value, round_cap=g[2].value, min_scan_bytes=g[3].value)
+
+
+def decode_jpeg_entropy_debug(files, component=0, round_cap=0):
+    """The device Huffman decode alone (pixo_hip_debug_jpeg_entropy_batch; tests): per file a dict of `vouched`, `why` (ENTROPY_*),
+    `subs`, `rounds` and `coef` — the coefficients of `component` as decode_jpeg_coefficients returns them, or None where the
+    device does not vouch or the file has no such component.  No host decoder behind it."""
+    L = _lib.load()
+    arr, held = _files_c(files)
+    n = len(held)
+    shapes, at, total = [], [], 0
+    for f in held:
+        bw, bh = C.c_uint32(), C.c_uint32()
+        rc = L.pixo_hip_debug_jpeg_decode_coefficients(f.ctypes.data, f.size, component, None, 0, C.byref(bw), C.byref(bh))
+        if rc not in (0, -9):
+            bw.value = bh.value = 0  # (no such component)
+        shapes.append((bh.value, bw.value))
+        at.append(total)
+        total += bh.value * bw.value * 64
+    out = np.zeros(max(total, 1), np.int16)
+    info = (C.c_uint32 * (4 * max(n, 1)))()
+    _lib.check(L.pixo_hip_debug_jpeg_entropy_batch(arr, n, component, round_cap, out.ctypes.data, (C.c_uint64 * max(n, 1))(*at), info))
+    res = []
+    for i in range(n):
+        vouched = bool(info[4 * i])
+        bh, bw = shapes[i]
+        coef = out[at[i]:at[i] + bh * bw * 64].reshape(bh, bw, 64).copy() if vouched and bh * bw else None
+        res.append(dict(vouched=vouched, why=info[4 * i + 1], subs=info[4 * i + 2], rounds=info[4 * i + 3], coef=coef))
+    return res
+
+
+def decode_jpeg_entropy_last() -> dict:
+    """MEASUREMENT: of this thread's last batch call with `device_entropy` — `device_ms` (the entropy launches and the waits
+    between them), `rounds` (the most a file used), `files_device`, `files_redone`."""
+    ms, r, d, h = C.c_double(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _lib.load().pixo_hip_debug_jpeg_entropy_last(C.byref(ms), C.byref(r), C.byref(d), C.byref(h))
+    return dict(device_ms=ms.value, rounds=r.value, files_device=d.value, files_redone=h.value)
